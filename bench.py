@@ -3,6 +3,8 @@
 Conformer decode path on MI355X (BASELINE.json `metric`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]        # N > 1: starts its own N ranks
+    python bench.py --full ...           # + transparency legs, roofline, verification, CPU baseline
+    python bench.py --dump-outputs DIR   # + the last timed step's decode results as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...   # or under a launcher
 
@@ -16,18 +18,25 @@ worker thread + side stream, drained inside the timed region:
 wenet_amd/dist.py ResultGatherer).  Weights are random-init (sharpened CTC head,
 wenet_amd/synthetic.py), inputs synthetic.
 
-Timing: W warm-up steps, then ROUNDS of exactly K steps, each round bracketed by a
-barrier + torch.cuda.synchronize() on both sides and max-reduced over the ranks;
-rounds repeat until they cover >= 2 s, and `value` / `ms_per_step` are the MEDIAN
-round (`rounds` carries min / max).  After the timed rounds the tokens the last
-timed step produced are compared with what the REAL reference produced on the same
-batch (tests/golden/bench_*.npz): `verified`.
+Timing: W warm-up steps, then ONE round of exactly K timed steps, bracketed by a
+barrier + torch.cuda.synchronize() on both sides and max-reduced over the ranks:
+`ms_per_step` = round / K, `value` = audio seconds of K steps / round.
+`--min-seconds S` repeats rounds of K steps until they cover S seconds; `value` /
+`ms_per_step` are then the MEDIAN round (`rounds` carries min / max).
 
 `--workload configN` / `--dtype bf16|fp8` measure the other BASELINE configs and
 the opt-in reduced-precision modes as extra data points; the default line
 (config2, fp32 = the reference's dtype) is the headline.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+`--dump-outputs DIR`: rank 0 writes the results of the decode its last timed step
+returned as DIR/<field>.npy (dump_outputs); inputs and weights are seeded, so two
+builds can be compared output for output.
+
+Rank 0 prints ONE JSON line with the contract fields, `config`, `rounds` and `ranks`.
+`--full` also runs and reports what the headline does not need (each `--no-*`
+switch drops one part of it):
+  verified     : the tokens the last timed step produced against what the REAL
+                 reference produced on the same batch (tests/golden/bench_*.npz);
   roofline     : the feed-forward kernel (d_model 256: both contractions fused in
                  ffn_x6f_kernel; 512: the w_1 GEMM), achieved = algorithmic FLOP of its
                  launches / their HIP-event durations inside the timed rounds, peak =
@@ -63,7 +72,6 @@ _lib_mod = None
 # dense MFMA peaks, /opt/skills/guides/MI355X_MICROARCH.md:41-43
 PEAK_TFLOPS = {'fp32': 157.3, 'bf16': 2500.0, 'fp8': 5000.0}
 NOMINAL_GHZ = 2.4      # peak engine clock the dense peaks are quoted at (MI355X_MICROARCH.md)
-MIN_TIMED_SECONDS = 2.0
 MAX_ROUNDS = 400
 
 
@@ -105,6 +113,41 @@ def contraction_flops(configs, feat_lens) -> float:
                      + tp * d * 2 * d + tp * d * K + tp * d * d)  # conv module
         mac += L * per_layer + tp * d * V
     return 2.0 * mac
+
+
+def dump_outputs(out_dir, indices, results):
+    """The DecodeResult fields (wenet_amd/search.py) of one decode as float64 arrays
+    out_dir/<field>.npy, rows in global utterance order (`utterance_index`): a number per
+    utterance -> (B, ); a list -> (B, L); a list of lists (n-best) -> (B, K, L).  Ragged rows
+    are padded with -1 and their lengths go to <field>_len.  Fields the method leaves None
+    and the detokenised text are not written."""
+    os.makedirs(out_dir, exist_ok=True)
+    order = sorted(range(len(indices)), key=lambda i: indices[i])
+    rows = [results[i].as_dict() for i in order]
+    arrays = {'utterance_index': np.asarray([indices[i] for i in order], dtype=np.float64)}
+    for name in rows[0]:
+        vals = [r[name] for r in rows]
+        if name == 'text' or all(v is None for v in vals):
+            continue
+        if all(np.isscalar(v) for v in vals):
+            arrays[name] = np.asarray(vals, dtype=np.float64)
+            continue
+        vals = [[] if v is None else list(v) for v in vals]
+        if any(len(v) and not np.isscalar(v[0]) for v in vals):
+            width = max(len(h) for v in vals for h in v)
+            a = np.full((len(vals), max(len(v) for v in vals), width), -1.0)
+            n = np.zeros(a.shape[:2])
+            for b, v in enumerate(vals):
+                for k, h in enumerate(v):
+                    a[b, k, :len(h)], n[b, k] = h, len(h)
+        else:
+            a = np.full((len(vals), max(len(v) for v in vals)), -1.0)
+            n = np.zeros(a.shape[:1])
+            for b, v in enumerate(vals):
+                a[b, :len(v)], n[b] = v, len(v)
+        arrays[name], arrays[name + '_len'] = a, n
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(configs, sd, feats, lens, method, kw, beam):
@@ -244,8 +287,16 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--min-seconds', type=float, default=MIN_TIMED_SECONDS,
-                    help='rounds of --steps steps are repeated until they cover this')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='repeat rounds of --steps steps until they cover this many seconds '
+                         '(default: one round, i.e. exactly --steps timed steps)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run and report what the headline does not need: the transparency '
+                         'legs, the roofline pass, the shader-clock sample, the check against the '
+                         'reference goldens (`verified`) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the results of the decode the last timed step returned as '
+                         'DIR/<field>.npy (rank 0; see dump_outputs)')
     ap.add_argument('--streams', type=int, default=6,
                     help='decodes kept in flight per GPU (wenet_amd/pipeline.py: up to two '
                          'the encoders are chained by events, above they run free -- r17c: '
@@ -359,8 +410,10 @@ def main():
                                     'cpu' if share_gpu else device)
 
     sync_gather = os.environ.get('WN_BENCH_SYNC_GATHER') == '1'   # A/B: gather on the decode thread
+    last_res = [None]
 
     def finish(res):
+        last_res[0] = res
         if sync_gather:
             rec = wdist.pack_results(mine, [r.tokens for r in res], [r.score for r in res],
                                      batch_per_gpu, max_tok, 'cpu' if share_gpu else device)
@@ -404,17 +457,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    out = run_steps(args.warmup)
     L = _lib.lib()
     # (one bracketed launch of the roofline kernel per decode inside the timed rounds: every event
     # pair idles the GPU for ~10 us around the launch -- four per decode were 0.8 % of a step in
     # the two-stream timeline, r13b; the roofline figures come from the single-stream pass below,
     # which brackets every 6th launch)
     ffn_launches_per_decode = 2 * configs['encoder_conf']['num_blocks']
+    prof_stride = int(os.environ.get('WN_BENCH_PROF_STRIDE', max(6, ffn_launches_per_decode)))
+    # the warm-up's brackets name the kernel the feed-forward modules run on (`dtype`); the
+    # timed rounds are bracketed only under --full (or when there is no warm-up to name it)
     for mdl in pipe.models:
+        _lib.check(L.wn_profile_enable(mdl._h, prof_stride), 'profile')
+    out = run_steps(args.warmup)
+    for mdl in pipe.models:     # (re-enabling restarts the counts: warm-up launches drop out)
         _lib.check(L.wn_profile_enable(
-            mdl._h, int(os.environ.get('WN_BENCH_PROF_STRIDE', max(6, ffn_launches_per_decode)))),
-            'profile')
+            mdl._h, prof_stride if args.full or args.warmup == 0 else 0), 'profile')
     # The host's cyclic GC walks every tracked object (torch modules, state dicts, the
     # goldens: a large, static heap) on each full collection -- measured 25 % slower rounds
     # about once a second and 4 % on the median (r02ax).  After warm-up the objects alive so
@@ -448,6 +505,8 @@ def main():
     if gc_off:
         gc.enable()
         gc.unfreeze()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mine, last_res[0])
     prof_name = L.wn_profile_kernel_name(pipe.models[0]._h).decode()
     n_launch, ms, flops = ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
     tot_launch, tot_ms, tot_flops = 0, 0.0, 0.0
@@ -467,25 +526,26 @@ def main():
     # what `rocprofv3 --kernel-trace --stats ... --streams 1` (profiles/) reproduces; the
     # figures of the timed rounds stay in `roofline.timed_rounds`.
     timed_launch, timed_ms, timed_flops = tot_launch, tot_ms, tot_flops
-    _lib.check(L.wn_profile_enable(model._h, 1), 'profile')
     roof_steps = max(4, min(args.steps, 12))
-    for _ in range(2):
-        model.decode([method], feats_dev, lens, beam_size=beam, **decode_kw)
-    _lib.check(L.wn_profile_collect(model._h, ctypes.byref(n_launch), ctypes.byref(ms),
-                                    ctypes.byref(flops)), 'profile')   # drop the warm-up's
-    for _ in range(roof_steps):
-        model.decode([method], feats_dev, lens, beam_size=beam, **decode_kw)
-    torch.cuda.synchronize()
-    _lib.check(L.wn_profile_collect(model._h, ctypes.byref(n_launch), ctypes.byref(ms),
-                                    ctypes.byref(flops)), 'profile')
-    _lib.check(L.wn_profile_enable(model._h, 0), 'profile')
-    if n_launch.value > 0:
-        tot_launch, tot_ms, tot_flops = n_launch.value, ms.value, flops.value
-        prof_name = L.wn_profile_kernel_name(model._h).decode()
+    if args.full:
+        _lib.check(L.wn_profile_enable(model._h, 1), 'profile')
+        for _ in range(2):
+            model.decode([method], feats_dev, lens, beam_size=beam, **decode_kw)
+        _lib.check(L.wn_profile_collect(model._h, ctypes.byref(n_launch), ctypes.byref(ms),
+                                        ctypes.byref(flops)), 'profile')   # drop the warm-up's
+        for _ in range(roof_steps):
+            model.decode([method], feats_dev, lens, beam_size=beam, **decode_kw)
+        torch.cuda.synchronize()
+        _lib.check(L.wn_profile_collect(model._h, ctypes.byref(n_launch), ctypes.byref(ms),
+                                        ctypes.byref(flops)), 'profile')
+        _lib.check(L.wn_profile_enable(model._h, 0), 'profile')
+        if n_launch.value > 0:
+            tot_launch, tot_ms, tot_flops = n_launch.value, ms.value, flops.value
+            prof_name = L.wn_profile_kernel_name(model._h).decode()
     # transparency leg: the same decode with every GEMM on v_mfma_f32 (gemm_x6 = 0), one
     # round of --steps steps; reported beside the headline, never as `value`
     f32_only = None
-    if args.dtype == 'fp32' and 'x6' in prof_name and not args.no_f32_mfma_leg:
+    if args.full and args.dtype == 'fp32' and 'x6' in prof_name and not args.no_f32_mfma_leg:
         _lib.check(L.wn_tune_set(b'gemm_x6', 0), 'tune')
         try:
             run_steps(max(2, args.warmup // 2))
@@ -500,7 +560,7 @@ def main():
     # the reference (wenet/bin/recognize.py:289) gets without the two-decodes-in-flight
     # pipeline -- one round of --steps steps; reported beside the headline, never as `value`
     plain = None
-    if args.streams != 1 and not args.no_plain_leg:
+    if args.full and args.streams != 1 and not args.no_plain_leg:
         def plain_steps(n):
             for _ in range(n):
                 finish(model.decode([method], feats_dev, lens, beam_size=beam,
@@ -515,7 +575,7 @@ def main():
     # transparency leg: the headline of rounds 2-5 -- TWO decodes in flight, their encoders chained
     # by events -- for continuity with the earlier rounds' numbers; one round of --steps steps
     two_chained = None
-    if args.streams > 2 and not args.no_two_stream_leg:
+    if args.full and args.streams > 2 and not args.no_two_stream_leg:
         pipe2 = DecodePipeline(model, n_streams=2)
         try:
             def two_steps(n):
@@ -536,7 +596,7 @@ def main():
     # materialised inside the timed round (Python lists of the reference's DecodeResult fields;
     # the headline reads tokens / score only and leaves them lazy)
     nbest_leg = None
-    if method == 'ctc_prefix_beam_search' and not args.no_nbest_leg:
+    if args.full and method == 'ctc_prefix_beam_search' and not args.no_nbest_leg:
         run_steps(max(2, args.warmup // 2), finish_nbest)
         barrier()
         t0 = time.perf_counter()
@@ -548,7 +608,7 @@ def main():
     # more steps with the clock-stamp variant of the kernel (csrc/ffn_x6f.hip VAR & 8192: cycle
     # counter and 100-MHz real-time counter at its entry and end) -- outside every timed region
     clock_ghz = None
-    if 'ffn_x6f' in prof_name and not args.no_clock_sample:
+    if args.full and 'ffn_x6f' in prof_name and not args.no_clock_sample:
         _lib.check(L.wn_tune_set(b'ffn_x6f_var', 25088), 'tune')
         try:
             run_steps(2)
@@ -564,7 +624,7 @@ def main():
         finally:
             _lib.check(L.wn_tune_set(b'ffn_x6f_var', 0), 'tune')
     e2e = None
-    if world == 1 and not whisper and not args.no_e2e_leg:
+    if args.full and world == 1 and not whisper and not args.no_e2e_leg:
         e2e = end_to_end_leg(model, pipe, finish, gatherer.drain, barrier, lens, device,
                              total_audio, args.steps, method, beam, decode_kw,
                              max(1, args.streams))
@@ -683,7 +743,9 @@ def main():
                         'gathers of the run.  ms_per_step is the max over ranks of the whole '
                         'round, these are its parts',
             },
-            'roofline': {
+        }
+        if args.full:
+            line['roofline'] = {
                 'bound': 'mfma',
                 'kernel': (f'{prof_name}, M={enc_rows} F={ffn} D={d_model}, hidden split '
                            f'{ffn_split}: {4 * enc_rows * ffn * d_model / 1e9:.2f} algorithmic '
@@ -733,79 +795,78 @@ def main():
                                      'batch (SURVEY.md 8d formula) / ms_per_step / '
                                      'whole_decode_peak (fp32 mode: the six-product ceiling, '
                                      'dense bf16 peak / 6)',
-            },
-        }
-        # HBM traffic of that kernel from the PMC passes (tools/gpu_pmc.sh; cannot
-        # be collected inside a timed run): bytes per launch, committed summary
-        # one record per workload and dtype: profiles/pmc_roofline_kernels.json (written by
-        # tools/pmc_table.py --key from the end-of-round PMC passes)
-        pmc = os.path.join(ROOT, 'profiles', 'pmc_roofline_kernels.json')
-        rec = None
-        if os.path.exists(pmc):
-            with open(pmc) as f:
-                rec = json.load(f).get(f'{args.workload}:{args.dtype}')
-            kind = lambda n: ('ffn_x6f' if 'ffn_x6f' in n else 'ffn_fused' if 'ffn_fused' in n
-                              else 'x6' if 'x6' in n else 'lp' if 'gemm_lp' in n else 'gemm')
-            # (the bf16 / fp8 modes name their FFN w_1 launch "gemm (FFN w_1)": at these shapes
-            # it IS the pipelined low-precision kernel the record was taken from)
-            same = (kind(rec.get('kernel', '')) == kind(prof_name) or
-                    (args.dtype != 'fp32' and kind(prof_name) == 'gemm' and
-                     kind(rec.get('kernel', '')) == 'lp')) if rec is not None else False
-            if rec is not None and not same:
-                rec = None     # the committed counters describe another kernel
-        if rec is not None:
-            line['roofline']['traffic'] = rec['hbm_bytes_per_launch']
-            line['roofline']['traffic_unit'] = 'bytes/launch (HBM read + write, PMC)'
-            line['roofline']['traffic_source'] = ('profiles/pmc_roofline_kernels.json, '
-                                                  'visit ' + str(rec.get('visit', '?')) +
-                                                  ' (' + str(rec.get('table', '')) + ')')
-            if 'ffn_x6f' in prof_name:
-                # the ALGORITHM's bytes: X planes in once (6 B / element: LN(x) arrives as
-                # its plane image), W_1 + W_2 planes once, the result Y out once (fp32); the
-                # hidden tensor never leaves the registers.  What this launch geometry adds
-                # -- Y leaves as `ffn_split` hidden-slice partials instead of once -- is NOT
-                # algorithmic: it is listed beside it as launch_geometry_bytes
-                line['roofline']['algorithmic_bytes'] = int(
-                    6 * enc_rows * d_model + 4 * enc_rows * d_model
-                    + 6 * 2 * ffn * d_model)
-                line['roofline']['launch_geometry_bytes'] = int(
-                    6 * enc_rows * d_model + 4 * enc_rows * d_model * ffn_split
-                    + 6 * 2 * ffn * d_model)
-            elif x6:
-                # A planes in (6 B / element), W planes (L2-resident across row tiles),
-                # hidden-tensor planes out
-                line['roofline']['algorithmic_bytes'] = int(
-                    6 * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
-            elif 'gemm_lp' in rec.get('kernel', ''):
-                # operands and result in their storage types: bf16 A / W / C (2 B), or MXFP8
-                # (1 B + one scale byte per 32 elements)
-                esz = 2.0 if args.dtype == 'bf16' else 1.0 + 1.0 / 32
-                line['roofline']['algorithmic_bytes'] = int(
-                    esz * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
-            elif 'ffn_fused' in rec.get('kernel', ''):
-                # fused v_mfma_f32 FFN: X in, S hidden-slice partials out, W_1 + W_2 once
-                line['roofline']['algorithmic_bytes'] = int(
-                    4 * (enc_rows * d_model * (1 + ffn_split) + 2 * ffn * d_model))
-            else:
-                line['roofline']['algorithmic_bytes'] = int(
-                    4 * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
-        if line['roofline'].get('traffic') and line['roofline'].get('algorithmic_bytes'):
-            line['roofline']['traffic_over_algorithmic'] = round(
-                line['roofline']['traffic'] / line['roofline']['algorithmic_bytes'], 2)
-        if clock_ghz is not None:
-            line['roofline']['shader_clock_ghz_sampled'] = round(clock_ghz, 3)
-            line['roofline']['frac_at_sampled_clock'] = round(
-                achieved / (peak * clock_ghz / NOMINAL_GHZ), 4)
-            line['roofline']['clock_note'] = (
-                f'peak is priced at the {NOMINAL_GHZ} GHz peak engine clock; the kernel\'s own '
-                'cycle / real-time stamps (one block, last launch of two extra untimed steps) give '
-                'the clock the power management held under this load -- frac_at_sampled_clock '
-                'prices the same achieved rate against the peak at that clock')
-        if x6:
-            line['roofline']['executed_mfma_tflops'] = round(6 * achieved, 1)
-            line['roofline']['fp32_mfma_peak'] = PEAK_TFLOPS['fp32']
-            line['roofline']['whole_decode_frac_of_fp32_mfma_peak'] = round(
-                line['roofline']['whole_decode_tflops'] / PEAK_TFLOPS['fp32'], 4)
+            }
+            # HBM traffic of that kernel from the PMC passes (tools/gpu_visit.sh pmc; cannot
+            # be collected inside a timed run): bytes per launch, committed summary
+            # one record per workload and dtype: profiles/pmc_roofline_kernels.json (written by
+            # tools/pmc_table.py --key from the end-of-round PMC passes)
+            pmc = os.path.join(ROOT, 'profiles', 'pmc_roofline_kernels.json')
+            rec = None
+            if os.path.exists(pmc):
+                with open(pmc) as f:
+                    rec = json.load(f).get(f'{args.workload}:{args.dtype}')
+                kind = lambda n: ('ffn_x6f' if 'ffn_x6f' in n else 'ffn_fused' if 'ffn_fused' in n
+                                  else 'x6' if 'x6' in n else 'lp' if 'gemm_lp' in n else 'gemm')
+                # (the bf16 / fp8 modes name their FFN w_1 launch "gemm (FFN w_1)": at these shapes
+                # it IS the pipelined low-precision kernel the record was taken from)
+                same = (kind(rec.get('kernel', '')) == kind(prof_name) or
+                        (args.dtype != 'fp32' and kind(prof_name) == 'gemm' and
+                         kind(rec.get('kernel', '')) == 'lp')) if rec is not None else False
+                if rec is not None and not same:
+                    rec = None     # the committed counters describe another kernel
+            if rec is not None:
+                line['roofline']['traffic'] = rec['hbm_bytes_per_launch']
+                line['roofline']['traffic_unit'] = 'bytes/launch (HBM read + write, PMC)'
+                line['roofline']['traffic_source'] = ('profiles/pmc_roofline_kernels.json, '
+                                                      'visit ' + str(rec.get('visit', '?')) +
+                                                      ' (' + str(rec.get('table', '')) + ')')
+                if 'ffn_x6f' in prof_name:
+                    # the ALGORITHM's bytes: X planes in once (6 B / element: LN(x) arrives as
+                    # its plane image), W_1 + W_2 planes once, the result Y out once (fp32); the
+                    # hidden tensor never leaves the registers.  What this launch geometry adds
+                    # -- Y leaves as `ffn_split` hidden-slice partials instead of once -- is NOT
+                    # algorithmic: it is listed beside it as launch_geometry_bytes
+                    line['roofline']['algorithmic_bytes'] = int(
+                        6 * enc_rows * d_model + 4 * enc_rows * d_model
+                        + 6 * 2 * ffn * d_model)
+                    line['roofline']['launch_geometry_bytes'] = int(
+                        6 * enc_rows * d_model + 4 * enc_rows * d_model * ffn_split
+                        + 6 * 2 * ffn * d_model)
+                elif x6:
+                    # A planes in (6 B / element), W planes (L2-resident across row tiles),
+                    # hidden-tensor planes out
+                    line['roofline']['algorithmic_bytes'] = int(
+                        6 * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
+                elif 'gemm_lp' in rec.get('kernel', ''):
+                    # operands and result in their storage types: bf16 A / W / C (2 B), or MXFP8
+                    # (1 B + one scale byte per 32 elements)
+                    esz = 2.0 if args.dtype == 'bf16' else 1.0 + 1.0 / 32
+                    line['roofline']['algorithmic_bytes'] = int(
+                        esz * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
+                elif 'ffn_fused' in rec.get('kernel', ''):
+                    # fused v_mfma_f32 FFN: X in, S hidden-slice partials out, W_1 + W_2 once
+                    line['roofline']['algorithmic_bytes'] = int(
+                        4 * (enc_rows * d_model * (1 + ffn_split) + 2 * ffn * d_model))
+                else:
+                    line['roofline']['algorithmic_bytes'] = int(
+                        4 * (enc_rows * d_model + ffn * d_model + enc_rows * ffn))
+            if line['roofline'].get('traffic') and line['roofline'].get('algorithmic_bytes'):
+                line['roofline']['traffic_over_algorithmic'] = round(
+                    line['roofline']['traffic'] / line['roofline']['algorithmic_bytes'], 2)
+            if clock_ghz is not None:
+                line['roofline']['shader_clock_ghz_sampled'] = round(clock_ghz, 3)
+                line['roofline']['frac_at_sampled_clock'] = round(
+                    achieved / (peak * clock_ghz / NOMINAL_GHZ), 4)
+                line['roofline']['clock_note'] = (
+                    f'peak is priced at the {NOMINAL_GHZ} GHz peak engine clock; the kernel\'s own '
+                    'cycle / real-time stamps (one block, last launch of two extra untimed steps) give '
+                    'the clock the power management held under this load -- frac_at_sampled_clock '
+                    'prices the same achieved rate against the peak at that clock')
+            if x6:
+                line['roofline']['executed_mfma_tflops'] = round(6 * achieved, 1)
+                line['roofline']['fp32_mfma_peak'] = PEAK_TFLOPS['fp32']
+                line['roofline']['whole_decode_frac_of_fp32_mfma_peak'] = round(
+                    line['roofline']['whole_decode_tflops'] / PEAK_TFLOPS['fp32'], 4)
         if f32_only is not None:
             line['f32_mfma_only'] = {
                 'value': round(total_audio * args.steps / f32_only, 1),
@@ -840,24 +901,25 @@ def main():
                         'lists per step, built on first access: wenet_amd/search.py '
                         '_NBestBatch), one round of --steps steps',
             }
-        # what the timed steps produced vs the real reference's answer
-        ver = verify.verify_bench_output(args.workload, world, out, method)
-        line['verified'] = ver.pop('verified')
-        line['verify'] = ver
-        line['verify']['scope'] = ('1-best tokens of every utterance of the LAST timed step '
-                                   'against the real reference\'s (tests/golden/bench_*.npz); '
-                                   'scores, n-best lists and per-frame rules are the -m gpu '
-                                   'tests\' job (tests/test_gpu_bench_parity.py)')
-        if reduced and line['verified'] is False:
-            # reduced-precision modes are not bit-comparable with the fp32 reference
-            line['verify']['note'] = ('reduced-precision run: token identity with the fp32 '
-                                      'reference is reported, not required; the pass criterion of '
-                                      'this mode is per frame against the oracle under the same '
-                                      'operand rounding at this shape (tests/golden/'
-                                      'bench_config5_{bf16,fp8}.npz, tests/test_gpu_bench_parity.py)')
+        if args.full:
+            # what the timed steps produced vs the real reference's answer
+            ver = verify.verify_bench_output(args.workload, world, out, method)
+            line['verified'] = ver.pop('verified')
+            line['verify'] = ver
+            line['verify']['scope'] = ('1-best tokens of every utterance of the LAST timed step '
+                                       'against the real reference\'s (tests/golden/bench_*.npz); '
+                                       'scores, n-best lists and per-frame rules are the -m gpu '
+                                       'tests\' job (tests/test_gpu_bench_parity.py)')
+            if reduced and line['verified'] is False:
+                # reduced-precision modes are not bit-comparable with the fp32 reference
+                line['verify']['note'] = ('reduced-precision run: token identity with the fp32 '
+                                          'reference is reported, not required; the pass criterion of '
+                                          'this mode is per frame against the oracle under the same '
+                                          'operand rounding at this shape (tests/golden/'
+                                          'bench_config5_{bf16,fp8}.npz, tests/test_gpu_bench_parity.py)')
         if e2e is not None:
             line['end_to_end'] = e2e
-        if not args.no_cpu_baseline and world == 1 and not whisper:
+        if args.full and not args.no_cpu_baseline and world == 1 and not whisper:
             line['cpu_baseline'] = cpu_baseline(configs, sd, feats, lens, method,
                                                 decode_kw, beam)
         print(json.dumps(line), flush=True)

@@ -123,3 +123,26 @@ def test_pmc_roofline_records_are_keyed_by_workload_and_dtype(tmp_path, monkeypa
     merged = json.loads((prof / 'pmc_roofline_kernels.json').read_text())
     assert merged == {'config2:fp32': {'kernel': 'a'}, 'config9:bf16': {'kernel': 'b',
                                                                         'avg_us': 1.0}}
+
+
+def test_dump_outputs_writes_every_result_field(tmp_path):
+    """bench.py --dump-outputs: the DecodeResult fields of the last timed step as float64
+    arrays in global utterance order, ragged rows padded with -1 beside their lengths."""
+    import bench
+    from wenet_amd.search import DecodeResult
+    res = [DecodeResult(tokens=(3, 4), score=-1.5, times=[2, 9], nbest=[(3, 4), (3, )],
+                        nbest_scores=[-1.5, -2.0], nbest_times=[[2, 9], [2]]),
+           DecodeResult(tokens=(), score=-0.5, times=[], nbest=[()], nbest_scores=[-0.5],
+                        nbest_times=[[]])]
+    bench.dump_outputs(str(tmp_path), [7, 2], res)
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.glob('*.npy')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert 'text' not in got and 'tokens_confidence' not in got
+    assert got['utterance_index'].tolist() == [2, 7]
+    assert got['tokens'].tolist() == [[-1, -1], [3, 4]] and got['tokens_len'].tolist() == [0, 2]
+    assert got['score'].tolist() == [-0.5, -1.5]
+    assert got['nbest'].tolist() == [[[-1, -1], [-1, -1]], [[3, 4], [3, -1]]]
+    assert got['nbest_len'].tolist() == [[0, 0], [2, 1]]
+    assert got['nbest_scores'].tolist() == [[-0.5, -1], [-1.5, -2.0]]
+    assert got['nbest_scores_len'].tolist() == [1, 2]
+    assert got['nbest_times'].tolist() == [[[-1, -1], [-1, -1]], [[2, 9], [2, -1]]]

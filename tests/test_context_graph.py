@@ -2,10 +2,12 @@
 own ContextGraph against the oracle's restatement (itself pinned against the
 reference in tests/test_oracle.py), the flat tables the C ABI takes, and the
 flattening of a reference-style graph object."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
-from conftest import needs_reference
+from golden_util import load_case
 from oracle import wenet_oracle as O
 from wenet_amd.context_graph import ContextGraph, FlatGraph, flatten, tokenize
 
@@ -83,44 +85,52 @@ def test_empty_graph_is_only_the_root():
     assert f.n_nodes == 1 and f.n_edges == 0 and f.fail.tolist() == [0]
 
 
-@needs_reference
+def _reference_style_graph(rec):
+    """A graph object shaped like the reference's ContextGraph (``root``; ContextState
+    nodes with ``id``, ``next``, ``fail`` and the three scores), rebuilt from a reference
+    graph recorded state by state in tests/golden/live_context_graph.npz."""
+    states = {r['id']: SimpleNamespace(id=r['id'], token_score=r['token_score'],
+                                       node_score=r['node_score'],
+                                       output_score=r['output_score'])
+              for r in rec['states']}
+    for r in rec['states']:
+        states[r['id']].fail = states[r['fail']]
+        states[r['id']].next = {tok: states[child] for tok, child in r['next']}
+    return SimpleNamespace(root=states[0], num_nodes=rec['num_nodes'])
+
+
 def test_flatten_accepts_the_reference_graph_object():
-    from oracle import gen_golden_context
+    recs = load_case('live_context_graph')[0]['flatten']
     rng = np.random.RandomState(5)
-    for _ in range(10):
+    for rec in recs:
         vocab = int(rng.randint(3, 9))
         phrases = _random_phrases(rng, vocab, int(rng.randint(1, 12)))
-        ref = gen_golden_context.reference_graph(phrases, 2.0)
+        assert phrases == rec['phrases']
+        ref = _reference_style_graph(rec)
         f = flatten(ref)
         assert flatten(ref) is f  # cached on the object
         assert f.n_nodes == ref.num_nodes + 1
+        steps = iter(rec['walk'])      # the reference's forward_one_step / finalize answers
         for _ in range(10):
-            rs, s = ref.root, 0
+            s = 0
             for tok in rng.randint(0, vocab + 1, 30):
-                a, rs = ref.forward_one_step(rs, int(tok))
+                a, _, r_final = next(steps)
                 b, s = _walk_flat(f, s, int(tok))
                 assert a == b
-                assert -f.node_score[s] == ref.finalize(rs)[0]
+                assert -f.node_score[s] == r_final
 
 
-@needs_reference
 def test_tokenize_bpe_matches_reference(tmp_path):
+    """The reference's tokenize on the same sentencepiece model (model and answer recorded
+    in tests/golden/live_tokenizers.npz)."""
     spm = pytest.importorskip('sentencepiece')
-    from oracle import _ref_harness
-    _ref_harness.install()
-    from wenet.utils.context_graph import tokenize as ref_tokenize
-    corpus = tmp_path / 'corpus.txt'
-    corpus.write_text('\n'.join(['HELLO WORLD', 'THE CAT SAT ON THE MAT',
-                                 'SPEECH RECOGNITION', 'A QUICK BROWN FOX'] * 30))
-    prefix = str(tmp_path / 'bpe')
-    spm.SentencePieceTrainer.train(input=str(corpus), model_prefix=prefix,
-                                   vocab_size=40, model_type='bpe',
-                                   character_coverage=1.0)
+    meta, arrays = load_case('live_tokenizers')
+    model = tmp_path / 'bpe.model'
+    model.write_bytes(arrays['context_bpe_model'].tobytes())
     sp = spm.SentencePieceProcessor()
-    sp.load(prefix + '.model')
+    sp.load(str(model))
     table = {sp.id_to_piece(i): i for i in range(sp.get_piece_size())}
     table['你'] = len(table)
     ctx = tmp_path / 'ctx.txt'
     ctx.write_text('the cat\nhello 你 world\nzebra\n', encoding='utf8')
-    assert tokenize(str(ctx), table, prefix + '.model') == \
-        ref_tokenize(str(ctx), table, prefix + '.model')
+    assert tokenize(str(ctx), table, str(model)) == meta['context_bpe']

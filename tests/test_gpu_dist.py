@@ -42,7 +42,7 @@ def _torchrun(nproc, argv, timeout=600):
 
 
 def test_bench_two_ranks_on_one_gpu_equals_the_reference_per_utterance():
-    r = _torchrun(2, ['bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1',
+    r = _torchrun(2, ['bench.py', '--full', '--gpus', '2', '--steps', '2', '--warmup', '1',
                       '--no-cpu-baseline', '--min-seconds', '0.1'])
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -59,7 +59,7 @@ def test_bench_eight_ranks_on_one_gpu_equals_the_reference_per_utterance(workloa
     8 MI355X): 8 ranks x 32 utterances, snake-dealt by length over the ranks, every rank's
     results gathered by the worker-thread all_gather; all 256 token lists equal the REAL
     reference's (tests/golden/bench_<workload>_w8.npz)."""
-    r = _torchrun(8, ['bench.py', '--gpus', '8', '--workload', workload, '--steps', '2',
+    r = _torchrun(8, ['bench.py', '--full', '--gpus', '8', '--workload', workload, '--steps', '2',
                       '--warmup', '1', '--no-cpu-baseline', '--no-f32-mfma-leg',
                       '--no-clock-sample', '--no-plain-leg', '--no-nbest-leg',
                       '--min-seconds', '0.1'], timeout=900)
@@ -88,7 +88,7 @@ def test_bench_starts_its_own_eight_ranks_without_a_launcher():
            if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(WN_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0',
                PYTHONPATH=ROOT + os.pathsep + os.environ.get('PYTHONPATH', ''))
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '8', '--steps', '2'],
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--gpus', '8', '--steps', '2'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -125,7 +125,7 @@ def test_bench_rccl_process_group_of_one_rank():
                MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()), RANK='0',
                LOCAL_RANK='0', WORLD_SIZE='1',
                PYTHONPATH=ROOT + os.pathsep + os.environ.get('PYTHONPATH', ''))
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '2', '--warmup',
+    r = subprocess.run([sys.executable, 'bench.py', '--full', '--gpus', '1', '--steps', '2', '--warmup',
                         '1', '--no-cpu-baseline', '--no-f32-mfma-leg', '--min-seconds', '0.1'],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -3,7 +3,8 @@
     (runtime/core/test/ctc_prefix_beam_search_test.cc:29-72),
   * against the mask docstring examples (wenet/utils/mask.py:109-113,212-216),
   * against the committed outputs of the real reference (tests/golden/),
-  * and, when /root/reference is present, against the live reference.
+  * and against answers of the live reference recorded for these tests
+    (tests/golden/live_*.npz, oracle/gen_golden_live.py).
 """
 import math
 import os
@@ -12,7 +13,6 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import needs_reference
 from golden_util import (attention_case_names, build_inputs, case_names,
                          chunk_case_names, chunk_windows,
                          context_case_names, context_search_case_names, load_case,
@@ -51,13 +51,13 @@ def test_fbank_matches_reference_cpp_golden():
 
 
 def test_fbank_matches_live_reference_cpp():
-    from oracle import ref_fbank
-    if not ref_fbank.available():
-        pytest.skip('oracle/_ref/libref_fbank.so not built (make -C oracle)')
+    """The reference's own C++ fbank (oracle/_ref) on three more waveforms, recorded in
+    tests/golden/live_fbank_cpp.npz."""
     from wenet_amd import synthetic as S
+    _, arrays = load_case('live_fbank_cpp')
     for n, seed in [(8000, 21), (401, 22), (33333, 23)]:
         w = S.make_audio(n, seed=seed)
-        ref = ref_fbank.ref_fbank(w)
+        ref = arrays[f'feats_{n}_{seed}']
         got = O.fbank(w)
         assert got.shape == ref.shape
         assert np.abs(got - ref).max() < 5e-4
@@ -233,82 +233,67 @@ def test_oracle_attention_mode_matches_committed_reference_outputs(name):
     assert [list(r.tokens) for r in got] == meta['tokens']
 
 
-@needs_reference
 def test_oracle_whisper_encoder_matches_live_reference():
-    from oracle import gen_golden_whisper
+    """The reference's TransformerEncoder (recorded: tests/golden/live_whisper_encoder.npz)."""
     from wenet_amd import synthetic as S
+    _, arrays = load_case('live_whisper_encoder')
     configs = S.make_configs('whisper_tiny_like')
     sd = S.make_state_dict(configs, 5)
-    enc, _ = gen_golden_whisper.build_reference_encoder(configs, sd)
-    for B, fr, seed in [(3, (30, 71), 1), (2, (40, 41), 2), (4, (9, 33), 3)]:
+    for i, (B, fr, seed) in enumerate([(3, (30, 71), 1), (2, (40, 41), 2), (4, (9, 33), 3)]):
         f, l = S.make_features(B, fr, seed=seed, feat_dim=configs['input_dim'])
         with torch.no_grad():
-            ref, rmask = enc(f, l)
             got, gmask = O.encoder_forward(configs, sd, f, l)
-        n = rmask.squeeze(1).sum(1)
+        ref, n = torch.from_numpy(arrays[f'out{i}']), torch.from_numpy(arrays[f'n{i}'])
         assert n.tolist() == gmask.squeeze(1).sum(1).tolist()
         for b in range(B):
             assert (ref[b, :n[b]] - got[b, :n[b]]).abs().max() < 1e-5
 
 
-@needs_reference
 @pytest.mark.parametrize('config', ['tiny_causal', 'tiny_sym', 'aishell_u2pp'])
 def test_synthetic_state_dict_matches_reference_names(config):
-    import argparse
-    import copy
-    from oracle import _ref_harness
+    """Names and shapes of the reference's init_model state_dict, and its positional table
+    bit for bit (recorded as a sha256: tests/golden/live_state_dict_names.npz)."""
+    import hashlib
     from wenet_amd import synthetic as S
-    _ref_harness.install()
-    from wenet.utils.init_model import init_model
+    ref = load_case('live_state_dict_names')[0][config]
     configs = S.make_configs(config)
     sd = S.make_state_dict(configs, 0)
-    rc = copy.deepcopy(configs)
-    rc['cmvn'] = None
-    model, _ = init_model(argparse.Namespace(), rc)
-    ref = model.state_dict()
     extra = {'encoder.global_cmvn.mean', 'encoder.global_cmvn.istd'}
-    assert set(ref.keys()) | extra == set(sd.keys())
-    for k, v in ref.items():
-        assert tuple(v.shape) == tuple(sd[k].shape), k
-    np.testing.assert_array_equal(ref['encoder.embed.pos_enc.pe'].numpy(),
-                                  sd['encoder.embed.pos_enc.pe'].numpy())
+    assert set(ref['shapes']) | extra == set(sd.keys())
+    for k, shape in ref['shapes'].items():
+        assert tuple(shape) == tuple(sd[k].shape), k
+    pe = np.ascontiguousarray(sd['encoder.embed.pos_enc.pe'].numpy())
+    assert str(pe.dtype) == ref['pe_dtype']
+    assert hashlib.sha256(pe.tobytes()).hexdigest() == ref['pe_sha256']
 
 
-@needs_reference
 @pytest.mark.parametrize('config,chunk,left,beam', [
     ('tiny_causal', -1, -1, 7), ('tiny_causal', 3, 1, 2), ('tiny_sym', -1, -1, 4),
     ('tiny_sym', 5, -1, 3)])
 def test_oracle_matches_live_reference(config, chunk, left, beam):
-    from oracle import _ref_harness, gen_golden
+    """The reference's ASRModel.decode (recorded: tests/golden/live_decode.npz)."""
     from wenet_amd import synthetic as S
-    _ref_harness.install()
+    ref = next(c for c in load_case('live_decode')[0]
+               if (c['config'], c['chunk'], c['left'], c['beam']) == (config, chunk, left, beam))
     configs = S.make_configs(config)
     sd = S.make_state_dict(configs, 3)
-    model = gen_golden.build_reference_model(configs, sd)
     feats, lens = S.make_features(4, (50, 220), seed=21)
     methods = ['ctc_greedy_search', 'ctc_prefix_beam_search',
                'attention_rescoring']
     rw = 0.4 if configs['decoder'] == 'bitransformer' else 0.0
-    with torch.no_grad():
-        ref = model.decode(methods, feats, lens, beam_size=beam,
-                           decoding_chunk_size=chunk,
-                           num_decoding_left_chunks=left, ctc_weight=0.4,
-                           reverse_weight=rw)
     got = O.decode(configs, sd, methods, feats, lens, beam_size=beam,
                    decoding_chunk_size=chunk, num_decoding_left_chunks=left,
                    ctc_weight=0.4, reverse_weight=rw)
     for b in range(4):
-        assert ref['ctc_greedy_search'][b].tokens == \
-            got['ctc_greedy_search'][b].tokens
-        rp, gp = ref['ctc_prefix_beam_search'][b], \
-            got['ctc_prefix_beam_search'][b]
-        assert [list(x) for x in rp.nbest] == [list(x) for x in gp.nbest]
-        assert rp.nbest_scores == gp.nbest_scores  # same fp64 arithmetic
-        assert rp.nbest_times == gp.nbest_times
-        rr, gr = ref['attention_rescoring'][b], got['attention_rescoring'][b]
-        assert list(rr.tokens) == list(gr.tokens)
-        assert abs(rr.score - gr.score) < 1e-5
-        assert abs(rr.confidence - gr.confidence) < 1e-6
+        assert ref['greedy'][b] == list(got['ctc_greedy_search'][b].tokens)
+        gp = got['ctc_prefix_beam_search'][b]
+        assert ref['nbest'][b] == [list(x) for x in gp.nbest]
+        assert ref['nbest_scores'][b] == list(gp.nbest_scores)  # same fp64 arithmetic
+        assert ref['nbest_times'][b] == [list(t) for t in gp.nbest_times]
+        gr = got['attention_rescoring'][b]
+        assert ref['rescoring'][b] == list(gr.tokens)
+        assert abs(ref['rescoring_scores'][b] - gr.score) < 1e-5
+        assert abs(ref['rescoring_confidence'][b] - gr.confidence) < 1e-6
 
 
 # --------------------------------------------------------------------------
@@ -381,47 +366,42 @@ def test_oracle_context_decode_matches_committed_reference_outputs(name):
                                meta['rescoring_scores'], rtol=0, atol=2e-3)
 
 
-@needs_reference
-def test_context_graph_matches_live_reference(tmp_path):
+def test_context_graph_matches_live_reference():
     """Graph arrays, every transition and the char tokenizer against
-    wenet/utils/context_graph.py on random phrase lists."""
-    from oracle import _ref_harness, gen_golden_context
-    _ref_harness.install()
-    from wenet.utils.context_graph import ContextGraph as RefGraph
+    wenet/utils/context_graph.py on random phrase lists (the reference's answers recorded
+    in tests/golden/live_context_graph.npz)."""
+    meta, _ = load_case('live_context_graph')
     rng = np.random.RandomState(0)
     for trial in range(20):
         vocab = int(rng.randint(3, 9))
         phrases = [[int(t) for t in rng.randint(1, vocab, rng.randint(1, 6))]
                    for _ in range(rng.randint(1, 12))]
-        ref = gen_golden_context.reference_graph(phrases, 1.5)
+        ref = meta['graph'][trial]
+        assert phrases == ref['phrases']
         g = O.ContextGraph(phrases, 1.5)
-        assert g.num_nodes == ref.num_nodes
-        # walk both automata in lock step over random token streams
+        assert g.num_nodes == ref['num_nodes']
+        # walk the automaton over the token streams the reference walked
+        steps = iter(ref['walk'])
         for _ in range(30):
-            rs, s = ref.root, 0
+            s = 0
             for tok in rng.randint(0, vocab + 1, 25):
-                r_score, rs = ref.forward_one_step(rs, int(tok))
+                r_score, r_state, r_final = next(steps)
                 o_score, s = g.forward_one_step(s, int(tok))
-                assert r_score == o_score and rs.id == s
-                assert ref.finalize(rs)[0] == g.finalize(s)[0]
+                assert r_score == o_score and r_state == s
+                assert r_final == g.finalize(s)[0]
     # tokenizer (char units): spaces, unknown symbols, <unk>
     table = {'<blank>': 0, '<unk>': 1, 'a': 2, 'b': 3, '\u2581': 4, '\u4f60': 5}
     lines = ['ab a\n', ' b\u4f60z \n', '\n', 'zzz\n']
-    path = tmp_path / 'ctx.txt'
-    path.write_text(''.join(lines), encoding='utf8')
-    ref = RefGraph(str(path), table, None, 2.0)
-    assert O.tokenize_context(lines, table) == ref.context_list
+    assert O.tokenize_context(lines, table) == meta['tokenize_with_unk']
     table.pop('<unk>')
-    ref = RefGraph(str(path), table, None, 2.0)
-    assert O.tokenize_context(lines, table) == ref.context_list
+    assert O.tokenize_context(lines, table) == meta['tokenize_without_unk']
 
 
-@needs_reference
 def test_oracle_context_search_matches_live_reference():
-    from oracle import _ref_harness, gen_golden_context
+    """The reference's context-biased ctc_prefix_beam_search (recorded:
+    tests/golden/live_context_graph.npz)."""
     from wenet_amd import synthetic as S
-    _ref_harness.install()
-    from wenet.models.transformer.search import ctc_prefix_beam_search as ref_search
+    want = load_case('live_context_graph')[0]['search']
     rng = np.random.RandomState(7)
     for trial in range(6):
         vocab = int(rng.randint(5, 30))
@@ -431,12 +411,13 @@ def test_oracle_context_search_matches_live_reference():
         phrases = [[int(t) for t in rng.randint(1, vocab, rng.randint(1, 5))]
                    for _ in range(rng.randint(1, 15))]
         cs = float(rng.choice([0.5, 2.0, 6.0]))
-        ref = ref_search(logp, lens, beam, gen_golden_context.reference_graph(phrases, cs), 0)
         got = O.ctc_prefix_beam_search(logp, lens, beam, 0, O.ContextGraph(phrases, cs))
-        for r, o in zip(ref, got):
-            assert [tuple(h) for h in r.nbest] == [tuple(h) for h in o.nbest]
-            assert r.nbest_scores == o.nbest_scores
-            assert r.nbest_times == o.nbest_times
+        ref = want[trial]
+        assert len(got) == len(ref['nbest'])
+        for b, o in enumerate(got):
+            assert ref['nbest'][b] == [list(h) for h in o.nbest]
+            assert ref['nbest_scores'][b] == list(o.nbest_scores)
+            assert ref['nbest_times'][b] == [list(t) for t in o.nbest_times]
 
 
 # --------------------------------------------------------------------------
@@ -589,16 +570,15 @@ def test_resample_vs_the_independent_fp64_definition(orig, new):
     assert np.abs(y.astype(np.float64) - z['y']).max() < 1e-6
 
 
-@needs_reference
 @pytest.mark.parametrize('config,rw', [('tiny_causal', 0.0), ('tiny_causal', 0.4),
                                        ('tiny_sym', 0.0)])
 def test_forward_attention_decoder_matches_live_reference(config, rw):
-    """All positions of the padded (N, L, V) outputs, padded rows included."""
-    from oracle import gen_golden
+    """All positions of the padded (N, L, V) outputs, padded rows included (the reference's
+    recorded in tests/golden/live_attention_decoder.npz)."""
     from wenet_amd import synthetic as S
+    _, arrays = load_case('live_attention_decoder')
     configs = S.make_configs(config)
     sd = S.make_state_dict(configs, 4)
-    model = gen_golden.build_reference_model(configs, sd)
     sos, eos = O.special_symbols(configs)
     g = torch.Generator().manual_seed(9)
     V = configs['output_dim']
@@ -608,8 +588,8 @@ def test_forward_attention_decoder_matches_live_reference(config, rw):
         hyps[i, 0] = sos
         hyps[i, 1:n] = torch.randint(1, V - 1, (n - 1, ), generator=g)
     enc = torch.randn(1, 23, configs['encoder_conf']['output_size'], generator=g)
-    with torch.no_grad():
-        r_l, r_r = model.forward_attention_decoder(hyps, lens, enc, rw)
+    r_l = torch.from_numpy(arrays[f'{config}_{rw}_l'])
+    r_r = torch.from_numpy(arrays[f'{config}_{rw}_r'])
     o_l, o_r = O.forward_attention_decoder(configs, sd, hyps, lens, enc, rw, sos, eos)
     assert r_l.shape == o_l.shape and (r_l - o_l).abs().max() < 1e-5
     assert r_r.shape == o_r.shape and (r_r - o_r).abs().max() < 1e-5
@@ -659,28 +639,25 @@ def test_bf16_operand_emulation_is_scoped_and_selective():
         assert torch.equal(O._mm(xb, wb.T), torch.matmul(xb, wb.T))
 
 
-@needs_reference
 @pytest.mark.parametrize('config', ['tiny_causal', 'tiny_sym'])
 def test_bf16_operand_mode_is_at_least_as_close_to_fp32_as_reference_autocast(config):
     """The reference's `--dtype bf16` is torch autocast around decode()
     (wenet/bin/recognize.py:250-255,278-280), which rounds operands AND results of
     every linear / conv / matmul to bf16.  The product's bf16 mode rounds operands
     only; its emulation must sit closer to the fp32 encoder output than the real
-    reference under CPU autocast does, and the two must agree to bf16 accuracy."""
-    from oracle import _ref_harness, gen_golden
+    reference under CPU autocast does, and the two must agree to bf16 accuracy.  (The
+    reference's fp32 and autocast outputs: tests/golden/live_bf16_autocast.npz.)"""
     from wenet_amd import synthetic as S
-    _ref_harness.install()
+    _, arrays = load_case('live_bf16_autocast')
     configs = S.make_configs(config)
     sd = S.make_state_dict(configs, 3)
-    model = gen_golden.build_reference_model(configs, sd)
     feats, lens = S.make_features(4, (60, 200), seed=8)
+    ref32 = torch.from_numpy(arrays[f'{config}_fp32'])
+    ref_ac = torch.from_numpy(arrays[f'{config}_autocast'])
     with torch.no_grad():
-        ref32, mask = model._forward_encoder(feats, lens)
-        with torch.autocast('cpu', dtype=torch.bfloat16):
-            ref_ac, _ = model._forward_encoder(feats, lens)
         with O.bf16_operands(sd):
             emu, _ = O.encoder_forward(configs, sd, feats, lens)
-    n = mask.squeeze(1).sum(1)
+    n = torch.from_numpy(arrays[f'{config}_n'])
     d_ac = max((ref_ac[b, :n[b]].float() - ref32[b, :n[b]]).abs().max().item()
                for b in range(4))
     d_emu = max((emu[b, :n[b]] - ref32[b, :n[b]]).abs().max().item() for b in range(4))
@@ -776,12 +753,11 @@ def test_slaney_filters_window_and_whisper_norm_pinned_by_the_reference_cpp_fron
 
 
 def test_whisper_frontend_pins_live_against_oracle_ref():
-    from oracle import ref_fbank
-    if not ref_fbank.has_whisper_frontend():
-        pytest.skip('oracle/_ref not built with the Whisper frontend (make -C oracle)')
+    """The reference C++ frontend in its Whisper configuration (oracle/_ref), recorded in
+    tests/golden/live_fbank_cpp.npz."""
     from wenet_amd import synthetic as S
     wave = np.asarray(S.make_audio(16000 * 2 + 123, seed=9), dtype=np.float32)
-    ref = ref_fbank.ref_whisper_fbank(wave, 80)
+    ref = load_case('live_fbank_cpp')[1]['whisper_80']
     assert np.abs(O.whisper_frontend_512(wave, 80) - ref).max() < 2e-4
 
 

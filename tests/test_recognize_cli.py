@@ -6,7 +6,7 @@ import os
 
 import pytest
 
-from conftest import needs_reference
+from golden_util import load_case
 from wenet_amd.bin import recognize as R
 from wenet_amd.tokenizer import Tokenizer, get_blank_id, init_tokenizer
 
@@ -231,38 +231,40 @@ def test_tokenizer_char_and_bpe_detokenize():
         get_blank_id({}, {'a': 1})
 
 
-@needs_reference
 def test_tokenizers_match_the_reference(tmp_path):
-    from oracle import _ref_harness
-    _ref_harness.install()
-    from wenet.utils.init_tokenizer import init_tokenizer as ref_init
+    """Against the reference's init_tokenizer: its detokenize answers, symbol tables and
+    the sentencepiece model they were taken with are recorded in
+    tests/golden/live_tokenizers.npz (oracle/gen_golden_live.py)."""
+    meta, arrays = load_case('live_tokenizers')
     units = tmp_path / 'units.txt'
     syms = ['<blank>', '<unk>', '▁he', 'llo', '▁wor', 'ld', '你', '好', '<sos/eos>']
     units.write_text(''.join(f'{s} {i}\n' for i, s in enumerate(syms)))
-    for kind, extra in (('char', {}), ('char', {'connect_symbol': ' '}),
-                        ('char', {'split_with_space': True})):
-        cfg = {'tokenizer': kind,
+    assert [r['extra'] for r in meta['char']] == [{}, {'connect_symbol': ' '},
+                                                  {'split_with_space': True}]
+    for ref in meta['char']:
+        cfg = {'tokenizer': 'char',
                'tokenizer_conf': dict(symbol_table_path=str(units), non_lang_syms_path=None,
-                                      **extra)}
-        ref, got = ref_init(dict(cfg)), init_tokenizer(cfg)
-        for ids in ([6, 7], [2, 3, 4, 5], []):
-            assert ref.detokenize(ids) == got.detokenize(ids)
-        assert ref.symbol_table == got.symbol_table
+                                      **ref['extra'])}
+        got = init_tokenizer(cfg)
+        for ids, want in zip(([6, 7], [2, 3, 4, 5], []), ref['detokenize']):
+            text, tokens = got.detokenize(ids)
+            assert [text, list(tokens)] == want
+        assert got.symbol_table == ref['symbol_table']
     spm = pytest.importorskip('sentencepiece')
-    corpus = tmp_path / 'c.txt'
-    corpus.write_text('\n'.join(['HELLO WORLD', 'THE CAT SAT'] * 40))
-    spm.SentencePieceTrainer.train(input=str(corpus), model_prefix=str(tmp_path / 'b'),
-                                   vocab_size=30, model_type='bpe')
+    model = tmp_path / 'b.model'
+    model.write_bytes(arrays['cli_bpe_model'].tobytes())
     sp = spm.SentencePieceProcessor()
-    sp.load(str(tmp_path / 'b.model'))
+    sp.load(str(model))
     units.write_text(''.join(f'{sp.id_to_piece(i)} {i}\n'
                              for i in range(sp.get_piece_size())))
     cfg = {'tokenizer': 'bpe',
            'tokenizer_conf': dict(symbol_table_path=str(units), non_lang_syms_path=None,
-                                  bpe_path=str(tmp_path / 'b.model'))}
-    ref, got = ref_init(dict(cfg)), init_tokenizer(cfg)
+                                  bpe_path=str(model))}
+    got = init_tokenizer(cfg)
     ids = sp.encode('HELLO THE CAT')
-    assert ref.detokenize(ids) == got.detokenize(ids)
+    assert ids == meta['bpe']['ids']
+    text, tokens = got.detokenize(ids)
+    assert [text, list(tokens)] == meta['bpe']['detokenize']
 
 
 def test_transcribe_cli_args():
@@ -281,17 +283,11 @@ def test_read_wav_matches_the_reference_wav_reader(tmp_path):
     (runtime/core/frontend/wav.h:59-134, built from where it lies into
     oracle/_ref): identical samples for PCM16 / PCM32, mono and stereo, with and
     without extra chunks between `fmt ` and `data`, and the reference's own test
-    file."""
+    file.  The reader's answers and that file are recorded in
+    tests/golden/live_wav_reader.npz (oracle/gen_golden_live.py)."""
     import numpy as np
-    from oracle import ref_fbank as RF
     from wenet_amd.model import read_wav
-    if not RF.has_wav_reader() and os.path.isdir('/root/reference/runtime/core'):
-        import subprocess  # a library from before ref_wav_read existed: rebuild it
-        subprocess.run(['make', '-s', '-C', os.path.join(os.path.dirname(
-            os.path.dirname(os.path.abspath(__file__))), 'oracle')], check=False)
-    if not RF.has_wav_reader():
-        pytest.skip('oracle/_ref/libref_fbank.so without ref_wav_read '
-                    '(needs /root/reference: make -C oracle)')
+    meta, arrays = load_case('live_wav_reader')
     rng = np.random.Generator(np.random.PCG64(9))
     x = rng.random((3000, 2)) * 1.6 - 0.8
     for bits, scale in ((16, 32768.0), (32, 2147483648.0)):
@@ -302,7 +298,8 @@ def test_read_wav_matches_the_reference_wav_reader(tmp_path):
                 p = tmp_path / f'w{bits}_{nch}_{int(extra)}.wav'
                 p.write_bytes(_wav_bytes(x[:, :nch], 22050, 1, bits, nch=nch,
                                          extra_chunk=extra))
-                ref, ch, sr, b = RF.ref_wav_read(str(p))
+                name = f'w{bits}_{nch}_{int(extra)}'
+                ref, (ch, sr, b) = arrays[name], meta[name]
                 got, rate = read_wav(str(p), return_rate=True)
                 assert (ch, sr, b) == (nch, 22050, bits) and rate == 22050
                 ref0 = ref.reshape(-1, nch)[:, 0]      # first channel (singal_channel)
@@ -312,12 +309,12 @@ def test_read_wav_matches_the_reference_wav_reader(tmp_path):
                 np.testing.assert_array_equal(
                     (got.astype(np.float64) * scale).astype(np.float32),
                     ref0.astype(np.float32))
-    ref_file = '/root/reference/test/resources/aishell-BAC009S0724W0121.wav'
-    if os.path.exists(ref_file):
-        ref, ch, sr, b = RF.ref_wav_read(ref_file)
-        got, rate = read_wav(ref_file, return_rate=True)
-        assert (ch, sr, b, rate) == (1, 16000, 16, 16000)
-        np.testing.assert_array_equal(got * np.float32(32768.0), ref)
+    ref_file = tmp_path / 'aishell-BAC009S0724W0121.wav'
+    ref_file.write_bytes(arrays['aishell_riff'].tobytes())
+    ref, (ch, sr, b) = arrays['aishell'].astype(np.float32), meta['aishell']
+    got, rate = read_wav(str(ref_file), return_rate=True)
+    assert (ch, sr, b, rate) == (1, 16000, 16, 16000)
+    np.testing.assert_array_equal(got * np.float32(32768.0), ref)
 
 
 def test_compute_feature_follows_feats_type():
@@ -364,26 +361,21 @@ def test_compute_feature_follows_feats_type():
              ).compute_feature('a')
 
 
-@needs_reference
 def test_every_reference_recipe_is_accepted_or_refused_cleanly():
     """The reference's own construction test (test/wenet/utils/test_init_model.py:
     every examples/*/*/conf/*.yaml builds) mirrored for this path: each recipe either
     maps to a wn_config or is refused with NotImplementedError naming the key -- never
-    a crash, never a silent mis-configuration.  The BASELINE recipes are accepted."""
-    import glob
-    import yaml
+    a crash, never a silent mis-configuration.  The BASELINE recipes are accepted.  The
+    recipes, parsed, are recorded in tests/golden/live_recipes.npz."""
     from wenet_amd.model import config_from_yaml
     accepted, refused = [], {}
-    paths = sorted(glob.glob('/root/reference/examples/*/*/conf/*.yaml'))
-    assert len(paths) > 50
-    for p in paths:
-        with open(p) as f:
-            c = yaml.load(f, Loader=yaml.FullLoader)
+    recipes = load_case('live_recipes')[0]
+    assert len(recipes) > 50
+    for name, c in sorted(recipes.items()):
         if not isinstance(c, dict) or 'encoder_conf' not in c:
             continue
         c.setdefault('input_dim', 80)
         c.setdefault('output_dim', 5000)
-        name = p.split('examples/')[1]
         try:
             cfg = config_from_yaml(c)
         except NotImplementedError as e:

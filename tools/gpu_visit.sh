@@ -37,7 +37,7 @@ for step in "$@"; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
     bench)
       f=$OUT/bench_${a1}_$n.json
-      timeout 900 python bench.py --workload $a1 $a2 > $f 2>> $OUT/bench.err
+      timeout 900 python bench.py --full --min-seconds 2 --workload $a1 $a2 > $f 2>> $OUT/bench.err
       python - "$f" "$a1 $a2" <<'PY'
 import json, sys
 try:
