@@ -295,6 +295,74 @@ int wn_ctc_prefix_beam_search(wn_model* m, int32_t beam, int32_t blank_id,
                               int32_t* hyp_times_host, double* hyp_scores_host,
                               int32_t max_len, void* stream);
 
+/* ---- streaming sessions: resumable CTC prefix beam search ------------------ */
+/* The search half of the streaming decoder (runtime/core/decoder/ctc_prefix_beam_search.cc:
+ * Search() keeps cur_hyps_ and abs_time_step_ across calls; asr_decoder.cc:87-132
+ * AdvanceDecoding feeds it chunk by chunk) with the Python search's order rules
+ * (search.py:127-249): a set of `n_slots` independent sessions whose beam, prefix / time
+ * node pools, frame counter and endpoint counters live in HBM between calls.  Every call
+ * names the sessions it touches by slot id; calls on one set must be ordered (one stream, or
+ * events between streams).  A set belongs to the handle it was created on and must be
+ * destroyed before it. */
+typedef struct wn_stream_set wn_stream_set;
+
+/* Where wn_stream_advance* put their results (all HOST arrays, the layout of
+ * wn_ctc_prefix_beam_search with B = the n sessions of the call, in call order): n_hyps (n);
+ * hyp_lens, hyp_tlens (n, beam); hyp_tokens, hyp_times (n, beam, max_len), of each row the
+ * first hyp_lens / hyp_tlens entries written; hyp_scores = score(), hyp_viterbi =
+ * viterbi_score() (n, beam) fp64; frames_decoded, trailing_blank (n): CtcEndpoint's
+ * num_frames_decoded_ / num_frames_trailing_blank_ (ctc_endpoint.cc:48-60).  max_len must be
+ * >= the frames any named session has consumed after the call.  hyp_viterbi may be NULL. */
+typedef struct wn_stream_result {
+  int32_t* n_hyps;
+  int32_t* hyp_lens;
+  int32_t* hyp_tlens;
+  int32_t* hyp_tokens;
+  int32_t* hyp_times;
+  double* hyp_scores;
+  double* hyp_viterbi;
+  int32_t* frames_decoded;
+  int32_t* trailing_blank;
+  int32_t max_len;
+} wn_stream_result;
+
+/* Allocate the state of n_slots sessions, once: beam 1..16 (17..64 are the one-shot search's
+ * range and are refused here), at most max_frames encoder frames per session (the node pools
+ * hold max_frames * beam + 1 nodes each).  Every slot starts reset.  The handle may be a
+ * weight-less workspace (wn_workspace_create) when only wn_stream_advance is used. */
+int wn_stream_create(wn_model* m, int32_t n_slots, int32_t beam, int32_t max_frames,
+                     int32_t blank_id, wn_stream_set** out, void* stream);
+int wn_stream_destroy(wn_stream_set* set);
+
+/* CtcEndpointConfig's blank_threshold / blank_scale (ctc_endpoint.h:27-54; defaults 0.8, 1.0):
+ * a frame counts as trailing blank when expf(logp[blank]) > blank_threshold * blank_scale. */
+int wn_stream_set_endpoint(wn_stream_set* set, float blank_threshold, float blank_scale);
+
+/* Back to the root prefix (search.py:144-150), frame and endpoint counters to zero
+ * (CtcPrefixBeamSearch::Reset, CtcEndpoint::Reset) for the n sessions in slot_ids (host). */
+int wn_stream_reset(wn_stream_set* set, int32_t n, const int32_t* slot_ids, void* stream);
+
+/* CtcPrefixBeamSearch::Search on the next frames of n sessions: logp_dev is (n, Tp, V)
+ * log-probs on the device, session i consumes its first n_t_host[i] rows (0 <= n_t <= Tp; 0
+ * leaves the session's state bit for bit).  Per-frame top-k as wn_set_ctc_probs, then the
+ * resumable search; the result is each session's hypothesis list over everything it has
+ * consumed so far -- exactly what wn_ctc_prefix_beam_search returns for those frames in one
+ * call.  nbest == 0: only the 1-best of each session is walked out (n_hyps <= 1);
+ * nbest != 0: the whole beam.  A call that would take a session past max_frames, or whose
+ * max_len is too small, fails with -1 and changes no session.  A handle with a context graph
+ * installed is refused: finalize() of the graph mutates the beam (search.py:229-234), which
+ * a partial result must not do. */
+int wn_stream_advance(wn_stream_set* set, int32_t n, const int32_t* slot_ids,
+                      const float* logp_dev, const int32_t* n_t_host, int32_t Tp, int32_t V,
+                      int32_t nbest, const wn_stream_result* out, void* stream);
+
+/* The same on the encoder output of wn_encode_chunk_batch: enc_out_dev is (n, chunk, d_model)
+ * on the device; the CTC head (Linear + log_softmax + top-k, as wn_ctc_logprobs) runs here, so
+ * a streaming step is encoder chunk -> CTC head -> search without a host round trip between. */
+int wn_stream_advance_encoded(wn_stream_set* set, int32_t n, const int32_t* slot_ids,
+                              const float* enc_out_dev, const int32_t* n_t_host, int32_t chunk,
+                              int32_t nbest, const wn_stream_result* out, void* stream);
+
 /* ---- attention rescoring ------------------------------------------------- */
 /* attention_rescoring + ASRModel.forward_attention_decoder
  * (search.py:374-458, asr_model.py:453-547) for ALL utterances and hypotheses

@@ -13,6 +13,15 @@ top-10, what a streaming prefix beam consumes).  Reported per N: median / p99 st
 steady state (caches full) and audio-seconds per second = N x 0.64 / step.
 
     python tools/bench_streaming.py [--sessions 16,32,64] [--left 4] [--steps 200]
+
+--search: the step also runs the resumable prefix beam search of the streaming recognizer
+(wenet_amd.streaming.StreamSearch.advance_encoded: CTC head + search in one call, 1-best
+partials) and the line reports the step latency with it (`search_step_ms_*`) next to the one
+without it, measured in the same process in alternating blocks.  `--utt-seconds 5,20,60`: the
+sessions have that much audio behind them when the measurement starts (the search state is
+brought there first).  `--requadratic`: also time what a caller had to do before the
+resumable search existed to get a partial after every chunk -- search.ctc_prefix_beam_search
+over ALL log-probs received so far (`rerun_step_ms_*`).
 """
 import argparse
 import json
@@ -37,6 +46,13 @@ def main():
     ap.add_argument('--max-cache', type=int, default=512)
     ap.add_argument('--config', default='wenetspeech_u2pp')
     ap.add_argument('--out', default='')
+    ap.add_argument('--search', action='store_true',
+                    help='also measure the step with the resumable prefix beam search')
+    ap.add_argument('--utt-seconds', default='5',
+                    help='--search: audio seconds every session has consumed before timing')
+    ap.add_argument('--requadratic', action='store_true',
+                    help='--search: also time the one-shot search over everything so far')
+    ap.add_argument('--nbest', action='store_true', help='--search: n-best partials')
     args = ap.parse_args()
     from wenet_amd import synthetic as S
     from wenet_amd.model import ASRModel
@@ -75,6 +91,9 @@ def main():
                    step_ms_p99=round(float(np.percentile(lat, 99)), 3),
                    audio_s_per_s=round(audio / (float(np.median(lat)) * 1e-3), 1),
                    audio_s_per_step=round(audio, 2))
+        if args.search:
+            row['search'] = [search_rows(args, model, dev, n, xs, att, cnn, offsets, req, secs)
+                             for secs in [float(x) for x in args.utt_seconds.split(',')]]
         rows.append(row)
         print(json.dumps(row), flush=True)
         del top
@@ -83,6 +102,69 @@ def main():
             json.dump(dict(model=args.config, note='encoder chunk forward for all sessions + '
                            'CTC head (log-softmax, top-10) per step, host-synchronous; one '
                            'MI355X', rows=rows), f, indent=1)
+
+
+def search_rows(args, model, dev, n, xs, att, cnn, offsets, req, secs):
+    """Step latency without / with the resumable search (/ with the one-shot search over all
+    frames so far) for sessions that have `secs` of audio behind them: blocks of 10 steps of
+    each kind in turn, so that all three see the same clocks and cache state."""
+    from wenet_amd import search as SR
+    from wenet_amd.streaming import StreamSearch
+    chunk = args.chunk
+    hist = int(round(secs / 0.04))                 # encoder frames already consumed
+    total = hist + chunk * (args.warmup + args.steps + 8)
+    ss = StreamSearch(model._h, dev, n, 10, total)
+    slots = list(range(n))
+    ys, att, cnn = model.forward_encoder_chunk_batch(xs, offsets, req, att, cnn)
+    logp1 = model.ctc_logprobs(ys)                 # one chunk of realistic posteriors ...
+    fill = logp1.repeat(1, (hist + chunk - 1) // chunk, 1)[:, :hist].contiguous()
+    for t in range(0, hist, 256):                  # ... repeated: the sessions' history
+        k = min(256, hist - t)
+        ss.advance(slots, fill[:, t:t + k].contiguous(), [k] * n)
+    sofar = fill
+
+    def step(kind):
+        nonlocal att, cnn, sofar
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys, att, cnn = model.forward_encoder_chunk_batch(xs, offsets, req, att, cnn)
+        if kind == 'none':
+            logp = model.ctc_logprobs(ys)
+            top = logp.topk(10, dim=-1)
+            del top
+        elif kind == 'search':
+            ss.advance_encoded(slots, ys, nbest=args.nbest)
+        else:
+            logp = model.ctc_logprobs(ys)
+            sofar = torch.cat([sofar, logp], 1)
+            SR.ctc_prefix_beam_search(sofar, torch.full((n, ), sofar.size(1)), 10)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if args.left < 0 and att[0].size(2) > args.max_cache:
+            att = [a[:, :, -args.max_cache:].contiguous() for a in att]
+        return dt
+
+    kinds = ['none', 'search'] + (['rerun'] if args.requadratic else [])
+    lat = {k: [] for k in kinds}
+    for k in kinds:
+        for _ in range(max(args.warmup // 2, 3)):
+            step(k)
+    blocks = max(args.steps // 10, 1)
+    for _ in range(blocks):
+        for k in kinds:
+            for _ in range(10):
+                if k == 'search' and ss.frames[0] + chunk > total:
+                    break
+                lat[k].append(step(k))
+    ss.close()
+    out = dict(utt_seconds=secs, history_frames=hist, nbest=bool(args.nbest))
+    names = dict(none='step_ms', search='search_step_ms', rerun='rerun_step_ms')
+    for k in kinds:
+        a = np.asarray(lat[k]) * 1e3
+        out[names[k] + '_median'] = round(float(np.median(a)), 3)
+        out[names[k] + '_p99'] = round(float(np.percentile(a, 99)), 3)
+    out['search_minus_step_ms'] = round(out['search_step_ms_median'] - out['step_ms_median'], 3)
+    return out
 
 
 if __name__ == '__main__':

@@ -11,7 +11,8 @@
   tools/isa_audit.py diff <git-rev> [file.hip ...]
       every kernel of the working tree against the same kernel at <git-rev>, instruction by
       instruction (labels and comments normalised; a defaulted template parameter appended to
-      a kernel's signature is folded back): which kernels are unchanged, changed, new, gone.
+      a kernel's signature -- a `bool = false`, or a type that restates the argument -- is
+      folded back): which kernels are unchanged, changed, new, gone.
       Used to show that a prepared-but-unmeasured variant leaves the shipped kernels alone.
 
 Assembly goes to $TMPDIR/wn_isa/{work,<rev>}/ and is reused when newer than the source.
@@ -62,6 +63,16 @@ def assemble(root, tag, files):
 
 
 _DEFAULTED = re.compile(r'(I(?:L[ib]\d+E)+)(Lb0E)(EEv)')
+# ... and a defaulted trailing TYPE parameter that only restates the kernel's one argument
+# (`template <.., class Args = X> kernel(Args)`: ...I<values>X EEv T<n>_  <-  ...I<values>EEv X)
+_DEFAULTED_TYPE = re.compile(r'(I(?:L[ib]\d+E)+)(NS_\d+\w+?E)(EEv)T\d*_$')
+
+
+def _fold_once(name):
+    k = _DEFAULTED_TYPE.sub(lambda m: m.group(1) + m.group(3) + m.group(2), name, count=1)
+    if k != name:
+        return k
+    return _DEFAULTED.sub(lambda m: m.group(1) + m.group(3), name, count=1)
 
 
 def kernels(path, strip_defaulted=False):
@@ -124,7 +135,7 @@ def cmd_diff(rev, files):
     wt = os.path.join(OUT, 'tree_' + rev)
     if not os.path.isdir(wt):
         os.makedirs(wt)
-        ar = subprocess.run(['git', '-C', ROOT, 'archive', rev, 'wenet_amd'], check=True,
+        ar = subprocess.run(['git', '-C', ROOT, 'archive', rev, 'wenet_amd', 'include'], check=True,
                             capture_output=True).stdout
         subprocess.run(['tar', '-x', '-C', wt], input=ar, check=True)
     base = assemble(wt, rev, files)
@@ -141,7 +152,7 @@ def cmd_diff(rev, files):
         for k in B:
             k2 = k
             while k2 not in A:
-                k3 = _DEFAULTED.sub(lambda m: m.group(1) + m.group(3), k2, count=1)
+                k3 = _fold_once(k2)
                 if k3 == k2:
                     break
                 k2 = k3

@@ -6,7 +6,8 @@ The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
-__all__ = ["load_model", "ASRModel", "DecodeResult"]
+__all__ = ["load_model", "ASRModel", "DecodeResult", "StreamingRecognizer",
+           "CtcEndpointConfig", "CtcEndpointRule"]
 
 
 def __getattr__(name):
@@ -16,4 +17,7 @@ def __getattr__(name):
     if name == "DecodeResult":
         from wenet_amd.search import DecodeResult
         return DecodeResult
+    if name in ("StreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule"):
+        from wenet_amd import streaming as _s
+        return getattr(_s, name)
     raise AttributeError(name)

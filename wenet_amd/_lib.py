@@ -27,6 +27,15 @@ class WnTensor(Structure):
                 ('numel', c_int64)]
 
 
+class WnStreamResult(Structure):
+    """wn_stream_result: where wn_stream_advance* put a call's results (host arrays)."""
+    _fields_ = [('n_hyps', POINTER(c_int32)), ('hyp_lens', POINTER(c_int32)),
+                ('hyp_tlens', POINTER(c_int32)), ('hyp_tokens', POINTER(c_int32)),
+                ('hyp_times', POINTER(c_int32)), ('hyp_scores', POINTER(c_double)),
+                ('hyp_viterbi', POINTER(c_double)), ('frames_decoded', POINTER(c_int32)),
+                ('trailing_blank', POINTER(c_int32)), ('max_len', c_int32)]
+
+
 # every symbol include/wenet_amd.h declares
 EXPORTS = [
     'wn_last_error', 'wn_version', 'wn_model_create', 'wn_model_destroy', 'wn_model_clone',
@@ -38,6 +47,8 @@ EXPORTS = [
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
     'wn_op_layernorm', 'wn_op_log_add', 'wn_debug_set', 'wn_profile_enable',
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
+    'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
+    'wn_stream_advance', 'wn_stream_advance_encoded',
 ]
 
 _lib = None
@@ -91,6 +102,14 @@ def lib():
                                        pi32, vp]
     L.wn_ctc_prefix_beam_search.argtypes = [vp, i32, i32, pi32, pi32, pi32,
                                             pi32, pi32, pf64, i32, vp]
+    L.wn_stream_create.argtypes = [vp, i32, i32, i32, i32, POINTER(vp), vp]
+    L.wn_stream_destroy.argtypes = [vp]
+    L.wn_stream_set_endpoint.argtypes = [vp, f32, f32]
+    L.wn_stream_reset.argtypes = [vp, i32, pi32, vp]
+    L.wn_stream_advance.argtypes = [vp, i32, pi32, vp, pi32, i32, i32, i32,
+                                    POINTER(WnStreamResult), vp]
+    L.wn_stream_advance_encoded.argtypes = [vp, i32, pi32, vp, pi32, i32, i32,
+                                            POINTER(WnStreamResult), vp]
     L.wn_attention_rescoring.argtypes = [vp, i32, pi32, pi32, pi32, i32, f32,
                                          POINTER(f32), POINTER(f32), vp]
     L.wn_rescore.argtypes = [vp, i32, pi32, pi32, pi32, pf64, i32, c_double, c_double, pi32,

@@ -9,6 +9,11 @@
 (no network) and no CPU device.  Like the reference's `main`, the text of
 `model.transcribe(audio_file)` is printed; `--beam`, `--context_path` /
 `--context_score` are honoured here (the reference parses and ignores them).
+
+    python -m wenet_amd.bin.transcribe audio.wav -m /path/to/model_dir --stream [--chunk 16]
+
+feeds the file's features through one streaming session (wenet_amd.streaming) in chunk-sized
+pieces, prints every partial result that differs from the one before, then the final text.
 """
 import argparse
 import sys
@@ -26,7 +31,34 @@ def get_args(argv=None):
                    help='beam size (default: the decode() default of transcribe)')
     p.add_argument('--context_path', type=str, default=None, help='context list file')
     p.add_argument('--context_score', type=float, default=6.0, help='context score')
+    p.add_argument('--stream', action='store_true',
+                   help='decode through a streaming session, printing partial results')
+    p.add_argument('--chunk', type=int, default=16,
+                   help='decoding_chunk_size of --stream (encoder frames per step)')
     return p.parse_args(argv)
+
+
+def stream_file(model, audio_file, chunk, beam_size=10, out=print):
+    """One streaming session over the file; `out` gets each changed partial, then the final
+    result's text.  Returns the final DecodeResult."""
+    from wenet_amd.streaming import StreamingRecognizer
+    speech = model.compute_feature(audio_file).to(model.device)
+    rec = StreamingRecognizer(model, 1, chunk, beam_size=beam_size,
+                              max_seconds=speech.size(0) / 100.0 + 1.0)
+    sid = rec.open()
+    piece = chunk * model.subsampling_rate()
+    shown = None
+    for i in range(0, speech.size(0), piece):
+        rec.accept(sid, speech[i:i + piece])
+        for r in rec.step().values():
+            text = model.tokenizer.detokenize(list(r.tokens))[0]
+            if text != shown:
+                out(f'[partial] {text}')
+                shown = text
+    result = rec.finish(sid)
+    rec.close(sid)
+    result.text = model.tokenizer.detokenize(list(result.tokens))[0]
+    return result
 
 
 def main(argv=None):
@@ -34,7 +66,11 @@ def main(argv=None):
     import torch
     import wenet_amd
     model = wenet_amd.load_model(args.model, device=args.device)
-    if args.beam is None and args.context_path is None:
+    if args.stream:
+        if args.context_path is not None:
+            raise SystemExit('--stream does not support --context_path')
+        result = stream_file(model, args.audio_file, args.chunk, args.beam or 10)
+    elif args.beam is None and args.context_path is None:
         result = model.transcribe(args.audio_file)      # asr_model.py:345-358
     else:
         graph = None

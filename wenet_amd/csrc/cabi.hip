@@ -1174,6 +1174,273 @@ int wn_ctc_prefix_beam_search(wn_model* m, int32_t beam, int32_t blank_id,
 }
 
 // ---------------------------------------------------------------------------
+// streaming sessions (include/wenet_amd.h: wn_stream_*): the resumable prefix beam search
+}  // extern "C"
+
+// Everything a set owns is allocated in wn_stream_create or grows on the first call that needs
+// it (the top-k / logits scratch, whose size depends on the chunk): a steady stream of chunks
+// allocates nothing.
+struct wn_stream_set {
+  wn_model* m = nullptr;
+  int n_slots = 0, beam = 0, max_frames = 0, blank = 0;
+  float blank_thr = 0.8f;
+  int64_t pool_ints = 0;             // per slot
+  DevBuf state, pool;                // StreamState[n_slots] | 4 pools per slot (ctc.hip)
+  DevBuf emit;                       // per slot: the last 1-best walked out (ctc.hip)
+  std::vector<int> abs_t;            // host mirror of every slot's frame counter
+  DevBuf desc;                       // slot | off | len of the call in flight
+  Stager stage;
+  DevBuf topk_val, topk_idx, logits;
+  DevBuf out;                        // the results of a call, one block
+  PinnedBuf host;                    // ... and where they land on the host
+};
+
+namespace {
+struct StreamOutLayout {
+  size_t sc, vit, nh, len, tlen, fd, tb, tok, tim, end;
+  StreamOutLayout(size_t n, size_t rows, size_t max_len) {
+    const size_t nr = n * rows;
+    sc = 0; vit = sc + nr * sizeof(double); nh = vit + nr * sizeof(double);
+    len = nh + n * sizeof(int); tlen = len + nr * sizeof(int); fd = tlen + nr * sizeof(int);
+    tb = fd + n * sizeof(int); tok = tb + n * sizeof(int);
+    tim = tok + nr * max_len * sizeof(int); end = tim + nr * max_len * sizeof(int);
+  }
+};
+
+// argument checks of an advance call: nothing here touches the device or a session
+int stream_check(const wn_stream_set* S, int n, const int32_t* slot_ids, const int32_t* n_t,
+                 int Tp, const wn_stream_result* out) {
+  WN_CHECK(n >= 1 && n <= S->n_slots, "wn_stream_advance: n must be in [1, n_slots]");
+  WN_CHECK(out->n_hyps && out->hyp_lens && out->hyp_tlens && out->hyp_tokens &&
+               out->hyp_times && out->hyp_scores && out->frames_decoded && out->trailing_blank,
+           "wn_stream_advance: null output");
+  WN_CHECK(S->m->ctx.keys == nullptr,
+           "wn_stream_advance: a context graph is installed on this handle; context biasing "
+           "is not supported in streaming sessions (its finalize() mutates the beam)");
+  std::vector<char> seen(S->n_slots, 0);
+  int longest = 1;
+  for (int i = 0; i < n; ++i) {
+    const int sl = slot_ids[i];
+    WN_CHECK(sl >= 0 && sl < S->n_slots, "wn_stream_advance: slot id out of range");
+    WN_CHECK(!seen[sl], "wn_stream_advance: a slot is named twice in one call");
+    seen[sl] = 1;
+    WN_CHECK(n_t[i] >= 0 && n_t[i] <= Tp, "wn_stream_advance: need 0 <= n_t <= Tp");
+    if (S->abs_t[sl] + n_t[i] > S->max_frames) {
+      set_error("wn_stream_advance: the session in slot " + std::to_string(sl) + " has " +
+                std::to_string(S->abs_t[sl]) + " frames and would pass max_frames = " +
+                std::to_string(S->max_frames) + " with " + std::to_string(n_t[i]) +
+                " more; no session was advanced");
+      return -1;
+    }
+    longest = std::max(longest, S->abs_t[sl] + n_t[i]);
+  }
+  WN_CHECK(out->max_len >= longest,
+           "wn_stream_advance: max_len smaller than the frames a session has consumed");
+  return 0;
+}
+
+// the search itself on top-k pairs already in S->topk_*; logp (pitch ld): the full rows
+int stream_search(wn_stream_set* S, int n, const int32_t* slot_ids, const int32_t* n_t, int Tp,
+                  const float* logp, int ld, int nbest, const wn_stream_result* out,
+                  hipStream_t s) {
+  const int beam = S->beam, rows = nbest ? beam : 1, max_len = out->max_len;
+  std::vector<int> d(3 * (size_t)n);
+  for (int i = 0; i < n; ++i) { d[i] = slot_ids[i]; d[n + i] = i * Tp; d[2 * n + i] = n_t[i]; }
+  WN_TRY(S->stage.begin(d.size() * sizeof(int) + 64));
+  WN_TRY(S->stage.put(S->desc, d.data(), d.size() * sizeof(int), s));
+  WN_TRY(S->stage.end(s));
+  const StreamOutLayout o(n, rows, max_len);
+  WN_TRY(S->out.ensure(o.end));
+  WN_TRY(S->host.ensure(o.end));
+  char* ob = S->out.as<char>();
+  StreamPrefixBeamArgs a;
+  a.topk_val = S->topk_val.as<float>(); a.topk_idx = S->topk_idx.as<int>(); a.k = beam;
+  a.off = S->desc.as<int>() + n; a.len = S->desc.as<int>() + 2 * n; a.B = n;
+  a.beam = beam; a.blank = S->blank; a.max_len = S->max_frames;
+  a.pool = S->pool.as<int>(); a.pool_stride = S->pool_ints;
+  a.n_hyps = reinterpret_cast<int*>(ob + o.nh); a.hyp_lens = reinterpret_cast<int*>(ob + o.len);
+  a.hyp_tlens = reinterpret_cast<int*>(ob + o.tlen);
+  a.hyp_tokens = reinterpret_cast<int*>(ob + o.tok);
+  a.hyp_times = reinterpret_cast<int*>(ob + o.tim);
+  a.hyp_scores = reinterpret_cast<double*>(ob + o.sc);
+  a.st.state = S->state.p; a.st.slot = S->desc.as<int>();
+  a.st.nbest = nbest ? 1 : 0; a.st.out_stride = max_len;
+  a.st.logp = logp; a.st.ld = ld; a.st.blank_thr = S->blank_thr;
+  a.st.hyp_vit = reinterpret_cast<double*>(ob + o.vit);
+  a.st.emit = S->emit.as<int>();
+  a.st.frames = reinterpret_cast<int*>(ob + o.fd); a.st.trail = reinterpret_cast<int*>(ob + o.tb);
+  static const bool pb_dbg = getenv("WN_PB_CYCLES") != nullptr;  // debugging aid (as one-shot)
+  if (pb_dbg) {
+    WN_TRY(S->m->pb_dbg.ensure(8 * sizeof(long long)));
+    a.dbg_cycles = S->m->pb_dbg.as<long long>();
+  }
+  WN_TRY(ctc_prefix_beam_stream(a, s));
+  if (pb_dbg) {
+    long long h[5];
+    WN_HIP(hipMemcpyAsync(h, a.dbg_cycles, sizeof(h), hipMemcpyDeviceToHost, s));
+    WN_HIP(hipStreamSynchronize(s));
+    if (h[3] > 0)
+      fprintf(stderr, "[wn] stream search wg0: frames %lld, cycles/frame eval %.0f rank %.0f "
+              "select %.0f; state store + emit %lld cycles\n", h[3], (double)h[0] / h[3],
+              (double)h[1] / h[3], (double)h[2] / h[3], h[4]);
+  }
+  WN_HIP(hipMemcpyAsync(S->host.p, ob, o.end, hipMemcpyDeviceToHost, s));
+  // the kernel is queued: the sessions have consumed their frames whatever the copy does
+  for (int i = 0; i < n; ++i) S->abs_t[slot_ids[i]] += n_t[i];
+  WN_HIP(stream_wait(s));
+  const char* hb = S->host.p;
+  const int* nh = reinterpret_cast<const int*>(hb + o.nh);
+  const int* hl = reinterpret_cast<const int*>(hb + o.len);
+  const int* htl = reinterpret_cast<const int*>(hb + o.tlen);
+  const double* sc = reinterpret_cast<const double*>(hb + o.sc);
+  const double* vit = reinterpret_cast<const double*>(hb + o.vit);
+  memcpy(out->n_hyps, nh, (size_t)n * sizeof(int));
+  memcpy(out->frames_decoded, hb + o.fd, (size_t)n * sizeof(int));
+  memcpy(out->trailing_blank, hb + o.tb, (size_t)n * sizeof(int));
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < beam; ++j) {
+      const size_t dst = (size_t)i * beam + j, src = (size_t)i * rows + j;
+      const bool have = j < rows;   // (1-best mode: the other rows read as an empty beam slot)
+      const int nl = have ? std::min(std::max(hl[src], 0), max_len) : 0;
+      const int ntl = have ? std::min(std::max(htl[src], 0), max_len) : 0;
+      out->hyp_lens[dst] = nl; out->hyp_tlens[dst] = ntl;
+      out->hyp_scores[dst] = have ? sc[src] : -HUGE_VAL;
+      if (out->hyp_viterbi) out->hyp_viterbi[dst] = have ? vit[src] : -HUGE_VAL;
+      if (have) {
+        memcpy(out->hyp_tokens + dst * max_len, hb + o.tok + src * max_len * sizeof(int),
+               (size_t)nl * sizeof(int));
+        memcpy(out->hyp_times + dst * max_len, hb + o.tim + src * max_len * sizeof(int),
+               (size_t)ntl * sizeof(int));
+      }
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int wn_stream_create(wn_model* m, int32_t n_slots, int32_t beam, int32_t max_frames,
+                     int32_t blank_id, wn_stream_set** out, void* stream) {
+  WN_CHECK(m && out, "wn_stream_create: null argument");
+  WN_CHECK(n_slots >= 1 && max_frames >= 1 && blank_id >= 0, "wn_stream_create: bad argument");
+  WN_CHECK(beam >= 1, "wn_stream_create: beam_size must be positive");
+  WN_CHECK(beam <= 16, "wn_stream_create: streaming sessions support beam sizes 1..16; larger "
+                       "beams (17..64) are served by the one-shot wn_ctc_prefix_beam_search only");
+  WN_CHECK((int64_t)max_frames * beam + 1 < (1ll << 29), "wn_stream_create: max_frames too large");
+  WN_CHECK(m->ctx.keys == nullptr,
+           "wn_stream_create: a context graph is installed on this handle; context biasing is "
+           "not supported in streaming sessions (its finalize() mutates the beam)");
+  WN_ENTER(m);
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  std::unique_ptr<wn_stream_set> S(new wn_stream_set());
+  S->m = m; S->n_slots = n_slots; S->beam = beam; S->max_frames = max_frames; S->blank = blank_id;
+  S->pool_ints = prefix_beam_pool_ints(max_frames, beam);
+  S->abs_t.assign(n_slots, 0);
+  WN_TRY(S->state.ensure((size_t)n_slots * stream_state_bytes()));
+  WN_TRY(S->pool.ensure((size_t)n_slots * S->pool_ints * sizeof(int)));
+  WN_TRY(S->emit.ensure((size_t)n_slots * stream_emit_ints(max_frames) * sizeof(int)));
+  WN_TRY(S->desc.ensure(3 * (size_t)n_slots * sizeof(int)));
+  // results: the worst case of a 1-best call over all slots up front; an n-best call (the
+  // final one of a session) grows it to what it needs once
+  const StreamOutLayout o(n_slots, 1, max_frames);
+  WN_TRY(S->out.ensure(o.end));
+  WN_TRY(S->host.ensure(o.end));
+  std::vector<int> all(n_slots);
+  for (int i = 0; i < n_slots; ++i) all[i] = i;
+  WN_TRY(S->stage.begin(all.size() * sizeof(int) + 64));
+  WN_TRY(S->stage.put(S->desc, all.data(), all.size() * sizeof(int), s));
+  WN_TRY(S->stage.end(s));
+  WN_TRY(ctc_stream_reset(S->state.p, S->pool.as<int>(), S->pool_ints, max_frames, beam,
+                          S->desc.as<int>(), n_slots, s));
+  WN_HIP(hipStreamSynchronize(s));
+  *out = S.release();
+  return 0;
+}
+
+int wn_stream_destroy(wn_stream_set* set) {
+  delete set;
+  return 0;
+}
+
+int wn_stream_set_endpoint(wn_stream_set* set, float blank_threshold, float blank_scale) {
+  WN_CHECK(set, "wn_stream_set_endpoint: null argument");
+  WN_CHECK(blank_threshold > 0.f && blank_scale > 0.f, "wn_stream_set_endpoint: bad argument");
+  set->blank_thr = blank_threshold * blank_scale;
+  return 0;
+}
+
+int wn_stream_reset(wn_stream_set* set, int32_t n, const int32_t* slot_ids, void* stream) {
+  WN_CHECK(set && slot_ids, "wn_stream_reset: null argument");
+  WN_CHECK(n >= 1 && n <= set->n_slots, "wn_stream_reset: n must be in [1, n_slots]");
+  for (int i = 0; i < n; ++i)
+    WN_CHECK(slot_ids[i] >= 0 && slot_ids[i] < set->n_slots, "wn_stream_reset: slot id out of range");
+  WN_ENTER(set->m);
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(set->m->device));
+  WN_TRY(set->stage.begin((size_t)n * sizeof(int) + 64));
+  WN_TRY(set->stage.put(set->desc, slot_ids, (size_t)n * sizeof(int), s));
+  WN_TRY(set->stage.end(s));
+  WN_TRY(ctc_stream_reset(set->state.p, set->pool.as<int>(), set->pool_ints, set->max_frames,
+                          set->beam, set->desc.as<int>(), n, s));
+  for (int i = 0; i < n; ++i) set->abs_t[slot_ids[i]] = 0;
+  return 0;
+}
+
+int wn_stream_advance(wn_stream_set* set, int32_t n, const int32_t* slot_ids,
+                      const float* logp_dev, const int32_t* n_t_host, int32_t Tp, int32_t V,
+                      int32_t nbest, const wn_stream_result* out, void* stream) {
+  WN_CHECK(set && slot_ids && logp_dev && n_t_host && out, "wn_stream_advance: null argument");
+  WN_CHECK(Tp >= 1 && V >= 1, "wn_stream_advance: bad argument");
+  WN_CHECK(set->beam <= V, "wn_stream_advance: top-k larger than the vocabulary");
+  WN_CHECK(set->blank < V, "wn_stream_advance: blank_id outside the vocabulary");
+  WN_TRY(stream_check(set, n, slot_ids, n_t_host, Tp, out));
+  WN_ENTER(set->m);
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(set->m->device));
+  const int M = n * Tp, k = set->beam;
+  WN_TRY(set->topk_val.ensure((size_t)M * k * sizeof(float)));
+  WN_TRY(set->topk_idx.ensure((size_t)M * k * sizeof(int)));
+  hipLaunchKernelGGL(topk_raw_kernel, dim3(M), dim3(256), 0, s, logp_dev, V, V, k,
+                     set->topk_val.as<float>(), set->topk_idx.as<int>());
+  WN_HIP(hipGetLastError());
+  return stream_search(set, n, slot_ids, n_t_host, Tp, logp_dev, V, nbest, out, s);
+}
+
+int wn_stream_advance_encoded(wn_stream_set* set, int32_t n, const int32_t* slot_ids,
+                              const float* enc_out_dev, const int32_t* n_t_host, int32_t chunk,
+                              int32_t nbest, const wn_stream_result* out, void* stream) {
+  WN_CHECK(set && slot_ids && enc_out_dev && n_t_host && out,
+           "wn_stream_advance_encoded: null argument");
+  WN_CHECK(chunk >= 1, "wn_stream_advance_encoded: bad argument");
+  wn_model* m = set->m;
+  WN_CHECK(m->ctc.w, "wn_stream_advance_encoded: this handle has no weights");
+  WN_CHECK(set->beam <= m->cfg.vocab && set->blank < m->cfg.vocab,
+           "wn_stream_advance_encoded: beam / blank_id outside the vocabulary");
+  WN_TRY(stream_check(set, n, slot_ids, n_t_host, chunk, out));
+  WN_ENTER(m);
+  PrecisionScope prec_scope(m);
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  const wn_config& c = m->cfg;
+  const int M = n * chunk, V = c.vocab, k = set->beam;
+  const int V4 = (V + 31) / 32 * 32;   // the row pitch of wn_ctc_logprobs
+  WN_TRY(set->logits.ensure((size_t)M * V4 * sizeof(float)));
+  WN_TRY(set->topk_val.ensure((size_t)M * k * sizeof(float)));
+  WN_TRY(set->topk_idx.ensure((size_t)M * k * sizeof(int)));
+  WN_TRY(vocab_linear(m, m->ctc, enc_out_dev, c.d_model, set->logits.as<float>(), V4, M, s));
+  CtcRowArgs r;
+  r.logits = set->logits.as<float>(); r.ld = V4; r.M = M; r.V = V; r.k = k;
+  r.blank = set->blank; r.blank_penalty = 0.f;
+  r.topk_val = set->topk_val.as<float>(); r.topk_idx = set->topk_idx.as<int>();
+  r.logp = set->logits.as<float>(); r.ld_out = V4;   // normalised in place: the endpoint reads it
+  WN_TRY(ctc_logsoftmax_topk(r, s));
+  return stream_search(set, n, slot_ids, n_t_host, chunk, set->logits.as<float>(), V4, nbest, out,
+                       s);
+}
+
+// ---------------------------------------------------------------------------
 namespace {
 // embed + the decoder layers over a ragged batch of R token rows (n_seq
 // sequences); the result stays in m->r_x.  With `mem_cache` the cross-attention

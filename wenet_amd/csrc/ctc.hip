@@ -2,6 +2,8 @@
 // CTC prefix beam search of wenet/models/transformer/search.py:127-249.
 #include <math.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace wn {
@@ -440,8 +442,37 @@ constexpr size_t PB_LPOOL_BYTES = 128 * 1024;   // dynamic LDS the node pool may
 // the n-best emission (one DEPENDENT load per token and hypothesis: 113 us of the 1.17 ms search
 // at config 2 through L2, r06x) run at LDS latency.  The launcher takes it whenever the pool fits
 // (PB_LPOOL_BYTES), i.e. up to ~32 s of audio at beam 10.
-template <int NCH, bool CTX, bool LPOOL>
-__global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs a) {
+//
+// STREAM (Args = StreamPrefixBeamArgs, launched by ctc_prefix_beam_stream): the same search,
+// resumable.  Workgroup b serves the session in slot a.st.slot[b]: the beam, its size and abs_t
+// (frames consumed so far) are loaded from that slot's StreamState instead of being set to the
+// root prefix, this launch's a.len[b] frames run through the SAME frame loop with the time
+// stamps / pool slots of frames abs_t .. abs_t + len - 1, and the state goes back to HBM next to
+// the partial result.  The node pools are the slot's own and persist between launches (never
+// LPOOL).  The prefix-identity rule across a launch boundary: a sequence walk must only read
+// nodes whose stores are complete.  Inside a launch that is the vmcnt(0) a frame after the
+// stores plus the frame's last barrier; between two launches it is the kernel boundary itself --
+// advances of one session set are ordered on their stream, the end of a kernel completes and
+// writes back all of its stores to L2, and the walk reads through L2 (sc1 loads) -- so every
+// node of an earlier launch is at least as settled as a node written two frames ago.  The beam
+// read back at the start is data the previous launch stored with plain vector stores before it
+// ended: the same guarantee.
+// The one-shot instantiations (Args = PrefixBeamArgs) compile to the code they had before the
+// parameter existed (tools/isa_audit.py diff): every streaming statement sits under
+// `if constexpr (STREAM)`, and `a.st` is only named there.
+struct StreamState {
+  HypSoA hyp;            // the beam after abs_t frames
+  int nb;                // its valid members
+  int abs_t;             // frames consumed
+  int frames_decoded;    // CtcEndpoint::num_frames_decoded_
+  int trailing_blank;    // CtcEndpoint::num_frames_trailing_blank_
+  int e_len, e_tlen;     // valid entries of the slot's 1-best emission cache (a.st.emit)
+};
+static_assert(sizeof(HypSoA) % sizeof(int) == 0, "the beam is copied int by int");
+
+template <int NCH, bool CTX, bool LPOOL, class Args = PrefixBeamArgs>
+__global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(Args a) {
+  constexpr bool STREAM = std::is_same<Args, StreamPrefixBeamArgs>::value;
   extern __shared__ __attribute__((aligned(16))) int lds_pool[];
   // NCH = 2 <=> MAXB + beam^2 <= 128 <=> beam <= 10: the scans over the beam stop there
   constexpr int BMAX = NCH == 2 ? 10 : MAXB;
@@ -450,8 +481,20 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
   // wave-uniform values must be PROVABLY uniform (SGPRs) or every loop on
   // them is compiled as a divergent, exec-masked loop
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int T = a.len[b], off = a.off[b];
+  int T = a.len[b];
+  const int off = a.off[b];
   const int beam = a.beam;
+  // streaming (a.st exists in StreamPrefixBeamArgs only): the session's slot, its state, the
+  // frames it has consumed; never more frames than the slot's pools have room for (the host
+  // refuses such a call before it launches)
+  int pslot = b, t0 = 0;
+  StreamState* st = nullptr;
+  if constexpr (STREAM) {
+    pslot = __builtin_amdgcn_readfirstlane(a.st.slot[b]);
+    st = static_cast<StreamState*>(a.st.state) + pslot;
+    t0 = __builtin_amdgcn_readfirstlane(st->abs_t);
+    T = __builtin_amdgcn_readfirstlane(min(T, max(a.max_len - t0, 0)));
+  }
   __shared__ HypSoA hyp[2];
   __shared__ double e_score[MAXE];
   __shared__ int e_seq[MAXE];
@@ -463,7 +506,7 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
   __shared__ float lp[2][PB_CHUNK][MAXB];
 
   const int cap = a.max_len * beam + 1;
-  int* pool = LPOOL ? lds_pool : a.pool + (int64_t)b * a.pool_stride;
+  int* pool = LPOOL ? lds_pool : a.pool + (int64_t)pslot * a.pool_stride;
   int* n_parent = pool;            // prefix nodes
   int* n_token = pool + cap;
   int* t_prev = pool + 2 * cap;    // time nodes
@@ -473,7 +516,15 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
     else return same_prefix_nodes(n_parent, n_token, x, y);
   };
 
-  if (tid == 0) {
+  if constexpr (STREAM) {
+    const int* src = reinterpret_cast<const int*>(&st->hyp);
+    int* dst = reinterpret_cast<int*>(&hyp[0]);
+    for (int i = tid; i < (int)(sizeof(HypSoA) / sizeof(int)); i += PB_THREADS) dst[i] = src[i];
+    if (tid == 0) {
+      s_nvalid[0] = 0; s_nvalid[1] = 0;
+      s_tie[0] = 0; s_tie[1] = 0;
+    }
+  } else if (tid == 0) {
     n_parent[0] = -1; n_token[0] = -1;
     t_prev[0] = 0; t_val[0] = -1;
     HypSoA& h = hyp[0];
@@ -510,7 +561,10 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
   const bool dbg = a.dbg_cycles != nullptr && b == 0 && tid == 0;
   long long c_eval = 0, c_rank = 0, c_sel = 0;
   int cur = 0, nb = 1;
+  if constexpr (STREAM) nb = __builtin_amdgcn_readfirstlane(st->nb);
   for (int t = 0; t < T; ++t) {
+    int tt = t;                        // the frame's time stamp and its row of pool slots
+    if constexpr (STREAM) tt += t0;
     const long long c0 = dbg ? __builtin_amdgcn_s_memtime() : 0;
     const HypSoA& H = hyp[cur];
     const int* tk = tok[(t / PB_CHUNK) & 1][t % PB_CHUNK];
@@ -787,7 +841,7 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
       const int rank = e_rank[my_slot];
       if (rank < beam) {
         HypSoA& Hn = hyp[cur ^ 1];
-        const int slot = 1 + t * beam + rank;
+        const int slot = 1 + tt * beam + rank;
         int node = Ekey;
         if (Ekey < 0) {
           node = slot;
@@ -796,9 +850,9 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
         }
         int tns = 0, tnsp = 0;
         if (Etns_op == 1) {
-          t_prev[slot] = Etns_src; t_val[slot] = t; tns = slot; tnsp = Etns_src;
+          t_prev[slot] = Etns_src; t_val[slot] = tt; tns = slot; tnsp = Etns_src;
         } else if (Etns_op == 2) {
-          t_prev[slot] = Etnsp; t_val[slot] = t; tns = slot; tnsp = Etnsp;
+          t_prev[slot] = Etnsp; t_val[slot] = tt; tns = slot; tnsp = Etnsp;
         }
         Hn.node[rank] = node; Hn.par[rank] = Epar; Hn.last[rank] = Etoken;
         Hn.depth[rank] = Edepth;
@@ -826,12 +880,119 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
   const long long c_loop_end = dbg ? __builtin_amdgcn_s_memtime() : 0;
   __syncthreads();  // node-pool stores visible to the emitting threads
 
+  if constexpr (STREAM) {
+    // ---- the state goes back (ordinary vector stores); a session without new frames keeps
+    // its state untouched
+    if (T > 0) {
+      const int* src = reinterpret_cast<const int*>(&hyp[cur]);
+      int* dst = reinterpret_cast<int*>(&st->hyp);
+      for (int i = tid; i < (int)(sizeof(HypSoA) / sizeof(int)); i += PB_THREADS) dst[i] = src[i];
+      if (tid == 0) { st->nb = nb; st->abs_t = t0 + T; }
+    }
+    // ---- endpoint counters (ctc_endpoint.cc:48-60) from the FULL log-prob rows: wave 1 finds
+    // the last frame of this chunk whose blank posterior does not exceed the threshold
+    if (wave == 1) {
+      int last = -1;
+      for (int t = lane; t < T; t += 64) {
+        const float pb = expf(a.st.logp[(int64_t)(off + t) * a.st.ld + a.blank]);
+        if (!(pb > a.st.blank_thr)) last = t;
+      }
+      for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+      if (lane == 0) {
+        const int fd = st->frames_decoded + T;
+        const int tb = last < 0 ? st->trailing_blank + T : T - 1 - last;
+        if (T > 0) { st->frames_decoded = fd; st->trailing_blank = tb; }
+        a.st.frames[b] = fd; a.st.trail[b] = tb;
+      }
+    }
+  }
+
   // ---- emit the n-best list -------------------------------------------------
-  if (tid == 0) a.n_hyps[b] = nb;
-  if (tid < beam) {
-    const int64_t o = (int64_t)b * beam + tid;
-    if (tid < nb) {
+  // (streaming: `rows` result rows per session -- the whole beam, or the 1-best alone)
+  int rows = beam, n_out = nb;
+  if constexpr (STREAM) {
+    rows = a.st.nbest ? beam : 1;
+    n_out = min(nb, rows);
+  }
+  if constexpr (STREAM) {
+    if (!a.st.nbest) {
+      // The 1-best of a partial result, incrementally.  Walking a hypothesis out of the pools is
+      // one DEPENDENT load per token (~700 cycles each from HBM: 0.4 ms for 1500 tokens,
+      // measured), and consecutive partials share all but their last few tokens.  So the slot
+      // keeps the path it emitted last -- node id and token per depth, time node and time per
+      // position -- and a walk stops at the first depth whose node is the cached one: a node's
+      // parent never changes, so everything below it is the cached path.  Invariant: entries
+      // [0, e_len) are a complete root-to-node path (each entry's parent is the entry before
+      // it), likewise [0, e_tlen) for the time list.  Thread 0 walks the tokens, thread 64 (its
+      // own wave) the times; then the whole workgroup copies the cached rows out, coalesced.
+      __shared__ int s_emit[2];
+      int* e_node = a.st.emit + (int64_t)pslot * 4 * a.max_len;
+      int* e_tok = e_node + a.max_len;
+      int* e_tnode = e_tok + a.max_len;
+      int* e_tval = e_tnode + a.max_len;
       const HypSoA& h = hyp[cur];
+      const int L = n_out > 0 ? h.depth[0] : 0;
+      if (tid == 0) {
+        const int old = st->e_len;
+        int node = h.node[0];
+        for (int i = L - 1; i >= 0; --i) {
+          if (i < old && e_node[i] == node) break;
+          e_node[i] = node;
+          e_tok[i] = n_token[node];
+          node = n_parent[node];
+        }
+        st->e_len = L;
+        s_emit[0] = L;
+      }
+      if (tid == 64) {
+        // times() is never set (head 0) or has one entry per token; anything else is walked
+        // in full and leaves the cache empty
+        const int old = st->e_tlen;
+        int x = n_out > 0 ? h.tim[0] : 0;
+        int n_t = 0, keep = 0;
+        if (x != 0) {
+          bool per_token = true;
+          int i = L - 1;
+          for (; i >= 0; --i) {
+            if (x == 0) { per_token = false; break; }
+            if (i < old && e_tnode[i] == x) break;
+            e_tnode[i] = x;
+            e_tval[i] = t_val[x];
+            x = t_prev[x];
+          }
+          if (i < 0 && x != 0) per_token = false;
+          if (per_token) {
+            n_t = L; keep = L;
+          } else {
+            for (int y = h.tim[0]; y != 0; y = t_prev[y]) ++n_t;
+            int y = h.tim[0];
+            for (int j = n_t - 1; j >= 0; --j) { e_tval[j] = t_val[y]; y = t_prev[y]; }
+          }
+        }
+        st->e_tlen = keep;
+        s_emit[1] = n_t;
+      }
+      __syncthreads();
+      const int n_t = s_emit[1];
+      int* tkn = a.hyp_tokens + (int64_t)b * a.st.out_stride;
+      int* tm = a.hyp_times + (int64_t)b * a.st.out_stride;
+      for (int i = tid; i < L; i += PB_THREADS) tkn[i] = e_tok[i];
+      for (int i = tid; i < n_t; i += PB_THREADS) tm[i] = e_tval[i];
+      if (tid == 0) {
+        a.hyp_lens[b] = L;
+        a.hyp_tlens[b] = n_t;
+        a.hyp_scores[b] = n_out > 0 ? h.score[0] : NEG_INF;
+        a.st.hyp_vit[b] = n_out > 0 ? h.vit[0] : NEG_INF;
+      }
+      rows = 0;   // nothing left for the n-best walk below
+    }
+  }
+  if (tid == 0) a.n_hyps[b] = n_out;
+  if (tid < rows) {
+    const int64_t o = (int64_t)b * rows + tid;
+    if (tid < n_out) {
+      const HypSoA& h = hyp[cur];
+      if constexpr (STREAM) a.st.hyp_vit[o] = h.vit[tid];
       const int L = h.depth[tid];
       a.hyp_lens[o] = L;
       // search.py:229-237: finalize() REPLACES the bonus by -node_score(state)
@@ -843,6 +1004,10 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
       // back to the two-pass walk.
       int* tkn = a.hyp_tokens + o * a.max_len;
       int* tm = a.hyp_times + o * a.max_len;
+      if constexpr (STREAM) {   // rows as long as the caller asked for, not the frame capacity
+        tkn = a.hyp_tokens + o * a.st.out_stride;
+        tm = a.hyp_times + o * a.st.out_stride;
+      }
       int node = h.node[tid];
       int x = h.tim[tid];
       const bool has_t = x != 0;
@@ -864,12 +1029,34 @@ __global__ __launch_bounds__(PB_THREADS) void prefix_beam_kernel(PrefixBeamArgs 
       a.hyp_lens[o] = 0;
       a.hyp_tlens[o] = 0;
       a.hyp_scores[o] = NEG_INF;
+      if constexpr (STREAM) a.st.hyp_vit[o] = NEG_INF;
     }
   }
   if (dbg) {
     a.dbg_cycles[0] = c_eval; a.dbg_cycles[1] = c_rank; a.dbg_cycles[2] = c_sel;
     a.dbg_cycles[3] = T;
     a.dbg_cycles[4] = __builtin_amdgcn_s_memtime() - c_loop_end;
+  }
+}
+
+// Root prefix (search.py:144-150) and zeroed endpoint counters (CtcEndpoint::Reset) for the
+// sessions in slot[0..n): the state a fresh one-shot search starts from, node 0 of both pools.
+__global__ __launch_bounds__(64) void stream_reset_kernel(StreamState* state, int* pool,
+                                                          int64_t pool_stride, int cap,
+                                                          const int* slot) {
+  const int sl = slot[blockIdx.x], tid = threadIdx.x;
+  StreamState* st = state + sl;
+  int* w = reinterpret_cast<int*>(st);
+  for (int i = tid; i < (int)(sizeof(StreamState) / sizeof(int)); i += 64) w[i] = 0;
+  __syncthreads();
+  if (tid == 0) {
+    int* p = pool + (int64_t)sl * pool_stride;
+    p[0] = -1; p[cap] = -1;            // n_parent[0], n_token[0]
+    p[2 * cap] = 0; p[3 * cap] = -1;   // t_prev[0], t_val[0]
+    HypSoA& h = st->hyp;
+    h.hash[0] = ROOT_HASH; h.last[0] = -1; h.par[0] = -1;
+    h.ns[0] = NEG_INF;                 // s = v_s = v_ns = score = vit = 0, ns = -inf
+    st->nb = 1;
   }
 }
 
@@ -1294,6 +1481,37 @@ int ctc_prefix_beam(const PrefixBeamArgs& a_in, hipStream_t s) {
     else rc = lpool ? launch_pb<PB_CHUNKS, true, true>(a, pool_bytes, s) : launch_pb<PB_CHUNKS, true, false>(a, 0, s);
   }
   if (rc != 0) return rc;
+  WN_HIP(hipGetLastError());
+  return 0;
+}
+
+int64_t stream_state_bytes() { return (int64_t)sizeof(StreamState); }
+
+int64_t stream_emit_ints(int max_frames) { return 4 * (int64_t)max_frames; }
+
+int ctc_stream_reset(void* state, int* pool, int64_t pool_stride, int max_frames, int beam,
+                     const int* slot_dev, int n, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(stream_reset_kernel, dim3(n), dim3(64), 0, s,
+                     static_cast<StreamState*>(state), pool, pool_stride, max_frames * beam + 1,
+                     slot_dev);
+  WN_HIP(hipGetLastError());
+  return 0;
+}
+
+int ctc_prefix_beam_stream(const StreamPrefixBeamArgs& a_in, hipStream_t s) {
+  StreamPrefixBeamArgs a = a_in;
+  a.weak_hash = tune().beam_weak_hash;
+  WN_CHECK(a.B > 0, "stream search: no session");
+  WN_CHECK(a.beam >= 1 && a.beam <= MAXB, "stream search: beam_size must be in [1, 16]");
+  WN_CHECK(a.k == a.beam, "stream search: top-k width must equal the beam");
+  WN_CHECK(a.cg.keys == nullptr, "stream search: context biasing is not supported");
+  if (MAXB + a.beam * a.beam <= 128)
+    hipLaunchKernelGGL((prefix_beam_kernel<2, false, false, StreamPrefixBeamArgs>), dim3(a.B),
+                       dim3(PB_THREADS), 0, s, a);
+  else
+    hipLaunchKernelGGL((prefix_beam_kernel<PB_CHUNKS, false, false, StreamPrefixBeamArgs>),
+                       dim3(a.B), dim3(PB_THREADS), 0, s, a);
   WN_HIP(hipGetLastError());
   return 0;
 }

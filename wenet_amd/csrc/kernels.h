@@ -311,6 +311,24 @@ __host__ __device__ inline unsigned ctx_slot(unsigned long long key, unsigned ma
   return (unsigned)z & mask;
 }
 
+// The resumable search (ctc.hip, prefix_beam_kernel<.., StreamPrefixBeamArgs>): PrefixBeamArgs
+// (below) with len[b] = new frames of the session in workgroup b, off[b] = its first top-k /
+// log-prob row, max_len = the sessions' frame capacity, pool / pool_stride = the per-SLOT
+// persistent pools; the outputs hold `nbest ? beam : 1` rows per session, token / time rows
+// `out_stride` long.
+struct StreamBeamArgs {
+  void* state = nullptr;        // StreamState[n_slots] (ctc.hip)
+  const int* slot = nullptr;    // [B] slot of each session of this launch (distinct)
+  int nbest = 0;                // 1: emit the whole beam, 0: the 1-best only
+  int out_stride = 0;
+  const float* logp = nullptr;  // full log-prob rows (endpoint counters), pitch ld
+  int ld = 0;
+  float blank_thr = 0.f;        // blank_threshold * blank_scale
+  double* hyp_vit = nullptr;    // [B][rows] viterbi_score()
+  int* frames = nullptr;        // [B] frames decoded
+  int* trail = nullptr;         // [B] trailing blank frames
+  int* emit = nullptr;          // per slot stream_emit_ints(max_frames): the 1-best emission cache
+};
 struct PrefixBeamArgs {
   const float* topk_val; const int* topk_idx; int k;  // [rows][k]
   const int* off; const int* len; int B;
@@ -330,11 +348,18 @@ struct PrefixBeamArgs {
   CtxGraph cg;  // keys == nullptr: no context biasing
   int weak_hash = 0;  // tests: 2-bit prefix hash, so that the exact sequence test decides
 };
+struct StreamPrefixBeamArgs : PrefixBeamArgs { StreamBeamArgs st; };
 int64_t prefix_beam_pool_ints(int max_len, int beam);
 // out[i] = log_add(a[i], b[i]) with the search's own fp64 routine (parity test)
 int log_add_pairs(const double* a, const double* b, double* out, int n,
                   hipStream_t s);
 int ctc_prefix_beam(const PrefixBeamArgs& a, hipStream_t s);
+
+int64_t stream_state_bytes();
+int64_t stream_emit_ints(int max_frames);
+int ctc_stream_reset(void* state, int* pool, int64_t pool_stride, int max_frames, int beam,
+                     const int* slot_dev, int n, hipStream_t s);
+int ctc_prefix_beam_stream(const StreamPrefixBeamArgs& a, hipStream_t s);
 
 // Kaldi fbank (see fbank.hip).
 struct FbankArgs {
