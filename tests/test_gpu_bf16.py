@@ -511,6 +511,27 @@ def test_bf16_is_a_per_handle_switch_and_fp32_comes_back_bit_exact():
         model.set_compute_dtype('fp16')
 
 
+def test_bf16_image_built_after_a_clone_is_shared_with_it():
+    """A clone made BEFORE the switch to bf16: the bf16 image of the weights belongs to the model
+    block the two handles share, whichever of them asks first builds it and both read it -- the
+    same bits from both (a fresh model, so that no earlier test has built the image)."""
+    from gpu_util import make_model
+    from wenet_amd import synthetic as S
+    configs = S.make_configs('tiny_causal')
+    model = make_model(configs, S.make_state_dict(configs, 0))
+    twin = model.clone()
+    feats, lens = S.make_features(3, (50, 120), seed=3, feat_dim=configs['input_dim'])
+    ref, _ = model._forward_encoder(feats.cuda(), lens)
+    ref = ref.clone()
+    _set_dtype(model, 'bf16')
+    _set_dtype(twin, 'bf16')
+    a, _ = model._forward_encoder(feats.cuda(), lens)
+    a = a.clone()
+    b, _ = twin._forward_encoder(feats.cuda(), lens)
+    assert torch.equal(a, b)
+    assert not torch.equal(a, ref)      # (both really ran on the bf16 image)
+
+
 def test_bf16_whisper_golden_stays_close_to_the_fp32_reference():
     """Whisper-tiny-like encoder in bf16 against the REAL reference's committed fp32
     output: reported distance, bounded loosely (bf16 operands: ~3 significant

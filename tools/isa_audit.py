@@ -15,6 +15,10 @@
       folded back): which kernels are unchanged, changed, new, gone.
       Used to show that a prepared-but-unmeasured variant leaves the shipped kernels alone.
 
+  tools/isa_audit.py pool <git-rev> file.hip [file.hip ...]
+      the same comparison with the kernels of all named files (those that exist in each tree)
+      matched by NAME: for code that moved between files, or out of an extern "C" block.
+
 Assembly goes to $TMPDIR/wn_isa/{work,<rev>}/ and is reused when newer than the source.
 """
 import concurrent.futures
@@ -75,11 +79,11 @@ def _fold_once(name):
     return _DEFAULTED.sub(lambda m: m.group(1) + m.group(3), name, count=1)
 
 
-def kernels(path, strip_defaulted=False):
-    """{mangled name: [normalised instruction lines]}; with per-kernel wait statistics."""
+def kernels(path, any_label=False):
+    """{mangled name: [instruction lines]}; any_label: unmangled (extern "C") kernels too."""
     out, cur = {}, None
     for line in open(path):
-        m = re.match(r'^(_Z\S+):\s', line)
+        m = re.match(r'^([A-Za-z_]\w*):\s' if any_label else r'^(_Z\S+):\s', line)
         if m and '@' in line:
             cur = m.group(1)
             out[cur] = []
@@ -131,14 +135,42 @@ def cmd_waits(files):
                       f'asm vmcnt {n_asm:3d}  {demangle(name)[:110]}')
 
 
-def cmd_diff(rev, files):
+def _tree(rev):
     wt = os.path.join(OUT, 'tree_' + rev)
     if not os.path.isdir(wt):
         os.makedirs(wt)
         ar = subprocess.run(['git', '-C', ROOT, 'archive', rev, 'wenet_amd', 'include'], check=True,
                             capture_output=True).stdout
         subprocess.run(['tar', '-x', '-C', wt], input=ar, check=True)
-    base = assemble(wt, rev, files)
+    return wt
+
+
+def _pooled(root, tag, files):
+    have = [f for f in files if os.path.exists(os.path.join(root, 'wenet_amd', 'csrc', f))]
+    out = {}
+    for f, path in assemble(root, tag, have).items():
+        for k, v in kernels(path, any_label=True).items():
+            short = demangle(k).split('(')[0]
+            body = [l.replace(k, short) for l in _norm(v)
+                    if not re.match(r'\s+\.(text|section)\b', l)]     # linkage, not code
+            out.setdefault(short, []).append((f, body))
+    return out
+
+
+def cmd_pool(rev, files):
+    A, B = _pooled(_tree(rev), rev, files), _pooled(ROOT, 'work', files)
+    bad = 0
+    for k in sorted(set(A) | set(B)):
+        a, b = A.get(k, []), B.get(k, [])
+        same = bool(a and b) and all(x[1] == a[0][1] for x in a + b)
+        bad += not same
+        print(f'{k:28s} {rev}: {",".join(f for f, _ in a) or "-":22s} work: '
+              f'{",".join(f for f, _ in b) or "-":18s} {"same" if same else "DIFFERENT"}')
+    return 1 if bad else 0
+
+
+def cmd_diff(rev, files):
+    base = assemble(_tree(rev), rev, files)
     work = assemble(ROOT, 'work', files)
     tot = [0, 0, 0, 0]
     for f in sorted(work):
@@ -184,5 +216,7 @@ if __name__ == '__main__':
         cmd_waits(sys.argv[2:])
     elif len(sys.argv) >= 3 and sys.argv[1] == 'diff':
         sys.exit(cmd_diff(sys.argv[2], sys.argv[3:]))
+    elif len(sys.argv) >= 4 and sys.argv[1] == 'pool':
+        sys.exit(cmd_pool(sys.argv[2], sys.argv[3:]))
     else:
         raise SystemExit(__doc__)

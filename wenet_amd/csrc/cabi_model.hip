@@ -1,0 +1,662 @@
+// C ABI (include/wenet_amd.h), handle life cycle: weight ingestion into the shared model block
+// (ModelData, model_state.h), create / clone / destroy, operand precision, the encode gate,
+// profiling, debug and tuning switches.
+#include "model_state.h"
+
+namespace wn {
+namespace {
+
+// ---------------------------------------------------------------------------
+// weight ingestion
+struct HostStage {
+  std::vector<float> data;
+  std::map<std::string, std::pair<size_t, size_t>> at;  // name -> (offset, n)
+  void add(const std::string& name, const float* p, size_t n) {
+    size_t o = (data.size() + 63) / 64 * 64;
+    data.resize(o + n);
+    memcpy(data.data() + o, p, n * sizeof(float));
+    at[name] = {o, n};
+  }
+  float* alloc(const std::string& name, size_t n) {
+    size_t o = (data.size() + 63) / 64 * 64;
+    data.resize(o + n, 0.f);
+    at[name] = {o, n};
+    return data.data() + o;  // valid until the next add/alloc
+  }
+};
+
+struct Src {
+  std::map<std::string, std::pair<const float*, int64_t>> t;
+  const float* get(const std::string& n, int64_t numel) const {
+    auto it = t.find(n);
+    if (it == t.end()) { set_error("missing weight: " + n); return nullptr; }
+    if (numel >= 0 && it->second.second != numel) {
+      set_error("weight " + n + " has " + std::to_string(it->second.second) +
+                " elements, expected " + std::to_string(numel));
+      return nullptr;
+    }
+    return it->second.first;
+  }
+  bool has(const std::string& n) const { return t.count(n) != 0; }
+};
+
+#define WN_GET(var, name, numel)                 \
+  const float* var = src.get((name), (numel));   \
+  if (!var) return -3;
+
+int stage_linear(const Src& src, HostStage& hs, const std::string& pfx, int out,
+                 int in, bool bias = true) {
+  WN_GET(w, pfx + ".weight", (int64_t)out * in);
+  hs.add(pfx + ".weight", w, (size_t)out * in);
+  if (bias) {
+    WN_GET(b, pfx + ".bias", out);
+    hs.add(pfx + ".bias", b, out);
+  }
+  return 0;
+}
+int stage_norm(const Src& src, HostStage& hs, const std::string& pfx, int n) {
+  WN_GET(w, pfx + ".weight", n);
+  WN_GET(b, pfx + ".bias", n);
+  hs.add(pfx + ".weight", w, n);
+  hs.add(pfx + ".bias", b, n);
+  return 0;
+}
+// fuse several Linear layers along the output dimension
+int stage_fused(const Src& src, HostStage& hs, const std::string& name,
+                const std::vector<std::string>& parts, int out_each, int in) {
+  std::vector<float> w((size_t)parts.size() * out_each * in),
+      b((size_t)parts.size() * out_each);
+  for (size_t i = 0; i < parts.size(); ++i) {
+    WN_GET(pw, parts[i] + ".weight", (int64_t)out_each * in);
+    WN_GET(pb, parts[i] + ".bias", out_each);
+    memcpy(w.data() + i * out_each * in, pw, sizeof(float) * out_each * in);
+    memcpy(b.data() + i * out_each, pb, sizeof(float) * out_each);
+  }
+  hs.add(name + ".weight", w.data(), w.size());
+  hs.add(name + ".bias", b.data(), b.size());
+  return 0;
+}
+
+int stage_decoder(const Src& src, HostStage& hs, const std::string& pfx,
+                  int nlayers, const wn_config& c) {
+  const int d = c.d_model, V = c.vocab;
+  WN_GET(emb, pfx + ".embed.0.weight", (int64_t)V * d);
+  hs.add(pfx + ".embed", emb, (size_t)V * d);
+  WN_TRY(stage_norm(src, hs, pfx + ".after_norm", d));
+  WN_TRY(stage_linear(src, hs, pfx + ".output_layer", V, d));
+  for (int j = 0; j < nlayers; ++j) {
+    const std::string p = pfx + ".decoders." + std::to_string(j);
+    WN_TRY(stage_fused(src, hs, p + ".self_qkv",
+                       {p + ".self_attn.linear_q", p + ".self_attn.linear_k",
+                        p + ".self_attn.linear_v"}, d, d));
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d));
+    WN_TRY(stage_linear(src, hs, p + ".src_attn.linear_q", d, d));
+    WN_TRY(stage_fused(src, hs, p + ".src_kv",
+                       {p + ".src_attn.linear_k", p + ".src_attn.linear_v"}, d,
+                       d));
+    WN_TRY(stage_linear(src, hs, p + ".src_attn.linear_out", d, d));
+    WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_1", c.dec_ffn_dim, d));
+    WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_2", d, c.dec_ffn_dim));
+    for (const char* n : {"norm1", "norm2", "norm3"})
+      WN_TRY(stage_norm(src, hs, p + "." + n, d));
+  }
+  return 0;
+}
+
+}  // namespace
+}  // namespace wn
+
+// ===========================================================================
+extern "C" {
+
+const char* wn_last_error(void) { return last_error_cstr(); }
+const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
+
+int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
+                    int32_t n_weights, int32_t device, wn_model** out) {
+  WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
+  const wn_config& c = *cfg;
+  WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && c.d_model / c.n_heads == 64,
+           "d_model / n_heads must be 64 (all reference Conformer configs)");
+  WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
+           "decoder head dim must be 64");
+  WN_CHECK(c.ffn_dim % 32 == 0 && c.feat_dim >= 7 && c.feat_dim <= 128,
+           "unsupported ffn_dim / feat_dim");
+  const bool tf = c.encoder_type == 1;
+  WN_CHECK(c.encoder_type == 0 || c.encoder_type == 1, "unknown encoder_type");
+  WN_CHECK(tf ? c.input_layer == 1 : c.input_layer == 0,
+           "supported pairs: conformer + conv2d, transformer + conv1d2");
+  WN_CHECK(tf || (c.cnn_kernel >= 1 && (c.causal || c.cnn_kernel % 2 == 1)),
+           "cnn_module_kernel must be odd for a non-causal conv module");
+  WN_HIP(hipSetDevice(device));
+  std::unique_ptr<wn_model> m(new wn_model());
+  m->cfg = c;
+  m->device = device;
+  // the block this call fills; the handle (and every clone of it) sees it as const
+  const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
+  m->data = data;
+  ModelData& W = *data;
+  Src src;
+  for (int i = 0; i < n_weights; ++i)
+    src.t[weights[i].name] = {weights[i].data, weights[i].numel};
+
+  const int d = c.d_model, F = c.ffn_dim, V = c.vocab, K = c.cnn_kernel;
+  const int F2 = m->F2();
+  HostStage hs;
+  if (c.has_cmvn) {
+    WN_GET(mean, "encoder.global_cmvn.mean", c.feat_dim);
+    WN_GET(istd, "encoder.global_cmvn.istd", c.feat_dim);
+    hs.add("cmvn.mean", mean, c.feat_dim);
+    hs.add("cmvn.istd", istd, c.feat_dim);
+  }
+  const int Fin = c.feat_dim;
+  const int K1 = cdiv(3 * Fin, 32) * 32;  // conv1d K, padded with zero weights
+  if (tf) {
+    // Conv1d (n, c, tap) -> [n][tap * C + c] (the taps of one output frame are
+    // three consecutive channels-last input rows)
+    WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)d * Fin * 3);
+    WN_GET(b0, "encoder.embed.conv.0.bias", d);
+    float* t = hs.alloc("tconv1.w", (size_t)d * K1);
+    for (int n = 0; n < d; ++n)
+      for (int ch = 0; ch < Fin; ++ch)
+        for (int k = 0; k < 3; ++k)
+          t[(size_t)n * K1 + (size_t)k * Fin + ch] = w0[((size_t)n * Fin + ch) * 3 + k];
+    hs.add("tconv1.b", b0, d);
+    WN_GET(w2, "encoder.embed.conv.2.weight", (int64_t)d * d * 3);
+    WN_GET(b2, "encoder.embed.conv.2.bias", d);
+    t = hs.alloc("tconv2.w", (size_t)d * 3 * d);
+    for (int n = 0; n < d; ++n)
+      for (int ch = 0; ch < d; ++ch)
+        for (int k = 0; k < 3; ++k)
+          t[(size_t)n * 3 * d + (size_t)k * d + ch] = w2[((size_t)n * d + ch) * 3 + k];
+    hs.add("tconv2.b", b2, d);
+  } else {  // conv1 (d,1,3,3) -> [tap][c]
+    WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)d * 9);
+    WN_GET(b0, "encoder.embed.conv.0.bias", d);
+    float* t = hs.alloc("conv1.w", (size_t)9 * d);
+    for (int ch = 0; ch < d; ++ch)
+      for (int k = 0; k < 9; ++k) t[k * d + ch] = w0[ch * 9 + k];
+    hs.add("conv1.b", b0, d);
+    // conv2 (n, c, ky, kx) -> [n][(ky*3+kx)*d + c]
+    WN_GET(w2, "encoder.embed.conv.2.weight", (int64_t)d * d * 9);
+    WN_GET(b2, "encoder.embed.conv.2.bias", d);
+    t = hs.alloc("conv2.w", (size_t)d * 9 * d);
+    for (int n = 0; n < d; ++n)
+      for (int ch = 0; ch < d; ++ch)
+        for (int k = 0; k < 9; ++k)
+          t[(size_t)n * 9 * d + (size_t)k * d + ch] =
+              w2[((size_t)n * d + ch) * 9 + k];
+    hs.add("conv2.b", b2, d);
+    // out Linear(d*F2 -> d): input index c*F2+f  ->  f*d+c
+    WN_GET(wo, "encoder.embed.out.0.weight", (int64_t)d * d * F2);
+    WN_GET(bo, "encoder.embed.out.0.bias", d);
+    t = hs.alloc("sub_out.w", (size_t)d * d * F2);
+    for (int n = 0; n < d; ++n)
+      for (int ch = 0; ch < d; ++ch)
+        for (int f = 0; f < F2; ++f)
+          t[(size_t)n * d * F2 + (size_t)f * d + ch] =
+              wo[(size_t)n * d * F2 + (size_t)ch * F2 + f];
+    hs.add("sub_out.b", bo, d);
+  }
+  {  // positional table: the `pe` buffer (embedding.py:47-56)
+    float* t = hs.alloc("pe", (size_t)c.max_pos * d);
+    WN_CHECK(!tf || src.has("encoder.embed.pos_enc.pe"),
+             "transformer encoder: encoder.embed.pos_enc.pe is required");
+    if (src.has("encoder.embed.pos_enc.pe")) {
+      WN_GET(pe, "encoder.embed.pos_enc.pe", (int64_t)c.max_pos * d);
+      memcpy(t, pe, sizeof(float) * c.max_pos * d);
+    } else {
+      for (int pos = 0; pos < c.max_pos; ++pos)
+        for (int i = 0; i < d; i += 2) {
+          const float div = expf((float)i * -(logf(10000.0f) / (float)d));
+          t[(size_t)pos * d + i] = sinf((float)pos * div);
+          t[(size_t)pos * d + i + 1] = cosf((float)pos * div);
+        }
+    }
+  }
+  // ---- fbank tables (runtime/core/frontend/fbank.h:91-163) -----------------
+  std::vector<int> mel_start(c.feat_dim), mel_len(c.feat_dim), mel_off(c.feat_dim);
+  {
+    float* win = hs.alloc("fbank.window", 400);
+    const double a = 2.0 * M_PI / 399.0;
+    for (int i = 0; i < 400; ++i) win[i] = (float)pow(0.5 - 0.5 * cos(a * i), 0.85);
+    float* tw = hs.alloc("fbank.twiddle", 512);
+    for (int k = 0; k < 256; ++k) {
+      tw[2 * k] = (float)cos(2.0 * M_PI * k / 512.0);
+      tw[2 * k + 1] = (float)-sin(2.0 * M_PI * k / 512.0);
+    }
+    auto mel = [](float f) { return 1127.0f * logf(1.0f + f / 700.0f); };
+    const int nbins = c.feat_dim, nfft_bins = 256;
+    const float bin_w = 16000.0f / 512.0f;
+    const float mlo = mel(20.0f), mhi = mel(8000.0f);
+    const float delta = (mhi - mlo) / (float)(nbins + 1);
+    std::vector<float> wts;
+    for (int b = 0; b < nbins; ++b) {
+      const float left = mlo + b * delta, center = mlo + (b + 1) * delta,
+                  right = mlo + (b + 2) * delta;
+      int first = -1, last = -1;
+      std::vector<float> row(nfft_bins, 0.f);
+      for (int i = 0; i < nfft_bins; ++i) {
+        const float mf = mel(bin_w * i);
+        if (mf > left && mf < right) {
+          row[i] = mf <= center ? (mf - left) / (center - left)
+                                : (right - mf) / (right - center);
+          if (first < 0) first = i;
+          last = i;
+        }
+      }
+      if (first < 0) { W.fbank_ok = false; first = last = 0; }  // e.g. 128 bins
+      mel_start[b] = first; mel_len[b] = last + 1 - first; mel_off[b] = (int)wts.size();
+      for (int i = first; i <= last; ++i) wts.push_back(row[i]);
+    }
+    hs.add("fbank.mel_w", wts.data(), wts.size());
+  }
+  WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));
+  const bool has_ctc = src.has("ctc.ctc_lo.weight");
+  if (has_ctc) WN_TRY(stage_linear(src, hs, "ctc.ctc_lo", V, d));
+  for (int i = 0; tf && i < c.n_layers; ++i) {
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    WN_TRY(stage_norm(src, hs, p + ".norm1", d));
+    WN_TRY(stage_norm(src, hs, p + ".norm2", d));
+    {  // fused QKV; Whisper's linear_k has no bias (attention.py:29-75)
+      std::vector<float> w((size_t)3 * d * d), b((size_t)3 * d, 0.f);
+      const char* parts[3] = {"linear_q", "linear_k", "linear_v"};
+      for (int j = 0; j < 3; ++j) {
+        const std::string q = p + ".self_attn." + parts[j];
+        WN_GET(pw, q + ".weight", (int64_t)d * d);
+        memcpy(w.data() + (size_t)j * d * d, pw, sizeof(float) * d * d);
+        if (j != 1 || c.key_bias) {
+          WN_GET(pb, q + ".bias", d);
+          memcpy(b.data() + (size_t)j * d, pb, sizeof(float) * d);
+        }
+      }
+      hs.add(p + ".qkv.weight", w.data(), w.size());
+      hs.add(p + ".qkv.bias", b.data(), b.size());
+    }
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d));
+    WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_1", F, d));
+    WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_2", d, F));
+  }
+  for (int i = 0; !tf && i < c.n_layers; ++i) {
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
+                          "norm_final"})
+      WN_TRY(stage_norm(src, hs, p + "." + n, d));
+    if (c.cnn_norm == 0) {
+      WN_TRY(stage_norm(src, hs, p + ".conv_module.norm", d));
+    } else {
+      // eval-mode BatchNorm1d (convolution.py:77-81,139-143) as a per-channel
+      // affine: y = x * scale + shift, scale = w / sqrt(running_var + eps),
+      // shift = b - running_mean * scale; staged in the norm's weight / bias slots
+      const std::string q = p + ".conv_module.norm";
+      WN_GET(bw, q + ".weight", d);
+      WN_GET(bb, q + ".bias", d);
+      WN_GET(bm, q + ".running_mean", d);
+      WN_GET(bv, q + ".running_var", d);
+      std::vector<float> sc(d), sh(d);
+      for (int ch = 0; ch < d; ++ch) {
+        const float inv = 1.0f / sqrtf(bv[ch] + c.norm_eps);
+        sc[ch] = bw[ch] * inv;
+        sh[ch] = bb[ch] - bm[ch] * sc[ch];
+      }
+      hs.add(q + ".weight", sc.data(), sc.size());
+      hs.add(q + ".bias", sh.data(), sh.size());
+    }
+    for (const char* ff : {"feed_forward_macaron", "feed_forward"}) {
+      WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_1", F, d));
+      WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_2", d, F));
+    }
+    WN_TRY(stage_fused(src, hs, p + ".qkv",
+                       {p + ".self_attn.linear_q", p + ".self_attn.linear_k",
+                        p + ".self_attn.linear_v"}, d, d));
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d));
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_pos", d, d, false));
+    WN_GET(bu, p + ".self_attn.pos_bias_u", d);
+    WN_GET(bv, p + ".self_attn.pos_bias_v", d);
+    hs.add(p + ".pos_bias_u", bu, d);
+    hs.add(p + ".pos_bias_v", bv, d);
+    {  // pointwise_conv1 (2d, d, 1): rows permuted per 64 as [32 a | 32 gate]
+      WN_GET(w1, p + ".conv_module.pointwise_conv1.weight", (int64_t)2 * d * d);
+      WN_GET(b1, p + ".conv_module.pointwise_conv1.bias", 2 * d);
+      std::vector<float> w((size_t)2 * d * d), b(2 * d), cp(d);
+      for (int g = 0; g < d / 32; ++g)
+        for (int j = 0; j < 32; ++j) {
+          const int ch = g * 32 + j;
+          memcpy(&w[(size_t)(g * 64 + j) * d], &w1[(size_t)ch * d],
+                 sizeof(float) * d);
+          memcpy(&w[(size_t)(g * 64 + 32 + j) * d], &w1[(size_t)(d + ch) * d],
+                 sizeof(float) * d);
+          b[g * 64 + j] = b1[ch];
+          b[g * 64 + 32 + j] = b1[d + ch];
+          // GLU of a zero input frame: bias_a * sigmoid(bias_gate)
+          cp[ch] = b1[ch] * (1.0f / (1.0f + expf(-b1[d + ch])));
+        }
+      hs.add(p + ".pw1.weight", w.data(), w.size());
+      hs.add(p + ".pw1.bias", b.data(), b.size());
+      hs.add(p + ".cpad", cp.data(), cp.size());
+    }
+    {  // depthwise (d,1,K) -> [K][d]
+      WN_GET(wd, p + ".conv_module.depthwise_conv.weight", (int64_t)d * K);
+      WN_GET(bd, p + ".conv_module.depthwise_conv.bias", d);
+      std::vector<float> w((size_t)K * d);
+      for (int ch = 0; ch < d; ++ch)
+        for (int k = 0; k < K; ++k) w[(size_t)k * d + ch] = wd[(size_t)ch * K + k];
+      hs.add(p + ".dw.weight", w.data(), w.size());
+      hs.add(p + ".dw.bias", bd, d);
+    }
+    WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d));
+  }
+  const bool has_dec = c.dec_layers > 0;
+  if (has_dec) {
+    if (c.bidirectional) {
+      WN_TRY(stage_decoder(src, hs, "decoder.left_decoder", c.dec_layers, c));
+      if (c.dec_r_layers > 0)
+        WN_TRY(stage_decoder(src, hs, "decoder.right_decoder", c.dec_r_layers, c));
+    } else {
+      WN_TRY(stage_decoder(src, hs, "decoder", c.dec_layers, c));
+    }
+  }
+  // ---- upload ---------------------------------------------------------------
+  WN_TRY(W.weights.ensure(hs.data.size() * sizeof(float)));
+  W.n_weight_elems = (int64_t)hs.data.size();
+  WN_HIP(hipMemcpy(W.weights.p, hs.data.data(), hs.data.size() * sizeof(float),
+                   hipMemcpyHostToDevice));
+  const float* base = W.weights.as<float>();
+  for (auto& kv : hs.at) W.w[kv.first] = base + kv.second.first;
+  auto P = [&](const std::string& n) { return W.w.at(n); };
+  auto LIN = [&](const std::string& p, int o, int i, bool bias = true) {
+    Linear l; l.w = P(p + ".weight"); l.b = bias ? P(p + ".bias") : nullptr;
+    l.out = o; l.in = i; return l;
+  };
+  auto NORM = [&](const std::string& p) {
+    Norm n; n.w = P(p + ".weight"); n.b = P(p + ".bias"); return n;
+  };
+  if (c.has_cmvn) { W.cmvn_mean = P("cmvn.mean"); W.cmvn_istd = P("cmvn.istd"); }
+  if (tf) {
+    W.tconv1.w = P("tconv1.w"); W.tconv1.b = P("tconv1.b");
+    W.tconv1.out = d; W.tconv1.in = K1;
+    W.tconv2.w = P("tconv2.w"); W.tconv2.b = P("tconv2.b");
+    W.tconv2.out = d; W.tconv2.in = 3 * d;
+  } else {
+    W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
+    W.conv2.w = P("conv2.w"); W.conv2.b = P("conv2.b");
+    W.conv2.out = d; W.conv2.in = 9 * d;
+    W.sub_out.w = P("sub_out.w"); W.sub_out.b = P("sub_out.b");
+    W.sub_out.out = d; W.sub_out.in = d * F2;
+  }
+  W.pe = P("pe");
+  W.fb_window = P("fbank.window"); W.fb_twiddle = P("fbank.twiddle");
+  W.fb_mel_w = P("fbank.mel_w");
+  {
+    std::vector<int> tab;
+    tab.insert(tab.end(), mel_start.begin(), mel_start.end());
+    tab.insert(tab.end(), mel_len.begin(), mel_len.end());
+    tab.insert(tab.end(), mel_off.begin(), mel_off.end());
+    WN_TRY(W.fb_tab_i.ensure(tab.size() * sizeof(int)));
+    WN_HIP(hipMemcpy(W.fb_tab_i.p, tab.data(), tab.size() * sizeof(int),
+                     hipMemcpyHostToDevice));
+  }
+  W.after_norm = NORM("encoder.after_norm");
+  if (has_ctc) W.ctc = LIN("ctc.ctc_lo", V, d);
+  if (tf) {
+    W.tf_layers.resize(c.n_layers);
+    for (int i = 0; i < c.n_layers; ++i) {
+      const std::string p = "encoder.encoders." + std::to_string(i);
+      TfLayer& L = W.tf_layers[i];
+      L.n1 = NORM(p + ".norm1"); L.n2 = NORM(p + ".norm2");
+      L.qkv = LIN(p + ".qkv", 3 * d, d);
+      L.out = LIN(p + ".self_attn.linear_out", d, d);
+      L.ff1 = LIN(p + ".feed_forward.w_1", F, d);
+      L.ff2 = LIN(p + ".feed_forward.w_2", d, F);
+    }
+  } else {
+    W.layers.resize(c.n_layers);
+    WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
+  }
+  for (int i = 0; !tf && i < c.n_layers; ++i) {
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    EncLayer& L = W.layers[i];
+    L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
+    L.norm_mha = NORM(p + ".norm_mha");
+    L.norm_conv = NORM(p + ".norm_conv");
+    L.norm_ff = NORM(p + ".norm_ff");
+    L.norm_final = NORM(p + ".norm_final");
+    L.conv_norm = NORM(p + ".conv_module.norm");
+    L.ffm1 = LIN(p + ".feed_forward_macaron.w_1", F, d);
+    L.ffm2 = LIN(p + ".feed_forward_macaron.w_2", d, F);
+    L.ff1 = LIN(p + ".feed_forward.w_1", F, d);
+    L.ff2 = LIN(p + ".feed_forward.w_2", d, F);
+    L.qkv = LIN(p + ".qkv", 3 * d, d);
+    L.out = LIN(p + ".self_attn.linear_out", d, d);
+    L.pw1 = LIN(p + ".pw1", 2 * d, d);
+    L.pw2 = LIN(p + ".conv_module.pointwise_conv2", d, d);
+    L.bias_u = P(p + ".pos_bias_u");
+    L.bias_v = P(p + ".pos_bias_v");
+    L.pos_w = P(p + ".self_attn.linear_pos.weight");
+    L.dw_wt = P(p + ".dw.weight");
+    L.dw_b = P(p + ".dw.bias");
+    L.cpad = P(p + ".cpad");
+    // p = linear_pos(pos_emb) depends on weights only (attention.py:395-396):
+    // project the whole table once instead of per batch and layer.
+    L.pos_tab = W.pos_tabs.as<float>() + (size_t)i * c.max_pos * d;
+    Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = d; lp.in = d;
+    WN_TRY(linear(lp, W.pe, d, L.pos_tab, d, c.max_pos, 0));
+  }
+  auto DEC = [&](Decoder& D, const std::string& pfx, int nl) {
+    D.embed = P(pfx + ".embed");
+    D.pe = W.pe;  // same sinusoid table (embedding.py:47-56), same d_model
+    D.after = NORM(pfx + ".after_norm");
+    D.out = LIN(pfx + ".output_layer", V, d);
+    D.layers.resize(nl);
+    for (int j = 0; j < nl; ++j) {
+      const std::string p = pfx + ".decoders." + std::to_string(j);
+      DecLayer& L = D.layers[j];
+      L.n1 = NORM(p + ".norm1"); L.n2 = NORM(p + ".norm2"); L.n3 = NORM(p + ".norm3");
+      L.self_qkv = LIN(p + ".self_qkv", 3 * d, d);
+      L.self_out = LIN(p + ".self_attn.linear_out", d, d);
+      L.src_q = LIN(p + ".src_attn.linear_q", d, d);
+      L.src_kv = LIN(p + ".src_kv", 2 * d, d);
+      L.src_out = LIN(p + ".src_attn.linear_out", d, d);
+      L.ff1 = LIN(p + ".feed_forward.w_1", c.dec_ffn_dim, d);
+      L.ff2 = LIN(p + ".feed_forward.w_2", d, c.dec_ffn_dim);
+    }
+  };
+  if (has_dec) {
+    if (c.bidirectional) {
+      DEC(W.left, "decoder.left_decoder", c.dec_layers);
+      if (c.dec_r_layers > 0) DEC(W.right, "decoder.right_decoder", c.dec_r_layers);
+    } else {
+      DEC(W.left, "decoder", c.dec_layers);
+    }
+  }
+  WN_TRY(build_x6_images(c, W));
+  WN_HIP(hipDeviceSynchronize());
+  *out = m.release();
+  return 0;
+}
+
+void wn_model_destroy(wn_model* m) { delete m; }
+
+int wn_model_clone(const wn_model* src, wn_model** out) {
+  WN_CHECK(src && out, "wn_model_clone: null argument");
+  WN_HIP(hipSetDevice(src->device));
+  std::unique_ptr<wn_model> m(new wn_model());
+  m->data = src->data;      // weights, views and tables are read-only: shared
+  m->cfg = src->cfg;
+  m->device = src->device;
+  m->prec = src->prec;
+  m->fp8_ffn = src->fp8_ffn;
+  m->tune_ovr = src->tune_ovr;
+  m->ctx_buf = src->ctx_buf; m->ctx = src->ctx;
+  *out = m.release();
+  return 0;
+}
+
+int wn_model_set_precision(wn_model* m, int32_t precision) {
+  WN_CHECK(m, "wn_model_set_precision: null model");
+  WN_CHECK(precision == PREC_F32 || precision == PREC_BF16 || precision == PREC_FP8,
+           "wn_model_set_precision: 0 (fp32), 1 (bf16 operands, fp32 accumulate) or 2 "
+           "(bf16 + MXFP8 feed-forward GEMMs)");
+  const ModelData& W = *m->data;
+  // the images belong to the model block: whichever handle asks first builds them, every
+  // clone (made before or after) reads the same ones
+  std::lock_guard<std::mutex> lock(W.lazy);
+  if (precision != PREC_F32 && !W.weights_bf16.p && W.n_weight_elems > 0) {
+    // one-time bf16 image of the weight slab for the bf16-storage GEMMs (same
+    // element offsets)
+    WN_HIP(hipSetDevice(m->device));
+    DevBuf img;
+    WN_TRY(img.ensure((size_t)W.n_weight_elems * 2));
+    WN_TRY(convert_f32_to_bf16(W.weights.as<float>(), img.p, W.n_weight_elems, nullptr));
+    WN_HIP(hipStreamSynchronize(nullptr));
+    W.weights_bf16.swap(img);
+  }
+  if (precision == PREC_FP8 && !W.mx_built) {
+    // one-time MXFP8 images of the feed-forward weights (w_1, w_2 of every encoder
+    // layer): e4m3 [N][K] + block scales [K/128][N]
+    WN_HIP(hipSetDevice(m->device));
+    std::vector<const Linear*> ws;
+    for (const auto& L : W.layers) { ws.push_back(&L.ffm1); ws.push_back(&L.ffm2);
+                                     ws.push_back(&L.ff1); ws.push_back(&L.ff2); }
+    for (const auto& L : W.tf_layers) { ws.push_back(&L.ff1); ws.push_back(&L.ff2); }
+    size_t bytes = 0;
+    for (const Linear* l : ws)
+      if (l->w && l->in % 128 == 0)
+        bytes += ((size_t)l->out * l->in + 255) / 256 * 256 + (size_t)(l->in / 128) * l->out * 4;
+    DevBuf buf;
+    std::map<const float*, ModelData::MxW> at;
+    if (bytes > 0) {
+      WN_TRY(buf.ensure(bytes));
+      char* p = buf.as<char>();
+      for (const Linear* l : ws) {
+        if (!l->w || l->in % 128 != 0) continue;
+        char* q = p;
+        p += ((size_t)l->out * l->in + 255) / 256 * 256;
+        unsigned* sc = reinterpret_cast<unsigned*>(p);
+        p += (size_t)(l->in / 128) * l->out * 4;
+        WN_TRY(mx_quantize(l->w, l->in, l->out, l->in, q, sc, l->out, nullptr));
+        at[l->w] = ModelData::MxW{q, sc};
+      }
+      WN_HIP(hipStreamSynchronize(nullptr));
+    }
+    W.weights_mx.swap(buf);
+    W.mx_at.swap(at);
+    W.mx_built = true;
+  }
+  m->prec = precision == PREC_F32 ? PREC_F32 : PREC_BF16;
+  m->fp8_ffn = precision == PREC_FP8;
+  return 0;
+}
+
+int32_t wn_model_get_precision(const wn_model* m) {
+  return m ? (m->fp8_ffn ? (int32_t)PREC_FP8 : m->prec) : -1;
+}
+
+int32_t wn_batch_size(const wn_model* m) { return m ? m->B : -1; }
+
+int wn_model_set_encode_gate(wn_model* m, void* event) {
+  WN_CHECK(m, "wn_model_set_encode_gate: null handle");
+  m->enc_gate = (hipEvent_t)event;
+  return 0;
+}
+
+int wn_profile_enable(wn_model* m, int32_t on) {
+  WN_CHECK(m, "wn_profile_enable: null model");
+  m->prof_on = on != 0;
+  m->prof_stride = on > 1 ? (unsigned)on : 6u;   // on = 1: every 6th launch; on = N > 1: every N-th
+  m->prof_used = 0;
+  m->prof_flops = 0.0;
+  return 0;
+}
+
+const char* wn_profile_kernel_name(const wn_model* m) {
+  return m ? m->prof_kernel : "";
+}
+
+int32_t wn_profile_ffn_split(const wn_model* m) { return m ? m->prof_split : 0; }
+
+int wn_profile_gemm_clocks(uint64_t* out64) {
+  WN_CHECK(out64, "wn_profile_gemm_clocks: null output");
+  if (wn::tune().x6_probe == 8)   // the row-block kernel's phase stamps (tools/x6r_clocks.py)
+    return wn::gemm_x6r_clocks(reinterpret_cast<unsigned long long*>(out64));
+  if (wn::tune().lp_probe & 4)   // the pipelined bf16 / MXFP8 kernel stamped last (tools/lp_clocks.py)
+    return wn::gemm_lp_clocks(reinterpret_cast<unsigned long long*>(out64));
+  return wn::gemm_x6_clocks(reinterpret_cast<unsigned long long*>(out64));
+}
+
+int wn_profile_ffn_clocks(uint64_t* out64) {
+  WN_CHECK(out64, "wn_profile_ffn_clocks: null output");
+  return wn::ffn_x6f_clocks(reinterpret_cast<unsigned long long*>(out64));
+}
+
+int wn_profile_collect(wn_model* m, int32_t* n_launches, double* total_ms,
+                       double* total_flops) {
+  WN_CHECK(m && n_launches && total_ms && total_flops, "wn_profile_collect: null");
+  double ms = 0.0;
+  for (size_t i = 0; i + 1 < m->prof_used; i += 2) {
+    WN_HIP(hipEventSynchronize(m->prof_ev[i + 1]));
+    float t = 0.f;
+    WN_HIP(hipEventElapsedTime(&t, m->prof_ev[i], m->prof_ev[i + 1]));
+    ms += t;
+  }
+  *n_launches = (int32_t)(m->prof_used / 2);
+  *total_ms = ms;
+  *total_flops = m->prof_flops;
+  m->prof_used = 0;
+  m->prof_flops = 0.0;
+  return 0;
+}
+
+int wn_debug_set(wn_model* m, const char* key, int32_t value) {
+  WN_CHECK(m && key, "wn_debug_set: null argument");
+  const std::string k(key);
+  if (k == "n_layers") m->dbg_layers = value;
+  else if (k == "skip_after_norm") m->dbg_skip_after_norm = value;
+  else { set_error("wn_debug_set: unknown key " + k); return -1; }
+  return 0;
+}
+
+int wn_tune_set(const char* key, int32_t value) {
+  WN_CHECK(key, "wn_tune_set: null key");
+  const std::string k(key);
+  int* f = tune_field(g_tune_default, k);
+  if (!f) { set_error("wn_tune_set: unknown key " + k); return -1; }
+  WN_CHECK(value != TUNE_INHERIT, "wn_tune_set: INT32_MIN is the per-handle 'inherit' marker");
+  if (tune_check(k, value, "wn_tune_set") != 0) return -1;
+  *f = value;
+  return 0;
+}
+
+int wn_model_tune_set(wn_model* m, const char* key, int32_t value) {
+  WN_CHECK(m && key, "wn_model_tune_set: null argument");
+  WN_ENTER(m);
+  const std::string k(key);
+  int* f = tune_field(m->tune_ovr, k);
+  if (!f) { set_error("wn_model_tune_set: unknown key " + k); return -1; }
+  if (tune_check(k, value, "wn_model_tune_set") != 0) return -1;
+  *f = value;
+  return 0;
+}
+
+int wn_tune_get(const wn_model* m, const char* key, int32_t* value) {
+  WN_CHECK(key && value, "wn_tune_get: null argument");
+  const std::string k(key);
+  Tune eff = g_tune_default;
+  if (m) tune_resolve(m->tune_ovr, &eff);
+  const int* f = tune_field(eff, k);
+  if (!f) { set_error("wn_tune_get: unknown key " + k); return -1; }
+  *value = *f;
+  return 0;
+}
+
+int wn_workspace_create(int32_t device, wn_model** out) {
+  WN_CHECK(out, "wn_workspace_create: null argument");
+  WN_HIP(hipSetDevice(device));
+  wn_model* m = new wn_model();
+  memset(&m->cfg, 0, sizeof(m->cfg));
+  m->device = device;
+  *out = m;
+  return 0;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // Engine of libwenet_amd: the launch sequences of the feature -> encoder -> CTC-head path
 // (subsampling, Conformer / Transformer layers, streaming chunks), the GEMM routing
 // (v_mfma_f32 / six-product / bf16 / MXFP8 kernels) and the weight plane images.  The state
-// it works on is model_state.h; the C ABI over it is cabi.hip.
+// it works on is model_state.h; the C ABI over it is cabi_*.hip.
 #include <algorithm>
 #include "model_state.h"
 
@@ -13,7 +13,7 @@ const char* last_error_cstr() { return g_error.c_str(); }
 
 }  // namespace wn
 
-thread_local const std::map<const float*, wn_model::MxW>* t_mx = nullptr;
+thread_local const std::map<const float*, ModelData::MxW>* t_mx = nullptr;
 // plane images of the current model's weights and its activation-image scratch: linear()
 // routes the large fp32 GEMMs to the six-product kernel through them (gemm_x6.hip)
 thread_local const std::map<const float*, const void*>* t_x6 = nullptr;
@@ -169,7 +169,7 @@ int ffn_module(wn_model* m, const Norm& nrm, const Linear& w1, const Linear& w2,
   float* t1 = m->t1.as<float>();
   float* hb = m->hbuf.as<float>();
   bool mx = false;
-  const wn_model::MxW *q1 = nullptr, *q2 = nullptr;
+  const ModelData::MxW *q1 = nullptr, *q2 = nullptr;
   if (t_mx && h16 && !ln_done) {
     auto i1 = t_mx->find(w1.w), i2 = t_mx->find(w2.w);
     const int64_t t256 = (int64_t)cdiv(M, 256) * cdiv(std::min(w1.out, w2.out), 256);
@@ -223,13 +223,13 @@ int ffn_module(wn_model* m, const Norm& nrm, const Linear& w1, const Linear& w2,
 }
 
 // Plane images (gemm_x6.hip) of the encoder's feed-forward weights, once per model.
-int build_x6_images(wn_model* m) {
+int build_x6_images(const wn_config& cfg, ModelData& W) {
   std::vector<const Linear*> ws;
-  for (const auto& L : m->layers) { ws.push_back(&L.ffm1); ws.push_back(&L.ffm2);
+  for (const auto& L : W.layers) { ws.push_back(&L.ffm1); ws.push_back(&L.ffm2);
                                     ws.push_back(&L.ff1); ws.push_back(&L.ff2);
                                     ws.push_back(&L.qkv); ws.push_back(&L.out);
                                     ws.push_back(&L.pw2); ws.push_back(&L.pw1); }
-  for (const Decoder* D : {&m->left, &m->right})
+  for (const Decoder* D : {&W.left, &W.right})
     for (const auto& L : D->layers) {
       ws.push_back(&L.self_qkv); ws.push_back(&L.self_out); ws.push_back(&L.src_q);
       ws.push_back(&L.src_kv); ws.push_back(&L.src_out); ws.push_back(&L.ff1);
@@ -237,73 +237,63 @@ int build_x6_images(wn_model* m) {
     }
   // the Transformer encoder of the Whisper configuration (round 3): its fp32 mode goes through
   // linear() -> split pass + six-product GEMM like every other large fp32 GEMM
-  for (const auto& L : m->tf_layers) { ws.push_back(&L.qkv); ws.push_back(&L.out);
+  for (const auto& L : W.tf_layers) { ws.push_back(&L.qkv); ws.push_back(&L.out);
                                        ws.push_back(&L.ff1); ws.push_back(&L.ff2); }
-  if (m->conv2.w) ws.push_back(&m->conv2);   // [d][(ky*3+kx)*d + c]: 16-channel k blocks per tap
-  if (m->sub_out.w) ws.push_back(&m->sub_out);   // K slices straight from conv2's fp32 output
+  if (W.conv2.w) ws.push_back(&W.conv2);   // [d][(ky*3+kx)*d + c]: 16-channel k blocks per tap
+  if (W.sub_out.w) ws.push_back(&W.sub_out);   // K slices straight from conv2's fp32 output
   std::vector<const Linear*> vocab;          // V rows; the image pads them to a multiple of 32
-  if (m->ctc.w) vocab.push_back(&m->ctc);
-  for (const Decoder* D : {&m->left, &m->right})
+  if (W.ctc.w) vocab.push_back(&W.ctc);
+  for (const Decoder* D : {&W.left, &W.right})
     if (D->out.w) vocab.push_back(&D->out);
   for (const Linear* l : vocab) ws.push_back(l);
   size_t bytes = 0;
   for (const Linear* l : ws)
     if (l->w && l->in % 16 == 0) bytes += x6_bytes(l->out, l->in);
-  auto buf = std::make_shared<DevBuf>();
-  auto at = std::make_shared<std::map<const float*, const void*>>();
   if (bytes > 0) {
-    WN_TRY(buf->ensure(bytes));
-    char* p = buf->as<char>();
+    WN_TRY(W.weights_x6.ensure(bytes));
+    char* p = W.weights_x6.as<char>();
     for (const Linear* l : ws) {
-      if (!l->w || l->in % 16 != 0 || at->count(l->w)) continue;
+      if (!l->w || l->in % 16 != 0 || W.x6_at.count(l->w)) continue;
       WN_TRY(x6_split(l->w, l->out, l->in, l->in, p, nullptr));
-      (*at)[l->w] = p;
+      W.x6_at[l->w] = p;
       p += x6_bytes(l->out, l->in);
     }
   }
-  m->weights_x6 = buf;
-  m->x6_at = at;
   // fused six-product feed-forward module (ffn_x6f.hip, d_model 256): the second layer's image
   // with the k slots of a 16-unit block in the order a lane holds its hidden values
-  auto pbuf = std::make_shared<DevBuf>();
-  auto pat = std::make_shared<std::map<const float*, const void*>>();
-  if (m->cfg.d_model == 256) {
+  if (cfg.d_model == 256) {
     std::vector<const Linear*> w2s;
-    for (const auto& L : m->layers) { w2s.push_back(&L.ffm2); w2s.push_back(&L.ff2); }
+    for (const auto& L : W.layers) { w2s.push_back(&L.ffm2); w2s.push_back(&L.ff2); }
     size_t pbytes = 0;
     for (const Linear* l : w2s)
       if (l->w && l->in % 64 == 0 && l->out == 256) pbytes += x6_bytes(l->out, l->in);
     if (pbytes > 0) {
-      WN_TRY(pbuf->ensure(pbytes));
-      char* q = pbuf->as<char>();
+      WN_TRY(W.weights_x6p.ensure(pbytes));
+      char* q = W.weights_x6p.as<char>();
       for (const Linear* l : w2s) {
-        if (!l->w || l->in % 64 != 0 || l->out != 256 || pat->count(l->w)) continue;
+        if (!l->w || l->in % 64 != 0 || l->out != 256 || W.x6p_at.count(l->w)) continue;
         WN_TRY(x6_split_perm(l->w, l->out, l->in, l->in, q, nullptr));
-        (*pat)[l->w] = q;
+        W.x6p_at[l->w] = q;
         q += x6_bytes(l->out, l->in);
       }
     }
   }
-  m->weights_x6p = pbuf;
-  m->x6p_at = pat;
   // QKV projections of 4-head / d_model-256 encoders, rows regrouped per head (gemm_x6r.hip
   // epi 4: wave h of a row block owns [Q_h | K_h | V_h]): new row h 192 + part 64 + j = old row
   // part 256 + h 64 + j.  One fp32 staging copy, then the ordinary split
-  auto qbuf = std::make_shared<DevBuf>();
-  auto qat = std::make_shared<std::map<const float*, std::pair<const void*, const float*>>>();
-  if (m->cfg.d_model == 256 && m->cfg.n_heads == 4) {
+  if (cfg.d_model == 256 && cfg.n_heads == 4) {
     size_t n_q = 0;
-    for (const auto& L : m->layers)
+    for (const auto& L : W.layers)
       if (L.qkv.w && L.qkv.b && L.qkv.out == 768 && L.qkv.in == 256 && L.pos_tab) ++n_q;
     if (n_q > 0) {
       const size_t img = x6_bytes(768, 256), per = img + 768 * sizeof(float);
       DevBuf stage;
       WN_TRY(stage.ensure((size_t)768 * 256 * sizeof(float)));
-      WN_TRY(qbuf->ensure(n_q * per));
-      char* q = qbuf->as<char>();
-      for (const auto& L : m->layers) {
+      WN_TRY(W.weights_x6q.ensure(n_q * per));
+      char* q = W.weights_x6q.as<char>();
+      for (const auto& L : W.layers) {
         if (!(L.qkv.w && L.qkv.b && L.qkv.out == 768 && L.qkv.in == 256 && L.pos_tab) ||
-            qat->count(L.qkv.w))
+            W.x6q_at.count(L.qkv.w))
           continue;
         float* qb = reinterpret_cast<float*>(q + img);
         for (int h = 0; h < 4; ++h)
@@ -315,36 +305,30 @@ int build_x6_images(wn_model* m) {
                                   hipMemcpyDeviceToDevice, nullptr));
           }
         WN_TRY(x6_split(stage.as<float>(), 768, 256, 256, q, nullptr));
-        (*qat)[L.qkv.w] = {q, qb};
+        W.x6q_at[L.qkv.w] = {q, qb};
         q += per;
       }
       WN_HIP(hipStreamSynchronize(nullptr));   // `stage` goes away with this scope
     }
   }
-  m->weights_x6q = qbuf;
-  m->x6q_at = qat;
   // the six-product kernel stores 16-B pieces: the vocabulary-sized layers run with N = V
   // rounded up to 4 (the image rows past V are zero, their bias too) and their logits rows
   // get that pitch
-  auto b4 = std::make_shared<DevBuf>();
-  auto bmap = std::make_shared<std::map<const float*, const float*>>();
   size_t b4_floats = 0;
   for (const Linear* l : vocab)
     if (l->b && l->out % 4 != 0) b4_floats += (size_t)(l->out + 3) / 4 * 4;
   if (b4_floats > 0) {
-    WN_TRY(b4->ensure(b4_floats * sizeof(float)));
-    WN_HIP(hipMemsetAsync(b4->p, 0, b4_floats * sizeof(float), nullptr));
-    float* q = b4->as<float>();
+    WN_TRY(W.bias4_buf.ensure(b4_floats * sizeof(float)));
+    WN_HIP(hipMemsetAsync(W.bias4_buf.p, 0, b4_floats * sizeof(float), nullptr));
+    float* q = W.bias4_buf.as<float>();
     for (const Linear* l : vocab) {
-      if (!l->b || l->out % 4 == 0 || bmap->count(l->w)) continue;
+      if (!l->b || l->out % 4 == 0 || W.bias4.count(l->w)) continue;
       WN_HIP(hipMemcpyAsync(q, l->b, (size_t)l->out * sizeof(float), hipMemcpyDeviceToDevice,
                             nullptr));
-      (*bmap)[l->w] = q;
+      W.bias4[l->w] = q;
       q += (l->out + 3) / 4 * 4;
     }
   }
-  m->bias4_buf = b4;
-  m->bias4 = bmap;
   return 0;
 }
 
@@ -353,20 +337,19 @@ int build_x6_images(wn_model* m) {
 // 0, a padded bias), else linear().
 int vocab_linear(wn_model* m, const Linear& l, const float* A, int lda, float* C, int ldc,
                  int M, hipStream_t s) {
+  const ModelData& W = *m->data;
   const int V = l.out, V4 = (V + 3) / 4 * 4;
   WN_CHECK(ldc >= V4 && ldc % 4 == 0, "vocab_linear: pitch");
   const void* w6 = nullptr;
   const float* bias = l.b;
-  if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && tune().x6_linear != 0 && m->x6_at &&
+  if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && tune().x6_linear != 0 &&
       l.in % 16 == 0 && lda % 4 == 0 && M >= 512) {
-    auto it = m->x6_at->find(l.w);
-    if (it != m->x6_at->end()) w6 = it->second;
+    auto it = W.x6_at.find(l.w);
+    if (it != W.x6_at.end()) w6 = it->second;
     if (w6 && V != V4 && l.b) {     // ragged V: the padded copy of the bias, or no x6
       bias = nullptr;
-      if (m->bias4) {
-        auto ib = m->bias4->find(l.w);
-        if (ib != m->bias4->end()) bias = ib->second;
-      }
+      auto ib = W.bias4.find(l.w);
+      if (ib != W.bias4.end()) bias = ib->second;
       if (!bias) w6 = nullptr;
     }
   }
@@ -396,17 +379,18 @@ int ffn_x6_split(int M, int F) {
 // LN(x) as an X3 plane image: the producers of LN(x) ask before they decide to write that image
 // instead of fp32 rows (t1_image_for) -- ONE predicate, so producer and consumer cannot disagree.
 int ffn_x6_route(wn_model* m, const Linear& w1, const Linear& w2, int act) {
+  const ModelData& W = *m->data;
   const int d = m->cfg.d_model, M = m->rows, F = w1.out;
-  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || !m->x6_at || w1.out != w2.in ||
+  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || w1.out != w2.in ||
       !(d == 256 || d == 512) || F % 16 != 0)
     return 0;
   // batches under 512 rows: only the fused kernel (the tile-GEMM pair is all prologue and
   // epilogue there; 2 = tests force it)
   const bool small = M < 512 && tune().gemm_x6 != 2;
-  const bool fused_ok = tune().ffn_x6f != 0 && tune().x6_af32 == 0 && m->x6p_at &&
+  const bool fused_ok = tune().ffn_x6f != 0 && tune().x6_af32 == 0 &&
                         ffn_x6f_supported(M, d, F, act) && !(small && tune().ffn_x6f == 3);
-  if (m->x6_at->count(w1.w) == 0 || m->x6_at->count(w2.w) == 0) return 0;
-  const bool fused = fused_ok && m->x6p_at->count(w2.w) != 0;
+  if (W.x6_at.count(w1.w) == 0 || W.x6_at.count(w2.w) == 0) return 0;
+  const bool fused = fused_ok && W.x6p_at.count(w2.w) != 0;
   // small batches never take the tile-GEMM pair: the fused kernel or the v_mfma_f32 paths
   if (small) return fused ? 1 : 0;
   return fused ? 1 : 2;
@@ -422,6 +406,7 @@ void* t1_image_for(wn_model* m, const Linear& w1, const Linear& w2, int act) {
 }
 
 int ffn_x6_try(wn_model* m, const Linear& w1, const Linear& w2, int act, hipStream_t s) {
+  const ModelData& W = *m->data;
   const int d = m->cfg.d_model, M = m->rows, F = w1.out;
   const bool ximg = m->t1_img_ok;      // t1 exists ONLY as its plane image
   m->t1_img_ok = false;
@@ -434,11 +419,11 @@ int ffn_x6_try(wn_model* m, const Linear& w1, const Linear& w2, int act, hipStre
     }
     return 0;
   }
-  auto i1 = m->x6_at->find(w1.w), i2 = m->x6_at->find(w2.w);
+  auto i1 = W.x6_at.find(w1.w), i2 = W.x6_at.find(w2.w);
   static thread_local int tick = 0;
   if (route == 1) {
     // hidden tensor on chip (ffn_x6f.hip)
-    auto ip = m->x6p_at->find(w2.w);
+    auto ip = W.x6p_at.find(w2.w);
     {
       FfnX6Args a;
       a.S = ffn_x6f_split(M, F);
@@ -526,13 +511,14 @@ int ffn_x6_try(wn_model* m, const Linear& w1, const Linear& w2, int act, hipStre
 // Returns the slice count, 0 if the shape stays on linear(), < 0 on error.
 int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const float* A, int M,
                 hipStream_t s) {
+  const ModelData& W = *m->data;
   const int d = w1.in, F = w1.out;
-  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || tune().x6_linear == 0 || !m->x6_at ||
+  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || tune().x6_linear == 0 ||
       w1.out != w2.in || w2.out != d || !(d == 256 || d == 512) || F % 16 != 0 || M < 512 ||
       2.0 * M * (double)F * d < 1e8 * g_x6_linear_min)
     return 0;
-  auto i1 = m->x6_at->find(w1.w), i2 = m->x6_at->find(w2.w);
-  if (i1 == m->x6_at->end() || i2 == m->x6_at->end()) return 0;
+  auto i1 = W.x6_at.find(w1.w), i2 = W.x6_at.find(w2.w);
+  if (i1 == W.x6_at.end() || i2 == W.x6_at.end()) return 0;
   const int S = ffn_x6_split(M, F);
   if (m->ffn_part.ensure((size_t)S * M * d * sizeof(float)) != 0 ||
       m->x6_a.ensure(x6_bytes(M, d)) != 0 || m->x6_h.ensure(x6_bytes(M, F)) != 0)
@@ -583,6 +569,93 @@ int ffn_fused_try(wn_model* m, const Linear& w1, const Linear& w2, int act, hipS
   }
   m->prof_split = a.S;
   return a.S;
+}
+
+// ---- small kernels of the subsampling front ends and the padded-output scatter ---------------
+namespace wn {
+namespace {
+
+// x6 conv2: base pixel (plane image row of conv1's output, even-first order inside a
+// frame) of GEMM row (g, f2): frame off1[u] + 2 t2, position f2 (= f1 2 f2)
+// (fstep 1: plane image with the even f1 first; 2: the plain channels-last tensor)
+__global__ void build_conv2_pix_kernel(const int* row_utt2, const int* off2, const int* off1,
+                                       int M, int F1, int F2, int fstep, int* a_pix) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * F2) return;
+  const int g = i / F2, f2 = i % F2;
+  const int u = row_utt2[g];
+  a_pix[i] = (off1[u] + 2 * (g - off2[u])) * F1 + fstep * f2;
+}
+
+__global__ void build_conv2_rows_kernel(const int* row_utt2, const int* off2,
+                                        const int* off1, int M, int F1, int F2,
+                                        int C, int64_t* a_row_off) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * F2) return;
+  const int g = i / F2, f2 = i % F2;
+  const int u = row_utt2[g];
+  const int t2 = g - off2[u];
+  const int64_t t1 = off1[u] + 2 * t2;
+  a_row_off[i] = (t1 * F1 + 2 * f2) * (int64_t)C;
+}
+
+// packed rows -> padded (B, Tp, D) with zero fill
+__global__ void scatter_padded_kernel(const float* src, int lds, const int* off,
+                                      const int* len, int Tp, int D4,
+                                      float* dst) {
+  const int b = blockIdx.y, t = blockIdx.x;
+  f32x4* d = reinterpret_cast<f32x4*>(dst + ((int64_t)b * Tp + t) * D4 * 4);
+  if (t < len[b]) {
+    const f32x4* s =
+        reinterpret_cast<const f32x4*>(src + (int64_t)(off[b] + t) * lds);
+    for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = s[i];
+  } else {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = z;
+  }
+}
+
+// Conv1dSubsampling2 front end: utterance b becomes the packed segment
+// [0, x_0 .. x_{len-1}, 0, 0] (len + 3 rows of F floats) so that the k=3, pad=1
+// convolution over time is a plain GEMM over three consecutive rows.
+__global__ void pad_feats_kernel(const float* feats, int T, int F, const int* seg_off,
+                                 const int* len, const float* mean,
+                                 const float* istd, float* xpad) {
+  const int b = blockIdx.y, j = blockIdx.x;
+  const int L = len[b];
+  if (j >= L + 3) return;
+  float* dst = xpad + (int64_t)(seg_off[b] + j) * F;
+  const int t = j - 1;
+  if (t >= 0 && t < L) {
+    const float* src = feats + ((int64_t)b * T + t) * F;
+    for (int i = threadIdx.x; i < F; i += blockDim.x) {
+      float v = src[i];
+      if (mean) v = (v - mean[i]) * istd[i];
+      dst[i] = v;
+    }
+  } else {
+    for (int i = threadIdx.x; i < F; i += blockDim.x) dst[i] = 0.f;
+  }
+}
+
+__global__ void zero_rows_kernel(float* base, int D4, const int* rows, int n) {
+  const int r = blockIdx.x;
+  if (r >= n) return;
+  f32x4* d = reinterpret_cast<f32x4*>(base + (int64_t)rows[r] * D4 * 4);
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = z;
+}
+
+}  // namespace
+}  // namespace wn
+
+// packed encoder rows -> the caller's padded (B, Tp, D) tensor (wn_encode, encode_transformer)
+int scatter_padded(const float* src, int lds, const int* off, const int* len, int B, int Tp, int D,
+                   float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(scatter_padded_kernel, dim3(Tp, B), dim3(64), 0, s, src, lds, off, len, Tp,
+                     D / 4, dst);
+  WN_HIP(hipGetLastError());
+  return 0;
 }
 
 // ---- set the per-utterance row layout of the current batch -----------------
@@ -643,14 +716,15 @@ int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
 // (x starts as zeros: 0 + alpha (sum + b) is alpha (sum + b) exactly).  191 us on v_mfma_f32
 // (102 TF, r05e) before.  Returns 1 if it ran, 0 if the shape stays on linear().
 int sub_out_linear(wn_model* m, int M, int F2, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, K = F2 * d;
-  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || !m->x6_at || m->layers.empty() ||
+  if (t_gemm_prec != PREC_F32 || tune().gemm_x6 == 0 || W.layers.empty() ||
       (d != 256 && d != 512) || K % 16 != 0 || M < 512 || (int64_t)M * K * 4 >= ((int64_t)1 << 31) ||
       bf16_store_active())
     return 0;
-  auto it = m->x6_at->find(m->sub_out.w);
-  if (it == m->x6_at->end()) return 0;
+  auto it = W.x6_at.find(W.sub_out.w);
+  if (it == W.x6_at.end()) return 0;
   const int bm = 256;
   const int tiles = cdiv(M, bm) * cdiv(d, 256), nkb = K / 16;
   int S = 0;
@@ -664,8 +738,8 @@ int sub_out_linear(wn_model* m, int M, int F2, hipStream_t s) {
   g.C = m->ffn_part.as<float>();
   WN_TRY(gemm_x6(g, s));
   WN_HIP(hipMemsetAsync(m->x.p, 0, (size_t)M * d * sizeof(float), s));
-  const EncLayer& L0 = m->layers[0];
-  WN_TRY(ffn_reduce_ln(m->x.as<float>(), m->ffn_part.as<float>(), S, m->sub_out.b, sqrtf((float)d),
+  const EncLayer& L0 = W.layers[0];
+  WN_TRY(ffn_reduce_ln(m->x.as<float>(), m->ffn_part.as<float>(), S, W.sub_out.b, sqrtf((float)d),
                        L0.norm_ff_mac.w, L0.norm_ff_mac.b, nullptr, nullptr, m->t1.as<float>(), M,
                        d, c.norm_eps, 0, s));
   m->ln0_done = true;
@@ -689,6 +763,7 @@ int encode_gate_wait(wn_model* m, hipStream_t s) {
 int subsample_conv2d4(wn_model* m, const float* feats_dev,
                       const int32_t* feat_lens_host, int B, int T,
                       int32_t* enc_lens_host, int pos0, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, F1 = m->F1(), F2 = m->F2();
   const int Tp = ((T - 1) / 2 - 1) / 2;
@@ -729,11 +804,11 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
     // fp32 on the bf16 matrix cores (gemm_x6.hip): conv1 writes the plane image of its
     // output, conv2 gathers its rows from it
     const void* w6 = nullptr;
-    if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && m->x6_at && d % 32 == 0 &&
+    if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && d % 32 == 0 &&
         F1 <= 64 &&
         (M * F2 >= 4096 || tune().gemm_x6 == 2)) {
-      auto it = m->x6_at->find(m->conv2.w);
-      if (it != m->x6_at->end()) w6 = it->second;
+      auto it = W.x6_at.find(W.conv2.w);
+      if (it != W.x6_at.end()) w6 = it->second;
     }
     if (w6 && (tune().x6_af32 != 0 || tune().x6_conv_af32 != 0) &&
         (int64_t)M1 * F1 * d * 4 < ((int64_t)1 << 31)) {
@@ -741,8 +816,8 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       // pixel and k block, and splits them in registers
       WN_TRY(m->c1.ensure((size_t)M1 * F1 * d * sizeof(float)));
       Conv1Args c1;
-      c1.feats = feats_dev; c1.mean = m->cmvn_mean; c1.istd = m->cmvn_istd;
-      c1.w = m->conv1_w; c1.bias = m->conv1_b; c1.out = m->c1.as<float>();
+      c1.feats = feats_dev; c1.mean = W.cmvn_mean; c1.istd = W.cmvn_istd;
+      c1.w = W.conv1_w; c1.bias = W.conv1_b; c1.out = m->c1.as<float>();
       c1.t1_off = m->d_off1.as<int>(); c1.t1_len = m->d_len1.as<int>();
       c1.B = B; c1.T = T; c1.F = c.feat_dim; c1.F1 = F1; c1.C = d; c1.max_t1 = max_t1;
       WN_TRY(cmvn_conv1_relu(c1, s));
@@ -754,12 +829,12 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       X6Args g;
       g.A = m->c1.as<float>(); g.a_bytes = (int64_t)M1 * F1 * d * 4;
       g.B3 = w6; g.M = M * F2; g.N = d; g.K = 9 * d;
-      g.epi = 0; g.bias = m->conv2.b; g.act = ACT_RELU; g.C = m->c2.as<float>(); g.ldc = d;
+      g.epi = 0; g.bias = W.conv2.b; g.act = ACT_RELU; g.C = m->c2.as<float>(); g.ldc = d;
       g.a_pix = pix; g.conv_kbc = d / 16;
       for (int ky = 0; ky < 3; ++ky)
         for (int kx = 0; kx < 3; ++kx) g.tap_delta[ky * 3 + kx] = ky * F1 + kx;
       WN_TRY(gemm_x6(g, s));
-      WN_TRY(linear(m->sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
+      WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                     s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
       return 0;
     }
@@ -767,8 +842,8 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       const int tiles = cdiv(M1 * F1, 32);
       WN_TRY(m->c1.ensure(x6_bytes(M1 * F1, d)));
       Conv1Args c1;
-      c1.feats = feats_dev; c1.mean = m->cmvn_mean; c1.istd = m->cmvn_istd;
-      c1.w = m->conv1_w; c1.bias = m->conv1_b; c1.out = nullptr;
+      c1.feats = feats_dev; c1.mean = W.cmvn_mean; c1.istd = W.cmvn_istd;
+      c1.w = W.conv1_w; c1.bias = W.conv1_b; c1.out = nullptr;
       c1.out3 = m->c1.as<char>(); c1.tiles = tiles;
       c1.t1_off = m->d_off1.as<int>(); c1.t1_len = m->d_len1.as<int>();
       c1.B = B; c1.T = T; c1.F = c.feat_dim; c1.F1 = F1; c1.C = d; c1.max_t1 = max_t1;
@@ -783,7 +858,7 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       WN_TRY(encode_gate_wait(m, s));
       X6Args g;
       g.A3 = m->c1.as<char>(); g.B3 = w6; g.M = M * F2; g.N = d; g.K = 9 * d;
-      g.epi = 0; g.bias = m->conv2.b; g.act = ACT_RELU; g.C = m->c2.as<float>(); g.ldc = d;
+      g.epi = 0; g.bias = W.conv2.b; g.act = ACT_RELU; g.C = m->c2.as<float>(); g.ldc = d;
       g.a_pix = pix; g.a_tiles = tiles; g.conv_kbc = d / 16;
       g.conv_taps = 9;
       {   // scratch for the K-slice partials of the last, partial round of tiles (gemm_x6.hip)
@@ -806,14 +881,14 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       const int r = sub_out_linear(m, M, F2, s);
       if (r < 0) return r;
       if (r == 0)
-        WN_TRY(linear(m->sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
+        WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                       s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
       return 0;
     }
     // GlobalCMVN + conv1 + ReLU                        encoder.py:155, subsampling.py:188
     Conv1Args c1;
-    c1.feats = feats_dev; c1.mean = m->cmvn_mean; c1.istd = m->cmvn_istd;
-    c1.w = m->conv1_w; c1.bias = m->conv1_b; c1.out = m->c1.as<float>();
+    c1.feats = feats_dev; c1.mean = W.cmvn_mean; c1.istd = W.cmvn_istd;
+    c1.w = W.conv1_w; c1.bias = W.conv1_b; c1.out = m->c1.as<float>();
     c1.t1_off = m->d_off1.as<int>(); c1.t1_len = m->d_len1.as<int>();
     c1.B = B; c1.T = T; c1.F = c.feat_dim; c1.F1 = F1; c1.C = d; c1.max_t1 = max_t1;
     WN_TRY(cmvn_conv1_relu(c1, s));
@@ -824,19 +899,20 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
                        m->d_a_row_off.as<int64_t>());
     WN_HIP(hipGetLastError());
     GemmArgs g;
-    g.A = m->c1.as<float>(); g.W = m->conv2.w; g.bias = m->conv2.b;
+    g.A = m->c1.as<float>(); g.W = W.conv2.w; g.bias = W.conv2.b;
     g.C = m->c2.as<float>(); g.M = M * F2; g.N = d; g.K = 9 * d; g.ldc = d;
     g.act = ACT_RELU; g.a_row_off = m->d_a_row_off.as<int64_t>();
     g.conv_C = d; g.conv_sy = (int64_t)F1 * d; g.conv_sx = d;
     WN_TRY(gemm_f32(g, s));
     // Linear(d*F2 -> d) * sqrt(d)                      subsampling.py:225-226, embedding.py:144
-    WN_TRY(linear(m->sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
+    WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                   s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
   }
   return 0;
 }
 
 int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, M = m->rows;
   float* x = m->x.as<float>();
@@ -862,7 +938,7 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
   const bool h16 = bf16_store_active();
   m->t1_img_ok = false;
   for (int li = 0; li < n_run; ++li) {
-    const EncLayer& L = m->layers[li];
+    const EncLayer& L = W.layers[li];
     // x += 0.5 * FFN_macaron(LN(x))                 encoder_layer.py:220-228
     // (for li > 0 the previous layer's tail already left LN(x) in t1)
     // fp32: fused FFN (hidden tensor stays on chip), its partial reduction carries the
@@ -906,9 +982,9 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
     if (ax6 && m->attn_img.ensure(attention_x6_image_bytes(M, m->B, c.n_heads)) == 0)
       ax6_img = true;
     const std::pair<const void*, const float*>* qkv_q = nullptr;
-    if (ax6_img && pro && tune().attn_x6_galign == 2 && m->x6q_at) {
-      auto it = m->x6q_at->find(L.qkv.w);
-      if (it != m->x6q_at->end()) qkv_q = &it->second;
+    if (ax6_img && pro && tune().attn_x6_galign == 2) {
+      auto it = W.x6q_at.find(L.qkv.w);
+      if (it != W.x6q_at.end()) qkv_q = &it->second;
     }
     bool qkv_done = false;
     if (qkv_w6) {
@@ -1096,7 +1172,7 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
     if (fS > 0) {
       // partial reduction + residual + norm_final (+ the next layer's norm_ff_macaron)
       if (li + 1 < n_run) {
-        const EncLayer& Ln = m->layers[li + 1];
+        const EncLayer& Ln = W.layers[li + 1];
         void* mac_img = t1_image_for(m, Ln.ffm1, Ln.ffm2, ACT_SILU);
         if (mac_img) {
           WN_TRY(ffn_reduce_ln_img(x, m->ffn_part.as<float>(), fS, L.ff2.b, 0.5f, L.norm_final.w,
@@ -1117,7 +1193,7 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
     WN_TRY(ffn_module(m, L.norm_ff, L.ff1, L.ff2, ACT_SILU, 0.5f,
                       !h16 && t_gemm_prec == PREC_F32, h16, s));
     if (li + 1 < n_run && !(t_mx && h16)) {
-      const EncLayer& Ln = m->layers[li + 1];
+      const EncLayer& Ln = W.layers[li + 1];
       WN_TRY(layernorm2(x, L.norm_final.w, L.norm_final.b, Ln.norm_ff_mac.w,
                         Ln.norm_ff_mac.b, x, t1, M, d, eps, s, h16));
     } else {
@@ -1130,7 +1206,7 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
                           hipMemcpyDeviceToDevice, s));
     return 0;
   }
-  WN_TRY(ln(m->after_norm, x, m->enc.as<float>(), M, d, eps, s));
+  WN_TRY(ln(W.after_norm, x, m->enc.as<float>(), M, d, eps, s));
   return 0;
 }
 
@@ -1143,6 +1219,7 @@ int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s) {
 // context.  All masks are the all-ones fakes of forward_chunk.
 int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
                          std::vector<ChunkSess>& sess, float* out, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, H = c.n_heads, M = n_sess * R;
   const int lorder = c.causal ? c.cnn_kernel - 1 : 0;
@@ -1191,7 +1268,7 @@ int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
   float* xext = m->ck_xext.as<float>();
   float* glu = m->ck_glu.as<float>();
   for (int li = 0; li < c.n_layers; ++li) {
-    const EncLayer& L = m->layers[li];
+    const EncLayer& L = W.layers[li];
     WN_TRY(ln(L.norm_ff_mac, x, t1, M, d, eps, s));
     WN_TRY(linear(L.ffm1, t1, d, hb, c.ffn_dim, M, s, ACT_SILU));
     WN_TRY(linear(L.ffm2, hb, c.ffn_dim, x, d, M, s, ACT_NONE, x, d, 0.5f));
@@ -1242,13 +1319,14 @@ int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
     WN_TRY(linear(L.ff2, hb, c.ffn_dim, x, d, M, s, ACT_NONE, x, d, 0.5f));
     WN_TRY(ln(L.norm_final, x, x, M, d, eps, s));
   }
-  WN_TRY(ln(m->after_norm, x, out, M, d, eps, s));
+  WN_TRY(ln(W.after_norm, x, out, M, d, eps, s));
   return 0;
 }
 
 // TransformerEncoder (Whisper style): x += MHA(LN(x)); x += FFN(LN(x)); final LN
 // (encoder_layer.py:94-127, encoder.py:176-181).
 int transformer_layers(wn_model* m, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, M = m->rows;
   float* x = m->x.as<float>();
@@ -1264,7 +1342,7 @@ int transformer_layers(wn_model* m, hipStream_t s) {
   const int n_run = m->dbg_layers >= 0 ? std::min(m->dbg_layers, c.n_layers)
                                       : c.n_layers;
   for (int li = 0; li < n_run; ++li) {
-    const TfLayer& L = m->tf_layers[li];
+    const TfLayer& L = W.tf_layers[li];
     WN_TRY(ln(L.n1, x, t1, M, d, eps, s, h16));
     // bf16-storage form: Q | K | V leave the GEMM as bf16 (the attention kernel rounds
     // them to bf16 first thing anyway): half the GEMM's store and the attention's stream
@@ -1298,7 +1376,7 @@ int transformer_layers(wn_model* m, hipStream_t s) {
                           hipMemcpyDeviceToDevice, s));
     return 0;
   }
-  WN_TRY(ln(m->after_norm, x, m->enc.as<float>(), M, d, eps, s));
+  WN_TRY(ln(W.after_norm, x, m->enc.as<float>(), M, d, eps, s));
   return 0;
 }
 
@@ -1307,6 +1385,7 @@ int transformer_layers(wn_model* m, hipStream_t s) {
 int encode_transformer(wn_model* m, const float* feats_dev,
                        const int32_t* feat_lens_host, int B, int T,
                        float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s) {
+  const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, F = c.feat_dim;
   // output frames: conv(k3, s2, p1) keeps floor((T-1)/2)+1; the mask keeps
@@ -1372,7 +1451,7 @@ int encode_transformer(wn_model* m, const float* feats_dev,
     WN_TRY(upload_desc(m, m->d_zero_rows, zero_rows, s));
     WN_TRY(m->stage.put(m->d_a_row_off, a_off.data(), a_off.size() * sizeof(int64_t), s));
     WN_TRY(m->stage.end(s));
-    const int K1 = m->tconv1.in;  // 3F rounded up to 32 (zero weights)
+    const int K1 = W.tconv1.in;  // 3F rounded up to 32 (zero weights)
     WN_TRY(m->xpad.ensure(((size_t)rows_pad * F + K1 + 64) * sizeof(float)));
     WN_TRY(m->c1.ensure(((size_t)rows_pad + 2) * d * sizeof(float)));
     WN_TRY(m->x.ensure((size_t)M * d * sizeof(float)));
@@ -1389,12 +1468,12 @@ int encode_transformer(wn_model* m, const float* feats_dev,
                           (size_t)(K1 + 64) * sizeof(float), s));
     hipLaunchKernelGGL(pad_feats_kernel, dim3(max_len + 3, B), dim3(64), 0, s,
                        feats_dev, T, F, m->d_off1.as<int>(), m->d_len1.as<int>(),
-                       m->cmvn_mean, m->cmvn_istd, m->xpad.as<float>());
+                       W.cmvn_mean, W.cmvn_istd, m->xpad.as<float>());
     WN_HIP(hipGetLastError());
     // conv1 (k3, pad 1) + GELU: output row r = taps at xpad rows r, r+1, r+2
     // -> c1pad row r + 1 (row seg_b is the zero pad in front of utterance b)
     GemmArgs g1;
-    g1.A = m->xpad.as<float>(); g1.W = m->tconv1.w; g1.bias = m->tconv1.b;
+    g1.A = m->xpad.as<float>(); g1.W = W.tconv1.w; g1.bias = W.tconv1.b;
     g1.C = m->c1.as<float>() + d; g1.M = rows_pad - 2; g1.N = d; g1.K = K1;
     g1.lda = F; g1.ldc = d; g1.act = ACT_GELU;
     WN_CHECK(F % 4 == 0, "conv1d2 front end: feature dim must be a multiple of 4");
@@ -1404,11 +1483,11 @@ int encode_transformer(wn_model* m, const float* feats_dev,
                        (int)zero_rows.size());
     WN_HIP(hipGetLastError());
     // positional rows pe[t'] (xscale = 1, embedding.py:156)
-    WN_TRY(copy_rows(m->pe, d, m->d_row_t.as<int>(), m->pos_rows.as<float>(), d,
+    WN_TRY(copy_rows(W.pe, d, m->d_row_t.as<int>(), m->pos_rows.as<float>(), d,
                      nullptr, M, d, s));
     // conv2 (k3, stride 2, pad 1) + GELU, + pe: gathered rows of c1pad
     GemmArgs g2;
-    g2.A = m->c1.as<float>(); g2.W = m->tconv2.w; g2.bias = m->tconv2.b;
+    g2.A = m->c1.as<float>(); g2.W = W.tconv2.w; g2.bias = W.tconv2.b;
     g2.C = m->x.as<float>(); g2.M = M; g2.N = d; g2.K = 3 * d; g2.ldc = d;
     g2.act = ACT_GELU; g2.resid = m->pos_rows.as<float>(); g2.ldr = d;
     g2.a_row_off = m->d_a_row_off.as<int64_t>();
@@ -1418,10 +1497,8 @@ int encode_transformer(wn_model* m, const float* feats_dev,
   }
   if (enc_out_dev) {
     if (M > 0) {
-      hipLaunchKernelGGL(scatter_padded_kernel, dim3(Tp, B), dim3(64), 0, s,
-                         m->enc.as<float>(), d, m->d_off.as<int>(),
-                         m->d_len.as<int>(), Tp, d / 4, enc_out_dev);
-      WN_HIP(hipGetLastError());
+      WN_TRY(scatter_padded(m->enc.as<float>(), d, m->d_off.as<int>(), m->d_len.as<int>(), B, Tp,
+                            d, enc_out_dev, s));
     } else if (Tp > 0) {
       WN_HIP(hipMemsetAsync(enc_out_dev, 0, (size_t)B * Tp * d * sizeof(float), s));
     }

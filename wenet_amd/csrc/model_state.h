@@ -1,7 +1,9 @@
 // Internal state of libwenet_amd shared by the engine (model.hip: launch sequences of the
-// encoder / decoders, weight images) and the C ABI (cabi.hip: include/wenet_amd.h entry points):
-// device buffers, the re-laid-out weight views, the per-handle workspace `wn_model`, the
-// per-call guards (one host thread per handle, operand precision of the calling thread).
+// encoder, weight images) and the C ABI (cabi_*.hip: include/wenet_amd.h entry points, one file
+// per subsystem): device buffers, the model block clones share (`ModelData`: weights and their
+// re-laid-out views), the per-handle settings and workspace (`wn_model`), the per-call guards
+// (one host thread per handle, operand precision of the calling thread).  No kernels here:
+// each lives in the file that launches it.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -12,6 +14,7 @@
 #include <chrono>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -41,6 +44,7 @@ struct DevBuf {
     cap = want;
     return 0;
   }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -120,7 +124,7 @@ struct PinnedBuf {
 
 // A second stream of the handle + the two events that order it with the caller's stream: work
 // that does not depend on the search result runs there while the (latency-bound, few-CU) prefix
-// beam search runs on the caller's stream -- wn_rescore_prefetch in cabi.hip.
+// beam search runs on the caller's stream -- wn_rescore_prefetch in cabi_decoder.hip.
 struct SideStream {
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -172,165 +176,33 @@ struct Decoder {
   Linear out;
   std::vector<DecLayer> layers;
 };
-
-namespace {    // small kernels: a private copy per translation unit (-fno-gpu-rdc)
-
-
-// x6 conv2: base pixel (plane image row of conv1's output, even-first order inside a
-// frame) of GEMM row (g, f2): frame off1[u] + 2 t2, position f2 (= f1 2 f2)
-// (fstep 1: plane image with the even f1 first; 2: the plain channels-last tensor)
-__global__ void build_conv2_pix_kernel(const int* row_utt2, const int* off2, const int* off1,
-                                       int M, int F1, int F2, int fstep, int* a_pix) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * F2) return;
-  const int g = i / F2, f2 = i % F2;
-  const int u = row_utt2[g];
-  a_pix[i] = (off1[u] + 2 * (g - off2[u])) * F1 + fstep * f2;
-}
-
-__global__ void build_conv2_rows_kernel(const int* row_utt2, const int* off2,
-                                        const int* off1, int M, int F1, int F2,
-                                        int C, int64_t* a_row_off) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * F2) return;
-  const int g = i / F2, f2 = i % F2;
-  const int u = row_utt2[g];
-  const int t2 = g - off2[u];
-  const int64_t t1 = off1[u] + 2 * t2;
-  a_row_off[i] = (t1 * F1 + 2 * f2) * (int64_t)C;
-}
-
-// packed rows -> padded (B, Tp, D) with zero fill
-__global__ void scatter_padded_kernel(const float* src, int lds, const int* off,
-                                      const int* len, int Tp, int D4,
-                                      float* dst) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  f32x4* d = reinterpret_cast<f32x4*>(dst + ((int64_t)b * Tp + t) * D4 * 4);
-  if (t < len[b]) {
-    const f32x4* s =
-        reinterpret_cast<const f32x4*>(src + (int64_t)(off[b] + t) * lds);
-    for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = s[i];
-  } else {
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = z;
-  }
-}
-
-// generic (non multiple-of-4 width) variant used for the (B,Tp,V) log-probs
-__global__ void scatter_padded_any_kernel(const float* src, int lds,
-                                          const int* off, const int* len,
-                                          int Tp, int D, float* dst) {
-  const int b = blockIdx.y, t = blockIdx.x;
-  float* d = dst + ((int64_t)b * Tp + t) * D;
-  if (t < len[b]) {
-    const float* s = src + (int64_t)(off[b] + t) * lds;
-    for (int i = threadIdx.x; i < D; i += blockDim.x) d[i] = s[i];
-  } else {
-    for (int i = threadIdx.x; i < D; i += blockDim.x) d[i] = 0.f;
-  }
-}
-
-// Conv1dSubsampling2 front end: utterance b becomes the packed segment
-// [0, x_0 .. x_{len-1}, 0, 0] (len + 3 rows of F floats) so that the k=3, pad=1
-// convolution over time is a plain GEMM over three consecutive rows.
-__global__ void pad_feats_kernel(const float* feats, int T, int F, const int* seg_off,
-                                 const int* len, const float* mean,
-                                 const float* istd, float* xpad) {
-  const int b = blockIdx.y, j = blockIdx.x;
-  const int L = len[b];
-  if (j >= L + 3) return;
-  float* dst = xpad + (int64_t)(seg_off[b] + j) * F;
-  const int t = j - 1;
-  if (t >= 0 && t < L) {
-    const float* src = feats + ((int64_t)b * T + t) * F;
-    for (int i = threadIdx.x; i < F; i += blockDim.x) {
-      float v = src[i];
-      if (mean) v = (v - mean[i]) * istd[i];
-      dst[i] = v;
-    }
-  } else {
-    for (int i = threadIdx.x; i < F; i += blockDim.x) dst[i] = 0.f;
-  }
-}
-
-__global__ void zero_rows_kernel(float* base, int D4, const int* rows, int n) {
-  const int r = blockIdx.x;
-  if (r >= n) return;
-  f32x4* d = reinterpret_cast<f32x4*>(base + (int64_t)rows[r] * D4 * 4);
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < D4; i += blockDim.x) d[i] = z;
-}
-
-__global__ void embed_kernel(const int* tok, const int* pos, const float* emb,
-                             const float* pe, float scale, int D4, float* x) {
-  const int r = blockIdx.x;
-  const f32x4* e = reinterpret_cast<const f32x4*>(emb + (int64_t)tok[r] * D4 * 4);
-  const f32x4* p = reinterpret_cast<const f32x4*>(pe + (int64_t)pos[r] * D4 * 4);
-  f32x4* o = reinterpret_cast<f32x4*>(x + (int64_t)r * D4 * 4);
-  for (int i = threadIdx.x; i < D4; i += blockDim.x) o[i] = e[i] * scale + p[i];
-}
-
-// log_softmax(row)[target] -- forward_attention_decoder's log_softmax
-// (asr_model.py:541-546) fused with the gather of search.py:431-441.
-__global__ __launch_bounds__(256) void row_logp_at_kernel(
-    const float* logits, int ld, int V, const int* target, float* out) {
-  __shared__ float red[8];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* x = logits + (int64_t)row * ld;
-  float mx = -INFINITY;
-  for (int i = tid; i < V; i += 256) mx = fmaxf(mx, x[i]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sm = 0.f;
-  for (int i = tid; i < V; i += 256) sm += expf(x[i] - mx);
-  sm = wave_sum(sm);
-  if (lane == 0) red[4 + wave] = sm;
-  __syncthreads();
-  if (tid == 0)
-    out[row] = (x[target[row]] - mx) - logf(red[4] + red[5] + red[6] + red[7]);
-}
-
-}  // namespace
 }  // namespace wn
 
 using namespace wn;
 
 
 // ===========================================================================
-struct wn_model {
-  wn_config cfg;
-  int device = 0;
-  // immutable after create, shared by wn_model_clone()d handles
-  std::shared_ptr<DevBuf> weights = std::make_shared<DevBuf>();  // one slab for every weight
+// What wn_model_create builds and every wn_model_clone()d handle shares: fixed once create
+// returns (the handles hold it as const), except the tables at the end, which are built on
+// first use under `lazy` and never change afterwards.
+struct ModelData {
+  DevBuf weights;                        // one slab for every weight
   int64_t n_weight_elems = 0;            // floats in the slab
-  std::shared_ptr<DevBuf> weights_bf16;  // bf16 image of the slab (bf16 mode, lazily)
-  // MXFP8 images of the FFN weights (fp8 mode, lazily): fp32 weight pointer ->
-  // (e4m3 [N][K], block scales [K/128][N] dwords); clones share it
-  struct MxW { const void* q; const unsigned* scale; };
-  std::shared_ptr<DevBuf> weights_mx;
-  std::shared_ptr<std::map<const float*, MxW>> mx_at;
-  bool fp8_ffn = false;                  // WN_PREC_FP8: prec == PREC_BF16 + MXFP8 FFN GEMMs
   // plane images of the weights the six-product fp32 GEMM runs (gemm_x6.hip): fp32 weight
-  // pointer -> X3 image; built at create, shared by clones
-  std::shared_ptr<DevBuf> weights_x6;
-  std::shared_ptr<std::map<const float*, const void*>> x6_at;
-  DevBuf nb_map, nb_keep, nb_enc, nb_off_old;   // filter_blank_embedding scratch
-  std::shared_ptr<DevBuf> weights_x6p;      // k-slot-permuted FFN w_2 images (ffn_x6f.hip)
-  std::shared_ptr<std::map<const float*, const void*>> x6p_at;
+  // pointer -> X3 image
+  DevBuf weights_x6;
+  std::map<const float*, const void*> x6_at;
+  DevBuf weights_x6p;                    // k-slot-permuted FFN w_2 images (ffn_x6f.hip)
+  std::map<const float*, const void*> x6p_at;
   // QKV weights with the rows permuted per head ([Q_h | K_h | V_h] x 64) as X3 images + the
   // biases in the same order: the QKV projection that writes the attention's key-tile images
   // itself (gemm_x6r.hip epi 4); fp32 weight pointer -> (image, bias)
-  std::shared_ptr<DevBuf> weights_x6q;
-  std::shared_ptr<std::map<const float*, std::pair<const void*, const float*>>> x6q_at;
-  DevBuf x6_a, x6_h;                     // images of the GEMM input rows / the FFN hidden tensor
-  DevBuf x6_lin;                         // image of linear()'s A operand (large fp32 GEMMs)
+  DevBuf weights_x6q;
+  std::map<const float*, std::pair<const void*, const float*>> x6q_at;
   // biases of the vocabulary-sized layers (CTC head, decoder output layers) padded with zeros
   // to a multiple of 4 columns: weight pointer -> padded bias
-  std::shared_ptr<DevBuf> bias4_buf;
-  std::shared_ptr<std::map<const float*, const float*>> bias4;
-  DevBuf mx_sa, mx_sh;                   // block scales of the LN output / FFN hidden
+  DevBuf bias4_buf;
+  std::map<const float*, const float*> bias4;
   std::map<std::string, const float*> w; // name -> device pointer
   // re-laid-out subsampling weights
   const float* conv1_w = nullptr; const float* conv1_b = nullptr;
@@ -344,7 +216,43 @@ struct wn_model {
   Linear tconv1, tconv2;                // Conv1dSubsampling2 as gathered-row GEMMs
   bool fbank_ok = true;
   Decoder left, right;
-  std::shared_ptr<DevBuf> pos_tabs = std::make_shared<DevBuf>();
+  DevBuf pos_tabs;
+  // fbank tables
+  const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
+  const float* fb_mel_w = nullptr;
+  DevBuf fb_tab_i;
+
+  // ---- built on first use ------------------------------------------------------------------
+  // Look up or build under `lazy`, publish a finished buffer only (DevBuf::swap), then read
+  // without the lock: a DevBuf that is set never changes, and std::map nodes do not move.  A
+  // handle reads a precision image only after its own wn_model_set_precision returned (or the
+  // one of the handle it was cloned from).
+  mutable std::mutex lazy;
+  mutable DevBuf weights_bf16;           // bf16 image of the slab (bf16 mode)
+  // MXFP8 images of the FFN weights (fp8 mode): fp32 weight pointer ->
+  // (e4m3 [N][K], block scales [K/128][N] dwords)
+  struct MxW { const void* q; const unsigned* scale; };
+  mutable DevBuf weights_mx;
+  mutable std::map<const float*, MxW> mx_at;
+  mutable bool mx_built = false;
+  // Whisper log-mel: DFT / window tables, mel matrix per bin count
+  mutable DevBuf lm_dft;
+  mutable std::map<int, DevBuf> lm_mel;
+  // resampler taps per (orig, new) rate pair (wn_resample)
+  mutable std::map<std::pair<int, int>, DevBuf> rs_taps;
+};
+
+// A handle: the shared model block + this handle's settings, current batch and workspace.
+struct wn_model {
+  wn_config cfg;
+  int device = 0;
+  // never null: wn_workspace_create gives an empty block
+  std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
+  bool fp8_ffn = false;                  // WN_PREC_FP8: prec == PREC_BF16 + MXFP8 FFN GEMMs
+  DevBuf nb_map, nb_keep, nb_enc, nb_off_old;   // filter_blank_embedding scratch
+  DevBuf x6_a, x6_h;                     // images of the GEMM input rows / the FFN hidden tensor
+  DevBuf x6_lin;                         // image of linear()'s A operand (large fp32 GEMMs)
+  DevBuf mx_sa, mx_sh;                   // block scales of the LN output / FFN hidden
 
   // ---- current batch ----------------------------------------------------
   int B = 0, Tp = 0, rows = 0;          // rows of the encoder-output layout
@@ -355,13 +263,6 @@ struct wn_model {
   DevBuf attn_kbias;                    // per-key score term of the folded rel-pos attention
   DevBuf xpad, pos_rows, d_row_t, d_zero_rows;
   DevBuf ck_kv, ck_xext, ck_glu, ck_desc, ck_rowutt, ck_sess;  // forward_chunk scratch
-  // Whisper log-mel: DFT / window tables (shared), mel matrix per bin count
-  std::shared_ptr<DevBuf> lm_dft = std::make_shared<DevBuf>();
-  // resampler taps per (orig, new) rate pair (wn_resample)
-  std::shared_ptr<std::map<std::pair<int, int>, std::shared_ptr<DevBuf>>> rs_taps =
-      std::make_shared<std::map<std::pair<int, int>, std::shared_ptr<DevBuf>>>();
-  std::shared_ptr<std::map<int, std::shared_ptr<DevBuf>>> lm_mel =
-      std::make_shared<std::map<int, std::shared_ptr<DevBuf>>>();
   DevBuf lm_off, lm_foff, lm_nfr, lm_rowutt, lm_frames, lm_spec, lm_pw, lm_melout, lm_umax;
   // ctc
   int ctc_rows = 0, ctc_k = 0;
@@ -433,10 +334,6 @@ struct wn_model {
   Tune tune_eff;
   int dbg_layers = -1;       // run only the first n encoder layers
   int dbg_skip_after_norm = 0;
-  // fbank tables
-  const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
-  const float* fb_mel_w = nullptr;
-  std::shared_ptr<DevBuf> fb_tab_i = std::make_shared<DevBuf>();
   // context biasing tables (wn_set_context_graph); ctx.keys == nullptr: none
   std::shared_ptr<DevBuf> ctx_buf;
   CtxGraph ctx;
@@ -493,7 +390,7 @@ struct HandleGuard {
     return -4;                                                                   \
   }
 
-extern thread_local const std::map<const float*, wn_model::MxW>* t_mx;
+extern thread_local const std::map<const float*, ModelData::MxW>* t_mx;
 // plane images of the current model's weights and its activation-image scratch: linear()
 // routes the large fp32 GEMMs to the six-product kernel through them (gemm_x6.hip)
 extern thread_local const std::map<const float*, const void*>* t_x6;
@@ -502,19 +399,20 @@ extern thread_local DevBuf* t_x6_a;
 struct PrecisionScope {
   int saved;
   const float* s_f32; const void* s_bf16; int64_t s_elems;
-  const std::map<const float*, wn_model::MxW>* s_mx;
+  const std::map<const float*, ModelData::MxW>* s_mx;
   const std::map<const float*, const void*>* s_x6; DevBuf* s_x6_a;
   explicit PrecisionScope(const wn_model* m)
       : saved(t_gemm_prec), s_f32(t_wslab_f32), s_bf16(t_wslab_bf16),
         s_elems(t_wslab_elems), s_mx(t_mx), s_x6(t_x6), s_x6_a(t_x6_a) {
-    t_mx = (m->fp8_ffn && m->mx_at) ? m->mx_at.get() : nullptr;
-    t_x6 = m->x6_at ? m->x6_at.get() : nullptr;
+    const ModelData& W = *m->data;
+    t_mx = m->fp8_ffn ? &W.mx_at : nullptr;
+    t_x6 = &W.x6_at;
     t_x6_a = const_cast<DevBuf*>(&m->x6_lin);
     t_gemm_prec = m->prec;
-    const bool img = m->prec == PREC_BF16 && m->weights_bf16 && m->weights_bf16->p;
-    t_wslab_f32 = img ? m->weights->as<float>() : nullptr;
-    t_wslab_bf16 = img ? m->weights_bf16->p : nullptr;
-    t_wslab_elems = img ? m->n_weight_elems : 0;
+    const bool img = m->prec == PREC_BF16 && W.weights_bf16.p;
+    t_wslab_f32 = img ? W.weights.as<float>() : nullptr;
+    t_wslab_bf16 = img ? W.weights_bf16.p : nullptr;
+    t_wslab_elems = img ? W.n_weight_elems : 0;
   }
   ~PrecisionScope() {
     t_gemm_prec = saved;
@@ -533,12 +431,14 @@ int linear(const Linear& l, const float* A, int lda, float* C, int ldc, int M, h
            bool glu = false, bool a_bf16 = false, bool c_bf16 = false);
 int ln(const Norm& n, const float* x, float* y, int M, int D, float eps, hipStream_t s,
        bool y_bf16 = false);
-int build_x6_images(wn_model* m);
+int build_x6_images(const wn_config& cfg, ModelData& W);
 int vocab_linear(wn_model* m, const Linear& l, const float* A, int lda, float* C, int ldc, int M,
                  hipStream_t s);
 int ffn_x6_split(int M, int F);
 int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const float* A, int M,
                 hipStream_t s);
+int scatter_padded(const float* src, int lds, const int* off, const int* len, int B, int Tp, int D,
+                   float* dst, hipStream_t s);
 int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
                const std::vector<int>& len, int rows, hipStream_t s);
 int subsample_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
