@@ -265,6 +265,33 @@ int wn_set_ctc_probs(wn_model* m, const float* logp_dev,
 int wn_ctc_greedy_search(wn_model* m, int32_t blank_id, int32_t* tokens_host,
                          int32_t* tok_lens_host, int32_t max_len, void* stream);
 
+/* CTC forced alignment (ctc_utils.py:106 force_align, bin/alignment.py) of the CURRENT batch
+ * (after wn_encode / wn_set_encoder_out) against given label lists: the CTC head, an emission
+ * gather fused into the log-softmax row pass (the (B, T', V) log-probs are never written) and a
+ * Viterbi trellis with its backtrace, one wave per utterance (DESIGN.md section 3 states the
+ * rule: fp32, ties to stay, then step, then skip; the last label ends the path unless the
+ * trailing blank is strictly better).  labels_host (B, max_label) int32, label_lens_host (B).
+ * logp_dev != NULL: caller-provided NORMALISED log-probs (B, Tp, V) with lens_host (B) are
+ * aligned INSTEAD of the current batch (works on a wn_workspace_create handle; the current
+ * batch and its posteriors stay as they are); otherwise logp_dev / lens_host are NULL and B, Tp
+ * must be the current batch's, V is ignored, blank_penalty as in wn_ctc_logprobs.
+ * Outputs, host, each may be NULL except status_host: path_host (B, Tp) int32 label per frame;
+ * score_host (B) float, the path's log-probability; status_host (B) 0 = ok, 1 = infeasible
+ * (T' < labels + adjacent repeats; nothing else is written for that utterance);
+ * frame_logp_host (B, Tp, 2) float: at frame t the log-prob of blank and of the label of the
+ * token group t belongs to, i.e. the next label at or behind t on the path (what
+ * bin/alignment.py get_frames_timestamp reads; trailing blank frames: blank twice);
+ * emit_host (B, Tp, max_label + 1) float: column 0 blank, column 1 + i label i, zeros behind an
+ * utterance's own labels.  Entries past an utterance's length are left untouched.  Label ids
+ * outside [0, V), label_len > max_label or blank_id among the labels fail with -1 before
+ * anything touches the device. */
+int wn_ctc_force_align(wn_model* m, int32_t blank_id, float blank_penalty,
+                       const int32_t* labels_host, const int32_t* label_lens_host,
+                       int32_t max_label, const float* logp_dev, const int32_t* lens_host,
+                       int32_t B, int32_t Tp, int32_t V, int32_t* path_host, float* score_host,
+                       int32_t* status_host, float* frame_logp_host, float* emit_host,
+                       void* stream);
+
 /* Context biasing: install (n_nodes > 0) or clear (n_nodes == 0) a flattened
  * ContextGraph (wenet/utils/context_graph.py:101-265) on this handle; later
  * wn_ctc_prefix_beam_search calls are biased by it exactly like

@@ -19,6 +19,10 @@
       the same comparison with the kernels of all named files (those that exist in each tree)
       matched by NAME: for code that moved between files, or out of an extern "C" block.
 
+  tools/isa_audit.py resources [file.hip ...]
+      per kernel, from the code object metadata: VGPRs, SGPRs, static LDS bytes and scratch
+      bytes (`scratch 0` = no spills, no runtime-indexed register array gone to memory).
+
 Assembly goes to $TMPDIR/wn_isa/{work,<rev>}/ and is reused when newer than the source.
 """
 import concurrent.futures
@@ -135,6 +139,20 @@ def cmd_waits(files):
                       f'asm vmcnt {n_asm:3d}  {demangle(name)[:110]}')
 
 
+def cmd_resources(files):
+    for f, path in sorted(assemble(ROOT, 'work', files).items()):
+        text = open(path).read()
+        for m in re.finditer(r'- \.agpr_count:.*?\.wavefront_size:\s*\d+', text, re.S):
+            blk = m.group(0)
+
+            def field(k):
+                r = re.search(r'\.%s:\s*(\S+)' % k, blk)
+                return r.group(1) if r else '?'
+            print(f'{f:22s} vgpr {field("vgpr_count"):>4s} agpr {field("agpr_count"):>4s} '
+                  f'sgpr {field("sgpr_count"):>4s}  lds {field("group_segment_fixed_size"):>6s}  '
+                  f'scratch {field("private_segment_fixed_size")}  {demangle(field("name"))}')
+
+
 def _tree(rev):
     wt = os.path.join(OUT, 'tree_' + rev)
     if not os.path.isdir(wt):
@@ -214,6 +232,8 @@ def cmd_diff(rev, files):
 if __name__ == '__main__':
     if len(sys.argv) >= 2 and sys.argv[1] == 'waits':
         cmd_waits(sys.argv[2:])
+    elif len(sys.argv) >= 2 and sys.argv[1] == 'resources':
+        cmd_resources(sys.argv[2:])
     elif len(sys.argv) >= 3 and sys.argv[1] == 'diff':
         sys.exit(cmd_diff(sys.argv[2], sys.argv[3:]))
     elif len(sys.argv) >= 4 and sys.argv[1] == 'pool':

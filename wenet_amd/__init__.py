@@ -1,13 +1,15 @@
 """wenet_amd: MI355X-native Conformer-ASR inference path behind WeNet's API.
 
 Public surface mirrors the reference (wenet/__init__.py:1, wenet/cli/model.py):
-``load_model``, plus the search free functions and ``DecodeResult``.
+``load_model``, plus the search free functions, ``DecodeResult`` and the forced
+alignment of ``ctc_utils.force_align`` (``wenet_amd.align``).
 The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
 __all__ = ["load_model", "ASRModel", "DecodeResult", "StreamingRecognizer",
-           "CtcEndpointConfig", "CtcEndpointRule"]
+           "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
+           "force_align_batch"]
 
 
 def __getattr__(name):
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name in ("StreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule"):
         from wenet_amd import streaming as _s
         return getattr(_s, name)
+    if name in ("AlignResult", "force_align", "force_align_batch"):
+        from wenet_amd import align as _a
+        return getattr(_a, name)
     raise AttributeError(name)

@@ -43,7 +43,7 @@ EXPORTS = [
     'wn_op_gemm_bf16_stored',
     'wn_attention_beam_search', 'wn_encode_chunk_batch', 'wn_op_gemm_lowp', 'wn_op_mx_quantize', 'wn_op_ffn_fused', 'wn_op_gemm_x6', 'wn_op_ffn_x6', 'wn_op_gemm_x6r', 'wn_op_gemm_x6r512', 'wn_profile_kernel_name', 'wn_profile_ffn_split', 'wn_profile_ffn_clocks', 'wn_profile_gemm_clocks', 'wn_filter_blank_embedding',
     'wn_workspace_create', 'wn_resample_length', 'wn_resample', 'wn_fbank', 'wn_log_mel', 'wn_encode', 'wn_encode_chunk', 'wn_set_encoder_out',
-    'wn_ctc_logprobs', 'wn_set_ctc_probs', 'wn_ctc_greedy_search',
+    'wn_ctc_logprobs', 'wn_set_ctc_probs', 'wn_ctc_greedy_search', 'wn_ctc_force_align',
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
     'wn_op_layernorm', 'wn_op_log_add', 'wn_debug_set', 'wn_profile_enable',
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
@@ -98,6 +98,8 @@ def lib():
     L.wn_resample.argtypes = [vp, vp, ctypes.c_int64, i32, i32, vp, ctypes.c_int64, vp]
     L.wn_set_ctc_probs.argtypes = [vp, vp, pi32, i32, i32, i32, i32, vp]
     L.wn_ctc_greedy_search.argtypes = [vp, i32, pi32, pi32, i32, vp]
+    L.wn_ctc_force_align.argtypes = [vp, i32, f32, pi32, pi32, i32, vp, pi32, i32, i32, i32,
+                                     pi32, POINTER(f32), pi32, POINTER(f32), POINTER(f32), vp]
     L.wn_set_context_graph.argtypes = [vp, i32, pi32, pf64, pf64, pf64, i32, pi32, pi32,
                                        pi32, vp]
     L.wn_ctc_prefix_beam_search.argtypes = [vp, i32, i32, pi32, pi32, pi32,

@@ -14,6 +14,11 @@
 
 feeds the file's features through one streaming session (wenet_amd.streaming) in chunk-sized
 pieces, prints every partial result that differs from the one before, then the final text.
+
+    python -m wenet_amd.bin.transcribe audio.wav -m /path/to/model_dir --align --label "TEXT"
+
+force-aligns the file with the given transcript (wenet/cli/transcribe.py:39-42 declares the two
+options) and prints the `.lab` lines of wenet/bin/alignment.py: `begin end token` per token.
 """
 import argparse
 import sys
@@ -35,7 +40,29 @@ def get_args(argv=None):
                    help='decode through a streaming session, printing partial results')
     p.add_argument('--chunk', type=int, default=16,
                    help='decoding_chunk_size of --stream (encoder frames per step)')
-    return p.parse_args(argv)
+    p.add_argument('--align', action='store_true',
+                   help='force align the input audio and transcript')
+    p.add_argument('--label', type=str, default=None, help='the input label to align')
+    args = p.parse_args(argv)
+    if args.align and args.label is None:
+        p.error('--align needs --label TEXT')
+    if args.label is not None and not args.align:
+        p.error('--label is only read with --align')
+    return args
+
+
+def align_file(model, audio_file, label, out=print):
+    """Force-align the file with `label`; `out` gets the .lab lines.  Returns the AlignResult."""
+    from wenet_amd.align import get_labformat
+    r = model.align_wav(audio_file, label)
+    if not r.ok:
+        raise SystemExit(f'--align: the {len(r.tokens)} tokens of the label do not fit into '
+                         f'the audio')
+    tok = model.tokenizer
+    char_dict = getattr(tok, 'char_dict', None) or getattr(tok, 'id2sym', None)
+    for line in get_labformat(r.frames, model.subsampling_rate(), char_dict):
+        out(line.rstrip('\n'))
+    return r
 
 
 def stream_file(model, audio_file, chunk, beam_size=10, out=print):
@@ -66,6 +93,9 @@ def main(argv=None):
     import torch
     import wenet_amd
     model = wenet_amd.load_model(args.model, device=args.device)
+    if args.align:
+        align_file(model, args.audio_file, args.label)
+        return 0
     if args.stream:
         if args.context_path is not None:
             raise SystemExit('--stream does not support --context_path')

@@ -361,6 +361,34 @@ int ctc_stream_reset(void* state, int* pool, int64_t pool_stride, int max_frames
                      const int* slot_dev, int n, hipStream_t s);
 int ctc_prefix_beam_stream(const StreamPrefixBeamArgs& a, hipStream_t s);
 
+// CTC forced alignment (ctc_align.hip).  Labels per utterance: lab[b][0] = blank, lab[b][1 + i] =
+// y[i], i < lab_len[b]; row pitch lab_pitch = longest label list + 1 = the width of E.
+struct AlignGatherArgs {
+  const float* x; int ld;          // [M][V] logits (normalize) or log-probs
+  int M, V;
+  int normalize;                   // take the log-softmax statistics of the row here
+  int blank; float blank_penalty;  // (normalize only)
+  const int* row_utt; int Tp;      // row -> utterance (-1: none), or null: row / Tp
+  const int* off; const int* len;  // [B] first row, rows of the utterance
+  const int* lab; int lab_pitch; const int* lab_len;
+  float* E; int ldE;               // [M][ldE]: E[row][j] = logp[row][lab[j]], j <= L; zeros behind
+};
+int ctc_align_gather(const AlignGatherArgs& a, hipStream_t s);
+constexpr int ALIGN_FAST_S = 256;  // states the one-wave trellis holds (4 per lane)
+struct AlignArgs {
+  const float* E; int ldE;
+  const int* off; const int* len; int B, Tp;
+  const int* lab; int lab_pitch; const int* lab_len;
+  unsigned char* bp; const int64_t* bp_off;   // back pointer workspace, byte offset per utterance
+  int fast_S;                      // = ALIGN_FAST_S
+  int* path;                       // [B][Tp], entries past the length untouched
+  float* frame_logp;               // [B][Tp][2]: E[t][blank], E[t][next label at or behind t]; or null
+  float* score; int* status;       // [B]; status 1 = infeasible (T < L + repeats), nothing written
+};
+int64_t ctc_align_bp_bytes(int T, int L, int fast_S);
+// max_fast_L / max_slow_L: the longest label list with 2 L + 1 <= / > ALIGN_FAST_S, -1 = none
+int ctc_align_viterbi(const AlignArgs& a, int max_fast_L, int max_slow_L, hipStream_t s);
+
 // Kaldi fbank (see fbank.hip).
 struct FbankArgs {
   const float* pcm;          // all utterances back to back, float in [-1, 1]

@@ -279,6 +279,10 @@ struct wn_model {
   bool pb_valid = false;
   int pb_B = 0, pb_beam = 0, pb_max_len = 0;
   size_t pb_o_sc = 0, pb_o_nh = 0, pb_o_len = 0, pb_o_tok = 0;
+  // forced alignment (cabi_align.hip): descriptors + labels | back pointers | results, one
+  // block: score | status | path | frame log-probs | emissions
+  DevBuf al_desc, al_bp, al_out;
+  PinnedBuf al_host;
   // rescoring
   DevBuf r_tok, r_rtok, r_pos, r_tgt, r_rtgt, r_qoff, r_qlen, r_kvoff, r_kvlen;
   DevBuf r_x, r_t1, r_t2, r_qkv, r_h, r_mem, r_logits, r_out;

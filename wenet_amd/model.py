@@ -969,6 +969,49 @@ class ASRModel:
                 f'feats_type {feats_type!r}: fbank and log_mel_spectrogram only')
         return feats[0, :int(lens[0])]
 
+    # ---- forced alignment (bin/alignment.py, ctc_utils.force_align) --------
+    def align(self, speech: torch.Tensor, speech_lengths: torch.Tensor, labels,
+              blank_id: int = 0, blank_penalty: float = 0.0, blank_thres: float = 0.999999,
+              thres: float = 0.000001, decoding_chunk_size: int = -1,
+              num_decoding_left_chunks: int = -1, return_raw: bool = False):
+        """CTC forced alignment of a batch against given label id lists (one per utterance):
+        encoder, CTC head, emission gather and Viterbi on the device (wn_ctc_force_align), then
+        the token groups / intervals of bin/alignment.py on the host.  Any batch size (the
+        reference's script takes one utterance at a time; decoding_chunk_size /
+        num_decoding_left_chunks as in decode()).  -> List[AlignResult]; an utterance whose
+        labels do not fit into its frames comes back with ok = False.  return_raw: also the
+        arrays of the C call (path, score, status, frame_logp, emit, lens)."""
+        from wenet_amd import align as A
+        assert speech.shape[0] == speech_lengths.shape[0] == len(labels)
+        labels = [[int(t) for t in (y.tolist() if hasattr(y, 'tolist') else y)] for y in labels]
+        speech, lens = self._prep(speech, speech_lengths)
+        assert decoding_chunk_size != 0
+        _, enc_lens, Tp = self._encode(speech, lens, decoding_chunk_size,
+                                       num_decoding_left_chunks, False)
+        raw = A.align_current_batch(self, labels, enc_lens, Tp, blank_id, blank_penalty,
+                                    want_emit=return_raw)
+        res = A.results_from_raw(raw, labels, self.subsampling_rate(), blank_id, blank_thres,
+                                 thres)
+        return (res, raw) if return_raw else res
+
+    def align_wav(self, wav: str, text: str, **kw):
+        """Align one wav file with its transcript (the model's tokenizer turns the text into
+        labels) -> AlignResult."""
+        from wenet_amd import align as A
+        from wenet_amd.tokenizer import get_blank_id
+        assert hasattr(self, 'tokenizer')
+        tok = self.tokenizer
+        labels = A.tokenize_text(text, tok.symbol_table, getattr(tok, 'bpe_path', None),
+                                 getattr(tok, 'kind', None))
+        if 'blank_id' not in kw:
+            try:
+                kw['blank_id'] = get_blank_id(dict(self.configs), tok.symbol_table)
+            except AssertionError:
+                kw['blank_id'] = 0
+        speech = self.compute_feature(wav)
+        return self.align(speech.unsqueeze(0), torch.tensor([speech.size(0)]), [labels],
+                          **kw)[0]
+
     def transcribe(self, wav: str) -> DecodeResult:
         """asr_model.py:345-358 (decode defaults: beam_size=1, ctc_weight=0)."""
         assert hasattr(self, 'tokenizer')
