@@ -594,6 +594,54 @@ int wn_op_log_add(const double* a_dev, const double* b_dev, double* out_dev,
 int wn_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev,
                     float* y_dev, int32_t M, int32_t D, float eps, void* stream);
 
+/* Operator hooks of the four kernel families that are not GEMMs (test infrastructure: the
+ * arguments of the library's own launchers, checked on the host BEFORE anything is launched, so
+ * that no accepted call can read or write outside the caller's buffers).  Offsets and lengths
+ * are HOST arrays; everything else is a device pointer. */
+typedef struct wn_attention_op {
+  const void* Q; const void* K; const void* V;   /* fp32 [rows][ld*]; d_k = 64 per head */
+  int32_t ldq, ldk, ldv;
+  int32_t q_rows, kv_rows;                        /* rows of the Q / O and of the K / V buffers */
+  const float* P; int32_t ldp, p_rows;            /* projected position table or NULL */
+  const int32_t* p_off;                           /* host [n_seq] or NULL */
+  const float* bias_u; const float* bias_v;       /* [n_heads][64], with P */
+  void* O; int32_t ldo;                           /* fp32, or bf16 with WN_ATTN_O_BF16 */
+  const int32_t* q_off; const int32_t* q_len;     /* host [n_seq]; ascending, disjoint */
+  const int32_t* kv_off; const int32_t* kv_len;   /* host [n_seq]; equal to q_*: self attention */
+  int32_t n_seq, n_heads;
+  int32_t mask_mode, chunk_size, left_chunks;     /* 0 keys < kv_len, 1 causal, 2 chunk window */
+  float scale;
+  int32_t flags;       /* WN_ATTN_* */
+  int32_t precision;   /* WN_PREC_F32 / WN_PREC_BF16 for this call */
+  int32_t x6_galign;   /* six-product form: key tiles on the global 32-row blocks */
+} wn_attention_op;
+#define WN_ATTN_FOLD 1       /* rel-pos term folded inside the kernel (AttnArgs::fold) */
+#define WN_ATTN_PREFOLD 2    /* ... by the separate pass (relpos_fold -> kbias); d = 256 / 512 */
+#define WN_ATTN_QKV_BF16 4   /* precision 1: Q, K, V converted to bf16 matrices first (dense ld) */
+#define WN_ATTN_O_BF16 8     /* precision 1: O is a bf16 matrix, ldo in elements */
+/* *form_out = the kernel form the dispatch chose: kind | key_split << 4 | waves << 8 |
+ * relpos << 12 | bf16_inputs << 13 | key_bias << 14; kind: 0 plain, 1 rel-pos (two contractions),
+ * 2 rel-pos folded in the kernel, 3 six-product, 4 bf16 register-staged, 5 bf16 LDS-DMA. */
+int wn_op_attention(const wn_attention_op* op, int32_t* form_out, void* stream);
+/* Depthwise conv over time + LayerNorm (norm_mode 0) / affine (1) + SiLU over packed rows:
+ * x [M][ldx], wt [K][D], y [M][ldy]; off / len host [B]; rows no utterance owns are skipped. */
+int wn_op_dwconv(const float* x, int32_t ldx, const float* wt, const float* bias,
+                 const float* cpad, const float* ln_w, const float* ln_b, int32_t norm_mode,
+                 float* y, int32_t ldy, const int32_t* off, const int32_t* len, int32_t B,
+                 int32_t M, int32_t D, int32_t K, int32_t causal, int32_t t_max, float eps,
+                 void* stream);
+/* GlobalCMVN (mean NULL: none) + Conv2d(1, C, 3, stride 2) + ReLU: feats (B, T, F), w [9][C],
+ * out [out_rows][(F - 1) / 2][C]; t1_off / t1_len host [B].  plane_image != 0: through the
+ * plane-image form of the six-product conv2 and back to the same layout. */
+int wn_op_conv1(const float* feats, const float* mean, const float* istd, const float* w,
+                const float* bias, float* out, const int32_t* t1_off, const int32_t* t1_len,
+                int32_t B, int32_t T, int32_t F, int32_t C, int32_t out_rows,
+                int32_t plane_image, void* stream);
+/* CTC head tail: blank penalty, log-softmax, top-k (logp NULL: the top-k only). */
+int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_t k,
+                   int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,
+                   float* logp, int32_t ld_out, void* stream);
+
 /* Measurement hook for bench.py: bracket launches of the dominant kernel (the
  * FFN w_1 GEMM, positionwise_feed_forward.py:58; every 6th launch, because each
  * event pair idles the GPU for ~10 us) with HIP events on the launch stream.  wn_profile_collect waits for them and returns the number of

@@ -540,15 +540,21 @@ def feed_forward(x, sd, pfx, activation):
                     sd[pfx + 'w_2.weight'], sd[pfx + 'w_2.bias'])
 
 
+def _at_least_f32(scores):
+    """`scores.float()` of attention.py:153,163 (softmax in fp32 under autocast); fp64 scores
+    -- the operator references of tests/test_kernel_refs.py run the module in fp64 -- stay fp64."""
+    return scores if scores.dtype == torch.float64 else scores.float()
+
+
 def _forward_attention(value, scores, mask, sd, pfx, h, d_k):
     """wenet/models/transformer/attention.py:133-178."""
     if mask.size(-1) > 0:
         m = mask.unsqueeze(-3).eq(0)
         m = m[..., :scores.size(-1)]
         scores = scores.masked_fill(m, -float('inf'))
-        attn = torch.softmax(scores.float(), dim=-1).masked_fill(m, 0.0)
+        attn = torch.softmax(_at_least_f32(scores), dim=-1).masked_fill(m, 0.0)
     else:
-        attn = torch.softmax(scores.float(), dim=-1)
+        attn = torch.softmax(_at_least_f32(scores), dim=-1)
     x = _mm(attn, value)
     x = x.transpose(-3, -2).contiguous()
     x = x.view(x.size()[:-2] + (h * d_k, ))

@@ -1,0 +1,435 @@
+"""Plain references of the four kernel families that are not GEMMs -- attention, depthwise conv +
+norm + SiLU, CMVN + conv1 + ReLU, CTC log-softmax + top-k -- and the input regimes the operator
+tests run them on (tests/test_kernel_refs.py on the CPU, tests/test_gpu_kernels.py on the GPU).
+
+Every `ref_*` is written from the reference's module text (the citations of
+oracle/wenet_oracle.py), at the level of loops, einsum-like matmuls and torch.nn.functional
+convolutions, in fp64.  `fp32=True` evaluates the SAME plain formula in fp32 (`bf16=True`, attention
+only: Q (+ bias), K, V, P and the probabilities rounded to bf16, fp32 accumulation): the distance
+of that evaluation from the fp64 one is the yardstick `e_plain` of the GPU tolerances.
+
+No GPU and no oracle import in here.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+ULP32 = 2.0 ** -23
+
+
+def _r16(t):
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def bf16_representable(t):
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+# ---------------------------------------------------------------------------------------------
+# attention
+
+
+def chunk_window(n_q, n_kv, mask_mode, chunk, left):
+    """Visible keys as a (n_q, n_kv) bool matrix: mode 0 every key, mode 1 subsequent_mask
+    (mask.py:51-85: key j <= query i), mode 2 subsequent_chunk_mask (mask.py:88-123: keys from
+    `left` chunks back -- `left` < 0: from the start -- to the end of the query's own chunk)."""
+    vis = torch.zeros(n_q, n_kv, dtype=torch.bool)
+    for i in range(n_q):
+        if mask_mode == 0:
+            lo, hi = 0, n_kv
+        elif mask_mode == 1:
+            lo, hi = 0, min(i + 1, n_kv)
+        else:
+            lo = 0 if left < 0 else max((i // chunk - left) * chunk, 0)
+            hi = min((i // chunk + 1) * chunk, n_kv)
+        vis[i, lo:hi] = True
+    return vis
+
+
+def ref_attention(q, k, v, pos, bias_u, bias_v, seqs, mask_mode=0, chunk=0, left=-1,
+                  scale=0.125, fp32=False, bf16=False, want_weights=False):
+    """q (q_rows, H * 64), k / v (kv_rows, H * 64), pos (p_rows, H * 64) or None, bias_u / bias_v
+    (H, 64); seqs = [(q_off, q_len, kv_off, kv_len, p_off)].  Per (sequence, head):
+    softmax(mask(((q + u) k^T + (q + v) p^T) * scale)) v  (attention.py:133-178, 410-428; no
+    rel_shift: key j uses position row p_off + j).  Returns (q_rows, H * 64) fp64, zero in rows no
+    sequence owns; with want_weights also the largest weight of every owned (row, head)."""
+    dt = torch.float32 if (fp32 or bf16) else torch.float64
+    rnd = _r16 if bf16 else (lambda t: t)
+    H = q.shape[1] // 64
+    out = torch.zeros(q.shape[0], H * 64, dtype=torch.float64)
+    wmax = []
+    for (qo, ql, ko, kl, po) in seqs:
+        if ql == 0:
+            continue
+        qs = q[qo:qo + ql].to(dt).view(ql, H, 64).transpose(0, 1)       # (H, ql, 64)
+        ks = rnd(k[ko:ko + kl].to(dt)).view(kl, H, 64).transpose(0, 1)
+        vs = rnd(v[ko:ko + kl].to(dt)).view(kl, H, 64).transpose(0, 1)
+        if pos is not None:
+            ps = rnd(pos[po:po + kl].to(dt)).view(kl, H, 64).transpose(0, 1)
+            qu = rnd(qs + bias_u.to(dt).unsqueeze(1))
+            qv = rnd(qs + bias_v.to(dt).unsqueeze(1))
+            scores = (torch.matmul(qu, ks.transpose(1, 2)) +
+                      torch.matmul(qv, ps.transpose(1, 2))) * scale
+        else:
+            scores = torch.matmul(rnd(qs), ks.transpose(1, 2)) * scale
+        hidden = ~chunk_window(ql, kl, mask_mode, chunk, left)
+        scores = scores.masked_fill(hidden, -float('inf'))
+        attn = torch.softmax(scores, dim=-1).masked_fill(hidden, 0.0)
+        if want_weights:
+            wmax.append(attn.max(dim=-1).values.reshape(-1).double())
+        o = torch.matmul(rnd(attn), vs)                                  # (H, ql, 64)
+        out[qo:qo + ql] = o.transpose(0, 1).reshape(ql, H * 64).double()
+    if want_weights:
+        return out, torch.cat(wmax)
+    return out
+
+
+def visible_v_scale(v, seqs):
+    """max |v| over the keys of the sequences: the scale of an attention output (a convex
+    combination of them)."""
+    m = 0.0
+    for (_, ql, ko, kl, _) in seqs:
+        if ql > 0:
+            m = max(m, v[ko:ko + kl].abs().max().item())
+    return m
+
+
+POISON = 1e18
+
+
+def pack_layout(lens, gap, lead):
+    """Offsets of a packed ragged batch: `lead` unowned rows in front, `gap` unowned rows behind
+    every sequence.  Returns (offsets, total rows)."""
+    offs, at = [], lead
+    for n in lens:
+        offs.append(at)
+        at += n + gap
+    return offs, max(at, 1)
+
+
+def make_attention_case(regime, H, q_lens, kv_lens=None, relpos=False, mask_mode=0, chunk=0,
+                        left=-1, seed=0, gap=3, lead=5, bf16=False, needle='first', param=None):
+    """Inputs of one attention case.  kv_lens None: self attention (one layout for Q and K / V).
+    Rows of K / V / Q no sequence owns hold +-POISON.  Regimes: see test_gpu_kernels.py."""
+    g = torch.Generator().manual_seed(seed)
+    self_attn = kv_lens is None
+    q_off, q_rows = pack_layout(q_lens, gap, lead)
+    if self_attn:
+        kv_lens, kv_off, kv_rows = list(q_lens), list(q_off), q_rows
+    else:
+        kv_off, kv_rows = pack_layout(kv_lens, gap + 1, lead + 2)
+    d = H * 64
+    scale = 0.125
+    q = torch.randn(q_rows, d, generator=g)
+    k = torch.randn(kv_rows, d, generator=g)
+    v = torch.randn(kv_rows, d, generator=g)
+    p_rows = max(kv_lens) + 7
+    p_off = [(3 * s) % 7 for s in range(len(q_lens))] if relpos else [0] * len(q_lens)
+    pos = torch.randn(p_rows, d, generator=g) if relpos else None
+    bu = torch.randn(H, 64, generator=g) * 0.5 if relpos else None
+    bv = torch.randn(H, 64, generator=g) * 0.5 if relpos else None
+    steer = regime in ('ascending', 'descending', 'shifted', 'needle')
+    if steer:
+        # coordinate 0 of every head steers the scores: keep the rel-pos term out of it
+        q.view(q_rows, H, 64)[:, :, 0] = 0
+        k.view(kv_rows, H, 64)[:, :, 0] = 0
+        if relpos:
+            pos.view(p_rows, H, 64)[:, :, 0] = 0
+            bu[:, 0] = 0
+            bv[:, 0] = 0
+    seqs = [(q_off[s], q_lens[s], kv_off[s], kv_lens[s], p_off[s]) for s in range(len(q_lens))]
+    q3, k3 = q.view(q_rows, H, 64), k.view(kv_rows, H, 64)
+    if regime == 'unit':
+        pass
+    elif regime == 'peaked':
+        # scale (q, u, v) together: the scores are linear in them
+        sd0 = _score_std(q, k, pos, bu, bv, seqs, scale)
+        c = float(param) / sd0
+        q *= c
+        if relpos:
+            bu *= c
+            bv *= c
+    elif regime in ('ascending', 'descending'):
+        step = float(param) * (1.0 if regime == 'ascending' else -1.0)
+        q3[:, :, 0] = 1.0 / scale
+        for (_, _, ko, kl, _) in seqs:
+            k3[ko:ko + kl, :, 0] = (torch.arange(kl, dtype=torch.float32) * step).unsqueeze(1)
+    elif regime == 'needle':
+        q3[:, :, 0] = 1.0 / scale
+        for (_, _, ko, kl, _) in seqs:
+            if kl == 0:
+                continue
+            if needle == 'last_visible':
+                # 40 more per key: under every mask the last visible key leads by 40
+                k3[ko:ko + kl, :, 0] = (torch.arange(kl, dtype=torch.float32) * 40.0).unsqueeze(1)
+                continue
+            tiles = (kl + 31) // 32
+            j = {'first': 0, '31': 31, '32': 32, 'last': kl - 1,
+                 'second_half': ((tiles + 1) // 2) * 32}[needle]
+            j = min(j, kl - 1)
+            # the other 63 coordinates give scores of a standard deviation near 1 (1.6 with the
+            # rel-pos term), at most ~8 over 1500 keys: 60 clears them by more than 40
+            k3[ko + j, :, 0] = 60.0
+    elif regime == 'shifted':
+        q3[:, :, 0] = float(param) / scale
+        k3[:, :, 0] = 1.0
+        v += 100.0
+    elif regime == 'tied':
+        q.zero_()
+        if relpos:
+            bu.zero_()
+            bv.zero_()
+    else:
+        raise ValueError(regime)
+    # unowned rows: large finite poison (the reference never reads them)
+    own_q = torch.zeros(q_rows, dtype=torch.bool)
+    own_k = torch.zeros(kv_rows, dtype=torch.bool)
+    for (qo, ql, ko, kl, _) in seqs:
+        own_q[qo:qo + ql] = True
+        own_k[ko:ko + kl] = True
+    sign = torch.where(torch.arange(d) % 2 == 0, 1.0, -1.0) * POISON
+    q[~own_q] = sign
+    k[~own_k] = -sign
+    v[~own_k] = sign
+    if bf16:
+        if relpos:
+            # The bf16 kernel rounds q + bias_u / q + bias_v: with free q and biases that rounding
+            # alone moves a score of standard deviation 10 by 0.04 and the plain bf16 evaluation
+            # breaks its cap (1.4e-2 of the scale at `peaked` 10).  So q and the biases go on a
+            # common grid of 256 steps per binade of their largest sum: q + u is then exact in
+            # bf16 and the rounding that is left is the one of the probabilities.  (The steering
+            # coordinate has zero biases and keeps its value.)
+            sl = slice(1, None) if steer else slice(None)
+            qq = q.view(q_rows, H, 64)
+            top = qq[own_q][:, :, sl].abs().max().item() + \
+                max(bu[:, sl].abs().max().item(), bv[:, sl].abs().max().item())
+            if top > 0:
+                grid = 2.0 ** math.ceil(math.log2(top)) / 256
+                qq[:, :, sl] = torch.round(qq[:, :, sl] / grid) * grid
+                bu[:, sl] = torch.round(bu[:, sl] / grid) * grid
+                bv[:, sl] = torch.round(bv[:, sl] / grid) * grid
+        q, k, v = bf16_representable(q), bf16_representable(k), bf16_representable(v)
+        if relpos:
+            pos, bu, bv = bf16_representable(pos), bf16_representable(bu), bf16_representable(bv)
+    return dict(q=q, k=k, v=v, pos=pos, bias_u=bu, bias_v=bv, seqs=seqs, H=H, scale=scale,
+                mask_mode=mask_mode, chunk=chunk, left=left, self_attn=self_attn,
+                q_rows=q_rows, kv_rows=kv_rows, own_q=own_q)
+
+
+def _score_std(q, k, pos, bu, bv, seqs, scale):
+    H = q.shape[1] // 64
+    vals = []
+    for (qo, ql, ko, kl, po) in seqs:
+        if ql == 0:
+            continue
+        qs = q[qo:qo + ql].double().view(ql, H, 64).transpose(0, 1)
+        ks = k[ko:ko + kl].double().view(kl, H, 64).transpose(0, 1)
+        if pos is not None:
+            ps = pos[po:po + kl].double().view(kl, H, 64).transpose(0, 1)
+            s = torch.matmul(qs + bu.double().unsqueeze(1), ks.transpose(1, 2)) + \
+                torch.matmul(qs + bv.double().unsqueeze(1), ps.transpose(1, 2))
+        else:
+            s = torch.matmul(qs, ks.transpose(1, 2))
+        vals.append((s * scale).reshape(-1))
+    return torch.cat(vals).std().item()
+
+
+def attention_refs(case, bf16=False):
+    """(fp64 reference, e_plain, scale, largest weight per (row, head)) of a case."""
+    args = (case['q'], case['k'], case['v'], case['pos'], case['bias_u'], case['bias_v'],
+            case['seqs'], case['mask_mode'], case['chunk'], case['left'], case['scale'])
+    ref, w = ref_attention(*args, want_weights=True)
+    plain = ref_attention(*args, fp32=not bf16, bf16=bf16)
+    return ref, (plain - ref).abs().max().item(), visible_v_scale(case['v'], case['seqs']), w
+
+
+# ---------------------------------------------------------------------------------------------
+# depthwise conv + LayerNorm / affine + SiLU
+
+
+def ref_dwconv(x, wt, bias, cpad, ln_w, ln_b, norm_mode, off, lens, K, causal, t_max, eps,
+               fp32=False):
+    """x (M, D) packed rows, wt (K, D) tap-major.  Per utterance the (t_max, D) tensor whose rows
+    >= len are `cpad` (masked_fill before pointwise_conv1, convolution.py:115-117, seen behind
+    it), causal: K - 1 rows of `cpad` in front (:122-124), symmetric: (K - 1) / 2 zero rows on
+    both sides (Conv1d padding); depthwise conv, LayerNorm over channels (mode 0) or the
+    per-channel affine of eval-mode BatchNorm1d (mode 1), SiLU (:132-146).  Returns (M, D) fp64,
+    zero in rows no utterance owns."""
+    dt = torch.float32 if fp32 else torch.float64
+    M, D = x.shape
+    out = torch.zeros(M, D, dtype=torch.float64)
+    w = wt.to(dt).t().contiguous().unsqueeze(1)            # (D, 1, K)
+    for o, n in zip(off, lens):
+        if n == 0:
+            continue
+        X = cpad.to(dt).unsqueeze(0).repeat(t_max, 1)
+        X[:n] = x[o:o + n].to(dt)
+        if causal:
+            X = torch.cat([cpad.to(dt).unsqueeze(0).repeat(K - 1, 1), X], 0)
+        else:
+            z = torch.zeros((K - 1) // 2, D, dtype=dt)
+            X = torch.cat([z, X, z], 0)
+        y = F.conv1d(X.t().unsqueeze(0), w, bias.to(dt), groups=D)[0].t()   # (t_max, D)
+        if norm_mode == 0:
+            y = F.layer_norm(y, (D, ), ln_w.to(dt), ln_b.to(dt), eps)
+        else:
+            y = y * ln_w.to(dt) + ln_b.to(dt)
+        y = y * torch.sigmoid(y)
+        out[o:o + n] = y[:n].double()
+    return out
+
+
+def make_dwconv_case(D, K, causal, norm_mode, lens, seed=0, gap=1, lead=0, t_extra=0, pad_ld=0,
+                     offset=0.0, tail=3):
+    g = torch.Generator().manual_seed(seed)
+    off, M = pack_layout(lens, gap, lead)
+    M += tail
+    x = torch.randn(M, D, generator=g)
+    if offset:
+        x += offset * torch.where(torch.arange(M) % 2 == 0, 1.0, -1.0).unsqueeze(1)
+    own = torch.zeros(M, dtype=torch.bool)
+    for o, n in zip(off, lens):
+        own[o:o + n] = True
+    x[~own] = torch.where(torch.arange(D) % 2 == 0, 1.0, -1.0) * POISON
+    wt = torch.randn(K, D, generator=g) / math.sqrt(K)
+    return dict(x=x, wt=wt, bias=torch.randn(D, generator=g) * 0.3,
+                cpad=torch.randn(D, generator=g),
+                ln_w=1.0 + 0.2 * torch.randn(D, generator=g), ln_b=0.2 * torch.randn(D, generator=g),
+                norm_mode=norm_mode, off=off, lens=list(lens), K=K, causal=causal,
+                t_max=max(lens) + t_extra, eps=1e-5, M=M, D=D, own=own, pad_ld=pad_ld)
+
+
+def dwconv_refs(c):
+    args = (c['x'], c['wt'], c['bias'], c['cpad'], c['ln_w'], c['ln_b'], c['norm_mode'], c['off'],
+            c['lens'], c['K'], c['causal'], c['t_max'], c['eps'])
+    ref = ref_dwconv(*args)
+    plain = ref_dwconv(*args, fp32=True)
+    return ref, (plain - ref).abs().max().item(), ref.abs().max().item()
+
+
+# ---------------------------------------------------------------------------------------------
+# CMVN + Conv2d(1, C, 3, stride 2) + ReLU
+
+
+def ref_conv1(feats, mean, istd, w, bias, t1_lens, fp32=False):
+    """feats (B, T, F), w (C, 1, 3, 3).  (x - mean) * istd (cmvn.py:36-47), Conv2d stride 2 +
+    ReLU (subsampling.py:188-190), channels last; utterance b keeps its first t1_lens[b] frames.
+    Returns a list of (t1_len, F1, C) fp64 tensors."""
+    dt = torch.float32 if fp32 else torch.float64
+    outs = []
+    for b, n in enumerate(t1_lens):
+        x = feats[b].to(dt)
+        if mean is not None:
+            x = (x - mean.to(dt)) * istd.to(dt)
+        y = F.relu(F.conv2d(x.unsqueeze(0).unsqueeze(0), w.to(dt), bias.to(dt), stride=2))[0]
+        outs.append(y.permute(1, 2, 0)[:n].double())
+    return outs
+
+
+def make_conv1_case(Fdim, C, t1_lens, cmvn=True, seed=0, gap=1, lead=2):
+    g = torch.Generator().manual_seed(seed)
+    B = len(t1_lens)
+    T = 2 * max(max(t1_lens), 1) + 1 + 2
+    feats = torch.randn(B, T, Fdim, generator=g) * 3.0 + (11.0 if cmvn else 0.0)
+    # frames behind an utterance's last window: finite poison
+    for b, n in enumerate(t1_lens):
+        feats[b, 2 * n + 1:] = POISON
+    mean = istd = None
+    if cmvn:
+        mean = 11.0 + torch.randn(Fdim, generator=g)
+        istd = 0.3 + 0.05 * torch.rand(Fdim, generator=g)
+    w = torch.randn(C, 1, 3, 3, generator=g) / 3.0
+    bias = torch.randn(C, generator=g) * 0.2
+    off, rows = pack_layout(t1_lens, gap, lead)
+    return dict(feats=feats, mean=mean, istd=istd, w=w, bias=bias, t1_lens=list(t1_lens), off=off,
+                rows=rows, F=Fdim, F1=(Fdim - 1) // 2, C=C, T=T, B=B)
+
+
+def conv1_refs(c):
+    args = (c['feats'], c['mean'], c['istd'], c['w'], c['bias'], c['t1_lens'])
+    ref = ref_conv1(*args)
+    plain = ref_conv1(*args, fp32=True)
+    e = max([(p - r).abs().max().item() for p, r in zip(plain, ref) if r.numel()] + [0.0])
+    s = max([r.abs().max().item() for r in ref if r.numel()] + [0.0])
+    return ref, e, s
+
+
+# ---------------------------------------------------------------------------------------------
+# CTC rows
+
+
+def ref_ctc_rows(logits, blank, penalty, k, fp32=False):
+    """logits (M, V): blank penalty (asr_model.py:258-259), log_softmax (ctc.py:73-81), topk
+    (search.py:158).  Returns (logp, topk_val, topk_idx)."""
+    dt = torch.float32 if fp32 else torch.float64
+    x = logits.to(dt).clone()
+    x[:, blank] -= penalty
+    logp = x.log_softmax(dim=1)
+    val, idx = logp.topk(k, dim=1)
+    return logp.double(), val.double(), idx
+
+
+def make_ctc_case(regime, M, V, blank=0, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, V, generator=g) * 3.0
+    x[:, blank] += 4.0                                   # the blank boost of a CTC head
+    if regime == 'randn':
+        pass
+    elif regime == 'shift_up':
+        x = (x.double() + 1e4).float()                   # shifted before the fp32 rounding
+    elif regime == 'shift_down':
+        x = (x.double() - 1e4).float()
+    elif regime == 'spread':
+        x = torch.rand(M, V, generator=g) * 300.0
+    elif regime == 'ties':
+        # few distinct values: exact ties among the leaders of every row
+        x = torch.randint(0, 3, (M, V), generator=g).float() * 2.0
+    else:
+        raise ValueError(regime)
+    return x
+
+
+def ctc_refs(x, blank, penalty, k):
+    logp, val, idx = ref_ctc_rows(x, blank, penalty, k)
+    logp32, _, _ = ref_ctc_rows(x, blank, penalty, k, fp32=True)
+    return logp, val, idx, (logp32 - logp).abs().max().item(), logp.abs().max().item()
+
+
+# (regime, param) of every attention data regime; the operator tests run each of them
+ATTENTION_REGIMES = [('unit', None), ('peaked', 10.0), ('peaked', 30.0), ('ascending', 1.0),
+                     ('ascending', 0.375), ('descending', 1.0), ('descending', 0.375),
+                     ('needle', 'first'), ('needle', '31'), ('needle', '32'), ('needle', 'last'),
+                     ('needle', 'second_half'), ('needle', 'last_visible'), ('shifted', 80.0),
+                     ('shifted', -80.0), ('tied', None)]
+# regimes whose reference weights must be peaked: (smallest share of (row, head) pairs whose
+# largest weight exceeds 0.5; a noiseless 1-per-key ramp puts 0.63 on its leader, the unit noise
+# of the other 63 coordinates takes some rows below one half).  The 0.375-per-key ramps move the maximum in every tile but
+# spread the weight over ~3 keys; they are not in this list.
+NON_FLAT = {('peaked', 10.0): 0.5, ('peaked', 30.0): 0.8, ('ascending', 1.0): 0.5,
+            ('descending', 1.0): 0.5, ('needle', 'first'): 0.95, ('needle', '31'): 0.9,
+            ('needle', '32'): 0.9, ('needle', 'last'): 0.95, ('needle', 'second_half'): 0.9,
+            ('needle', 'last_visible'): 0.95}
+
+
+def regime_case(regime, param, **kw):
+    if regime == 'needle':
+        return make_attention_case('needle', needle=param, **kw)
+    return make_attention_case(regime, param=param, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# the tolerance of the issue: err <= margin * e_plain + floor, and the cap on the yardstick
+
+MARGIN_F32, MARGIN_BF16 = 8.0, 4.0
+CAP_F32, CAP_BF16 = 1e-3, 1e-2
+
+
+def bound(e_plain, scale, bf16=False):
+    if bf16:
+        return MARGIN_BF16 * e_plain + 2.0 ** -9 * scale
+    return MARGIN_F32 * e_plain + 16 * ULP32 * scale
+
+
+def cap_ok(e_plain, scale, bf16=False):
+    return e_plain <= (CAP_BF16 if bf16 else CAP_F32) * scale

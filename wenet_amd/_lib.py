@@ -36,6 +36,21 @@ class WnStreamResult(Structure):
                 ('trailing_blank', POINTER(c_int32)), ('max_len', c_int32)]
 
 
+class WnAttentionOp(Structure):
+    """wn_attention_op: the arguments of wn_op_attention."""
+    _fields_ = [('Q', c_void_p), ('K', c_void_p), ('V', c_void_p),
+                ('ldq', c_int32), ('ldk', c_int32), ('ldv', c_int32),
+                ('q_rows', c_int32), ('kv_rows', c_int32),
+                ('P', c_void_p), ('ldp', c_int32), ('p_rows', c_int32),
+                ('p_off', POINTER(c_int32)), ('bias_u', c_void_p), ('bias_v', c_void_p),
+                ('O', c_void_p), ('ldo', c_int32),
+                ('q_off', POINTER(c_int32)), ('q_len', POINTER(c_int32)),
+                ('kv_off', POINTER(c_int32)), ('kv_len', POINTER(c_int32)),
+                ('n_seq', c_int32), ('n_heads', c_int32), ('mask_mode', c_int32),
+                ('chunk_size', c_int32), ('left_chunks', c_int32), ('scale', c_float),
+                ('flags', c_int32), ('precision', c_int32), ('x6_galign', c_int32)]
+
+
 # every symbol include/wenet_amd.h declares
 EXPORTS = [
     'wn_last_error', 'wn_version', 'wn_model_create', 'wn_model_destroy', 'wn_model_clone',
@@ -45,7 +60,8 @@ EXPORTS = [
     'wn_workspace_create', 'wn_resample_length', 'wn_resample', 'wn_fbank', 'wn_log_mel', 'wn_encode', 'wn_encode_chunk', 'wn_set_encoder_out',
     'wn_ctc_logprobs', 'wn_set_ctc_probs', 'wn_ctc_greedy_search', 'wn_ctc_force_align',
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
-    'wn_op_layernorm', 'wn_op_log_add', 'wn_debug_set', 'wn_profile_enable',
+    'wn_op_layernorm', 'wn_op_log_add', 'wn_op_attention', 'wn_op_dwconv', 'wn_op_conv1',
+    'wn_op_ctc_rows', 'wn_debug_set', 'wn_profile_enable',
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
     'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
     'wn_stream_advance', 'wn_stream_advance_encoded',
@@ -143,6 +159,12 @@ def lib():
     L.wn_model_set_encode_gate.argtypes = [vp, vp]
     L.wn_op_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp]
     L.wn_op_log_add.argtypes = [vp, vp, vp, i32, vp]
+    L.wn_op_attention.argtypes = [POINTER(WnAttentionOp), pi32, vp]
+    L.wn_op_dwconv.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, pi32, pi32, i32, i32,
+                               i32, i32, i32, i32, f32, vp]
+    L.wn_op_conv1.argtypes = [vp, vp, vp, vp, vp, vp, pi32, pi32, i32, i32, i32, i32, i32, i32,
+                              vp]
+    L.wn_op_ctc_rows.argtypes = [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp]
     L.wn_debug_set.argtypes = [vp, c_char_p, i32]
     L.wn_tune_set.argtypes = [c_char_p, i32]
     L.wn_model_tune_set.argtypes = [vp, c_char_p, i32]

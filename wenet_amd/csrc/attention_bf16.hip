@@ -851,11 +851,11 @@ int launch(const AttnArgs& a, hipStream_t s) {
 }  // namespace
 
 
-int attention_bf16(const AttnArgs& a, hipStream_t s) {
-  // argument checks are attention()'s (the only caller)
-  WN_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldp % 4 == 0,
-           "attention(bf16): strides must be multiples of 4 elements");
-  WN_CHECK(!(a.qkv_bf16 && a.P), "attention(bf16): bf16 Q/K/V only without the rel-pos term");
+AttnForm attention_bf16_form(const AttnArgs& a) {
+  AttnForm f;
+  f.kind = ATTN_BF16; f.ks = 1;
+  f.relpos = !a.qkv_bf16 && a.P != nullptr;
+  f.in16 = a.qkv_bf16;
   int nw = tune().attn_bf16_nw;
   if (nw != 2 && nw != 4 && nw != 8)
     nw = a.max_q_len >= 1024 ? 8 : a.max_q_len >= 384 ? 4 : 2;
@@ -869,11 +869,24 @@ int attention_bf16(const AttnArgs& a, hipStream_t s) {
     // barrier groups of four waves lose less to skew than groups of eight (config 5 fp8: 14.81 k
     // vs 14.62 k, r05v); attn_bf16_nw = 8 forces the 256-query blocks
     if (tune().attn_bf16_nw != 8) nw = 4;
+    f.kind = ATTN_BF16_DMA;
+  }
+  f.nw = nw;
+  return f;
+}
+
+int attention_bf16(const AttnArgs& a, hipStream_t s) {
+  // argument checks are attention()'s (the only caller)
+  WN_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldp % 4 == 0,
+           "attention(bf16): strides must be multiples of 4 elements");
+  WN_CHECK(!(a.qkv_bf16 && a.P), "attention(bf16): bf16 Q/K/V only without the rel-pos term");
+  const AttnForm f = attention_bf16_form(a);
+  if (f.kind == ATTN_BF16_DMA) {
     AttnArgs d = a;
     d.defer_thr = 0.1f * (float)tune().attn_bf16_defer;
-    return nw == 8 ? launch_dma_tra<8>(d, s) : launch_dma_tra<4>(d, s);
+    return f.nw == 8 ? launch_dma_tra<8>(d, s) : launch_dma_tra<4>(d, s);
   }
-  switch (nw) {
+  switch (f.nw) {
     case 8: return launch<8>(a, s);
     case 4: return launch<4>(a, s);
     default: return launch<2>(a, s);

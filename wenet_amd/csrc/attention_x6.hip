@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void attn_x6_pack_kernel(AttnArgs a, char* img
     if constexpr (GAL) {
       const int g = min(t * KT + r, a.x6_rows - 1);
       const int u = a.row_utt[g];
-      *prow = g - a.kv_off[u] + (a.p_off ? a.p_off[u] : 0);
+      // (a row no sequence owns: no kernel reads its slots unmasked; position row 0)
+      *prow = u < 0 ? 0 : g - a.kv_off[u] + (a.p_off ? a.p_off[u] : 0);
       return g;
     } else {
       const int j = min(t * KT + r, kvlen - 1);

@@ -1,6 +1,54 @@
 // C ABI (include/wenet_amd.h): the operator hooks (wn_op_*) the tests and tools call kernels
 // through.
 #include "model_state.h"
+#include "x6.h"
+
+namespace wn {
+namespace {
+
+// wn_op_conv1: the plane image cmvn_conv1_x3_kernel wrote (one image row per pixel, even f1
+// first) back to fp32 h0 + h1 + h2 in the [frame][F1][C] layout; one thread per (pixel, 8 channels)
+__global__ __launch_bounds__(256) void conv1_image_unpack_kernel(
+    const char* __restrict__ img, int tiles, const int* __restrict__ t1_off,
+    const int* __restrict__ t1_len, int F1, int C, float* __restrict__ out) {
+  const int b = blockIdx.y;
+  const int n = t1_len[b] * F1 * (C / 8);
+  const int ne = (F1 + 1) / 2;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int cg = i % (C / 8), px = i / (C / 8);
+    const int fr = px / F1, pos = px - fr * F1;
+    const int f1 = pos < ne ? 2 * pos : 2 * (pos - ne) + 1;
+    const int row = (t1_off[b] + fr) * F1;
+    const char* src = img + x3_piece(cg >> 1, tiles, row + pos, cg & 1);
+    const bf16x8 p0 = *reinterpret_cast<const bf16x8*>(src);
+    const bf16x8 p1 = *reinterpret_cast<const bf16x8*>(src + X3_REC);
+    const bf16x8 p2 = *reinterpret_cast<const bf16x8*>(src + 2 * X3_REC);
+    float* o = out + ((int64_t)row + f1) * C + cg * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = ((float)p0[e] + (float)p1[e]) + (float)p2[e];
+  }
+}
+
+// host descriptor arrays of a hook call -> one device buffer (the copy is complete on return)
+int upload_ints(DevBuf& buf, const std::vector<int>& v, hipStream_t s) {
+  WN_TRY(buf.ensure(v.size() * sizeof(int)));
+  WN_HIP(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+// offsets / lengths of a packed ragged batch: inside [0, rows), ascending, disjoint
+bool packed_ok(const int32_t* off, const int32_t* len, int n, int rows) {
+  int64_t end = 0;
+  for (int i = 0; i < n; ++i) {
+    if (len[i] < 0 || off[i] < end || (int64_t)off[i] + len[i] > rows) return false;
+    end = (int64_t)off[i] + len[i];
+  }
+  return true;
+}
+
+}  // namespace
+}  // namespace wn
 
 // ===========================================================================
 extern "C" {
@@ -235,6 +283,205 @@ int wn_op_log_add(const double* a_dev, const double* b_dev, double* out_dev,
 int wn_op_layernorm(const float* x, const float* w, const float* b, float* y,
                     int32_t M, int32_t D, float eps, void* stream) {
   return layernorm(x, D, w, b, y, D, M, D, eps, (hipStream_t)stream);
+}
+
+int wn_op_attention(const wn_attention_op* op, int32_t* form_out, void* stream) {
+  WN_CHECK(op && form_out, "attention: null argument");
+  const wn_attention_op& o = *op;
+  WN_CHECK(o.Q && o.K && o.V && o.O && o.q_off && o.q_len && o.kv_off && o.kv_len,
+           "attention: null argument");
+  WN_CHECK(o.n_seq > 0 && o.n_seq < 32768 && o.n_heads > 0 && o.n_heads < 256,
+           "attention: n_seq / n_heads");
+  const int H = o.n_heads, d = H * 64;
+  WN_CHECK(o.precision == PREC_F32 || o.precision == PREC_BF16, "attention: precision");
+  WN_CHECK(o.ldq % 4 == 0 && o.ldk % 4 == 0 && o.ldv % 4 == 0 && o.ldo % 4 == 0,
+           "attention: strides must be multiples of 4 elements");
+  WN_CHECK(o.ldq >= d && o.ldk >= d && o.ldv >= d && o.ldo >= d,
+           "attention: a stride is smaller than n_heads * 64");
+  WN_CHECK(o.q_rows > 0 && o.kv_rows > 0, "attention: empty buffers");
+  WN_CHECK(o.mask_mode >= 0 && o.mask_mode <= 2, "attention: mask mode");
+  WN_CHECK(o.mask_mode != 2 || o.chunk_size > 0, "attention: chunk size");
+  WN_CHECK(packed_ok(o.q_off, o.q_len, o.n_seq, o.q_rows),
+           "attention: query rows outside the buffer, unordered or overlapping");
+  bool self_attn = true;
+  int max_q = 0;
+  for (int s = 0; s < o.n_seq; ++s) {
+    WN_CHECK(o.kv_len[s] >= 0 && o.kv_off[s] >= 0 &&
+                 (int64_t)o.kv_off[s] + o.kv_len[s] <= o.kv_rows,
+             "attention: key rows outside the buffer");
+    WN_CHECK(o.q_len[s] == 0 || o.kv_len[s] > 0, "attention: queries without keys");
+    self_attn = self_attn && o.q_off[s] == o.kv_off[s] && o.q_len[s] == o.kv_len[s];
+    max_q = std::max(max_q, o.q_len[s]);
+  }
+  WN_CHECK(max_q > 0, "attention: empty");
+  const bool fold = (o.flags & WN_ATTN_FOLD) != 0, prefold = (o.flags & WN_ATTN_PREFOLD) != 0;
+  const bool in16 = (o.flags & WN_ATTN_QKV_BF16) != 0, o16 = (o.flags & WN_ATTN_O_BF16) != 0;
+  WN_CHECK(!(fold && prefold), "attention: fold and prefold exclude each other");
+  WN_CHECK(!((fold || prefold) && !o.P), "attention: folding needs the position table");
+  if (o.P) {
+    WN_CHECK(o.bias_u && o.bias_v, "attention: rel-pos needs bias_u and bias_v");
+    WN_CHECK(o.ldp % 4 == 0 && o.ldp >= d && o.p_rows > 0, "attention: position table stride");
+    for (int s = 0; s < o.n_seq; ++s) {
+      const int po = o.p_off ? o.p_off[s] : 0;
+      WN_CHECK(po >= 0 && (int64_t)po + o.kv_len[s] <= o.p_rows,
+               "attention: position rows outside the table");
+    }
+  }
+  WN_CHECK(!(in16 || o16) || o.precision == PREC_BF16,
+           "attention: bf16 matrices only with precision 1");
+  WN_CHECK(!in16 || (!o.P && o.ldq == d && o.ldk == d && o.ldv == d),
+           "attention: bf16 Q/K/V without rel-pos and with dense rows only");
+  WN_CHECK(!prefold || (o.precision == PREC_F32 && (d == 256 || d == 512) && self_attn),
+           "attention: prefold needs fp32, d = 256 / 512, self attention");
+  WN_CHECK(o.x6_galign == 0 || o.x6_galign == 1, "attention: x6_galign");
+
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc, img, q16, kfold, kb;
+  // descriptor block: q_off | q_len | kv_off | kv_len | p_off | row_utt (of the K / V rows)
+  const int n = o.n_seq;
+  std::vector<int> h((size_t)5 * n + o.kv_rows, -1);
+  for (int i = 0; i < n; ++i) {
+    h[i] = o.q_off[i]; h[n + i] = o.q_len[i]; h[2 * n + i] = o.kv_off[i];
+    h[3 * n + i] = o.kv_len[i]; h[4 * n + i] = o.p_off ? o.p_off[i] : 0;
+    for (int t = 0; t < o.kv_len[i]; ++t) h[5 * n + o.kv_off[i] + t] = i;
+  }
+  WN_TRY(upload_ints(desc, h, s));
+  const int* dd = desc.as<int>();
+  AttnArgs a;
+  a.Q = (const float*)o.Q; a.K = (const float*)o.K; a.V = (const float*)o.V;
+  a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv;
+  a.O = (float*)o.O; a.ldo = o.ldo; a.o_bf16 = o16;
+  a.q_off = dd; a.q_len = dd + n;
+  // self attention hands the launchers ONE offset / length array, as the encoder does
+  a.kv_off = self_attn ? a.q_off : dd + 2 * n;
+  a.kv_len = self_attn ? a.q_len : dd + 3 * n;
+  a.n_seq = n; a.n_heads = H; a.max_q_len = max_q;
+  a.mask_mode = o.mask_mode; a.chunk_size = o.chunk_size; a.left_chunks = o.left_chunks;
+  a.scale = o.scale;
+  if (o.P && !prefold) {
+    a.P = o.P; a.ldp = o.ldp; a.p_off = o.p_off ? dd + 4 * n : nullptr;
+    a.bias_u = o.bias_u; a.bias_v = o.bias_v; a.fold = fold;
+  }
+  if (prefold) {
+    // the fold as its own pass over a copy of the key rows (tune attn_fold = 2 in the encoder)
+    WN_TRY(kfold.ensure((size_t)o.kv_rows * d * sizeof(float)));
+    WN_TRY(kb.ensure((size_t)o.kv_rows * H * sizeof(float)));
+    WN_HIP(hipMemcpy2DAsync(kfold.p, (size_t)d * 4, o.K, (size_t)o.ldk * 4, (size_t)d * 4,
+                            o.kv_rows, hipMemcpyDeviceToDevice, s));
+    WN_TRY(relpos_fold(kfold.as<float>(), d, o.P, o.ldp, o.bias_u, o.bias_v, dd + 5 * n,
+                       dd + 2 * n, o.p_off ? dd + 4 * n : nullptr, kb.as<float>(), H, o.kv_rows,
+                       d, s));
+    a.K = kfold.as<float>(); a.ldk = d; a.kbias = kb.as<float>();
+  }
+  if (in16) {
+    const size_t nq = (size_t)o.q_rows * d, nk = (size_t)o.kv_rows * d;
+    WN_TRY(q16.ensure((nq + 2 * nk) * 2));
+    char* base = q16.as<char>();
+    WN_TRY(convert_f32_to_bf16((const float*)o.Q, base, (int64_t)nq, s));
+    WN_TRY(convert_f32_to_bf16((const float*)o.K, base + nq * 2, (int64_t)nk, s));
+    WN_TRY(convert_f32_to_bf16((const float*)o.V, base + (nq + nk) * 2, (int64_t)nk, s));
+    a.Q = (const float*)base; a.K = (const float*)(base + nq * 2);
+    a.V = (const float*)(base + (nq + nk) * 2);
+    a.qkv_bf16 = true;
+  }
+  if (o.precision == PREC_F32 && self_attn && a.P && a.fold) {
+    // the six-product form's scratch image (the pack pass of this launch fills it)
+    WN_TRY(img.ensure(attention_x6_image_bytes(o.kv_rows, n, H)));
+    a.x6_img = img.p; a.x6_img_bytes = img.cap; a.x6_rows = o.kv_rows;
+    if (o.x6_galign) { a.x6_galign = 1; a.row_utt = dd + 5 * n; }
+  }
+  const int saved = t_gemm_prec;
+  t_gemm_prec = o.precision;
+  *form_out = attention_form(a).code();
+  const int r = attention(a, s);
+  t_gemm_prec = saved;
+  return r;
+}
+
+int wn_op_dwconv(const float* x, int32_t ldx, const float* wt, const float* bias,
+                 const float* cpad, const float* ln_w, const float* ln_b, int32_t norm_mode,
+                 float* y, int32_t ldy, const int32_t* off, const int32_t* len, int32_t B,
+                 int32_t M, int32_t D, int32_t K, int32_t causal, int32_t t_max, float eps,
+                 void* stream) {
+  WN_CHECK(x && wt && bias && cpad && ln_w && ln_b && y && off && len, "dwconv: null argument");
+  WN_CHECK(D == 64 || D == 128 || D == 256 || D == 512 || D == 768 || D == 1024 || D == 1280,
+           "dwconv: unsupported width " + std::to_string(D));
+  WN_CHECK(M > 0 && B > 0 && K >= 1 && K <= 255, "dwconv: M / B / K");
+  WN_CHECK(causal != 0 || K % 2 == 1, "dwconv: a symmetric kernel has an odd size");
+  WN_CHECK(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, "dwconv: strides");
+  WN_CHECK(norm_mode == 0 || norm_mode == 1, "dwconv: norm mode");
+  WN_CHECK(packed_ok(off, len, B, M), "dwconv: rows outside the buffer, unordered or overlapping");
+  std::vector<int> h((size_t)2 * B + M, -1);
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(len[b] <= t_max, "dwconv: t_max is smaller than a length");
+    h[b] = off[b]; h[B + b] = len[b];
+    for (int t = 0; t < len[b]; ++t) h[2 * B + off[b] + t] = b;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  DwConvArgs a;
+  a.x = x; a.ldx = ldx; a.wt = wt; a.bias = bias; a.cpad = cpad; a.ln_w = ln_w; a.ln_b = ln_b;
+  a.norm_mode = norm_mode; a.y = y; a.ldy = ldy;
+  a.off = desc.as<int>(); a.len = a.off + B; a.row_utt = a.off + 2 * B;
+  a.M = M; a.D = D; a.K = K; a.causal = causal != 0; a.t_max = t_max; a.eps = eps;
+  return dwconv_ln_silu(a, s);
+}
+
+int wn_op_conv1(const float* feats, const float* mean, const float* istd, const float* w,
+                const float* bias, float* out, const int32_t* t1_off, const int32_t* t1_len,
+                int32_t B, int32_t T, int32_t F, int32_t C, int32_t out_rows,
+                int32_t plane_image, void* stream) {
+  WN_CHECK(feats && w && bias && out && t1_off && t1_len, "conv1: null argument");
+  WN_CHECK((mean == nullptr) == (istd == nullptr), "conv1: mean and istd come together");
+  WN_CHECK(F >= 3 && F <= 128, "conv1: feature dim outside [3, 128]");
+  WN_CHECK(B > 0 && B < 65536 && T >= 3 && C > 0 && out_rows > 0, "conv1: B / T / C");
+  const int F1 = (F - 1) / 2;
+  WN_CHECK((int64_t)out_rows * F1 < ((int64_t)1 << 30), "conv1: too many pixels");
+  WN_CHECK(packed_ok(t1_off, t1_len, B, out_rows),
+           "conv1: frames outside the buffer, unordered or overlapping");
+  int max_t1 = 0;
+  std::vector<int> h((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(2 * (int64_t)t1_len[b] + 1 <= T, "conv1: T is too short for t1_len");
+    h[b] = t1_off[b]; h[B + b] = t1_len[b];
+    max_t1 = std::max(max_t1, t1_len[b]);
+  }
+  WN_CHECK(max_t1 > 0, "conv1: empty");
+  WN_CHECK(!plane_image || (F1 <= 64 && C % 32 == 0), "conv1: plane image shape");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc, img;
+  WN_TRY(upload_ints(desc, h, s));
+  Conv1Args a;
+  a.feats = feats; a.mean = mean; a.istd = istd; a.w = w; a.bias = bias; a.out = out;
+  a.t1_off = desc.as<int>(); a.t1_len = a.t1_off + B;
+  a.B = B; a.T = T; a.F = F; a.F1 = F1; a.C = C; a.max_t1 = max_t1;
+  if (plane_image) {
+    a.tiles = cdiv(out_rows * F1, 32);
+    WN_TRY(img.ensure(x6_bytes(a.tiles * 32, C)));
+    a.out3 = img.as<char>();
+    WN_TRY(cmvn_conv1_relu(a, s));
+    hipLaunchKernelGGL(conv1_image_unpack_kernel, dim3(cdiv(max_t1 * F1 * (C / 8), 256), B),
+                       dim3(256), 0, s, a.out3, a.tiles, a.t1_off, a.t1_len, F1, C, out);
+    WN_HIP(hipGetLastError());
+    return 0;
+  }
+  return cmvn_conv1_relu(a, s);
+}
+
+int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_t k,
+                   int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,
+                   float* logp, int32_t ld_out, void* stream) {
+  WN_CHECK(logits && topk_val && topk_idx, "ctc_rows: null argument");
+  WN_CHECK(M > 0 && V > 0 && ld >= V, "ctc_rows: M / V / ld");
+  WN_CHECK(k >= 1 && k <= V, "ctc: top-k must be in [1, vocab]");
+  WN_CHECK(blank >= 0 && blank < V, "ctc_rows: blank outside the vocabulary");
+  WN_CHECK(logp == nullptr || ld_out >= V, "ctc_rows: ld_out");
+  CtcRowArgs a;
+  a.logits = logits; a.ld = ld; a.M = M; a.V = V; a.k = k; a.blank = blank;
+  a.blank_penalty = blank_penalty; a.topk_val = topk_val; a.topk_idx = topk_idx;
+  a.logp = logp; a.ld_out = ld_out;
+  return ctc_logsoftmax_topk(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

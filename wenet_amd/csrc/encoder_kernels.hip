@@ -976,15 +976,34 @@ int relpos_fold(float* K, int ldk, const float* P, int ldp, const float* bias_u,
 }
 
 
+AttnForm attention_form(const AttnArgs& a) {
+  if (t_gemm_prec == PREC_BF16 && tune().attn_bf16 != 0) return attention_bf16_form(a);
+  AttnForm f;
+  if (t_gemm_prec == PREC_F32 && tune().attn_x6 != 0 && (a.mask_mode == 0 || tune().attn_x6 == 2) &&
+      attention_x6_supported(a)) {
+    f.kind = ATTN_X6; f.ks = 2;
+    return f;
+  }
+  // key split for the encoder's self attention over long sequences: twice the
+  // waves for the same tiles (tune().attn_split: 0 auto, 1 off, 2 on)
+  const bool split = tune().attn_split == 2 ||
+                     (tune().attn_split == 0 && (a.P != nullptr || a.kbias != nullptr) &&
+                      a.max_q_len >= 128);
+  const bool fold = a.P != nullptr && a.fold && a.bias_u && a.bias_v;
+  f.kind = fold ? ATTN_FOLD : a.P ? ATTN_RELPOS : ATTN_PLAIN;
+  f.ks = split ? 2 : 1;
+  f.kbias = !fold && !a.P && a.kbias != nullptr;
+  return f;
+}
+
 int attention(const AttnArgs& a, hipStream_t s) {
   WN_CHECK(a.n_seq > 0 && a.n_heads > 0 && a.max_q_len > 0, "attention: empty");
   WN_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0,
            "attention: strides must be multiples of 4 floats");
   WN_CHECK(a.mask_mode != 2 || a.chunk_size > 0, "attention: chunk size");
-  if (t_gemm_prec == PREC_BF16 && tune().attn_bf16 != 0) return attention_bf16(a, s);
-  if (t_gemm_prec == PREC_F32 && tune().attn_x6 != 0 && (a.mask_mode == 0 || tune().attn_x6 == 2) &&
-      attention_x6_supported(a))
-    return attention_x6(a, s);
+  const AttnForm f = attention_form(a);
+  if (f.kind == ATTN_BF16 || f.kind == ATTN_BF16_DMA) return attention_bf16(a, s);
+  if (f.kind == ATTN_X6) return attention_x6(a, s);
   constexpr int NW = 2;
   dim3 g(cdiv(a.max_q_len, NW * 32), a.n_heads, a.n_seq), t(NW * 64);
   AttnArgs ax = a;
@@ -994,23 +1013,17 @@ int attention(const AttnArgs& a, hipStream_t s) {
     ax.xcd_nqb = g.x;
     g = dim3(g.x * g.y * g.z);
   }
-  // key split for the encoder's self attention over long sequences: twice the
-  // waves for the same tiles (tune().attn_split: 0 auto, 1 off, 2 on)
-  const bool split = tune().attn_split == 2 ||
-                     (tune().attn_split == 0 && (a.P != nullptr || a.kbias != nullptr) &&
-                      a.max_q_len >= 128);
-  const bool fold = a.P != nullptr && a.fold && a.bias_u && a.bias_v;
-  if (split) {
+  if (f.ks == 2) {
     dim3 t2(NW * 2 * 64);
-    if (fold)
+    if (f.kind == ATTN_FOLD)
       hipLaunchKernelGGL((attention_kernel<NW, false, 2, true>), g, t2, 0, s, ax);
-    else if (a.P)
+    else if (f.kind == ATTN_RELPOS)
       hipLaunchKernelGGL((attention_kernel<NW, true, 2>), g, t2, 0, s, ax);
     else
       hipLaunchKernelGGL((attention_kernel<NW, false, 2>), g, t2, 0, s, ax);
-  } else if (fold)
+  } else if (f.kind == ATTN_FOLD)
     hipLaunchKernelGGL((attention_kernel<NW, false, 1, true>), g, t, 0, s, ax);
-  else if (a.P)
+  else if (f.kind == ATTN_RELPOS)
     hipLaunchKernelGGL((attention_kernel<NW, true, 1>), g, t, 0, s, ax);
   else
     hipLaunchKernelGGL((attention_kernel<NW, false, 1>), g, t, 0, s, ax);

@@ -105,6 +105,29 @@ struct AttnArgs {
   const int* row_utt = nullptr;
 };
 int attention(const AttnArgs& a, hipStream_t s);
+// The kernel attention() runs for `a` under the calling thread's precision and tune(): the
+// launchers branch on these, and wn_op_attention reports them to the tests.
+enum AttnKind {
+  ATTN_PLAIN = 0,      // attention_kernel<NW, false, KS> (with kbias: the pre-folded rel-pos form)
+  ATTN_RELPOS = 1,     // attention_kernel<NW, true, KS>: two contractions per score
+  ATTN_FOLD = 2,       // attention_kernel<NW, false, KS, true>: rel-pos folded while staging
+  ATTN_X6 = 3,         // attention_x6.hip: pack pass + six-product kernel
+  ATTN_BF16 = 4,       // attention_bf16_kernel, register-staged, nw waves
+  ATTN_BF16_DMA = 5    // attention_bf16_dma_kernel, nw waves
+};
+struct AttnForm {
+  int kind = ATTN_PLAIN;
+  int ks = 1;             // fp32 kernels: key split
+  int nw = 2;             // waves (32-query groups) per key half
+  bool relpos = false;    // bf16 kernel: the rel-pos instantiation
+  bool in16 = false;      // bf16 kernels: bf16 Q / K / V
+  bool kbias = false;     // ATTN_PLAIN with the per-key score term
+  int code() const {
+    return kind | ks << 4 | nw << 8 | (int)relpos << 12 | (int)in16 << 13 | (int)kbias << 14;
+  }
+};
+AttnForm attention_form(const AttnArgs& a);
+AttnForm attention_bf16_form(const AttnArgs& a);
 // rel-pos self attention as six bf16 plane products (attention_x6.hip): pack pass + kernel
 size_t attention_x6_image_bytes(int rows, int n_seq, int n_heads);
 bool attention_x6_supported(const AttnArgs& a);
