@@ -69,6 +69,14 @@ typedef struct {
   int32_t key_bias;          /* attention linear_k has a bias (Whisper: 0) */
   int32_t cnn_norm;          /* conv-module norm: 0 layer_norm, 1 batch_norm (eval:
                                 running statistics; convolution.py:77-81) */
+  /* decoder variants (the Whisper decoder, decoder.py:59-135); all 0 = the classic
+   * TransformerDecoder: ReLU, sinusoid positions x sqrt(d), every projection biased */
+  int32_t dec_activation;    /* decoder FFN activation: 0 relu, 1 gelu (exact erf) */
+  int32_t dec_key_bias;      /* 0: self-attention linear_k has a bias; 1: it has none */
+  int32_t dec_src_key_bias;  /* the same for the cross attention's linear_k */
+  int32_t dec_learned_pos;   /* 1: decoder.embed.1.pe is a learned (1, dec_max_pos, d) weight,
+                                added to the UNSCALED embedding (embedding.py:167-175) */
+  int32_t dec_max_pos;       /* rows of that table (Whisper: 448) */
 } wn_config;
 
 /* One entry of the reference state_dict (fp32, host memory, C-contiguous). */
@@ -490,6 +498,26 @@ int wn_filter_blank_embedding(wn_model* m, float* padded_out_dev, int32_t* n_kee
 int wn_attention_beam_search(wn_model* m, int32_t beam, int32_t maxlen, float length_penalty,
                              int32_t* tokens_host, int32_t* lens_host, void* stream);
 
+/* attention_beam_search, the Whisper branch (search.py:267-289): every hypothesis starts from
+ * the P-token prompt of its utterance (add_whisper_tokens, common.py:159-238), prompt_host
+ * (B, P) int32.  Prefill: the P prompt rows of each utterance go through the decoder ONCE per
+ * utterance (causal self attention); their K | V land in cache steps 0..P-1 at the utterance's
+ * first slot and every hypothesis' ancestor path points there.  Steps then run for
+ * i = P .. min(maxlen, dec_max_pos): where the reference asserts in its positional table (a
+ * hypothesis still open at position dec_max_pos) this path stops and returns the best hypothesis
+ * so far; wn_attention_truncated() then reads 1.  Results are stripped of the prompt and of
+ * <eot>; the length penalty counts the non-<eot> tokens of the whole row, prompt included.  The
+ * cross attention runs one query sequence of `beam` rows per utterance (K / V rows staged once
+ * per utterance).  With the tune key dec_skinny != 0 the step's GEMMs run on the skinny kernel
+ * (gemm_skinny.hip); wn_attention_beam_search never does.  tokens_host (B, maxlen), lens_host
+ * (B,).  P == 1 with prompt = <sos> is the classic search. */
+int wn_attention_beam_search_prompt(wn_model* m, int32_t beam, int32_t maxlen,
+                                    float length_penalty, const int32_t* prompt_host, int32_t P,
+                                    int32_t* tokens_host, int32_t* lens_host, void* stream);
+/* 1 if the handle's last wn_attention_beam_search_prompt stopped at the positional table with
+ * a hypothesis still open, else 0 (-1: null handle). */
+int32_t wn_attention_truncated(const wn_model* m);
+
 /* One step of attention_beam_search (search.py:252-371): for every running
  * hypothesis (its utterance index in the current batch, its tokens so far
  * starting with <sos>), log_softmax(output_layer(after_norm(decoder(...)[:, -1])))
@@ -513,6 +541,15 @@ int wn_op_gemm(const float* A_dev, const float* W_dev, const float* bias_dev,
 int wn_op_gemm_bf16(const float* A_dev, const float* W_dev, const float* bias_dev,
                     const float* resid_dev, float* C_dev, int32_t M, int32_t N,
                     int32_t K, float alpha, int32_t act, void* stream);
+/* The skinny GEMM of the decoder step (gemm_skinny.hip), M <= 256 (more is refused, -1):
+ * C[M,N] = resid + act(A[M,K] * W[N,K]^T + bias), act 0 none / 2 ReLU / 3 exact GELU; a block
+ * owns all M rows of 128 columns and one of split_k K slices (0 = the shape rule), the slice
+ * partials are summed in slice order (no atomics: repeatable bits).  w_bf16 != 0: W is rounded
+ * to a bf16 image first (the handle's weight image in the model path), A is rounded to bf16 on
+ * its way into LDS, fp32 accumulate.  K % 32 == 0. */
+int wn_op_gemm_skinny(const float* A_dev, const float* W_dev, const float* bias_dev,
+                      const float* resid_dev, float* C_dev, int32_t M, int32_t N, int32_t K,
+                      int32_t act, int32_t w_bf16, int32_t split_k, void* stream);
 /* The bf16-STORAGE form of that contraction (the kernel the bf16 mode runs on
  * LayerNorm outputs / FFN hidden / attention context, which it keeps as bf16 in
  * HBM): A and W are rounded to bf16 images first, the GEMM reads those; C is fp32

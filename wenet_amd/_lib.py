@@ -19,7 +19,10 @@ class WnConfig(Structure):
         'has_cmvn', 'dec_heads', 'dec_ffn_dim', 'dec_layers', 'dec_r_layers',
         'bidirectional', 'sos', 'eos', 'max_pos')] + [('norm_eps', c_float)] + [
             (n, c_int32) for n in ('encoder_type', 'input_layer', 'activation',
-                                   'key_bias', 'cnn_norm')]
+                                   'key_bias', 'cnn_norm',
+                                   # decoder variants (the Whisper decoder); 0 = classic
+                                   'dec_activation', 'dec_key_bias', 'dec_src_key_bias',
+                                   'dec_learned_pos', 'dec_max_pos')]
 
 
 class WnTensor(Structure):
@@ -56,7 +59,8 @@ EXPORTS = [
     'wn_last_error', 'wn_version', 'wn_model_create', 'wn_model_destroy', 'wn_model_clone',
     'wn_model_set_precision', 'wn_model_get_precision', 'wn_batch_size', 'wn_model_set_encode_gate', 'wn_op_gemm_bf16',
     'wn_op_gemm_bf16_stored',
-    'wn_attention_beam_search', 'wn_encode_chunk_batch', 'wn_op_gemm_lowp', 'wn_op_mx_quantize', 'wn_op_ffn_fused', 'wn_op_gemm_x6', 'wn_op_ffn_x6', 'wn_op_gemm_x6r', 'wn_op_gemm_x6r512', 'wn_profile_kernel_name', 'wn_profile_ffn_split', 'wn_profile_ffn_clocks', 'wn_profile_gemm_clocks', 'wn_filter_blank_embedding',
+    'wn_attention_beam_search', 'wn_attention_beam_search_prompt', 'wn_attention_truncated',
+    'wn_op_gemm_skinny', 'wn_encode_chunk_batch', 'wn_op_gemm_lowp', 'wn_op_mx_quantize', 'wn_op_ffn_fused', 'wn_op_gemm_x6', 'wn_op_ffn_x6', 'wn_op_gemm_x6r', 'wn_op_gemm_x6r512', 'wn_profile_kernel_name', 'wn_profile_ffn_split', 'wn_profile_ffn_clocks', 'wn_profile_gemm_clocks', 'wn_filter_blank_embedding',
     'wn_workspace_create', 'wn_resample_length', 'wn_resample', 'wn_fbank', 'wn_log_mel', 'wn_encode', 'wn_encode_chunk', 'wn_set_encoder_out',
     'wn_ctc_logprobs', 'wn_set_ctc_probs', 'wn_ctc_greedy_search', 'wn_ctc_force_align',
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
@@ -137,7 +141,10 @@ def lib():
     L.wn_decoder_next_topk.argtypes = [vp, i32, pi32, pi32, pi32, i32, i32,
                                        POINTER(f32), pi32, vp]
     L.wn_attention_beam_search.argtypes = [vp, i32, i32, f32, pi32, pi32, vp]
+    L.wn_attention_beam_search_prompt.argtypes = [vp, i32, i32, f32, pi32, i32, pi32, pi32, vp]
+    L.wn_attention_truncated.argtypes = [vp]
     L.wn_op_gemm.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]
+    L.wn_op_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.wn_op_gemm_bf16.argtypes = L.wn_op_gemm.argtypes
     L.wn_op_gemm_bf16_stored.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp]
     L.wn_op_gemm_lowp.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32,

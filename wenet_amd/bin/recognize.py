@@ -67,6 +67,10 @@ def get_args(argv=None):
                    help="'decoding-graph' enables context biasing")
     p.add_argument('--context_list_path', type=str, default='')
     p.add_argument('--context_graph_score', type=float, default=0.0)
+    p.add_argument('--task', default='transcribe', choices=['transcribe', 'translate', 'vad'],
+                   help="Whisper models, mode 'attention': the task token of every prompt")
+    p.add_argument('--lang', default='en',
+                   help="Whisper models, mode 'attention': the language code of every prompt")
     p.add_argument('--streams', type=int, default=2,
                    help='decode() calls in flight on the GPU')
     p.add_argument('--report_rtf', default='',
@@ -309,6 +313,10 @@ def recognize(model, tokenizer, batches: List[List[Tuple[str, str]]], my_batches
               reverse_weight=args.reverse_weight, context_graph=context_graph,
               blank_id=blank_id, blank_penalty=args.blank_penalty,
               length_penalty=args.length_penalty)
+    from wenet_amd import whisper
+    whisper_prompts = 'attention' in args.modes and whisper.is_whisper(model.special_tokens)
+    if whisper_prompts:
+        whisper.language_index(args.lang)       # an unknown code fails here, not in a worker
     max_fmt = max(len(m) for m in args.modes)
     compute_features, frames_of = feature_function(model, model.configs)
     depth = max(2, 2 * args.streams)  # batches of wav data read ahead
@@ -396,7 +404,12 @@ def recognize(model, tokenizer, batches: List[List[Tuple[str, str]]], my_batches
                     t4 = clock()
                     stat['pad_sort'] += t4 - t3
                 keys = [batches[bi][i][0] for i in perm]
-                fut = pipe.submit(args.modes, feats, lens, **kw)
+                call_kw = kw
+                if whisper_prompts:
+                    # (the reference reads tasks / langs per utterance from the data list)
+                    call_kw = dict(kw, infos=dict(tasks=[args.task] * len(keys),
+                                                  langs=[args.lang] * len(keys)))
+                fut = pipe.submit(args.modes, feats, lens, **call_kw)
                 t5 = clock()
                 stat['submit'] += t5 - t4
                 handoff.put((bi, keys, fut))          # blocks while `streams` batches wait

@@ -36,6 +36,10 @@ def get_args(argv=None):
                    help='beam size (default: the decode() default of transcribe)')
     p.add_argument('--context_path', type=str, default=None, help='context list file')
     p.add_argument('--context_score', type=float, default=6.0, help='context score')
+    p.add_argument('--task', default=None, choices=['transcribe', 'translate', 'vad'],
+                   help='Whisper models: the task token of the prompt (default transcribe)')
+    p.add_argument('--lang', default=None,
+                   help='Whisper models: language code of the prompt, e.g. en, zh (default en)')
     p.add_argument('--stream', action='store_true',
                    help='decode through a streaming session, printing partial results')
     p.add_argument('--chunk', type=int, default=16,
@@ -100,7 +104,8 @@ def main(argv=None):
         if args.context_path is not None:
             raise SystemExit('--stream does not support --context_path')
         result = stream_file(model, args.audio_file, args.chunk, args.beam or 10)
-    elif args.beam is None and args.context_path is None:
+    elif args.beam is None and args.context_path is None and args.task is None \
+            and args.lang is None:
         result = model.transcribe(args.audio_file)      # asr_model.py:345-358
     else:
         graph = None
@@ -109,11 +114,18 @@ def main(argv=None):
             bpe = getattr(model.tokenizer, 'bpe_path', None)
             graph = ContextGraph(args.context_path, model.tokenizer.symbol_table, bpe,
                                  args.context_score)
+        infos = None
+        if args.task is not None or args.lang is not None:
+            from wenet_amd import whisper
+            if not whisper.is_whisper(model.special_tokens):
+                raise SystemExit('--task / --lang are read by Whisper models only')
+            infos = dict(tasks=[args.task or 'transcribe'], langs=[args.lang or 'en'])
         speech = model.compute_feature(args.audio_file)
         method = model.default_decode_method
         result = model.decode([method], speech.unsqueeze(0),
                               torch.tensor([speech.size(0)]),
-                              beam_size=args.beam or 10, context_graph=graph)[method][0]
+                              beam_size=args.beam or 10, context_graph=graph,
+                              infos=infos)[method][0]
         result.text = model.tokenizer.detokenize(result.tokens)[0]
     print(result.text)
     if args.show_tokens_info:

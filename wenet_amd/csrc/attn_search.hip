@@ -88,7 +88,8 @@ __global__ void beam_update_kernel(int N, int step, int max_len, int eos, int V,
                                    const int* __restrict__ tok_in, const int* __restrict__ path_in,
                                    float* __restrict__ score_out, int* __restrict__ end_out,
                                    int* __restrict__ tok_out, int* __restrict__ path_out,
-                                   int* __restrict__ last_tok, int* __restrict__ n_running_done) {
+                                   int* __restrict__ last_tok, int* __restrict__ n_running_done,
+                                   int shared_row) {
   extern __shared__ float cand[];          // [N*N] values, then N ints (winner flat index)
   int* win = reinterpret_cast<int*>(cand + N * N);
   const int b = blockIdx.x;
@@ -125,7 +126,9 @@ __global__ void beam_update_kernel(int N, int step, int max_len, int eos, int V,
       if (j + 1 < step) path_out[(int64_t)child * max_len + j] = path_in[(int64_t)parent * max_len + j];
     }
     // position step-1 (the parent's newest token) was computed in the parent's row
-    path_out[(int64_t)child * max_len + step - 1] = parent;
+    // (shared_row: the first step behind a prompt prefill -- position step-1 was computed once
+    // per utterance, in its first slot, for all of its identical hypotheses)
+    path_out[(int64_t)child * max_len + step - 1] = shared_row ? b * N : parent;
     path_out[(int64_t)child * max_len + step] = child;   // its own row at the next step
     tok_out[(int64_t)child * max_len + step] = tok;
     last_tok[child] = tok;
@@ -135,9 +138,12 @@ __global__ void beam_update_kernel(int N, int step, int max_len, int eos, int V,
   }
 }
 
+// prefix: tokens every row starts with (<sos>, or the Whisper prompt) -- counted by the length
+// penalty like the reference's hyps.ne(eos).sum(), not part of the result
 __global__ void beam_finish_kernel(int N, int len, int max_len, int eos, float length_penalty,
                                    const float* __restrict__ score, const int* __restrict__ tok,
-                                   int* __restrict__ out_tok, int* __restrict__ out_len) {
+                                   int* __restrict__ out_tok, int* __restrict__ out_len,
+                                   int prefix) {
   const int b = blockIdx.x;
   if (threadIdx.x != 0) return;
   int best = 0;
@@ -151,7 +157,7 @@ __global__ void beam_finish_kernel(int N, int len, int max_len, int eos, float l
   }
   const int* row = tok + (int64_t)(b * N + best) * max_len;
   int o = 0;
-  for (int j = 1; j < len; ++j)
+  for (int j = prefix; j < len; ++j)
     if (row[j] != eos) out_tok[(int64_t)b * max_len + o++] = row[j];
   out_len[b] = o;
 }
@@ -178,7 +184,49 @@ __global__ void beam_init_kernel(int BN, int N, int max_len, int sos, float* sco
   last_tok[r] = sos;
 }
 
+// The prompted search (search.py:267-289): every hypothesis of utterance b starts as its P
+// prompt tokens; positions 0..P-1 live ONCE per utterance, in the cache rows of its first slot
+__global__ void beam_init_prompt_kernel(int BN, int N, int max_len, const int* __restrict__ prompt,
+                                        int P, float* score, int* end, int* tok, int* path,
+                                        int* last_tok) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= BN) return;
+  const int b = r / N;
+  score[r] = (r % N) == 0 ? 0.f : -INFINITY;
+  end[r] = 0;
+  for (int j = 0; j < P; ++j) {
+    tok[(int64_t)r * max_len + j] = prompt[b * P + j];
+    path[(int64_t)r * max_len + j] = b * N;
+  }
+  last_tok[r] = prompt[b * P + P - 1];
+}
+
+// K | V of the prefill rows (utterance b, position j) = row b * P + j -> cache[j][b * N]
+__global__ void prompt_cache_store_kernel(const float* __restrict__ qkv, int d, int P, int N,
+                                          int BN, float* __restrict__ cache) {
+  const int r = blockIdx.x, b = r / P, j = r - b * P;
+  const f32x4* s = reinterpret_cast<const f32x4*>(qkv + (int64_t)r * 3 * d + d);
+  f32x4* o = reinterpret_cast<f32x4*>(cache + ((int64_t)j * BN + (int64_t)b * N) * 2 * d);
+  for (int i = threadIdx.x; i < 2 * d / 4; i += blockDim.x) o[i] = s[i];
+}
+
 }  // namespace
+
+int attn_beam_init_prompt(int BN, int N, int max_len, const int* prompt, int P, float* score,
+                          int* end, int* tok, int* path, int* last_tok, hipStream_t s) {
+  hipLaunchKernelGGL(beam_init_prompt_kernel, dim3(cdiv(BN, 256)), dim3(256), 0, s, BN, N,
+                     max_len, prompt, P, score, end, tok, path, last_tok);
+  WN_HIP(hipGetLastError());
+  return 0;
+}
+
+int attn_prompt_cache_store(const float* qkv, int d, int B, int P, int N, float* cache,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(prompt_cache_store_kernel, dim3(B * P), dim3(128), 0, s, qkv, d, P, N,
+                     B * N, cache);
+  WN_HIP(hipGetLastError());
+  return 0;
+}
 
 int attn_self_step(const float* qkv, int d, int heads, int n, float* cache, int step,
                    const int* path, int max_len, float* out, hipStream_t s) {
@@ -209,21 +257,22 @@ int attn_beam_init(int BN, int N, int max_len, int sos, float* score, int* end, 
 int attn_beam_update(int B, int N, int step, int max_len, int eos, int V, const float* topv,
                      const int* topi, const float* score_in, const int* end_in,
                      const int* tok_in, const int* path_in, float* score_out, int* end_out,
-                     int* tok_out, int* path_out, int* last_tok, int* n_done, hipStream_t s) {
+                     int* tok_out, int* path_out, int* last_tok, int* n_done, hipStream_t s,
+                     bool shared_row) {
   WN_CHECK(N >= 1 && N <= 64, "attention beam search: beam_size must be in [1, 64]");
   const int thr = std::min(1024, (N * N + 63) / 64 * 64);
   hipLaunchKernelGGL(beam_update_kernel, dim3(B), dim3(thr), (N * N + N) * sizeof(float), s, N,
                      step, max_len, eos, V, topv, topi, score_in, end_in, tok_in, path_in,
-                     score_out, end_out, tok_out, path_out, last_tok, n_done);
+                     score_out, end_out, tok_out, path_out, last_tok, n_done, shared_row ? 1 : 0);
   WN_HIP(hipGetLastError());
   return 0;
 }
 
 int attn_beam_finish(int B, int N, int len, int max_len, int eos, float length_penalty,
                      const float* score, const int* tok, int* out_tok, int* out_len,
-                     hipStream_t s) {
+                     hipStream_t s, int prefix) {
   hipLaunchKernelGGL(beam_finish_kernel, dim3(B), dim3(64), 0, s, N, len, max_len, eos,
-                     length_penalty, score, tok, out_tok, out_len);
+                     length_penalty, score, tok, out_tok, out_len, prefix);
   WN_HIP(hipGetLastError());
   return 0;
 }

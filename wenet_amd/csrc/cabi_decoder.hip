@@ -62,6 +62,17 @@ struct CrossGroups {
   int n_seq, max_q;
 };
 
+// Prompt prefill of the prompted beam search: the self-attention K | V of the B x P prompt rows
+// (utterance-major) of every layer go into the search's cache, steps 0..P-1 at the utterance's
+// first slot (attn_search.hip)
+struct PrefillCache {
+  float* cache; size_t layer_stride;
+  int B, P, N;
+};
+
+// FFN activation of the decoders: ReLU, or the Whisper decoder's exact GELU
+inline int dec_act(const wn_config& c) { return c.dec_activation == 1 ? ACT_GELU : ACT_RELU; }
+
 // embed + the decoder layers over a ragged batch of R token rows (n_seq
 // sequences); the result stays in m->r_x.  With `mem_cache` the cross-attention
 // K/V projections of the encoder output are computed once per batch and layer
@@ -69,9 +80,10 @@ struct CrossGroups {
 int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
                    const int* d_tok, bool mem_cache, hipStream_t s,
                    const int* self_kvlen = nullptr, const float* kv_base = nullptr,
-                   const CrossGroups* cg = nullptr) {
+                   const CrossGroups* cg = nullptr, const PrefillCache* pc = nullptr) {
   const wn_config& c = m->cfg;
   const int d = c.d_model, Menc = m->rows;
+  const int act = dec_act(c);
   float* x = m->r_x.as<float>();
   float* t1 = m->r_t1.as<float>();
   float* t2 = m->r_t2.as<float>();
@@ -85,8 +97,9 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
   else
     WN_TRY(m->r_mem.ensure(mem_layer * sizeof(float)));
   // embed(V,d) * sqrt(d) + pe                          embedding.py:58-76
+  // (the learned table of the Whisper decoder: xscale = 1, embedding.py:167-175)
   hipLaunchKernelGGL(embed_kernel, dim3(R), dim3(64), 0, s, d_tok,
-                     m->r_pos.as<int>(), D.embed, D.pe, sqrtf((float)d), d / 4, x);
+                     m->r_pos.as<int>(), D.embed, D.pe, D.xscale, d / 4, x);
   WN_HIP(hipGetLastError());
   int li = 0;
   bool ln1_done = false;      // t1 already holds this layer's norm1(x) (the previous FFN's reduce)
@@ -95,6 +108,9 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
     if (!ln1_done) WN_TRY(ln(L.n1, x, t1, R, d, eps, s));
     ln1_done = false;
     WN_TRY(linear(L.self_qkv, t1, d, qkv, 3 * d, R, s));
+    if (pc)
+      WN_TRY(attn_prompt_cache_store(qkv, d, pc->B, pc->P, pc->N,
+                                     pc->cache + (size_t)li * pc->layer_stride, s));
     AttnArgs a;
     a.Q = qkv; a.K = qkv + d; a.V = qkv + 2 * d; a.ldq = a.ldk = a.ldv = 3 * d;
     a.O = t2; a.ldo = d;
@@ -131,13 +147,13 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
     cx.mask_mode = 0; cx.scale = 0.125f;
     WN_TRY(attention(cx, s));
     WN_TRY(linear(L.src_out, t1, d, x, d, R, s, ACT_NONE, x, d));
-    // FFN (ReLU)                                         decoder_layer.py:140-147
+    // FFN (ReLU; GELU in the Whisper decoder)            decoder_layer.py:140-147
     WN_TRY(ln(L.n3, x, t1, R, d, eps, s));
     // large batches (a rescoring pass): the six-product GEMM pair with the hidden tensor as a
     // plane image; its reduce adds b_2 and the residual and applies the NEXT LayerNorm (the
     // next layer's norm1, or after_norm behind the last layer: the callers' own after_norm
     // call then recomputes the same rows)
-    const int fS = ffn_x6_pair(m, L.ff1, L.ff2, ACT_RELU, t1, R, s);
+    const int fS = ffn_x6_pair(m, L.ff1, L.ff2, act, t1, R, s);
     if (fS < 0) return -2;
     if (fS > 0) {
       const bool last = (size_t)li + 1 == D.layers.size();
@@ -146,7 +162,7 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
                            nullptr, t1, R, d, eps, 0, s));
       ln1_done = !last;
     } else {
-      WN_TRY(linear(L.ff1, t1, d, hb, c.dec_ffn_dim, R, s, ACT_RELU));
+      WN_TRY(linear(L.ff1, t1, d, hb, c.dec_ffn_dim, R, s, act));
       WN_TRY(linear(L.ff2, hb, c.dec_ffn_dim, x, d, R, s, ACT_NONE, x, d));
     }
     ++li;
@@ -321,7 +337,7 @@ int rescore_pass(wn_model* m, const char* who, int beam, const int32_t* n_hyps_h
     for (int i = 0; i < n_hyps_host[b]; ++i) {
       const int L = hyp_lens_host[b * beam + i];
       WN_CHECK(L >= 0 && L <= max_len, pfx + "hypothesis length");
-      WN_CHECK(L + 1 <= c.max_pos, pfx + "hypothesis longer than the positional table");
+      WN_CHECK(L + 1 <= W.left.max_pos, pfx + "hypothesis longer than the positional table");
       if (!from_beam) {
         const int32_t* h = hyp_tokens_host + ((int64_t)b * beam + i) * max_len;
         for (int j = 0; j < L; ++j)
@@ -417,6 +433,246 @@ int rescore_pass(wn_model* m, const char* who, int beam, const int32_t* n_hyps_h
   return 0;
 }
 
+// One GEMM of a decoder step of the prompted search, M = B x beam rows: the skinny kernel
+// (gemm_skinny.hip; tune dec_skinny) with the fp32 weights, or in the bf16 mode the handle's
+// bf16 weight image; shapes it does not take, and dec_skinny = 0, run on linear().
+int step_linear(wn_model* m, bool skinny, const Linear& l, const float* A, int lda, float* C,
+                int ldc, int M, hipStream_t s, int act = ACT_NONE, const float* resid = nullptr,
+                int ldr = 0) {
+  const void* wh = nullptr;
+  if (skinny && t_gemm_prec == PREC_BF16) {
+    if (t_wslab_bf16 && l.w >= t_wslab_f32 && l.w < t_wslab_f32 + t_wslab_elems)
+      wh = reinterpret_cast<const char*>(t_wslab_bf16) + (size_t)(l.w - t_wslab_f32) * 2;
+    else
+      skinny = false;
+  }
+  if (!skinny || M > 256 || l.in % 32 != 0 || lda % 4 != 0)
+    return linear(l, A, lda, C, ldc, M, s, act, resid, ldr);
+  SkinnyArgs g;
+  g.A = A; g.lda = lda; g.W = wh ? nullptr : l.w; g.Wh = wh; g.bias = l.b;
+  g.resid = resid; g.ldr = ldr; g.C = C; g.ldc = ldc; g.M = M; g.N = l.out; g.K = l.in;
+  g.act = act;
+  g.split_k = gemm_skinny_split(l.out, l.in, wh != nullptr);
+  WN_TRY(m->sk_part.ensure(gemm_skinny_ws_bytes(M, l.out, g.split_k)));
+  g.part = m->sk_part.as<float>(); g.part_bytes = m->sk_part.cap;
+  return gemm_skinny(g, s);
+}
+
+// attention_beam_search (search.py:252-371) for the current batch, entirely on the
+// device: one decoder row per running hypothesis and step (self-attention K/V cache
+// addressed through per-hypothesis ancestor paths, cross-attention K/V projected once),
+// beam bookkeeping in beam_update_kernel; the host only reads the "all ended" counter.
+//
+// prompt_host == nullptr: the classic search behind wn_attention_beam_search -- every hypothesis
+// starts as <sos>, one cross-attention sequence per hypothesis, every GEMM on linear().
+// prompt_host (B, P): the Whisper branch behind wn_attention_beam_search_prompt -- the prompt
+// rows are prefilled once per utterance and shared through the paths, the steps stop at the
+// decoder's positional table, the hypotheses of an utterance are ONE cross-attention sequence,
+// and the step GEMMs may run on the skinny kernel.
+int beam_search_run(wn_model* m, int beam, int maxlen, float length_penalty,
+                    const int32_t* prompt_host, int P, int32_t* tokens_host, int32_t* lens_host,
+                    hipStream_t s) {
+  const Decoder& D = m->data->left;
+  const bool prompted = prompt_host != nullptr;
+  WN_CHECK(!D.layers.empty(), "attention beam search: the model has no attention decoder");
+  WN_CHECK(beam >= 1 && beam <= 64 && maxlen >= 1 && tokens_host && lens_host,
+           "attention beam search: beam_size in [1, 64], maxlen >= 1");
+  WN_HIP(hipSetDevice(m->device));
+  const wn_config& c = m->cfg;
+  const int d = c.d_model, V = c.vocab, B = m->B, N = beam, BN = B * N, Menc = m->rows;
+  const int act = dec_act(c);
+  WN_CHECK(beam <= V, "attention beam search: beam larger than the vocabulary");
+  if (!prompted)
+    WN_CHECK(maxlen + 1 <= D.max_pos, "attention beam search: longer than the positional table");
+  else
+    WN_CHECK(P <= D.max_pos, "attention beam search: prompt longer than the positional table");
+  // the last step: hypotheses of `last` tokens produce token last + 1.  The reference asserts
+  // in PositionalEncoding.position_encoding once a step needs position max_pos; the prompted
+  // search stops there and returns the best hypothesis so far (deviations)
+  const int last = prompted ? std::min(maxlen, D.max_pos) : maxlen;
+  const int first = prompted ? P : 1;
+  const int W = std::max(maxlen, P) + 2;          // columns of the token / path rows
+  const int nl = (int)D.layers.size();
+  const bool skinny = prompted && tune().dec_skinny != 0;
+  m->ab_truncated = false;
+  for (int b = 0; b < B; ++b)
+    WN_CHECK(m->len[b] > 0, "attention beam search: utterance without encoder frames");
+  // ---- descriptors -------------------------------------------------------------------
+  // cross attention of the steps: one query row per hypothesis, or (prompted) the N
+  // consecutive rows of an utterance as one sequence -- its keys staged once, the same keys in
+  // the same tile order per query row
+  const int n_cx = prompted ? B : BN, cx_q = prompted ? N : 1;
+  std::vector<int> qoff(n_cx), qlen(n_cx, cx_q), kvoff(n_cx), kvlen(n_cx);
+  for (int r = 0; r < n_cx; ++r) {
+    const int b = prompted ? r : r / N;
+    qoff[r] = r * cx_q; kvoff[r] = m->off[b]; kvlen[r] = m->len[b];
+  }
+  const int RP = prompted ? B * P : 0;             // prefill rows
+  WN_TRY(m->stage.begin((size_t)(4 * n_cx + 3 * RP + 4 * B + BN + 128) * sizeof(int) + 8192));
+  DevBuf& b_qoff = prompted ? m->r_gqoff : m->r_qoff;
+  DevBuf& b_qlen = prompted ? m->r_gqlen : m->r_qlen;
+  DevBuf& b_kvoff = prompted ? m->r_gkvoff : m->r_kvoff;
+  DevBuf& b_kvlen = prompted ? m->r_gkvlen : m->r_kvlen;
+  WN_TRY(upload_desc(m, b_qoff, qoff, s));
+  WN_TRY(upload_desc(m, b_qlen, qlen, s));
+  WN_TRY(upload_desc(m, b_kvoff, kvoff, s));
+  WN_TRY(upload_desc(m, b_kvlen, kvlen, s));
+  if (prompted) {
+    // the prefill as a ragged decoder batch: B sequences of P rows; and, per hypothesis, the
+    // prefill row whose output it continues from (the utterance's last prompt position)
+    std::vector<int> tok(RP), pos(RP), poff(B), plen(B, P), pkvoff(B), pkvlen(B), lastrow(BN);
+    for (int b = 0; b < B; ++b) {
+      poff[b] = b * P; pkvoff[b] = m->off[b]; pkvlen[b] = m->len[b];
+      for (int j = 0; j < P; ++j) {
+        const int t = prompt_host[(size_t)b * P + j];
+        WN_CHECK(t >= 0 && t < V, "attention beam search: prompt token id out of range");
+        tok[b * P + j] = t; pos[b * P + j] = j;
+      }
+      for (int n = 0; n < N; ++n) lastrow[b * N + n] = b * P + P - 1;
+    }
+    WN_TRY(upload_desc(m, m->ab_prompt, tok, s));
+    WN_TRY(upload_desc(m, m->r_pos, pos, s));
+    WN_TRY(upload_desc(m, m->r_qoff, poff, s));
+    WN_TRY(upload_desc(m, m->r_qlen, plen, s));
+    WN_TRY(upload_desc(m, m->r_kvoff, pkvoff, s));
+    WN_TRY(upload_desc(m, m->r_kvlen, pkvlen, s));
+    WN_TRY(upload_desc(m, m->r_tgt, lastrow, s));
+  }
+  WN_TRY(m->stage.end(s));
+  WN_TRY(decoder_ws(m, std::max(BN, RP), BN, V, (size_t)2 * BN * N));
+  // self-attention K | V cache [layer][step][slot][2d]: sized for the steps actually run,
+  // not for maxlen = T' (the reference's cache grows with the decoded length too,
+  // decoder.py:226-281): starts at 32 steps and doubles, the used prefix of every layer is
+  // carried over
+  int cap_steps = std::max(std::min(last, 32), prompted ? P : 1);
+  size_t cache_layer = (size_t)cap_steps * BN * 2 * d;
+  WN_TRY(m->ab_cache.ensure(nl * cache_layer * sizeof(float)));
+  auto grow_cache = [&](int used_steps) -> int {
+    const int cap2 = std::min(last, cap_steps * 2);
+    const size_t layer2 = (size_t)cap2 * BN * 2 * d;
+    DevBuf nb;
+    WN_TRY(nb.ensure(nl * layer2 * sizeof(float)));
+    for (int li = 0; li < nl; ++li)
+      WN_HIP(hipMemcpyAsync(nb.as<float>() + li * layer2, m->ab_cache.as<float>() + li * cache_layer,
+                            (size_t)used_steps * BN * 2 * d * sizeof(float),
+                            hipMemcpyDeviceToDevice, s));
+    WN_HIP(hipStreamSynchronize(s));            // before the old buffer is freed
+    m->ab_cache.swap(nb);
+    cap_steps = cap2;
+    cache_layer = layer2;
+    return 0;
+  };
+  const size_t mem_layer = (size_t)Menc * 2 * d;
+  WN_TRY(m->r_mem_all.ensure(nl * mem_layer * sizeof(float)));
+  // state: 2 x {score, end, tok, path} + last_tok + n_done + out_tok + out_len
+  const size_t n_int = (size_t)2 * (BN + BN + (size_t)BN * W * 2) + BN + 16 + (size_t)B * W + B;
+  WN_TRY(m->ab_state.ensure(n_int * sizeof(int)));
+  int* base = m->ab_state.as<int>();
+  float* score[2]; int* endf[2]; int* tok[2]; int* path[2];
+  for (int k = 0; k < 2; ++k) {
+    score[k] = reinterpret_cast<float*>(base); base += BN;
+    endf[k] = base; base += BN;
+    tok[k] = base; base += (size_t)BN * W;
+    path[k] = base; base += (size_t)BN * W;
+  }
+  int* last_tok = base; base += BN;
+  int* n_done = base; base += 16;
+  int* out_tok = base; base += (size_t)B * W;
+  int* out_len = base;
+  if (prompted)
+    WN_TRY(attn_beam_init_prompt(BN, N, W, m->ab_prompt.as<int>(), P, score[0], endf[0], tok[0],
+                                 path[0], last_tok, s));
+  else
+    WN_TRY(attn_beam_init(BN, N, W, c.sos, score[0], endf[0], tok[0], path[0], last_tok, s));
+  WN_HIP(hipMemsetAsync(n_done, 0, sizeof(int), s));
+  float* x = m->r_x.as<float>();
+  float* t1 = m->r_t1.as<float>();
+  float* t2 = m->r_t2.as<float>();
+  float* qkv = m->r_qkv.as<float>();
+  float* hb = m->r_h.as<float>();
+  float* tv = m->r_out.as<float>();
+  int* ti = reinterpret_cast<int*>(tv + (size_t)BN * N);
+  const float eps = c.norm_eps;
+  int cur = 0, len = first, done_host = 0;
+  for (int i = first; i <= last; ++i) {
+    if (done_host == BN) break;
+    const int step = i - 1;                       // position of the newest token
+    const bool prefill = prompted && i == P;
+    if (prefill) {
+      // positions 0..P-1 of every utterance in one causal pass over B x P rows; K | V into the
+      // cache, then every hypothesis continues from its utterance's last prompt row
+      PrefillCache pc{m->ab_cache.as<float>(), cache_layer, B, P, N};
+      WN_TRY(decoder_layers(m, D, RP, B, P, m->ab_prompt.as<int>(), true, s, nullptr, nullptr,
+                            nullptr, &pc));
+      WN_TRY(copy_rows(x, d, m->r_tgt.as<int>(), t2, d, nullptr, BN, d, s));
+      WN_TRY(ln(D.after, t2, t1, BN, d, eps, s));
+    } else {
+    if (step >= cap_steps) WN_TRY(grow_cache(step));
+    WN_TRY(attn_step_embed(last_tok, step, D.embed, D.pe, D.xscale, d, BN, x, s));
+    for (int li = 0; li < nl; ++li) {
+      const DecLayer& L = D.layers[li];
+      WN_TRY(ln(L.n1, x, t1, BN, d, eps, s));
+      WN_TRY(step_linear(m, skinny, L.self_qkv, t1, d, qkv, 3 * d, BN, s));
+      WN_TRY(attn_self_step(qkv, d, c.dec_heads, BN, m->ab_cache.as<float>() + li * cache_layer,
+                            step, path[cur], W, t2, s));
+      WN_TRY(step_linear(m, skinny, L.self_out, t2, d, x, d, BN, s, ACT_NONE, x, d));
+      WN_TRY(ln(L.n2, x, t1, BN, d, eps, s));
+      WN_TRY(step_linear(m, skinny, L.src_q, t1, d, t2, d, BN, s));
+      float* mem = m->r_mem_all.as<float>() + (size_t)li * mem_layer;
+      if (!m->mem_cache_valid) WN_TRY(linear(L.src_kv, m->enc.as<float>(), d, mem, 2 * d, Menc, s));
+      AttnArgs cx;
+      cx.Q = t2; cx.ldq = d; cx.K = mem; cx.V = mem + d; cx.ldk = cx.ldv = 2 * d;
+      cx.O = t1; cx.ldo = d;
+      cx.q_off = b_qoff.as<int>(); cx.q_len = b_qlen.as<int>();
+      cx.kv_off = b_kvoff.as<int>(); cx.kv_len = b_kvlen.as<int>();
+      cx.n_seq = n_cx; cx.n_heads = c.dec_heads; cx.max_q_len = cx_q;
+      cx.mask_mode = 0; cx.scale = 0.125f;
+      WN_TRY(attention(cx, s));
+      WN_TRY(step_linear(m, skinny, L.src_out, t1, d, x, d, BN, s, ACT_NONE, x, d));
+      WN_TRY(ln(L.n3, x, t1, BN, d, eps, s));
+      WN_TRY(step_linear(m, skinny, L.ff1, t1, d, hb, c.dec_ffn_dim, BN, s, act));
+      WN_TRY(step_linear(m, skinny, L.ff2, hb, c.dec_ffn_dim, x, d, BN, s, ACT_NONE, x, d));
+    }
+    m->mem_cache_valid = true;
+    WN_TRY(ln(D.after, x, t1, BN, d, eps, s));
+    }
+    // log_softmax(output_layer(after_norm(x))) -> the N best (log-prob, token) per row
+    WN_TRY(step_linear(m, skinny, D.out, t1, d, m->r_logits.as<float>(), V, BN, s));
+    CtcRowArgs r;
+    r.logits = m->r_logits.as<float>(); r.ld = V; r.M = BN; r.V = V; r.k = N;
+    r.blank = -1; r.blank_penalty = 0.f;
+    r.topk_val = tv; r.topk_idx = ti; r.logp = nullptr; r.ld_out = V;
+    WN_TRY(ctc_logsoftmax_topk(r, s));
+    WN_HIP(hipMemsetAsync(n_done, 0, sizeof(int), s));
+    WN_TRY(attn_beam_update(B, N, i, W, c.eos, V, tv, ti, score[cur], endf[cur], tok[cur],
+                            path[cur], score[cur ^ 1], endf[cur ^ 1], tok[cur ^ 1],
+                            path[cur ^ 1], last_tok, n_done, s, prefill));
+    cur ^= 1;
+    len = i + 1;
+    // "all hypotheses ended" is polled every 4th step: a step run after the end only appends
+    // eos to finished hypotheses and leaves their scores alone (mask_finished_scores /
+    // _preds), and the result strips eos (search.py:355-371) -- same output, 3 of 4 host
+    // round trips fewer
+    if ((i & 3) == 0 || i == last) {
+      WN_HIP(hipMemcpyAsync(&done_host, n_done, sizeof(int), hipMemcpyDeviceToHost, s));
+      WN_HIP(hipStreamSynchronize(s));
+    }
+  }
+  // stopped by the positional table, not by T' or by the hypotheses: say so
+  m->ab_truncated = prompted && last < maxlen && last >= first && done_host != BN;
+  WN_TRY(attn_beam_finish(B, N, len, W, c.eos, length_penalty, score[cur], tok[cur], out_tok,
+                          out_len, s, first));
+  std::vector<int> ot((size_t)B * W), ol(B);
+  WN_HIP(hipMemcpyAsync(ot.data(), out_tok, ot.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(ol.data(), out_len, ol.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(stream_wait(s));
+  for (int b = 0; b < B; ++b) {
+    lens_host[b] = std::min(ol[b], maxlen);
+    for (int j = 0; j < lens_host[b]; ++j) tokens_host[(size_t)b * maxlen + j] = ot[(size_t)b * W + j];
+  }
+  return 0;
+}
+
 }  // namespace
 }  // namespace wn
 
@@ -445,7 +701,7 @@ int wn_decoder_next_topk(wn_model* m, int32_t n_seq, const int32_t* seq_utt_host
   for (int i = 0; i < n_seq; ++i) {
     const int u = seq_utt_host[i], L = seq_lens_host[i];
     WN_CHECK(u >= 0 && u < m->B, "decoder step: utterance index");
-    WN_CHECK(L >= 1 && L <= max_len && L <= c.max_pos, "decoder step: sequence length");
+    WN_CHECK(L >= 1 && L <= max_len && L <= W.left.max_pos, "decoder step: sequence length");
     WN_CHECK(m->len[u] > 0, "decoder step: utterance without encoder frames");
     qoff[i] = (int)tok.size(); qlen[i] = L;
     kvoff[i] = m->off[u]; kvlen[i] = m->len[u];
@@ -491,154 +747,27 @@ int wn_decoder_next_topk(wn_model* m, int32_t n_seq, const int32_t* seq_utt_host
   return 0;
 }
 
-// attention_beam_search (search.py:252-371) for the current batch, entirely on the
-// device: one decoder row per running hypothesis and step (self-attention K/V cache
-// addressed through per-hypothesis ancestor paths, cross-attention K/V projected once),
-// beam bookkeeping in beam_update_kernel; the host only reads the "all ended" counter.
 int wn_attention_beam_search(wn_model* m, int32_t beam, int32_t maxlen, float length_penalty,
                              int32_t* tokens_host, int32_t* lens_host, void* stream) {
   WN_CHECK(m && m->B > 0 && m->enc.p, "attention beam search: no current batch");
   WN_ENTER(m);
   PrecisionScope prec_scope(m);
-  const Decoder& D = m->data->left;
-  WN_CHECK(!D.layers.empty(), "attention beam search: the model has no attention decoder");
-  WN_CHECK(beam >= 1 && beam <= 64 && maxlen >= 1 && tokens_host && lens_host,
-           "attention beam search: beam_size in [1, 64], maxlen >= 1");
-  hipStream_t s = (hipStream_t)stream;
-  WN_HIP(hipSetDevice(m->device));
-  const wn_config& c = m->cfg;
-  const int d = c.d_model, V = c.vocab, B = m->B, N = beam, BN = B * N, Menc = m->rows;
-  WN_CHECK(beam <= V, "attention beam search: beam larger than the vocabulary");
-  WN_CHECK(maxlen + 1 <= c.max_pos, "attention beam search: longer than the positional table");
-  const int W = maxlen + 2;                       // columns of the token / path rows
-  const int nl = (int)D.layers.size();
-  for (int b = 0; b < B; ++b)
-    WN_CHECK(m->len[b] > 0, "attention beam search: utterance without encoder frames");
-  // ---- descriptors of the cross attention: one query row per hypothesis -------------
-  std::vector<int> qoff(BN), qlen(BN, 1), kvoff(BN), kvlen(BN);
-  for (int r = 0; r < BN; ++r) { qoff[r] = r; kvoff[r] = m->off[r / N]; kvlen[r] = m->len[r / N]; }
-  WN_TRY(m->stage.begin((size_t)(4 * BN + 64) * sizeof(int) + 4096));
-  WN_TRY(upload_desc(m, m->r_qoff, qoff, s));
-  WN_TRY(upload_desc(m, m->r_qlen, qlen, s));
-  WN_TRY(upload_desc(m, m->r_kvoff, kvoff, s));
-  WN_TRY(upload_desc(m, m->r_kvlen, kvlen, s));
-  WN_TRY(m->stage.end(s));
-  WN_TRY(decoder_ws(m, BN, BN, V, (size_t)2 * BN * N));
-  // self-attention K | V cache [layer][step][slot][2d]: sized for the steps actually run,
-  // not for maxlen = T' (the reference's cache grows with the decoded length too,
-  // decoder.py:226-281): starts at 32 steps and doubles, the used prefix of every layer is
-  // carried over
-  int cap_steps = std::min(maxlen, 32);
-  size_t cache_layer = (size_t)cap_steps * BN * 2 * d;
-  WN_TRY(m->ab_cache.ensure(nl * cache_layer * sizeof(float)));
-  auto grow_cache = [&](int used_steps) -> int {
-    const int cap2 = std::min(maxlen, cap_steps * 2);
-    const size_t layer2 = (size_t)cap2 * BN * 2 * d;
-    DevBuf nb;
-    WN_TRY(nb.ensure(nl * layer2 * sizeof(float)));
-    for (int li = 0; li < nl; ++li)
-      WN_HIP(hipMemcpyAsync(nb.as<float>() + li * layer2, m->ab_cache.as<float>() + li * cache_layer,
-                            (size_t)used_steps * BN * 2 * d * sizeof(float),
-                            hipMemcpyDeviceToDevice, s));
-    WN_HIP(hipStreamSynchronize(s));            // before the old buffer is freed
-    m->ab_cache.swap(nb);
-    cap_steps = cap2;
-    cache_layer = layer2;
-    return 0;
-  };
-  const size_t mem_layer = (size_t)Menc * 2 * d;
-  WN_TRY(m->r_mem_all.ensure(nl * mem_layer * sizeof(float)));
-  // state: 2 x {score, end, tok, path} + last_tok + n_done + out_tok + out_len
-  const size_t n_int = (size_t)2 * (BN + BN + (size_t)BN * W * 2) + BN + 16 + (size_t)B * W + B;
-  WN_TRY(m->ab_state.ensure(n_int * sizeof(int)));
-  int* base = m->ab_state.as<int>();
-  float* score[2]; int* endf[2]; int* tok[2]; int* path[2];
-  for (int k = 0; k < 2; ++k) {
-    score[k] = reinterpret_cast<float*>(base); base += BN;
-    endf[k] = base; base += BN;
-    tok[k] = base; base += (size_t)BN * W;
-    path[k] = base; base += (size_t)BN * W;
-  }
-  int* last_tok = base; base += BN;
-  int* n_done = base; base += 16;
-  int* out_tok = base; base += (size_t)B * W;
-  int* out_len = base;
-  WN_TRY(attn_beam_init(BN, N, W, c.sos, score[0], endf[0], tok[0], path[0], last_tok, s));
-  WN_HIP(hipMemsetAsync(n_done, 0, sizeof(int), s));
-  float* x = m->r_x.as<float>();
-  float* t1 = m->r_t1.as<float>();
-  float* t2 = m->r_t2.as<float>();
-  float* qkv = m->r_qkv.as<float>();
-  float* hb = m->r_h.as<float>();
-  float* tv = m->r_out.as<float>();
-  int* ti = reinterpret_cast<int*>(tv + (size_t)BN * N);
-  const float eps = c.norm_eps;
-  int cur = 0, len = 1, done_host = 0;
-  for (int i = 1; i <= maxlen; ++i) {
-    if (done_host == BN) break;
-    const int step = i - 1;                       // position of the newest token
-    if (step >= cap_steps) WN_TRY(grow_cache(step));
-    WN_TRY(attn_step_embed(last_tok, step, D.embed, D.pe, sqrtf((float)d), d, BN, x, s));
-    for (int li = 0; li < nl; ++li) {
-      const DecLayer& L = D.layers[li];
-      WN_TRY(ln(L.n1, x, t1, BN, d, eps, s));
-      WN_TRY(linear(L.self_qkv, t1, d, qkv, 3 * d, BN, s));
-      WN_TRY(attn_self_step(qkv, d, c.dec_heads, BN, m->ab_cache.as<float>() + li * cache_layer,
-                            step, path[cur], W, t2, s));
-      WN_TRY(linear(L.self_out, t2, d, x, d, BN, s, ACT_NONE, x, d));
-      WN_TRY(ln(L.n2, x, t1, BN, d, eps, s));
-      WN_TRY(linear(L.src_q, t1, d, t2, d, BN, s));
-      float* mem = m->r_mem_all.as<float>() + (size_t)li * mem_layer;
-      if (!m->mem_cache_valid) WN_TRY(linear(L.src_kv, m->enc.as<float>(), d, mem, 2 * d, Menc, s));
-      AttnArgs cx;
-      cx.Q = t2; cx.ldq = d; cx.K = mem; cx.V = mem + d; cx.ldk = cx.ldv = 2 * d;
-      cx.O = t1; cx.ldo = d;
-      cx.q_off = m->r_qoff.as<int>(); cx.q_len = m->r_qlen.as<int>();
-      cx.kv_off = m->r_kvoff.as<int>(); cx.kv_len = m->r_kvlen.as<int>();
-      cx.n_seq = BN; cx.n_heads = c.dec_heads; cx.max_q_len = 1;
-      cx.mask_mode = 0; cx.scale = 0.125f;
-      WN_TRY(attention(cx, s));
-      WN_TRY(linear(L.src_out, t1, d, x, d, BN, s, ACT_NONE, x, d));
-      WN_TRY(ln(L.n3, x, t1, BN, d, eps, s));
-      WN_TRY(linear(L.ff1, t1, d, hb, c.dec_ffn_dim, BN, s, ACT_RELU));
-      WN_TRY(linear(L.ff2, hb, c.dec_ffn_dim, x, d, BN, s, ACT_NONE, x, d));
-    }
-    m->mem_cache_valid = true;
-    // log_softmax(output_layer(after_norm(x))) -> the N best (log-prob, token) per row
-    WN_TRY(ln(D.after, x, t1, BN, d, eps, s));
-    WN_TRY(linear(D.out, t1, d, m->r_logits.as<float>(), V, BN, s));
-    CtcRowArgs r;
-    r.logits = m->r_logits.as<float>(); r.ld = V; r.M = BN; r.V = V; r.k = N;
-    r.blank = -1; r.blank_penalty = 0.f;
-    r.topk_val = tv; r.topk_idx = ti; r.logp = nullptr; r.ld_out = V;
-    WN_TRY(ctc_logsoftmax_topk(r, s));
-    WN_HIP(hipMemsetAsync(n_done, 0, sizeof(int), s));
-    WN_TRY(attn_beam_update(B, N, i, W, c.eos, V, tv, ti, score[cur], endf[cur], tok[cur],
-                            path[cur], score[cur ^ 1], endf[cur ^ 1], tok[cur ^ 1],
-                            path[cur ^ 1], last_tok, n_done, s));
-    cur ^= 1;
-    len = i + 1;
-    // "all hypotheses ended" is polled every 4th step: a step run after the end only appends
-    // eos to finished hypotheses and leaves their scores alone (mask_finished_scores /
-    // _preds), and the result strips eos (search.py:355-371) -- same output, 3 of 4 host
-    // round trips fewer
-    if ((i & 3) == 0 || i == maxlen) {
-      WN_HIP(hipMemcpyAsync(&done_host, n_done, sizeof(int), hipMemcpyDeviceToHost, s));
-      WN_HIP(hipStreamSynchronize(s));
-    }
-  }
-  WN_TRY(attn_beam_finish(B, N, len, W, c.eos, length_penalty, score[cur], tok[cur], out_tok,
-                          out_len, s));
-  std::vector<int> ot((size_t)B * W), ol(B);
-  WN_HIP(hipMemcpyAsync(ot.data(), out_tok, ot.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  WN_HIP(hipMemcpyAsync(ol.data(), out_len, ol.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  WN_HIP(stream_wait(s));
-  for (int b = 0; b < B; ++b) {
-    lens_host[b] = std::min(ol[b], maxlen);
-    for (int j = 0; j < lens_host[b]; ++j) tokens_host[(size_t)b * maxlen + j] = ot[(size_t)b * W + j];
-  }
-  return 0;
+  return beam_search_run(m, beam, maxlen, length_penalty, nullptr, 1, tokens_host, lens_host,
+                         (hipStream_t)stream);
 }
+
+int wn_attention_beam_search_prompt(wn_model* m, int32_t beam, int32_t maxlen,
+                                    float length_penalty, const int32_t* prompt_host, int32_t P,
+                                    int32_t* tokens_host, int32_t* lens_host, void* stream) {
+  WN_CHECK(m && m->B > 0 && m->enc.p, "attention beam search: no current batch");
+  WN_ENTER(m);
+  PrecisionScope prec_scope(m);
+  WN_CHECK(prompt_host && P >= 1, "attention beam search: null / empty prompt");
+  return beam_search_run(m, beam, maxlen, length_penalty, prompt_host, P, tokens_host,
+                         lens_host, (hipStream_t)stream);
+}
+
+int32_t wn_attention_truncated(const wn_model* m) { return m ? (m->ab_truncated ? 1 : 0) : -1; }
 
 int wn_decoder_forward(wn_model* m, int32_t utt, int32_t which, int32_t n_seq,
                        const int32_t* tokens_host, const int32_t* lens_host,
@@ -652,8 +781,8 @@ int wn_decoder_forward(wn_model* m, int32_t utt, int32_t which, int32_t n_seq,
   WN_CHECK(which == 0 || which == 1, "decoder forward: which must be 0 (left) or 1 (right)");
   const Decoder& D = which == 0 ? m->data->left : m->data->right;
   WN_CHECK(!D.layers.empty(), "decoder forward: the model has no such decoder");
-  WN_CHECK(n_seq > 0 && max_len > 0 && max_len <= m->cfg.max_pos,
-           "decoder forward: bad batch shape");
+  WN_CHECK(n_seq > 0 && max_len > 0 && max_len <= D.max_pos,
+           "decoder forward: bad batch shape / longer than the positional table");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
   const wn_config& c = m->cfg;

@@ -61,15 +61,18 @@ int stage_norm(const Src& src, HostStage& hs, const std::string& pfx, int n) {
   hs.add(pfx + ".bias", b, n);
   return 0;
 }
-// fuse several Linear layers along the output dimension
+// fuse several Linear layers along the output dimension; part `no_bias_part` (if >= 0) has no
+// bias in the state dict (key_bias: false): zeros in its place
 int stage_fused(const Src& src, HostStage& hs, const std::string& name,
-                const std::vector<std::string>& parts, int out_each, int in) {
+                const std::vector<std::string>& parts, int out_each, int in,
+                int no_bias_part = -1) {
   std::vector<float> w((size_t)parts.size() * out_each * in),
-      b((size_t)parts.size() * out_each);
+      b((size_t)parts.size() * out_each, 0.f);
   for (size_t i = 0; i < parts.size(); ++i) {
     WN_GET(pw, parts[i] + ".weight", (int64_t)out_each * in);
-    WN_GET(pb, parts[i] + ".bias", out_each);
     memcpy(w.data() + i * out_each * in, pw, sizeof(float) * out_each * in);
+    if ((int)i == no_bias_part) continue;
+    WN_GET(pb, parts[i] + ".bias", out_each);
     memcpy(b.data() + i * out_each, pb, sizeof(float) * out_each);
   }
   hs.add(name + ".weight", w.data(), w.size());
@@ -83,17 +86,30 @@ int stage_decoder(const Src& src, HostStage& hs, const std::string& pfx,
   WN_GET(emb, pfx + ".embed.0.weight", (int64_t)V * d);
   hs.add(pfx + ".embed", emb, (size_t)V * d);
   WN_TRY(stage_norm(src, hs, pfx + ".after_norm", d));
-  WN_TRY(stage_linear(src, hs, pfx + ".output_layer", V, d));
+  if (c.dec_learned_pos) {
+    // LearnablePositionalEncoding (embedding.py:167-175): `pe` is a weight, (1, max_len, d)
+    WN_GET(pe, pfx + ".embed.1.pe", (int64_t)c.dec_max_pos * d);
+    hs.add(pfx + ".pe", pe, (size_t)c.dec_max_pos * d);
+  }
+  if (src.has(pfx + ".output_layer.weight")) {
+    // (tie_word_embedding: init_model clones / ties the embedding into it, real checkpoints
+    // carry both)
+    WN_TRY(stage_linear(src, hs, pfx + ".output_layer", V, d));
+  } else {
+    // a state dict with the tied weight stored once: the embedding and a zero bias
+    hs.add(pfx + ".output_layer.weight", emb, (size_t)V * d);
+    hs.alloc(pfx + ".output_layer.bias", V);
+  }
   for (int j = 0; j < nlayers; ++j) {
     const std::string p = pfx + ".decoders." + std::to_string(j);
     WN_TRY(stage_fused(src, hs, p + ".self_qkv",
                        {p + ".self_attn.linear_q", p + ".self_attn.linear_k",
-                        p + ".self_attn.linear_v"}, d, d));
+                        p + ".self_attn.linear_v"}, d, d, c.dec_key_bias ? 1 : -1));
     WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d));
     WN_TRY(stage_linear(src, hs, p + ".src_attn.linear_q", d, d));
     WN_TRY(stage_fused(src, hs, p + ".src_kv",
                        {p + ".src_attn.linear_k", p + ".src_attn.linear_v"}, d,
-                       d));
+                       d, c.dec_src_key_bias ? 0 : -1));
     WN_TRY(stage_linear(src, hs, p + ".src_attn.linear_out", d, d));
     WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_1", c.dec_ffn_dim, d));
     WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_2", d, c.dec_ffn_dim));
@@ -122,6 +138,9 @@ int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
            "decoder head dim must be 64");
   WN_CHECK(c.ffn_dim % 32 == 0 && c.feat_dim >= 7 && c.feat_dim <= 128,
            "unsupported ffn_dim / feat_dim");
+  WN_CHECK(c.dec_activation == 0 || c.dec_activation == 1, "dec_activation: 0 relu, 1 gelu");
+  WN_CHECK(!c.dec_learned_pos || (c.dec_max_pos >= 1 && !c.bidirectional),
+           "learned decoder positions need dec_max_pos >= 1 and a single decoder");
   const bool tf = c.encoder_type == 1;
   WN_CHECK(c.encoder_type == 0 || c.encoder_type == 1, "unknown encoder_type");
   WN_CHECK(tf ? c.input_layer == 1 : c.input_layer == 0,
@@ -445,6 +464,9 @@ int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
   auto DEC = [&](Decoder& D, const std::string& pfx, int nl) {
     D.embed = P(pfx + ".embed");
     D.pe = W.pe;  // same sinusoid table (embedding.py:47-56), same d_model
+    D.xscale = sqrtf((float)d);
+    D.max_pos = c.max_pos;
+    if (c.dec_learned_pos) { D.pe = P(pfx + ".pe"); D.xscale = 1.0f; D.max_pos = c.dec_max_pos; }
     D.after = NORM(pfx + ".after_norm");
     D.out = LIN(pfx + ".output_layer", V, d);
     D.layers.resize(nl);

@@ -95,6 +95,33 @@ int wn_op_gemm_bf16_stored(const float* A, const float* W, const float* bias,
   return gemm_bf16_stored(g, w16.p, s);
 }
 
+int wn_op_gemm_skinny(const float* A, const float* W, const float* bias, const float* resid,
+                      float* C, int32_t M, int32_t N, int32_t K, int32_t act, int32_t w_bf16,
+                      int32_t split_k, void* stream) {
+  // test hook of the decoder step's GEMM: with w_bf16 the weights are converted to a bf16 image
+  // in a scratch buffer first (the model path reads the handle's converted weight slab)
+  WN_CHECK(A && W && C && M > 0 && N > 0 && K > 0, "gemm_skinny: null / empty");
+  WN_CHECK(M <= 256, "gemm_skinny: M must be in [1, 256]");
+  WN_CHECK(K % 32 == 0 && split_k >= 0, "gemm_skinny: K must be a multiple of 32, split_k >= 0");
+  static thread_local DevBuf w16, part;
+  hipStream_t s = (hipStream_t)stream;
+  SkinnyArgs g;
+  g.A = A; g.lda = K; g.bias = bias; g.resid = resid; g.ldr = N; g.C = C; g.ldc = N;
+  g.M = M; g.N = N; g.K = K; g.act = act;
+  if (w_bf16) {
+    WN_TRY(w16.ensure((size_t)N * K * 2));
+    WN_TRY(convert_f32_to_bf16(W, w16.p, (int64_t)N * K, s));
+    g.Wh = w16.p;
+  } else {
+    g.W = W;
+  }
+  const int tiles = w_bf16 ? cdiv(K, 64) : K / 32;
+  g.split_k = std::min(split_k > 0 ? split_k : gemm_skinny_split(N, K, w_bf16 != 0), tiles);
+  WN_TRY(part.ensure(gemm_skinny_ws_bytes(M, N, g.split_k)));
+  g.part = part.as<float>(); g.part_bytes = part.cap;
+  return gemm_skinny(g, s);
+}
+
 int wn_op_gemm_lowp(const void* A, const void* W, const void* a_scale, const void* w_scale,
                     const float* bias, const float* resid, void* C, void* c_scale,
                     int32_t M, int32_t N, int32_t K, float alpha, int32_t act,

@@ -166,6 +166,23 @@ int gemm_lp_clocks(unsigned long long* out);   // [8 waves][8] stamps of the pip
 // fp32 [rows][ld] -> e4m3 [rows][K] + block scales [K/128][pitch] dwords
 int mx_quantize(const float* x, int ld, int rows, int K, void* q, unsigned* scale, int pitch,
                 hipStream_t s);
+// Skinny GEMM of the autoregressive decoder step (gemm_skinny.hip): M <= 256 rows, a block owns
+// all of them for its 128 columns and K slice; deterministic split K through `part`.
+struct SkinnyArgs {
+  const float* A = nullptr; int lda = 0;   // [M, lda] fp32
+  const float* W = nullptr;                // [N, K] fp32, or
+  const void* Wh = nullptr;                // [N, K] bf16 image of it (A is rounded to bf16 then)
+  const float* bias = nullptr;             // [N] or null
+  const float* resid = nullptr; int ldr = 0;   // may alias C
+  float* C = nullptr; int ldc = 0;         // C = resid + act(A W^T + bias)
+  int M = 0, N = 0, K = 0, act = ACT_NONE;
+  int split_k = 0;                         // K slices, 0 = gemm_skinny_split()
+  float* part = nullptr; size_t part_bytes = 0;   // >= gemm_skinny_ws_bytes(M, N, slices)
+};
+int gemm_skinny_split(int N, int K, bool bf16);
+size_t gemm_skinny_ws_bytes(int M, int N, int S);
+int gemm_skinny(const SkinnyArgs& a, hipStream_t stream);
+
 enum { PREC_FP8 = 2 };  // bf16 mode with MXFP8 FFN GEMMs (wn_model_set_precision)
 int convert_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t s);
 

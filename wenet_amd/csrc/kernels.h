@@ -457,10 +457,16 @@ int attn_beam_init(int BN, int N, int max_len, int sos, float* score, int* end, 
 int attn_beam_update(int B, int N, int step, int max_len, int eos, int V, const float* topv,
                      const int* topi, const float* score_in, const int* end_in,
                      const int* tok_in, const int* path_in, float* score_out, int* end_out,
-                     int* tok_out, int* path_out, int* last_tok, int* n_done, hipStream_t s);
+                     int* tok_out, int* path_out, int* last_tok, int* n_done, hipStream_t s,
+                     bool shared_row = false);
 int attn_beam_finish(int B, int N, int len, int max_len, int eos, float length_penalty,
                      const float* score, const int* tok, int* out_tok, int* out_len,
-                     hipStream_t s);
+                     hipStream_t s, int prefix = 1);
+// the prompted search: rows that start as the (B, P) prompts; the prefill's K | V into the cache
+int attn_beam_init_prompt(int BN, int N, int max_len, const int* prompt, int P, float* score,
+                          int* end, int* tok, int* path, int* last_tok, hipStream_t s);
+int attn_prompt_cache_store(const float* qkv, int d, int B, int P, int N, float* cache,
+                            hipStream_t s);
 
 // rows scatter/gather helpers
 // forward_chunk cache plumbing (see encoder_kernels.hip), one descriptor per streaming

@@ -171,7 +171,9 @@ struct DecLayer {
 
 struct Decoder {
   const float* embed = nullptr;  // [V][d]
-  const float* pe = nullptr;     // [max_pos][d]
+  const float* pe = nullptr;     // [max_pos][d] sinusoids, or the learned [dec_max_pos][d] table
+  float xscale = 1.0f;           // embedding scale: sqrt(d) with sinusoids, 1 with the learned table
+  int max_pos = 0;               // rows of pe
   Norm after;
   Linear out;
   std::vector<DecLayer> layers;
@@ -293,6 +295,9 @@ struct wn_model {
   DevBuf r_res;                // wn_rescore: results, one block
   PinnedBuf r_host;            // ... and where they land on the host
   DevBuf ab_cache, ab_state;   // `attention` mode: self-attention K|V cache, beam state
+  DevBuf ab_prompt;            // ... its prompts (B, P) and the prefill descriptors
+  DevBuf sk_part;              // split-K partials of the skinny step GEMMs (gemm_skinny.hip)
+  bool ab_truncated = false;   // the last prompted search stopped at the positional table
   bool mem_cache_valid = false;
 
   SideStream side;             // wn_rescore_prefetch

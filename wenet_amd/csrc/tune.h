@@ -127,7 +127,11 @@ namespace wn {
   /* result waits of the searches / rescoring: 1 = poll the stream, 0 = blocking wait (A/B) */  \
   X(sync_spin, 1)                                                                               \
   /* CTC log-softmax: 0 = always the block-per-row kernel (A/B, tests) */                       \
-  X(ctc_wave, 1)
+  X(ctc_wave, 1)                                                                                \
+  /* wn_attention_beam_search_prompt: 1 = the step's GEMMs (M = B x beam <= 256 rows) run on    \
+     the skinny kernel (gemm_skinny.hip), 0 = on linear() like wn_attention_beam_search.  Not   \
+     yet measured against each other on the GPU: the default stays the existing kernels */      \
+  X(dec_skinny, 0)
 
 struct Tune {
 #define X(name, dflt) int name = dflt;

@@ -99,9 +99,17 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
                        use_output_layer=True)
     if enc_type == 'conformer':
         dec_default.update(activation_type='relu', input_layer='embed')
-    dec_off = False   # Whisper-style decoders: the encoder (+ CTC head) runs, not the decoder
+    dec_type = configs.get('decoder', 'bitransformer')
+    # the Whisper decoder (examples/aishell/whisper/conf/finetune_whisper_largev3.yaml:20-37):
+    # these values of a left-to-right `transformer` decoder have kernels too
+    whisper_dec = dict(activation_type='gelu', input_layer='embed_learnable_pe', key_bias=False,
+                       src_key_bias=False, tie_word_embedding=True)
+    dec_default.setdefault('src_key_bias', True)
+    dec_off = False   # other decoder variants: the encoder (+ CTC head) runs, not the decoder
     for k, v in dec_default.items():
         if k in dc and dc[k] != v:
+            if dec_type == 'transformer' and k in whisper_dec and dc[k] == whisper_dec[k]:
+                continue
             if enc_type == 'transformer':
                 dec_off = True
                 continue
@@ -118,7 +126,6 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
     else:
         sos = vocab - 1 if st is None else st.get('<sos>', vocab - 1)
         eos = vocab - 1 if st is None else st.get('<eos>', vocab - 1)
-    dec_type = configs.get('decoder', 'bitransformer')
     bidir = dec_type == 'bitransformer'
     c = _lib.WnConfig()
     c.feat_dim = configs['input_dim']
@@ -149,14 +156,25 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         raise NotImplementedError(
             f'encoder_conf.cnn_module_norm={cnn_norm!r} is outside the accelerated path')
     c.cnn_norm = 1 if (enc_type == 'conformer' and cnn_norm == 'batch_norm') else 0
+    # decoder variants (all 0: the classic decoder)
+    dec_in, dec_act = dc.get('input_layer', 'embed'), dc.get('activation_type', 'relu')
+    whisper_ok = dec_type == 'transformer'
+    c.dec_activation = int(dec_act == 'gelu')
+    c.dec_key_bias = int(not dc.get('key_bias', True))          # 1: linear_k has no bias
+    c.dec_src_key_bias = int(not dc.get('src_key_bias', True))
+    c.dec_learned_pos = int(dec_in == 'embed_learnable_pe')
+    c.dec_max_pos = 448 if c.dec_learned_pos else 0             # embedding.py:171
     if enc_type == 'transformer':
         c.cnn_kernel, c.causal = 1, 0
-        # the Whisper decoder (learnable positions, tied embedding) is not on
-        # the accelerated path: encoder (+ CTC head) only
-        if dec_off or dc.get('input_layer', 'embed') != 'embed' or \
-                dc.get('activation_type', 'relu') != 'relu':
+        # decoder variants without kernels: encoder (+ CTC head) only
+        if dec_off or dec_in not in (('embed', 'embed_learnable_pe') if whisper_ok
+                                     else ('embed', )) or \
+                dec_act not in (('relu', 'gelu') if whisper_ok else ('relu', )):
             c.dec_layers = c.dec_r_layers = 0
             c.bidirectional = 0
+    if c.dec_layers == 0:
+        c.dec_activation = c.dec_key_bias = c.dec_src_key_bias = 0
+        c.dec_learned_pos = c.dec_max_pos = 0
     return c
 
 
@@ -242,6 +260,9 @@ class ASRModel:
         pe = state_dict.get('encoder.embed.pos_enc.pe')
         if pe is not None:  # WhisperPositionalEncoding keeps 1500 rows
             self._cfg.max_pos = int(pe.shape[-2])
+        dpe = state_dict.get('decoder.embed.1.pe')
+        if self._cfg.dec_learned_pos and dpe is not None:   # LearnablePositionalEncoding
+            self._cfg.dec_max_pos = int(dpe.shape[-2])
         self.vocab_size = self._cfg.vocab
         self.sos, self.eos = self._cfg.sos, self._cfg.eos
         self.ignore_id = -1
@@ -254,8 +275,14 @@ class ASRModel:
         # batch and rescored against the unfiltered encoder output (deviations);
         # reset by every decode, copied back to the caller's model by DecodePipeline
         self.last_non_blank_filter_empty = False
+        # True when the last prompted `attention` decode stopped at the decoder's positional
+        # table with a hypothesis still open (the reference asserts there; DESIGN.md,
+        # deviations); reset by every `attention` decode
+        self.last_attention_truncated = False
         self.special_tokens = (configs.get('tokenizer_conf') or {}).get(
             'special_tokens')
+        if configs.get('model') == 'whisper':   # whisper.py:30-31
+            self.default_decode_method = 'attention'
         L = _lib.lib()
         arrs, tensors = [], (_lib.WnTensor * len(state_dict))()
         for i, (k, v) in enumerate(state_dict.items()):
@@ -687,7 +714,7 @@ class ASRModel:
                                 decoding_chunk_size, num_decoding_left_chunks,
                                 simulate_streaming, context_graph, blank_id,
                                 blank_penalty)
-        return self._decode_end(st, ctc_weight, reverse_weight, length_penalty)
+        return self._decode_end(st, ctc_weight, reverse_weight, length_penalty, infos)
 
     def _decode_begin(self, methods, speech, speech_lengths, beam_size=1,
                       decoding_chunk_size=-1, num_decoding_left_chunks=-1,
@@ -725,7 +752,7 @@ class ASRModel:
         self._ctx_graph = graph
 
     def _decode_end(self, st, ctc_weight=0.0, reverse_weight=0.0,
-                    length_penalty=0.0):
+                    length_penalty=0.0, infos=None):
         """Second half of decode(): the searches (+ rescoring) and the result
         records; synchronises the stream."""
         methods, B, enc_lens = st['methods'], st['B'], st['enc_lens']
@@ -741,9 +768,11 @@ class ASRModel:
                 raise RuntimeError("'attention' mode: an utterance has no encoder "
                                    'frames')
             from wenet_amd.search import attention_beam_search
-            # maxlen = encoder_out.size(1) of the padded reference tensor
+            # maxlen = encoder_out.size(1) of the padded reference tensor; a Whisper model
+            # (special tokens with 'transcribe') starts from its prompts (search.py:267-289)
+            self.last_attention_truncated = False
             results['attention'] = attention_beam_search(
-                self, B, st['Tp'], beam_size, length_penalty)
+                self, B, st['Tp'], beam_size, length_penalty, infos)
         if 'ctc_greedy_search' in methods:
             results['ctc_greedy_search'] = _greedy(self._h, B, max_len,
                                                    blank_id, self.device)

@@ -109,7 +109,7 @@ class DecodePipeline:
             ctc_weight = kw.pop('ctc_weight', 0.0)
             reverse_weight = kw.pop('reverse_weight', 0.0)
             length_penalty = kw.pop('length_penalty', 0.0)
-            kw.pop('infos', None)
+            infos = kw.pop('infos', None)       # the Whisper prompts of `attention`
             with torch.cuda.stream(stream):
                 with self._enc_lock:
                     gated = False
@@ -138,10 +138,11 @@ class DecodePipeline:
                     done.record(stream)
                     self._enc_done = done
                 res = self.models[i]._decode_end(st, ctc_weight, reverse_weight,
-                                                 length_penalty)
+                                                 length_penalty, infos)
                 # per-decode status the caller reads on ITS model (the clones are private)
                 self._owner.last_non_blank_filter_empty = \
                     self.models[i].last_non_blank_filter_empty
+                self._owner.last_attention_truncated = self.models[i].last_attention_truncated
                 return res
         finally:
             self._free.put(i)

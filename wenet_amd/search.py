@@ -363,16 +363,31 @@ def _nbest_arrays(ctc_prefix_results: List[DecodeResult]):
 
 
 def attention_beam_search(model, batch_size: int, maxlen: int, beam_size: int = 10,
-                          length_penalty: float = 0.0) -> List[DecodeResult]:
-    """attention_beam_search (wenet/models/transformer/search.py:252-371, the
-    non-Whisper branch) over the model's CURRENT batch (the encoder output of the last
-    `_decode_begin` / `_forward_encoder` stays on the device).  The whole search --
-    one decoder step per token with a self-attention cache, the finished-hypothesis
-    masks, the beam x beam re-ranking and the length-penalised arg-max -- runs on the
-    device (wn_attention_beam_search); this function only shapes the result."""
+                          length_penalty: float = 0.0,
+                          infos: Optional[dict] = None) -> List[DecodeResult]:
+    """attention_beam_search (wenet/models/transformer/search.py:252-371) over the model's
+    CURRENT batch (the encoder output of the last `_decode_begin` / `_forward_encoder` stays
+    on the device).  The whole search -- one decoder step per token with a self-attention
+    cache, the finished-hypothesis masks, the beam x beam re-ranking and the length-penalised
+    arg-max -- runs on the device; this function only shapes the result.  A Whisper model
+    (special tokens with 'transcribe') takes the reference's Whisper branch: every hypothesis
+    starts from the prompt `infos` asks for (wenet_amd/whisper.py;
+    wn_attention_beam_search_prompt), which the result does not carry; every other model
+    starts from <sos> (wn_attention_beam_search) and `infos` is ignored."""
     assert maxlen >= 1
     tokens = np.zeros((batch_size, maxlen), dtype=np.int32)
     lens = np.zeros((batch_size, ), dtype=np.int32)
+    from wenet_amd import whisper
+    special = getattr(model, 'special_tokens', None)
+    if whisper.is_whisper(special):
+        prompts = np.ascontiguousarray(whisper.build_prompts(special, batch_size, infos))
+        _lib.check(
+            _lib.lib().wn_attention_beam_search_prompt(
+                model._h, beam_size, maxlen, float(length_penalty), _lib.i32p(prompts),
+                prompts.shape[1], _lib.i32p(tokens), _lib.i32p(lens),
+                _stream_ptr(model.device)), 'wn_attention_beam_search_prompt')
+        model.last_attention_truncated = bool(_lib.lib().wn_attention_truncated(model._h))
+        return [DecodeResult(tokens[b, :lens[b]].tolist()) for b in range(batch_size)]
     _lib.check(
         _lib.lib().wn_attention_beam_search(model._h, beam_size, maxlen,
                                             float(length_penalty), _lib.i32p(tokens),

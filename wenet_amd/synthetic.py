@@ -30,6 +30,16 @@ import torch
 
 _SPECIAL = {'<blank>': 0, '<unk>': 1, '<sos>': 2, '<eos>': 2}
 
+# decoder_conf of examples/aishell/whisper/conf/finetune_whisper_largev3.yaml:20-37
+_WHISPER_DEC = dict(activation_type='gelu', dropout_rate=0.0, input_layer='embed_learnable_pe',
+                    key_bias=False, src_key_bias=False, normalize_before=True,
+                    positional_dropout_rate=0.0, self_attention_dropout_rate=0.0,
+                    src_attention=True, src_attention_dropout_rate=0.0,
+                    tie_word_embedding=True, use_output_layer=True)
+_WHISPER_TOK = dict(bpe_path=None, is_multilingual=True, non_lang_syms_path=None,
+                    num_languages=100, split_with_space=False, symbol_table_path=None)
+WHISPER_DEC_MAX_POS = 448    # LearnablePositionalEncoding max_len (embedding.py:171)
+
 CONFIGS = {
     # examples/aishell/s0/conf/train_u2++_conformer.yaml:4-62
     'aishell_u2pp': {
@@ -230,6 +240,58 @@ CONFIGS = {
                              use_dynamic_left_chunk=False),
         'decoder': None, 'decoder_conf': {},
         'cmvn': None,
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1,
+                           length_normalized_loss=False),
+    },
+    # examples/aishell/whisper/conf/finetune_whisper_largev3.yaml:1-56 in miniature WITH its
+    # decoder (gelu, learnable positions, no key biases, tied-then-cloned output layer) and the
+    # Whisper special tokens inside the vocabulary: languages sot + 1 .. (en = 152, zh = 153)
+    'whisper_tiny_dec': {
+        'input_dim': 80, 'output_dim': 160,
+        'encoder': 'transformer',
+        'encoder_conf': dict(activation_type='gelu', attention_dropout_rate=0.0,
+                             attention_heads=2, dropout_rate=0.0,
+                             input_layer='conv1d2', key_bias=False,
+                             linear_units=256, normalize_before=True,
+                             num_blocks=2, output_size=128,
+                             pos_enc_layer_type='abs_pos_whisper',
+                             positional_dropout_rate=0.0, static_chunk_size=-1,
+                             use_dynamic_chunk=False,
+                             use_dynamic_left_chunk=False),
+        'decoder': 'transformer',
+        'decoder_conf': dict(_WHISPER_DEC, attention_heads=2, linear_units=256,
+                             num_blocks=2),
+        'cmvn': None,
+        'model': 'whisper',
+        'tokenizer': 'whisper',
+        'tokenizer_conf': dict(_WHISPER_TOK, special_tokens=dict(
+            eot=150, sot=151, translate=154, transcribe=155, sot_prev=156, no_speech=157,
+            no_timestamps=158, timestamp_begin=159)),
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1,
+                           length_normalized_loss=False),
+    },
+    # the whole Whisper-large-v3 (32 + 32 blocks, 51866 tokens) for tools/bench_whisper_decode.py
+    'whisper_largev3_dec': {
+        'input_dim': 128, 'output_dim': 51866,
+        'encoder': 'transformer',
+        'encoder_conf': dict(activation_type='gelu', attention_dropout_rate=0.0,
+                             attention_heads=20, dropout_rate=0.0,
+                             input_layer='conv1d2', key_bias=False,
+                             linear_units=5120, normalize_before=True,
+                             num_blocks=32, output_size=1280,
+                             pos_enc_layer_type='abs_pos_whisper',
+                             positional_dropout_rate=0.0, static_chunk_size=-1,
+                             use_dynamic_chunk=False,
+                             use_dynamic_left_chunk=False),
+        'decoder': 'transformer',
+        'decoder_conf': dict(_WHISPER_DEC, attention_heads=20, linear_units=5120,
+                             num_blocks=32),
+        'cmvn': None,
+        'model': 'whisper',
+        'tokenizer': 'whisper',
+        'tokenizer_conf': dict(_WHISPER_TOK, special_tokens=dict(
+            eot=50257, no_speech=50363, no_timestamps=50364, sot=50258, sot_prev=50362,
+            timestamp_begin=50365, transcribe=50360, translate=50359)),
         'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1,
                            length_normalized_loss=False),
     },
@@ -528,6 +590,40 @@ def _make_transformer_state_dict(configs, seed, sharpen_ctc):
         lin(p + '.feed_forward.w_2', d, ffn)
         norm(p + '.norm1', d)
         norm(p + '.norm2', d)
+    if configs.get('decoder') is not None:
+        # the Whisper decoder (decoder.py:59-135 as the recipe configures it): learnable `pe`,
+        # linear_k without bias, an output layer of its own (init_model clones the embedding
+        # into it and fine-tuning moves both, so checkpoints carry two different tensors).
+        # Scales: embedding ~ N(0, 0.3), pe ~ N(0, 0.9), layer matrices x 3 -- with smaller ones
+        # a random decoder's next token barely depends on its input or its position and every
+        # hypothesis is one token repeated; <eot> gets a logit bias of 1.25 so that some
+        # hypotheses end before the cap (with 3 everything ends at once)
+        dc = configs['decoder_conf']
+        dffn = dc['linear_units']
+        sd['decoder.embed.0.weight'] = _normal(seed, 'decoder.embed', (V, d), 0.3)
+        sd['decoder.embed.1.pe'] = _normal(
+            seed, 'decoder.pe', (1, WHISPER_DEC_MAX_POS, d), 0.9)
+        norm('decoder.after_norm', d)
+        lin('decoder.output_layer', V, d)
+        eot = ((configs.get('tokenizer_conf') or {}).get('special_tokens') or {}).get('eot')
+        if eot is not None:
+            sd['decoder.output_layer.bias'][eot] += np.float32(1.25)
+        first = len(sd)
+        for j in range(dc['num_blocks']):
+            p = f'decoder.decoders.{j}'
+            for a, kb in (('self_attn', dc.get('key_bias', True)),
+                          ('src_attn', dc.get('src_key_bias', True))):
+                lin(f'{p}.{a}.linear_q', d, d)
+                lin(f'{p}.{a}.linear_k', d, d, bias=bool(kb))
+                lin(f'{p}.{a}.linear_v', d, d)
+                lin(f'{p}.{a}.linear_out', d, d)
+            lin(p + '.feed_forward.w_1', dffn, d)
+            lin(p + '.feed_forward.w_2', d, dffn)
+            for n in ('norm1', 'norm2', 'norm3'):
+                norm(f'{p}.{n}', d)
+        for k in list(sd.keys())[first:]:
+            if k.endswith('.weight') and sd[k].ndim == 2:
+                sd[k] = sd[k] * np.float32(3.0)
     lin('ctc.ctc_lo', V, d)
     if sharpen_ctc:
         sd['ctc.ctc_lo.weight'] = sd['ctc.ctc_lo.weight'] * np.float32(12.0)
