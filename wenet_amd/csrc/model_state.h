@@ -1,9 +1,9 @@
-// Internal state of libwenet_amd shared by the engine (model.hip: launch sequences of the
-// encoder, weight images) and the C ABI (cabi_*.hip: include/wenet_amd.h entry points, one file
-// per subsystem): device buffers, the model block clones share (`ModelData`: weights and their
-// re-laid-out views), the per-handle settings and workspace (`wn_model`), the per-call guards
-// (one host thread per handle, operand precision of the calling thread).  No kernels here:
-// each lives in the file that launches it.
+// Internal state of libwenet_amd shared by the engine (model.hip: front ends, weight images;
+// conformer.hip: the Conformer layers) and the C ABI (cabi_*.hip: include/wenet_amd.h entry
+// points, one file per subsystem): device buffers, the model block clones share (`ModelData`:
+// weights and their re-laid-out views), the per-handle settings and workspace (`wn_model`), the
+// per-call guards (one host thread per handle, operand precision of the calling thread).  No
+// kernels here: each lives in the file that launches it.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -431,21 +431,22 @@ struct PrecisionScope {
   }
 };
 
-// ---- engine (model.hip) -------------------------------------------------------------------
+// ---- engine (model.hip, conformer.hip) ----------------------------------------------------
 
 bool bf16_store_active();
 int upload_desc(wn_model* m, DevBuf& buf, const std::vector<int>& v, hipStream_t s);
+// linear(): GEMMs from this many 0.1 GFLOP on go to the six-product kernel through a split pass
+constexpr int g_x6_linear_min = 60;   // (40 / 20 measured slower at configs 3 / 4, r05l)
+extern thread_local bool t_linear_took_x6;   // what the last linear() of this thread ran on
 int linear(const Linear& l, const float* A, int lda, float* C, int ldc, int M, hipStream_t s,
            int act = ACT_NONE, const float* resid = nullptr, int ldr = 0, float alpha = 1.0f,
            bool glu = false, bool a_bf16 = false, bool c_bf16 = false);
 int ln(const Norm& n, const float* x, float* y, int M, int D, float eps, hipStream_t s,
        bool y_bf16 = false);
+int after_norm_out(wn_model* m, hipStream_t s);
 int build_x6_images(const wn_config& cfg, ModelData& W);
 int vocab_linear(wn_model* m, const Linear& l, const float* A, int lda, float* C, int ldc, int M,
                  hipStream_t s);
-int ffn_x6_split(int M, int F);
-int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const float* A, int M,
-                hipStream_t s);
 int scatter_padded(const float* src, int lds, const int* off, const int* len, int B, int Tp, int D,
                    float* dst, hipStream_t s);
 int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
@@ -453,9 +454,16 @@ int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
 int subsample_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, int32_t* enc_lens_host, int pos0, hipStream_t s);
 int encode_gate_wait(wn_model* m, hipStream_t s);
+// (conformer.hip: the Conformer layers and the feed-forward routing)
+int ffn_module(wn_model* m, const Norm& nrm, const Linear& w1, const Linear& w2, int act,
+               float alpha, bool ln_done, bool h16, hipStream_t s);
+int ffn_x6_split(int M, int F);
+int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const float* A, int M,
+                hipStream_t s);
 int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s);
 int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
                          std::vector<ChunkSess>& sess, float* out, hipStream_t s);
+// (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 
