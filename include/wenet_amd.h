@@ -733,6 +733,78 @@ int wn_tune_set(const char* key, int32_t value);
 int wn_model_tune_set(wn_model* m, const char* key, int32_t value);
 int wn_tune_get(const wn_model* m, const char* key, int32_t* value);
 
+/* ---- hybrid transducer (csrc/transducer.hip, csrc/cabi_transducer.hip) -----------------------
+ *
+ * A hybrid transducer (wenet/models/transducer/transducer.py; init_model.py:137-160) is an
+ * asr_model -- encoder, CTC head, attention decoder: wn_config -- plus an RNNPredictor (LSTM,
+ * predictor.py:60-88) and a TransducerJoint (prejoin linears, 'add', tanh; joint.py:34-49). */
+typedef struct {
+  int32_t pred_embed;        /* predictor_conf.embed_size, 1..1024 */
+  int32_t pred_hidden;       /* predictor_conf.hidden_size, 1..1024 */
+  int32_t pred_layers;       /* predictor_conf.num_layers, 1..8 */
+  int32_t pred_out;          /* predictor_conf.output_size (= joint_conf.pred_output_size) */
+  int32_t join_dim;          /* joint_conf.join_dim, a multiple of 32 up to 1024 */
+  int32_t blank;             /* the transducer's blank id (init_model.py:146: 0) */
+} wn_transducer_config;
+
+/* wn_model_create for a `model: transducer` state dict: additionally ingests
+ * predictor.{embed.weight, rnn.weight_ih_l*, rnn.weight_hh_l*, rnn.bias_ih_l*, rnn.bias_hh_l*,
+ * projection.*} and joint.{enc_ffn, pred_ffn, ffn_out}.* into the shared model block (read-only
+ * afterwards, shared by clones).  Every entry point of an asr_model handle works on the result.
+ * The widths travel in a struct of their own and through an entry point of their own, NOT as
+ * fields appended to wn_config: wn_config is passed by pointer without a size, so a caller
+ * compiled against the shorter struct would have wn_model_create read past its end.  This way
+ * wn_config and wn_model_create are unchanged, in layout and in behaviour, for every caller. */
+int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
+                               const wn_tensor* weights, int32_t n_weights, int32_t device,
+                               wn_model** out);
+
+/* RNN-T greedy search over the handle's CURRENT batch (after wn_encode / wn_encode_chunk* /
+ * wn_set_encoder_out): basic_greedy_search (wenet/models/transducer/search/greedy_search.py:6-54,
+ * reached through Transducer.greedy_search, transducer.py:398-442), which the reference runs one
+ * utterance and one symbol at a time, for the whole batch in lock-step.  A step evaluates the
+ * joint network for the next F frames of every utterance under its current predictor output
+ * (F = tune key "rnnt_lookahead", 1..16), takes their arg-max and consumes the window up to and
+ * including its first non-blank frame; the predictor (embedding, LSTM layers, projection,
+ * joint.pred_ffn) advances for the utterances that emitted.  The token lists do not depend on F
+ * or on the batch: every joint row is summed over k in one fixed order.  Always fp32, whatever
+ * the handle's precision (the encoder follows the handle).  The arg-max follows torch.argmax:
+ * the lowest index on ties, and a NaN (from the caller's encoder output, say) counts as the
+ * largest value, so a token is always an id in [0, vocab).
+ *   n_steps        most symbols one frame may emit (the reference's n_steps, 64)
+ *   tokens_host    (B, max_len) int32, tok_lens_host (B) int32
+ *   max_len        row pitch of tokens_host; -1 with a message if an utterance decoded more
+ *   steps_out      lock-step steps taken (may be NULL)
+ * Returns -1 with a wn_last_error text on a handle that wn_model_create_transducer did not
+ * build (no transducer weights). */
+int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_host,
+                                int32_t* tok_lens_host, int32_t max_len, int32_t* steps_out,
+                                void* stream);
+
+/* Test hook, handle-less: one predictor step (RNNPredictor.forward_step, predictor.py:185-206,
+ * without the embedding lookup).  x_dev (B, E): the embedding rows; w_host: 4 device pointers
+ * per layer (weight_ih (4H, E or H), weight_hh (4H, H), bias_ih, bias_hh; gate order i, f, g, o);
+ * h_dev / c_dev (n_layers, B, H) are updated in place for the rows whose advance_dev[b] != 0
+ * (NULL: every row) and left bit for bit otherwise; with proj_w_dev (P, H) / proj_b_dev, out_dev
+ * (B, P) gets the projection of the last layer's h for the same rows. */
+int wn_op_lstm_step(const float* x_dev, const float* const* w_host, int32_t n_layers,
+                    const float* proj_w_dev, const float* proj_b_dev, float* h_dev, float* c_dev,
+                    const int32_t* advance_dev, float* out_dev, int32_t B, int32_t E, int32_t H,
+                    int32_t P, void* stream);
+
+/* Test hook, handle-less: the joint network + arg-max (TransducerJoint.forward, joint.py:62-92,
+ * behind its prejoin linears, then argmax over the vocabulary).  Row m of M is
+ * tanh(enc_proj_dev[row_enc_host[m]] + pred_proj_dev[row_pred_host[m]]) (rows of J floats;
+ * row_enc_host[m] < 0: a row past its utterance's end, answered with idx -1 / max -inf) times
+ * w_dev (V, J)^T plus bias_dev (V).  idx_host / max_host (M): the arg-max (lowest index on
+ * ties, the first NaN before any number; the column-block partials go through the device
+ * reduction of the search's advance kernel) and its logit.  J must be a multiple of 32, at most 1024. */
+int wn_op_joint_argmax(const float* enc_proj_dev, int32_t enc_rows, const float* pred_proj_dev,
+                       int32_t pred_rows, const int32_t* row_enc_host,
+                       const int32_t* row_pred_host, const float* w_dev, const float* bias_dev,
+                       int32_t M, int32_t J, int32_t V, int32_t* idx_host, float* max_host,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

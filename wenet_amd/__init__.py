@@ -7,7 +7,7 @@ The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
-__all__ = ["load_model", "ASRModel", "DecodeResult", "StreamingRecognizer",
+__all__ = ["load_model", "ASRModel", "Transducer", "DecodeResult", "StreamingRecognizer",
            "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
            "force_align_batch"]
 
@@ -16,6 +16,9 @@ def __getattr__(name):
     if name in ("load_model", "ASRModel"):
         from wenet_amd import model as _m
         return getattr(_m, name)
+    if name == "Transducer":
+        from wenet_amd.transducer import Transducer
+        return Transducer
     if name == "DecodeResult":
         from wenet_amd.search import DecodeResult
         return DecodeResult

@@ -25,6 +25,12 @@ class WnConfig(Structure):
                                    'dec_learned_pos', 'dec_max_pos')]
 
 
+class WnTransducerConfig(Structure):
+    """wn_transducer_config: predictor / joint widths of a hybrid transducer."""
+    _fields_ = [(n, c_int32) for n in ('pred_embed', 'pred_hidden', 'pred_layers', 'pred_out',
+                                       'join_dim', 'blank')]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -69,6 +75,8 @@ EXPORTS = [
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
     'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
     'wn_stream_advance', 'wn_stream_advance_encoded',
+    'wn_model_create_transducer', 'wn_transducer_greedy_search', 'wn_op_lstm_step',
+    'wn_op_joint_argmax',
 ]
 
 _lib = None
@@ -178,6 +186,13 @@ def lib():
     L.wn_tune_get.argtypes = [vp, c_char_p, pi32]
     L.wn_profile_enable.argtypes = [vp, i32]
     L.wn_profile_collect.argtypes = [vp, pi32, pf64, pf64]
+    L.wn_model_create_transducer.argtypes = [POINTER(WnConfig), POINTER(WnTransducerConfig),
+                                             POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_transducer_greedy_search.argtypes = [vp, i32, pi32, pi32, i32, pi32, vp]
+    L.wn_op_lstm_step.argtypes = [vp, POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, i32, i32,
+                                  i32, vp]
+    L.wn_op_joint_argmax.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, pi32,
+                                     POINTER(f32), vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

@@ -128,8 +128,10 @@ extern "C" {
 const char* wn_last_error(void) { return last_error_cstr(); }
 const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 
-int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
-                    int32_t n_weights, int32_t device, wn_model** out) {
+// wn_model_create / wn_model_create_transducer (tcfg == nullptr: no predictor / joint)
+static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
+                        const wn_tensor* weights, int32_t n_weights, int32_t device,
+                        wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && c.d_model / c.n_heads == 64,
@@ -151,6 +153,7 @@ int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
   std::unique_ptr<wn_model> m(new wn_model());
   m->cfg = c;
   m->device = device;
+  if (tcfg) { m->tr.on = true; m->tr.c = *tcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -375,6 +378,36 @@ int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
       WN_TRY(stage_decoder(src, hs, "decoder", c.dec_layers, c));
     }
   }
+  if (tcfg) {
+    // RNNPredictor (predictor.py:60-88) and TransducerJoint (joint.py:34-49)
+    const wn_transducer_config& tc = *tcfg;
+    const int E = tc.pred_embed, H = tc.pred_hidden, P = tc.pred_out, J = tc.join_dim;
+    WN_CHECK(!tf, "transducer: Conformer encoders only");
+    WN_CHECK(E >= 1 && E <= 1024 && H >= 1 && H <= 1024 && P >= 1 && P <= 1024 &&
+             tc.pred_layers >= 1 && tc.pred_layers <= 8,
+             "transducer: predictor widths must be in [1, 1024], 1 to 8 LSTM layers");
+    WN_CHECK(J >= 32 && J <= 1024 && J % 32 == 0,
+             "transducer: join_dim must be a multiple of 32 in [32, 1024]");
+    WN_CHECK(tc.blank >= 0 && tc.blank < V, "transducer: blank id outside the vocabulary");
+    WN_GET(emb, "predictor.embed.weight", (int64_t)V * E);
+    hs.add("predictor.embed.weight", emb, (size_t)V * E);
+    for (int l = 0; l < tc.pred_layers; ++l) {
+      const std::string sfx = "_l" + std::to_string(l);
+      const int in = l == 0 ? E : H;
+      WN_GET(wi, "predictor.rnn.weight_ih" + sfx, (int64_t)4 * H * in);
+      WN_GET(wh, "predictor.rnn.weight_hh" + sfx, (int64_t)4 * H * H);
+      WN_GET(bi, "predictor.rnn.bias_ih" + sfx, 4 * H);
+      WN_GET(bh, "predictor.rnn.bias_hh" + sfx, 4 * H);
+      hs.add("predictor.rnn.weight_ih" + sfx, wi, (size_t)4 * H * in);
+      hs.add("predictor.rnn.weight_hh" + sfx, wh, (size_t)4 * H * H);
+      hs.add("predictor.rnn.bias_ih" + sfx, bi, 4 * H);
+      hs.add("predictor.rnn.bias_hh" + sfx, bh, 4 * H);
+    }
+    WN_TRY(stage_linear(src, hs, "predictor.projection", P, H));
+    WN_TRY(stage_linear(src, hs, "joint.enc_ffn", J, d));
+    WN_TRY(stage_linear(src, hs, "joint.pred_ffn", J, P));
+    WN_TRY(stage_linear(src, hs, "joint.ffn_out", V, J));
+  }
   // ---- upload ---------------------------------------------------------------
   WN_TRY(W.weights.ensure(hs.data.size() * sizeof(float)));
   W.n_weight_elems = (int64_t)hs.data.size();
@@ -491,10 +524,36 @@ int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
       DEC(W.left, "decoder", c.dec_layers);
     }
   }
+  if (tcfg) {
+    const wn_transducer_config& tc = *tcfg;
+    W.pred_embed = P("predictor.embed.weight");
+    W.pred_rnn.resize(tc.pred_layers);
+    for (int l = 0; l < tc.pred_layers; ++l) {
+      const std::string sfx = "_l" + std::to_string(l);
+      W.pred_rnn[l] = {P("predictor.rnn.weight_ih" + sfx), P("predictor.rnn.weight_hh" + sfx),
+                       P("predictor.rnn.bias_ih" + sfx), P("predictor.rnn.bias_hh" + sfx)};
+    }
+    W.pred_proj = LIN("predictor.projection", tc.pred_out, tc.pred_hidden);
+    W.j_enc = LIN("joint.enc_ffn", tc.join_dim, d);
+    W.j_pred = LIN("joint.pred_ffn", tc.join_dim, tc.pred_out);
+    W.j_out = LIN("joint.ffn_out", V, tc.join_dim);
+  }
   WN_TRY(build_x6_images(c, W));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
+}
+
+int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
+                    int32_t n_weights, int32_t device, wn_model** out) {
+  return create_model(cfg, nullptr, weights, n_weights, device, out);
+}
+
+int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
+                               const wn_tensor* weights, int32_t n_weights, int32_t device,
+                               wn_model** out) {
+  WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
+  return create_model(cfg, tcfg, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -505,6 +564,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   std::unique_ptr<wn_model> m(new wn_model());
   m->data = src->data;      // weights, views and tables are read-only: shared
   m->cfg = src->cfg;
+  m->tr.on = src->tr.on; m->tr.c = src->tr.c;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;

@@ -487,4 +487,52 @@ int copy_rows(const float* src, int lds, const int* src_rows, float* dst,
               int ldd, const int* dst_rows, int n_rows, int D, hipStream_t s);
 int fill_zero(void* p, size_t bytes, hipStream_t s);
 
+// RNN-T greedy search with frame lookahead (transducer.hip), fp32
+// y[b, :N] = W1 x1[b] + b1 (+ W2 x2[b] + b2) for the rows with advance[b] != 0 (null: all rows)
+struct RnntLinearArgs {
+  const float* x1 = nullptr; int ldx1 = 0;
+  const int* x1_rows = nullptr;     // row b of the input is x1[x1_rows[b]] (embedding lookup)
+  const float* W1 = nullptr; int K1 = 0;   // [N][K1]
+  const float* b1 = nullptr;
+  const float* x2 = nullptr; int ldx2 = 0;  // optional second term (the recurrent one)
+  const float* W2 = nullptr; int K2 = 0;
+  const float* b2 = nullptr;
+  float* y = nullptr; int ldy = 0;
+  int N = 0, B = 0;
+  const int* advance = nullptr;
+  const int* n_active = nullptr;    // device flag: 0 = the batch is finished, return at once
+};
+int rnnt_linear(const RnntLinearArgs& a, hipStream_t s);
+// LSTM cell on gates [B][4H] (i | f | g | o), h / c [B][H] in place on the advancing rows
+int rnnt_cell(const float* gates, float* h, float* c, const int* advance, int B, int H,
+              const int* n_active, hipStream_t s);
+// per row m: arg-max over V of tanh(enc_proj[row_enc[m]] + pred_proj[row_pred[m]]) W^T + bias as
+// one (max, index) per 128-column block: part_*[m][rnnt_joint_col_blocks(V)]; row_enc[m] < 0:
+// an inert row (-inf, -1)
+struct RnntJointArgs {
+  const float* enc_proj = nullptr; int lde = 0;
+  const float* pred_proj = nullptr; int ldp = 0;
+  const int* row_enc = nullptr; const int* row_pred = nullptr;
+  const float* W = nullptr; const float* bias = nullptr;   // [V][J], [V]
+  int M = 0, J = 0, V = 0;
+  float* part_max = nullptr; int* part_idx = nullptr;
+  const int* n_active = nullptr;
+};
+int rnnt_joint_col_blocks(int V);
+int rnnt_joint_argmax(const RnntJointArgs& a, hipStream_t s);
+// search state of a batch, device arrays of B entries unless noted
+struct RnntState {
+  int* t; int* cnt; int* last_tok; int* advance; int* done; int* n_tok;
+  int* tokens; int max_tok;         // [B][max_tok]
+  int* row_enc; int* row_pred;      // [B x F] rows of the next joint launch
+  int* n_active; int* steps;        // [1]: unfinished utterances, steps taken
+  const int* off; const int* len;   // encoder-output rows of each utterance
+};
+int rnnt_init(const RnntState& st, int B, int F, int blank, hipStream_t s);
+int rnnt_advance(const float* part_max, const int* part_idx, int ncb, int V, const RnntState& st,
+                 int B, int F, int blank, int n_steps, hipStream_t s);
+// the advance kernel's reduction of the column-block partials alone: out_*[m] of M rows
+int rnnt_reduce_partials(const float* part_max, const int* part_idx, int ncb, int M,
+                         float* out_max, int* out_idx, hipStream_t s);
+
 }  // namespace wn

@@ -219,6 +219,11 @@ struct ModelData {
   bool fbank_ok = true;
   Decoder left, right;
   DevBuf pos_tabs;
+  // hybrid transducer (wn_model::tr.on): RNNPredictor + TransducerJoint
+  struct LstmLayer { const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh; };
+  const float* pred_embed = nullptr;     // [V][pred_embed]
+  std::vector<LstmLayer> pred_rnn;
+  Linear pred_proj, j_enc, j_pred, j_out;
   // fbank tables
   const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
   const float* fb_mel_w = nullptr;
@@ -247,6 +252,8 @@ struct ModelData {
 // A handle: the shared model block + this handle's settings, current batch and workspace.
 struct wn_model {
   wn_config cfg;
+  // wn_model_create_transducer: the predictor / joint widths (tr.on == false: an asr_model)
+  struct { bool on = false; wn_transducer_config c = {}; } tr;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
@@ -297,6 +304,12 @@ struct wn_model {
   DevBuf ab_cache, ab_state;   // `attention` mode: self-attention K|V cache, beam state
   DevBuf ab_prompt;            // ... its prompts (B, P) and the prefill descriptors
   DevBuf sk_part;              // split-K partials of the skinny step GEMMs (gemm_skinny.hip)
+  // wn_transducer_greedy_search: enc_proj | predictor state and outputs | joint partials |
+  // search state and tokens; the pinned n_active slots the host loop polls one group late
+  DevBuf tr_enc, tr_f32, tr_i32, tr_tok;
+  PinnedBuf tr_host;
+  hipEvent_t tr_ev[2] = {nullptr, nullptr};
+  ~wn_model() { for (hipEvent_t e : tr_ev) if (e) (void)hipEventDestroy(e); }
   bool ab_truncated = false;   // the last prompted search stopped at the positional table
   bool mem_cache_valid = false;
 

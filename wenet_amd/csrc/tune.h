@@ -131,7 +131,12 @@ namespace wn {
   /* wn_attention_beam_search_prompt: 1 = the step's GEMMs (M = B x beam <= 256 rows) run on    \
      the skinny kernel (gemm_skinny.hip), 0 = on linear() like wn_attention_beam_search.  Not   \
      yet measured against each other on the GPU: the default stays the existing kernels */      \
-  X(dec_skinny, 0)
+  X(dec_skinny, 0)                                                                              \
+  /* wn_transducer_greedy_search: frames of every utterance the joint network is evaluated     \
+     for per lock-step step (1 .. 16; the token lists do not depend on it).  Measured only on   \
+     a workload with too few symbols (docs/LOG_round12.md; 8 led 4 by 6 %): 4 until it is       \
+     measured in range by tools/bench_transducer.py */                                          \
+  X(rnnt_lookahead, 4)
 
 struct Tune {
 #define X(name, dflt) int name = dflt;

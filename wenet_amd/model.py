@@ -256,7 +256,7 @@ class ASRModel:
                 'CPU fallback -- use the reference for CPU decoding')
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        self._cfg = config_from_yaml(configs)
+        self._cfg = self._config(configs)
         pe = state_dict.get('encoder.embed.pos_enc.pe')
         if pe is not None:  # WhisperPositionalEncoding keeps 1500 rows
             self._cfg.max_pos = int(pe.shape[-2])
@@ -294,19 +294,25 @@ class ASRModel:
             tensors[i].data = _lib.f32p(a)
             tensors[i].numel = a.size
         h = ctypes.c_void_p()
-        _lib.check(
-            L.wn_model_create(ctypes.byref(self._cfg), tensors,
-                              len(state_dict), self.device.index,
-                              ctypes.byref(h)), 'wn_model_create')
+        _lib.check(self._create(L, tensors, len(state_dict), h), 'wn_model_create')
         self._h = h.value
         self._L = L
         self._last_prefix_raw = None
+
+    def _config(self, configs: dict) -> _lib.WnConfig:
+        """The wn_config of this model class (subclasses: wenet_amd/transducer.py)."""
+        return config_from_yaml(configs)
+
+    def _create(self, L, tensors, n: int, h) -> int:
+        """The C-ABI constructor of this model class."""
+        return L.wn_model_create(ctypes.byref(self._cfg), tensors, n, self.device.index,
+                                 ctypes.byref(h))
 
     def clone(self) -> 'ASRModel':
         """A second model object on the SAME device weights with its own
         workspace (wn_model_clone): one per in-flight batch
         (wenet_amd/pipeline.py)."""
-        other = object.__new__(ASRModel)
+        other = object.__new__(type(self))
         other.__dict__.update({k: v for k, v in self.__dict__.items()
                                if k not in ('_h', '_last_prefix_raw')})
         h = ctypes.c_void_p()
@@ -1153,7 +1159,11 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
         mean, istd = load_cmvn(cmvn_file, configs['cmvn_conf']['is_json_cmvn'])
         sd['encoder.global_cmvn.mean'] = torch.from_numpy(mean).float()
         sd['encoder.global_cmvn.istd'] = torch.from_numpy(istd).float()
-    model = ASRModel(configs, sd, device)
+    if configs.get('model') == 'transducer':   # init_model.py:137-154
+        from wenet_amd.transducer import Transducer
+        model = Transducer(configs, sd, device)
+    else:
+        model = ASRModel(configs, sd, device)
     # cli/model.py:35-46: the config's tokenizer with its files looked up in the
     # model directory; older packages without tokenizer_conf fall back to units.txt
     if 'tokenizer_conf' in configs and \

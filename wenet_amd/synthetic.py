@@ -361,6 +361,35 @@ CONFIGS = {
     },
 }
 
+# joint_conf / predictor_conf of examples/aishell/rnnt/conf/conformer_u2pp_rnnt.yaml:24-43 and
+# its model_conf (:80-87) at the given widths
+def _rnnt(base: str, enc_out: int, embed: int, hidden: int, out: int, join: int) -> dict:
+    c = copy.deepcopy(CONFIGS[base])
+    c['joint'] = 'transducer_joint'
+    c['joint_conf'] = dict(enc_output_size=enc_out, pred_output_size=out, join_dim=join,
+                           prejoin_linear=True, postjoin_linear=False, joint_mode='add',
+                           activation='tanh')
+    c['predictor'] = 'rnn'
+    c['predictor_conf'] = dict(embed_size=embed, output_size=out, embed_dropout=0.1,
+                               hidden_size=hidden, num_layers=2, bias=True, rnn_type='lstm',
+                               dropout=0.1)
+    c['model'] = 'transducer'
+    c['model_conf'] = dict(transducer_weight=0.75, ctc_weight=0.1, attention_weight=0.15,
+                           lsm_weight=0.1, length_normalized_loss=False, reverse_weight=0.3)
+    return c
+
+
+# hybrid transducers: the encoder / CTC head / bi-decoder of the base recipe + predictor + joint
+# tiny_causal with widths that are deliberately no multiples of 64 (join_dim: of 32 only)
+CONFIGS['tiny_rnnt'] = _rnnt('tiny_causal', 128, 64, 80, 96, 160)
+# the same with a vocabulary of 65 x 128 + 9: the joint kernel leaves 66 column-block partials
+# per row, more than the wave that reduces them has lanes
+CONFIGS['tiny_rnnt_wide'] = dict(CONFIGS['tiny_rnnt'], output_dim=8329)
+# examples/aishell/rnnt/conf/conformer_u2pp_rnnt.yaml:1-87 at full width (tools/bench_transducer.py)
+CONFIGS['aishell_u2pp_rnnt'] = _rnnt('aishell_u2pp', 256, 256, 256, 256, 512)
+
+RNNT_BLANK_BIAS = 6.0    # make_state_dict's default bias of the joint's blank logit
+
 
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
@@ -415,9 +444,42 @@ def positional_table(d_model: int, max_len: int = 5000) -> torch.Tensor:
     return pe.unsqueeze(0)
 
 
-def make_state_dict(configs: dict, seed: int = 0,
-                    sharpen_ctc: bool = True) -> "OrderedDict[str, torch.Tensor]":
-    """Deterministic random weights with the reference's names and shapes."""
+def _add_transducer(sd, configs: dict, seed: int, blank_bias: float):
+    """predictor.* / joint.* of a `model: transducer` configuration (RNNPredictor,
+    predictor.py:60-88; TransducerJoint, joint.py:34-49).  Matrices ~ N(0, 3 / sqrt(fan_in)) and
+    biases ~ N(0, 0.1) -- with the default inits a random joint's arg-max hardly depends on the
+    predictor state -- and `blank_bias` on the blank logit: about 6 leaves a few symbols per
+    frame group, 9 and more empties whole utterances."""
+    pc, jc = configs['predictor_conf'], configs['joint_conf']
+    V = configs['output_dim']
+    E, H, P, L = pc['embed_size'], pc['hidden_size'], pc['output_size'], pc['num_layers']
+    J = jc['join_dim']
+
+    def mat(name, out_f, in_f):
+        sd[name] = _normal(seed, name, (out_f, in_f), 3.0 / math.sqrt(in_f))
+
+    def vec(name, n):
+        sd[name] = _normal(seed, name, (n, ), 0.1)
+
+    sd['predictor.embed.weight'] = _normal(seed, 'predictor.embed.weight', (V, E), 1.0)
+    for l in range(L):
+        mat(f'predictor.rnn.weight_ih_l{l}', 4 * H, E if l == 0 else H)
+        mat(f'predictor.rnn.weight_hh_l{l}', 4 * H, H)
+        vec(f'predictor.rnn.bias_ih_l{l}', 4 * H)
+        vec(f'predictor.rnn.bias_hh_l{l}', 4 * H)
+    for name, o, i in (('predictor.projection', P, H), ('joint.enc_ffn', J, jc['enc_output_size']),
+                       ('joint.pred_ffn', J, P), ('joint.ffn_out', V, J)):
+        mat(name + '.weight', o, i)
+        vec(name + '.bias', o)
+    blank = ((configs.get('tokenizer_conf') or {}).get('special_tokens') or {}).get('<blank>', 0)
+    sd['joint.ffn_out.bias'][blank] += np.float32(blank_bias)
+
+
+def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
+                    rnnt_blank_bias: float = RNNT_BLANK_BIAS
+                    ) -> "OrderedDict[str, torch.Tensor]":
+    """Deterministic random weights with the reference's names and shapes.
+    `rnnt_blank_bias`: `model: transducer` configurations only (_add_transducer)."""
     ec, dc = configs['encoder_conf'], configs['decoder_conf']
     d = ec['output_size']
     h = ec['attention_heads']
@@ -539,6 +601,8 @@ def make_state_dict(configs: dict, seed: int = 0,
     for k in list(sd.keys()):
         if k.endswith('output_layer.weight') or k.endswith('output_layer.bias'):
             sd[k] = sd[k] * np.float32(4.0)
+    if configs.get('model') == 'transducer':
+        _add_transducer(sd, configs, seed, rnnt_blank_bias)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
 
