@@ -679,6 +679,43 @@ int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_
                    int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,
                    float* logp, int32_t ld_out, void* stream);
 
+/* Operator hooks of the `attention` decode mode's kernels (test infrastructure): each checks its
+ * arguments and calls the launcher the search itself calls.  Every array is a DEVICE array except
+ * n_done_host.  Index arrays a kernel dereferences (the path rows, last_tok of the embedding) are
+ * read back and range-checked before the launch; the other arrays are only copied or clamped.
+ * Layouts: qkv [n][3d] (Q | K | V), cache [steps][n][2d] (K | V), path / tok rows of max_len
+ * ints, d = heads * 64.
+ *   attn_self_step   stores K | V of qkv into cache[step], then row r attends over positions
+ *                    0..step, position j read from cache[j][path[r][j]]; out [n][d]
+ *   attn_step_embed  x[r] = emb[last_tok[r]] * scale + pe[pos]; emb [V][d], pe [max_pos][d]
+ *   attn_prompt_cache  K | V of prefill row b * P + j -> cache[j][b * N]; cache [P][B * N][2d]
+ *   beam_init        the start state; prompt (B, P) or NULL (every row starts as sos)
+ *   beam_update      one pruning step on parents of `step` tokens (1 <= step,
+ *                    step + 1 <= max_len); *n_done_host = number of children that ended.  A NaN
+ *                    candidate score ranks as -inf
+ *   beam_finish      length penalty, first maximum, the winner without its first `prefix` tokens
+ *                    and without eos into out_tok [B][max_len] / out_len [B] */
+int wn_op_attn_self_step(const float* qkv_dev, int32_t d, int32_t heads, int32_t n,
+                         float* cache_dev, int32_t step, const int32_t* path_dev,
+                         int32_t max_len, float* out_dev, void* stream);
+int wn_op_attn_step_embed(const int32_t* last_tok_dev, int32_t pos, const float* emb_dev,
+                          int32_t V, const float* pe_dev, int32_t max_pos, float scale, int32_t d,
+                          int32_t n, float* x_dev, void* stream);
+int wn_op_attn_prompt_cache(const float* qkv_dev, int32_t d, int32_t B, int32_t P, int32_t N,
+                            float* cache_dev, void* stream);
+int wn_op_beam_init(int32_t B, int32_t N, int32_t max_len, int32_t sos, const int32_t* prompt_dev,
+                    int32_t P, float* score_dev, int32_t* end_dev, int32_t* tok_dev,
+                    int32_t* path_dev, int32_t* last_tok_dev, void* stream);
+int wn_op_beam_update(int32_t B, int32_t N, int32_t step, int32_t max_len, int32_t eos,
+                      int32_t V, const float* topv_dev, const int32_t* topi_dev,
+                      const float* score_in, const int32_t* end_in, const int32_t* tok_in,
+                      const int32_t* path_in, float* score_out, int32_t* end_out,
+                      int32_t* tok_out, int32_t* path_out, int32_t* last_tok_dev,
+                      int32_t shared_row, int32_t* n_done_host, void* stream);
+int wn_op_beam_finish(int32_t B, int32_t N, int32_t len, int32_t max_len, int32_t eos,
+                      float length_penalty, const float* score_dev, const int32_t* tok_dev,
+                      int32_t* out_tok_dev, int32_t* out_len_dev, int32_t prefix, void* stream);
+
 /* Measurement hook for bench.py: bracket launches of the dominant kernel (the
  * FFN w_1 GEMM, positionwise_feed_forward.py:58; every 6th launch, because each
  * event pair idles the GPU for ~10 us) with HIP events on the launch stream.  wn_profile_collect waits for them and returns the number of

@@ -8,10 +8,15 @@ convolutions, in fp64.  `fp32=True` evaluates the SAME plain formula in fp32 (`b
 only: Q (+ bias), K, V, P and the probabilities rounded to bf16, fp32 accumulation): the distance
 of that evaluation from the fp64 one is the yardstick `e_plain` of the GPU tolerances.
 
+Further down: the kernels of the `attention` decode mode (csrc/attn_search.hip; CPU checks in
+tests/test_kernel_refs.py, GPU tests in tests/test_gpu_attn_search.py) -- the self-attention step
+as ref_attention on the rows gathered through the paths, the beam state kernels restated in NumPy.
+
 No GPU and no oracle import in here.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -165,7 +170,7 @@ def make_attention_case(regime, H, q_lens, kv_lens=None, relpos=False, mask_mode
                 k3[ko:ko + kl, :, 0] = (torch.arange(kl, dtype=torch.float32) * 40.0).unsqueeze(1)
                 continue
             tiles = (kl + 31) // 32
-            j = {'first': 0, '31': 31, '32': 32, 'last': kl - 1,
+            j = {'first': 0, '31': 31, '32': 32, '63': 63, '64': 64, 'last': kl - 1,
                  'second_half': ((tiles + 1) // 2) * 32}[needle]
             j = min(j, kl - 1)
             # the other 63 coordinates give scores of a standard deviation near 1 (1.6 with the
@@ -416,6 +421,197 @@ def regime_case(regime, param, **kw):
     if regime == 'needle':
         return make_attention_case('needle', needle=param, **kw)
     return make_attention_case(regime, param=param, **kw)
+
+
+# ---------------------------------------------------------------------------------------------
+# the `attention` decode mode: one self-attention step over the per-hypothesis paths
+
+# the attention regimes with the needle at the edges of the step kernel's 64-key blocks
+SELF_STEP_REGIMES = [('unit', None), ('peaked', 10.0), ('peaked', 30.0), ('ascending', 1.0),
+                     ('ascending', 0.375), ('descending', 1.0), ('descending', 0.375),
+                     ('needle', 'first'), ('needle', '63'), ('needle', '64'), ('needle', 'last'),
+                     ('shifted', 80.0), ('shifted', -80.0), ('tied', None)]
+SELF_STEP_NON_FLAT = {**NON_FLAT, ('needle', '63'): 0.9, ('needle', '64'): 0.9}
+
+
+def make_self_step_case(regime, param, H, n, length, seed=0, beam=0, prompt=0):
+    """One decoder step of n hypothesis rows that attend over `length` positions (the newest
+    included): qkv (n, 3d) = this step's Q | K | V, cache (max_len, n, 2d) = K | V of the earlier
+    positions, path (n, max_len): position j of row r lives in cache[j][path[r][j]], the newest
+    one in the row's own slot.  beam = 0: every ancestor is a random slot; beam = N > 0 with
+    prompt = P: rows are B x N hypotheses whose first P positions live in their utterance's
+    first slot and the later ones in random slots of the utterance.
+
+    The data is the cross-attention case of make_attention_case with n sequences of one query
+    and `length` keys (its regimes shape the scores by the key's POSITION, so they survive the
+    gather): slot s holds sequence s's key / value row of every position.  Cache rows no path
+    names, and every row of steps >= length, hold +-POISON (cache[length - 1] is what the step
+    itself stores).  `q`, `kg`, `vg`, `seqs` are the gathered rows ref_attention runs on."""
+    base = regime_case(regime, param, H=H, q_lens=[1] * n, kv_lens=[length] * n, seed=seed)
+    d, step, max_len = H * 64, length - 1, length + 2
+    g = torch.Generator().manual_seed(seed + 1000)
+    if beam:
+        assert n % beam == 0 and prompt < length
+        first = (torch.arange(n) // beam * beam).unsqueeze(1)
+        path = first + torch.randint(0, beam, (n, max_len), generator=g)
+        path[:, :prompt] = first
+    else:
+        path = torch.randint(0, n, (n, max_len), generator=g)
+    path[:, step] = torch.arange(n)
+    q = torch.stack([base['q'][s[0]] for s in base['seqs']])                    # (n, d)
+    ks = torch.stack([base['k'][s[2]:s[2] + length] for s in base['seqs']])     # (slot, pos, d)
+    vs = torch.stack([base['v'][s[2]:s[2] + length] for s in base['seqs']])
+    sign = torch.where(torch.arange(d) % 2 == 0, 1.0, -1.0) * POISON
+    cache = torch.cat([-sign, sign]).repeat(max_len, n, 1)
+    named = torch.zeros(max_len, n, dtype=torch.bool)
+    pos = torch.arange(step)
+    for r in range(n):
+        named[pos, path[r, :step]] = True
+    cache[:step][named[:step]] = torch.cat([ks, vs], 2).transpose(0, 1)[:step][named[:step]]
+    qkv = torch.cat([q, ks[:, step], vs[:, step]], 1)
+    # row r's keys: position j from slot path[r][j]
+    idx = path[:, :length].long()
+    kg = ks[idx, torch.arange(length).unsqueeze(0)].reshape(n * length, d)
+    vg = vs[idx, torch.arange(length).unsqueeze(0)].reshape(n * length, d)
+    seqs = [(r, 1, r * length, length, 0) for r in range(n)]
+    return dict(qkv=qkv.contiguous(), cache=cache.contiguous(), path=path.to(torch.int32),
+                named=named, n=n, H=H, d=d, step=step, length=length, max_len=max_len, q=q,
+                kg=kg, vg=vg, seqs=seqs, scale=base['scale'])
+
+
+def self_step_refs(case):
+    """(fp64 reference (n, d), e_plain, scale, largest weight per (row, head)) of a step case:
+    ref_attention on the gathered rows, one sequence of one query per hypothesis row."""
+    args = (case['q'], case['kg'], case['vg'], None, None, None, case['seqs'], 0, 0, -1,
+            case['scale'])
+    ref, w = ref_attention(*args, want_weights=True)
+    plain = ref_attention(*args, fp32=True)
+    return ref, (plain - ref).abs().max().item(), visible_v_scale(case['vg'], case['seqs']), w
+
+
+# ---------------------------------------------------------------------------------------------
+# the `attention` decode mode: the beam state kernels, restated in NumPy.  Scores are fp32 (one
+# fp32 add per step is bit-reproducible); token / path rows have max_len columns, and a column no
+# kernel writes keeps `fill`.
+
+FILL = 0x7fc0dead
+
+
+def ref_beam_init(B, N, max_len, sos=0, prompt=None, fill=FILL):
+    """The start state (search.py:287-294): slot 0 of every utterance alive, the others -inf;
+    every row <sos>, or (prompt (B, P)) its utterance's prompt, whose positions live in the
+    utterance's first slot."""
+    BN = B * N
+    st = dict(score=np.where(np.arange(BN) % N == 0, 0.0, -np.inf).astype(np.float32),
+              end=np.zeros(BN, np.int32), tok=np.full((BN, max_len), fill, np.int32),
+              path=np.full((BN, max_len), fill, np.int32))
+    if prompt is None:
+        st['tok'][:, 0] = sos
+        st['path'][:, 0] = np.arange(BN)
+        st['last_tok'] = np.full(BN, sos, np.int32)
+    else:
+        prompt = np.asarray(prompt, np.int32)
+        P = prompt.shape[1]
+        st['tok'][:, :P] = np.repeat(prompt, N, axis=0)
+        st['path'][:, :P] = (np.arange(BN) // N * N)[:, None]
+        st['last_tok'] = np.repeat(prompt[:, P - 1], N).astype(np.int32)
+    return st
+
+
+def beam_rank(cand, N):
+    """Flat indices of the N best of a row of candidates: NaN counts as -inf, then value
+    descending, flat index ascending (a stable sort)."""
+    c = np.where(np.isnan(cand), -np.inf, cand)
+    return np.argsort(-c, kind='stable')[:N]
+
+
+def ref_beam_update(st, topv, topi, B, N, step, eos, V, shared_row=False, fill=FILL):
+    """One pruning step (search.py:315-354) on parents of `step` tokens.  topv / topi (B * N, N):
+    the step's top-k log-probs (fp32) and tokens.  Returns (state, number of ended children)."""
+    BN, max_len = st['tok'].shape
+    topv = np.asarray(topv, np.float32).reshape(BN, N)
+    topi = np.asarray(topi, np.int32).reshape(BN, N)
+    ended = st['end'] != 0
+    lp = topv.copy()
+    lp[ended, 1:] = -np.inf                                  # mask_finished_scores
+    lp[ended, 0] = 0.0
+    with np.errstate(invalid='ignore'):
+        cand = (st['score'][:, None] + lp).astype(np.float32)
+    cand = np.where(np.isnan(cand), np.float32(-np.inf), cand)
+    pred = np.where(ended[:, None], eos, topi)               # mask_finished_preds
+    pred = np.where((pred < 0) | (pred >= V), eos, pred)     # the token clamp
+    out = dict(score=np.empty(BN, np.float32), end=np.empty(BN, np.int32),
+               tok=np.full((BN, max_len), fill, np.int32),
+               path=np.full((BN, max_len), fill, np.int32), last_tok=np.empty(BN, np.int32))
+    for b in range(B):
+        flat = cand[b * N:(b + 1) * N].reshape(-1)
+        for c, f in enumerate(beam_rank(flat, N)):
+            parent, child = b * N + f // N, b * N + c
+            t = pred[parent, f % N]
+            out['score'][child] = flat[f]
+            out['tok'][child, :step] = st['tok'][parent, :step]
+            out['tok'][child, step] = t
+            out['path'][child, :step - 1] = st['path'][parent, :step - 1]
+            out['path'][child, step - 1] = b * N if shared_row else parent
+            out['path'][child, step] = child
+            out['last_tok'][child] = t
+            out['end'][child] = int(t == eos)
+    return out, int(out['end'].sum())
+
+
+def beam_finish_scores(score, tok, B, N, length, eos, length_penalty):
+    """(B, N) fp64 penalised scores score / count(tokens != eos) ** length_penalty
+    (search.py:357-359)."""
+    cnt = (np.asarray(tok)[:, :length] != eos).sum(1).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return (np.asarray(score, np.float64) / cnt ** float(length_penalty)).reshape(B, N)
+
+
+def ref_beam_finish(score, tok, B, N, length, eos, length_penalty, prefix=1, fill=FILL):
+    """search.py:357-370: the first maximum of the penalised scores (a NaN never wins), its row
+    without the first `prefix` tokens and without <eos>.  Returns (out_tok (B, max_len), out_len
+    (B), best (B))."""
+    tok = np.asarray(tok)
+    max_len = tok.shape[1]
+    s = beam_finish_scores(score, tok, B, N, length, eos, length_penalty)
+    out_tok = np.full((B, max_len), fill, np.int32)
+    out_len, best = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        top = -np.inf
+        for n in range(N):
+            if s[b, n] > top:
+                top, best[b] = s[b, n], n
+        row = tok[b * N + best[b], prefix:length]
+        row = row[row != eos]
+        out_tok[b, :len(row)] = row
+        out_len[b] = len(row)
+    return out_tok, out_len, best
+
+
+def make_beam_finish_case(B, N, prefix, seed=0, V=50, eos=2):
+    """Token rows of prefix + 9 tokens (some ended early, row 0 empty behind its prefix, columns
+    behind the length garbage) and negative fp32 scores.  Returns (score, tok, length)."""
+    rng = np.random.default_rng(seed)
+    length = prefix + 9
+    tok = rng.integers(3, V, (B * N, length + 2)).astype(np.int32)
+    for r in range(B * N):
+        if rng.random() < 0.6:
+            tok[r, rng.integers(prefix, length):length] = eos
+    tok[0, prefix:length] = eos
+    score = (-rng.uniform(0.5, 30.0, B * N)).astype(np.float32)
+    return score, tok, length
+
+
+def beam_finish_margin_ok(s_row, same=()):
+    """True when the winner of a row of fp64 penalised scores leads every other entry (those in
+    `same`, rows with the winner's score and count and so its fp32 quotient, excepted) by more than 4 fp32 ulps of its size:
+    powf may differ from the fp64 power in the last place, the division rounds once more."""
+    s_row = np.asarray(s_row, np.float64)
+    w = int(np.argmax(s_row))
+    if not np.isfinite(s_row[w]):
+        return bool(np.all(np.isneginf(s_row)))           # every row -inf: the first wins
+    others = [s_row[i] for i in range(len(s_row)) if i != w and i not in same]
+    return all(s_row[w] - o > 4 * ULP32 * abs(s_row[w]) for o in others)
 
 
 # ---------------------------------------------------------------------------------------------

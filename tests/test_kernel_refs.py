@@ -2,9 +2,12 @@
 (oracle/wenet_oracle.py, itself pinned to the unmodified reference) reduced to the bare operator
 -- identity projections, zero biases -- to 1e-12 relative, the mask builder against the oracle's
 chunk masks, and the cap on the yardstick `e_plain` for every data regime of every operator, so
-that all of it is settled before any GPU time is spent."""
+that all of it is settled before any GPU time is spent.  At the end: the NumPy statements of the
+attention search's beam kernels against the reference's step and final selection, restated in
+torch from its text, and the invariant of the path rows."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -245,3 +248,300 @@ def test_ctc_regime_caps(regime, V):
         assert KR.cap_ok(e, scale), e / scale
     else:
         assert e == 0.0
+
+
+# ---- the `attention` decode mode (csrc/attn_search.hip) ----------------------------------------
+# The torch functions below restate the reference's step and its final selection line by line
+# (wenet/models/transformer/search.py and wenet/utils/mask.py at the cited lines), as the oracle
+# restates its modules; `logp.topk` is replaced by the top-k tables the caller hands in.
+
+
+def _mask_finished_scores(score, flag):                      # mask.py:258-285
+    beam_size = score.size(-1)
+    zero_mask = torch.zeros_like(flag, dtype=torch.bool)
+    if beam_size > 1:
+        unfinished = torch.cat((zero_mask, flag.repeat([1, beam_size - 1])), dim=1)
+        finished = torch.cat((flag, zero_mask.repeat([1, beam_size - 1])), dim=1)
+    else:
+        unfinished = zero_mask
+        finished = flag
+    score.masked_fill_(unfinished, -float('inf'))
+    score.masked_fill_(finished, 0)
+    return score
+
+
+def _mask_finished_preds(pred, flag, eos):                   # mask.py:288-304
+    return pred.masked_fill_(flag.repeat([1, pred.size(-1)]), eos)
+
+
+def _search_step(hyps, scores, end_flag, top_k_logp, top_k_index, batch_size, beam_size, eos):
+    """search.py:315-354 (the cache re-gather of :323-331 left out: it has no output here)."""
+    top_k_logp = _mask_finished_scores(top_k_logp.clone(), end_flag)
+    top_k_index = _mask_finished_preds(top_k_index.clone(), end_flag, eos)
+    scores = scores + top_k_logp
+    scores = scores.view(batch_size, beam_size * beam_size)
+    scores, offset_k_index = scores.topk(k=beam_size)
+    scores = scores.view(-1, 1)
+    base_k_index = torch.arange(batch_size).view(-1, 1).repeat([1, beam_size])
+    base_k_index = base_k_index * beam_size * beam_size
+    best_k_index = base_k_index.view(-1) + offset_k_index.view(-1)
+    best_k_pred = torch.index_select(top_k_index.view(-1), dim=-1, index=best_k_index)
+    best_hyps_index = best_k_index // beam_size
+    last_best_k_hyps = torch.index_select(hyps, dim=0, index=best_hyps_index)
+    hyps = torch.cat((last_best_k_hyps, best_k_pred.view(-1, 1)), dim=1)
+    end_flag = torch.eq(hyps[:, -1], eos).view(-1, 1)
+    return hyps, scores, end_flag
+
+
+def _search_finish(hyps, scores, batch_size, beam_size, eos, length_penalty, prefix_len):
+    """search.py:357-370."""
+    scores = scores.view(batch_size, beam_size)
+    lengths = hyps.ne(eos).sum(dim=1).view(batch_size, beam_size).float()
+    scores = scores / lengths.pow(length_penalty)
+    best_scores, best_index = scores.max(dim=-1)
+    best_hyps_index = best_index + torch.arange(batch_size, dtype=torch.long) * beam_size
+    best_hyps = torch.index_select(hyps, dim=0, index=best_hyps_index)
+    best_hyps = best_hyps[:, prefix_len:]
+    return [h[h != eos].tolist() for h in best_hyps]
+
+
+def _topk_tables(rng, BN, N, V, eos, p_eos=0.15):
+    """Top-k tables of one step: descending log-probs without repeated values, distinct tokens
+    per row, <eos> among them now and then."""
+    topv = -np.sort(rng.uniform(0.05, 9.0, (BN, N)), axis=1).astype(np.float32)
+    topi = np.stack([rng.choice(V, N, replace=False) for _ in range(BN)]).astype(np.int32)
+    for r in range(BN):
+        if rng.random() < p_eos and eos not in topi[r]:
+            topi[r, rng.integers(N)] = eos
+    return topv, topi
+
+
+def _untied(st, topv, N):
+    """No two of the N + 1 best candidates of any utterance are equal (the reference's topk
+    leaves the order of equal values open)."""
+    ended = st['end'] != 0
+    lp = topv.copy()
+    lp[ended, 1:] = -np.inf
+    lp[ended, 0] = 0.0
+    cand = (st['score'][:, None] + lp).reshape(-1, N * N)
+    top = -np.sort(-cand, axis=1)[:, :N + 1]
+    return bool(np.all(top[:, :-1] > top[:, 1:])) if N * N > 1 else True
+
+
+@pytest.mark.parametrize('B,N,prompt_len', [(1, 1, 0), (2, 2, 0), (3, 3, 0), (2, 10, 0), (1, 33, 0),
+                                            (2, 4, 3), (1, 10, 4)])
+def test_ref_beam_update_matches_reference_step(B, N, prompt_len):
+    """init + 9 steps: scores bit for bit, token rows, end flags against the reference's step."""
+    rng = np.random.default_rng(100 * B + N)
+    V, eos, sos, steps = max(2 * N, 11), 2, 1, 9
+    BN = B * N
+    prompt = rng.integers(3, V, (B, prompt_len)).astype(np.int32) if prompt_len else None
+    first = prompt_len if prompt_len else 1
+    max_len = first + steps + 2
+    st = KR.ref_beam_init(B, N, max_len, sos=sos, prompt=prompt)
+    if prompt_len:
+        hyps = torch.from_numpy(np.repeat(prompt, N, axis=0)).long()
+    else:
+        hyps = torch.ones([BN, 1], dtype=torch.long).fill_(sos)                  # search.py:287
+    scores = torch.tensor([0.0] + [-float('inf')] * (N - 1),
+                          dtype=torch.float).repeat([B]).unsqueeze(1)            # :290-293
+    end_flag = torch.zeros_like(scores, dtype=torch.bool)
+    assert np.array_equal(st['score'], scores.view(-1).numpy())
+    assert np.array_equal(st['tok'][:, :first], hyps.numpy())
+    n_ended = 0
+    for i in range(first, first + steps):
+        topv, topi = _topk_tables(rng, BN, N, V, eos)
+        assert _untied(st, topv, N)
+        st, done = KR.ref_beam_update(st, topv, topi, B, N, i, eos, V, shared_row=i == prompt_len)
+        hyps, scores, end_flag = _search_step(hyps, scores, end_flag, torch.from_numpy(topv),
+                                              torch.from_numpy(topi).long(), B, N, eos)
+        assert np.array_equal(st['score'].view(np.int32), scores.view(-1).numpy().view(np.int32))
+        assert np.array_equal(st['tok'][:, :i + 1], hyps.numpy())
+        assert np.array_equal(st['end'] != 0, end_flag.view(-1).numpy())
+        assert np.array_equal(st['last_tok'], hyps[:, -1].numpy())
+        assert done == int(end_flag.sum())
+        assert bool((st['tok'][:, i + 1:] == KR.FILL).all())
+        assert bool((st['path'][:, i + 1:] == KR.FILL).all())
+        n_ended = max(n_ended, done)
+    assert n_ended > 0 or N == 1                 # the masks of finished hypotheses were in play
+
+
+def test_ref_beam_update_ties_by_hand():
+    """The rule on exact ties and on NaN, the winners spelled out."""
+    eos, V = 2, 9
+    ti = np.array([[5, 6], [7, 8]], np.int32)
+
+    def run(score, end, topv, topi=ti):
+        st = dict(score=np.array(score, np.float32), end=np.array(end, np.int32),
+                  tok=np.array([[1, 3, 0], [1, 4, 0]], np.int32),
+                  path=np.array([[0, 0, 0], [1, 0, 0]], np.int32))
+        out, done = KR.ref_beam_update(st, np.array(topv, np.float32), topi, 1, 2, 2, eos, V)
+        return out, done
+
+    inf, nan = float('inf'), float('nan')
+    # the first step: slot 1 is -inf; flat 0, 1 win (parent 0 twice)
+    out, done = run([0, -inf], [0, 0], [[-1, -2], [-1, -2]])
+    assert out['score'].tolist() == [-1, -2] and out['last_tok'].tolist() == [5, 6]
+    assert out['tok'].tolist() == [[1, 3, 5], [1, 3, 6]] and done == 0
+    assert out['path'].tolist() == [[0, 0, 0], [0, 0, 1]]
+    # duplicated candidates across parents: -2 (flat 0), -2 (flat 2); the lower flat index first
+    out, _ = run([-1, -1], [0, 0], [[-1, -2], [-1, -2]])
+    assert out['score'].tolist() == [-2, -2] and out['last_tok'].tolist() == [5, 7]
+    assert out['tok'].tolist() == [[1, 3, 5], [1, 4, 7]]
+    assert out['path'].tolist() == [[0, 0, 0], [1, 1, 1]]
+    # three equal candidates: flat 0, 1 win over flat 2
+    out, _ = run([-1, -1.5], [0, 0], [[-1, -1], [-0.5, -3]])
+    assert out['score'].tolist() == [-2, -2] and out['last_tok'].tolist() == [5, 6]
+    # both parents ended, equal scores: each keeps its one live branch, in slot order
+    out, done = run([-3, -3], [1, 1], [[-1, -2], [-1, -2]])
+    assert out['score'].tolist() == [-3, -3] and out['last_tok'].tolist() == [eos, eos]
+    assert out['tok'].tolist() == [[1, 3, eos], [1, 4, eos]] and done == 2
+    # one parent ended and better than every live candidate; its dead branch (-inf) loses
+    out, done = run([-0.5, -1], [1, 0], [[-1, -2], [-1, -2]])
+    assert out['score'].tolist() == [-0.5, -2] and out['last_tok'].tolist() == [eos, 7]
+    assert done == 1
+    # tokens outside [0, V) end the hypothesis
+    out, done = run([0, -1], [0, 0], [[-1, -2], [-9, -9]],
+                    np.array([[-1, 0x7fffffff], [7, 8]], np.int32))
+    assert out['last_tok'].tolist() == [eos, eos] and done == 2
+    out, _ = run([0, -1], [0, 0], [[-1, -9], [-9, -9]], np.array([[V, 3], [7, 8]], np.int32))
+    assert out['last_tok'].tolist()[0] == eos
+    # one parent's row NaN: its candidates count as -inf, the clean parent takes both slots
+    out, _ = run([-1, -1], [0, 0], [[nan, nan], [-1, -2]])
+    assert out['score'].tolist() == [-2, -3] and out['last_tok'].tolist() == [7, 8]
+    # every candidate NaN: flat 0, 1 with -inf
+    out, done = run([-1, -1], [0, 0], [[nan, nan], [nan, nan]],
+                    np.full((2, 2), 0x7fffffff, np.int32))
+    assert out['score'].tolist() == [-inf, -inf] and out['last_tok'].tolist() == [eos, eos]
+    assert out['tok'].tolist() == [[1, 3, eos], [1, 3, eos]] and done == 2
+
+
+@pytest.mark.parametrize('nn', [1, 4, 9, 100, 4096])
+def test_beam_rank_is_a_permutation_for_every_input(nn):
+    """With NaN -> -inf the counting rule of beam_update_kernel (rank = number of candidates that
+    are larger, or equal with a lower flat index) is a permutation; without it every NaN gets
+    rank 0."""
+    rng = np.random.default_rng(nn)
+    for kind in ('random', 'nan_some', 'nan_all', 'inf_all', 'dup'):
+        c = rng.standard_normal(nn).astype(np.float32)
+        if kind == 'nan_some':
+            c[rng.random(nn) < 0.4] = np.nan
+        elif kind == 'nan_all':
+            c[:] = np.nan
+        elif kind == 'inf_all':
+            c[:] = -np.inf
+        elif kind == 'dup':
+            c = np.round(c)
+        v = np.where(np.isnan(c), np.float32(-np.inf), c)
+        idx = np.arange(nn)
+        rank = ((v[None, :] > v[:, None]) |
+                ((v[None, :] == v[:, None]) & (idx[None, :] < idx[:, None]))).sum(1)
+        assert sorted(rank.tolist()) == list(range(nn)), kind
+        N = int(round(nn ** 0.5))
+        assert np.array_equal(np.argsort(rank)[:N], KR.beam_rank(c, N)), kind
+    c = np.full(nn, np.nan, np.float32)
+    raw = ((c[None, :] > c[:, None]) | ((c[None, :] == c[:, None]))).sum(1)
+    assert (raw == 0).all()
+
+
+@pytest.mark.parametrize('B,N,prompt_len', [(2, 3, 0), (3, 10, 0), (2, 4, 3), (1, 33, 5)])
+def test_beam_paths_name_the_slot_that_held_the_prefix(B, N, prompt_len):
+    """After init (both kinds) and a chain of updates: for every row c and position j, the slot
+    path[c][j] held, when position j was computed (the decoder step on rows of j + 1 tokens, or
+    the prompt prefill in the utterance's first slot), exactly tok[c][:j + 1]."""
+    rng = np.random.default_rng(7 * B + N)
+    V, eos, sos, steps = 2 * N + 5, 2, 1, 12
+    BN = B * N
+    prompt = rng.integers(3, V, (B, prompt_len)).astype(np.int32) if prompt_len else None
+    first = prompt_len if prompt_len else 1
+    max_len = first + steps + 2
+    st = KR.ref_beam_init(B, N, max_len, sos=sos, prompt=prompt)
+    held = {}                                   # (position, slot) -> the token prefix it computed
+    for b in range(B):
+        for j in range(prompt_len):             # the prefill: utterance b's first slot
+            held[(j, b * N)] = tuple(prompt[b, :j + 1])
+
+    def check(st, n_tok):
+        for c in range(BN):
+            for j in range(n_tok):
+                assert held[(j, int(st['path'][c, j]))] == tuple(st['tok'][c, :j + 1]), (c, j)
+
+    check(st, prompt_len)
+    for i in range(first, first + steps):
+        if i != prompt_len:                     # the step on rows of i tokens computes position i - 1
+            for r in range(BN):
+                assert st['path'][r, i - 1] == r
+                held[(i - 1, r)] = tuple(st['tok'][r, :i])
+        topv, topi = _topk_tables(rng, BN, N, V, eos)
+        st, _ = KR.ref_beam_update(st, topv, topi, B, N, i, eos, V, shared_row=i == prompt_len)
+        check(st, i)
+        assert np.array_equal(st['path'][:, i], np.arange(BN))
+
+
+@pytest.mark.parametrize('length_penalty', [0.0, 0.3, 1.0])
+@pytest.mark.parametrize('prefix', [1, 4])
+@pytest.mark.parametrize('B,N', [(3, 1), (3, 10), (3, 64)])
+def test_ref_beam_finish_matches_reference(B, N, prefix, length_penalty):
+    """Every draw the GPU test uses: the margin that makes fp32 powf irrelevant holds for all of
+    them (none is rejected), and the NumPy statement gives the reference's answer."""
+    eos = 2
+    score, tok, length = KR.make_beam_finish_case(B, N, prefix, seed=N + prefix, eos=eos)
+    s = KR.beam_finish_scores(score, tok, B, N, length, eos, length_penalty)
+    assert all(KR.beam_finish_margin_ok(s[b]) for b in range(B))
+    out_tok, out_len, best = KR.ref_beam_finish(score, tok, B, N, length, eos, length_penalty,
+                                                prefix)
+    want = _search_finish(torch.from_numpy(tok[:, :length]).long(), torch.from_numpy(score), B, N,
+                          eos, length_penalty, prefix)
+    for b in range(B):
+        assert out_tok[b, :out_len[b]].tolist() == want[b]
+        assert bool((out_tok[b, out_len[b]:] == KR.FILL).all())
+
+
+def test_ref_beam_finish_edges():
+    """sos == eos (WeNet models): the count of [sos, eos] is 0, the penalised score -x / 0 = -inf
+    for a positive penalty; every row like that: row 0, length 0, as the reference's max gives.
+    Two best rows of equal score and count: the first."""
+    eos = 2
+    tok = np.array([[eos, eos, 0], [eos, eos, 0], [eos, eos, 0]], np.int32)
+    score = np.array([-3, -1, -2], np.float32)
+    for lp in (0.3, 1.0):
+        out_tok, out_len, best = KR.ref_beam_finish(score, tok, 1, 3, 2, eos, lp, 1)
+        assert best.tolist() == [0] and out_len.tolist() == [0]
+        assert _search_finish(torch.from_numpy(tok[:, :2]).long(), torch.from_numpy(score), 1, 3,
+                              eos, lp, 1) == [[]]
+    # penalty 0: 0 ** 0 = 1, the scores decide; the answer is empty either way
+    out_tok, out_len, best = KR.ref_beam_finish(score, tok, 1, 3, 2, eos, 0.0, 1)
+    assert best.tolist() == [1] and out_len.tolist() == [0]
+    tok = np.array([[eos, 5, eos], [eos, 7, 8], [eos, 8, 7], [eos, 9, 9]], np.int32)
+    score = np.array([-4, -2, -2, -2.5], np.float32)
+    for lp in (0.0, 0.3, 1.0):
+        out_tok, out_len, best = KR.ref_beam_finish(score, tok, 1, 4, 3, eos, lp, 1)
+        assert best.tolist() == [1] and out_tok[0, :2].tolist() == [7, 8]
+        assert _search_finish(torch.from_numpy(tok).long(), torch.from_numpy(score), 1, 4, eos,
+                              lp, 1) == [[7, 8]]
+
+
+@pytest.mark.parametrize('length', [129, 200])
+@pytest.mark.parametrize('regime', KR.SELF_STEP_REGIMES, ids=lambda r: f'{r[0]}-{r[1]}')
+def test_self_step_regime_caps(regime, length):
+    """The cap on the yardstick and the weight shares of the step cases the GPU test runs, and the
+    case's own layout: named cache rows hold the sequence data, every other row the poison."""
+    case = KR.make_self_step_case(regime[0], regime[1], H=4, n=5, length=length, seed=51)
+    ref, e, scale, w = KR.self_step_refs(case)
+    assert torch.isfinite(ref).all() and KR.cap_ok(e, scale), e / scale
+    if regime in KR.SELF_STEP_NON_FLAT:
+        assert (w > 0.5).double().mean().item() >= KR.SELF_STEP_NON_FLAT[regime]
+    if regime[0] == 'unit':
+        assert (w > 0.5).double().mean().item() < 0.2
+    cache, named, step = case['cache'], case['named'], case['step']
+    assert bool((cache[~named].abs() == KR.POISON).all()) and not bool(named[step:].any())
+    assert bool((cache[named].abs() < 1e3).all())
+    for r in range(case['n']):
+        for j in range(step):
+            row = cache[j, case['path'][r, j]]
+            assert torch.equal(row[:case['d']], case['kg'][r * length + j])
+            assert torch.equal(row[case['d']:], case['vg'][r * length + j])
+        assert torch.equal(case['qkv'][r, case['d']:2 * case['d']], case['kg'][r * length + step])
+    if regime[0] == 'tied':
+        mean = case['vg'].double().view(case['n'], length, -1).mean(1)
+        assert (ref - mean).abs().max().item() <= 1e-12 * scale

@@ -77,6 +77,8 @@ EXPORTS = [
     'wn_stream_advance', 'wn_stream_advance_encoded',
     'wn_model_create_transducer', 'wn_transducer_greedy_search', 'wn_op_lstm_step',
     'wn_op_joint_argmax',
+    'wn_op_attn_self_step', 'wn_op_attn_step_embed', 'wn_op_attn_prompt_cache', 'wn_op_beam_init',
+    'wn_op_beam_update', 'wn_op_beam_finish',
 ]
 
 _lib = None
@@ -193,6 +195,13 @@ def lib():
                                   i32, vp]
     L.wn_op_joint_argmax.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, pi32,
                                      POINTER(f32), vp]
+    L.wn_op_attn_self_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
+    L.wn_op_attn_step_embed.argtypes = [vp, i32, vp, i32, vp, i32, f32, i32, i32, vp, vp]
+    L.wn_op_attn_prompt_cache.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    L.wn_op_beam_init.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.wn_op_beam_update.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, i32, pi32, vp]
+    L.wn_op_beam_finish.argtypes = [i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

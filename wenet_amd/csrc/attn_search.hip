@@ -81,7 +81,11 @@ __global__ void cache_store_kernel(const float* __restrict__ qkv, int d, int n,
 // One block per utterance, the N*N candidates strided over its threads (N <= 64).  `step` =
 // length of the parents' token rows (the new token lands at index `step`).  A token index
 // outside [0, V) -- the top-k of a row of NaN / -inf logits has no valid entry -- ends the
-// hypothesis (eos) instead of indexing the embedding table with it.
+// hypothesis (eos) instead of indexing the embedding table with it.  The candidate score of
+// such a row is NaN; a NaN compares false with everything, so it would get rank 0 next to every
+// other NaN and leave winner slots unwritten.  A NaN candidate therefore counts as -inf: the
+// ranks are a permutation of 0..N*N-1 for every input, and an utterance whose candidates are
+// all NaN selects its flat candidates 0..N-1 with score -inf (their clamped tokens end it).
 __global__ void beam_update_kernel(int N, int step, int max_len, int eos, int V,
                                    const float* __restrict__ topv, const int* __restrict__ topi,
                                    const float* __restrict__ score_in, const int* __restrict__ end_in,
@@ -99,7 +103,8 @@ __global__ void beam_update_kernel(int N, int step, int max_len, int eos, int V,
     const int hyp = b * N + n;
     float lp = topv[(int64_t)hyp * N + k];
     if (end_in[hyp]) lp = k == 0 ? 0.f : -INFINITY;     // mask_finished_scores
-    cand[t] = score_in[hyp] + lp;
+    const float c = score_in[hyp] + lp;
+    cand[t] = (c == c) ? c : -INFINITY;                 // NaN -> -inf: a total order below
   }
   __syncthreads();
   // rank by (value descending, flat index ascending): what scores.view(B, N*N).topk(N) returns

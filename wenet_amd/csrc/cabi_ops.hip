@@ -47,6 +47,22 @@ bool packed_ok(const int32_t* off, const int32_t* len, int n, int rows) {
   return true;
 }
 
+// a device index array of a hook call that a kernel dereferences (path rows, token ids): read
+// back and checked on the host, columns [0, cols) of every row inside [0, hi), before any launch
+int device_ints_in_range(const int32_t* dev, int rows, int ld, int cols, int hi, hipStream_t s,
+                         bool* ok) {
+  std::vector<int> h((size_t)rows * ld);
+  WN_HIP(hipMemcpyAsync(h.data(), dev, h.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipStreamSynchronize(s));
+  *ok = true;
+  for (int r = 0; r < rows; ++r)
+    for (int j = 0; j < cols; ++j) {
+      const int v = h[(size_t)r * ld + j];
+      if (v < 0 || v >= hi) *ok = false;
+    }
+  return 0;
+}
+
 }  // namespace
 }  // namespace wn
 
@@ -509,6 +525,96 @@ int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_
   a.blank_penalty = blank_penalty; a.topk_val = topk_val; a.topk_idx = topk_idx;
   a.logp = logp; a.ld_out = ld_out;
   return ctc_logsoftmax_topk(a, (hipStream_t)stream);
+}
+
+// ---- the `attention` decode mode's kernels (attn_search.hip), one launcher per hook ----------
+
+int wn_op_attn_self_step(const float* qkv, int32_t d, int32_t heads, int32_t n, float* cache,
+                         int32_t step, const int32_t* path, int32_t max_len, float* out,
+                         void* stream) {
+  WN_CHECK(qkv && cache && path && out, "attn_self_step: null argument");
+  WN_CHECK(heads >= 1 && heads < 256 && d == heads * 64, "attn_self_step: d must be heads * 64");
+  WN_CHECK(n >= 1 && n <= 4096, "attn_self_step: n outside [1, 4096]");
+  WN_CHECK(step >= 0 && step + 1 <= max_len && max_len <= 65536,
+           "attn_self_step: step outside [0, max_len)");
+  hipStream_t s = (hipStream_t)stream;
+  bool ok = false;
+  WN_TRY(device_ints_in_range(path, n, max_len, step + 1, n, s, &ok));
+  WN_CHECK(ok, "attn_self_step: a path entry outside [0, n)");
+  return attn_self_step(qkv, d, heads, n, cache, step, path, max_len, out, s);
+}
+
+int wn_op_attn_step_embed(const int32_t* last_tok, int32_t pos, const float* emb, int32_t V,
+                          const float* pe, int32_t max_pos, float scale, int32_t d, int32_t n,
+                          float* x, void* stream) {
+  WN_CHECK(last_tok && emb && pe && x, "attn_step_embed: null argument");
+  WN_CHECK(d >= 4 && d % 4 == 0 && n >= 1 && n <= 65536 && V >= 1, "attn_step_embed: d / n / V");
+  WN_CHECK(pos >= 0 && pos < max_pos, "attn_step_embed: position outside the table");
+  hipStream_t s = (hipStream_t)stream;
+  bool ok = false;
+  WN_TRY(device_ints_in_range(last_tok, n, 1, 1, V, s, &ok));
+  WN_CHECK(ok, "attn_step_embed: a token outside [0, V)");
+  return attn_step_embed(last_tok, pos, emb, pe, scale, d, n, x, s);
+}
+
+int wn_op_attn_prompt_cache(const float* qkv, int32_t d, int32_t B, int32_t P, int32_t N,
+                            float* cache, void* stream) {
+  WN_CHECK(qkv && cache, "attn_prompt_cache: null argument");
+  WN_CHECK(d >= 4 && d % 4 == 0 && B >= 1 && P >= 1 && (int64_t)B * P <= 65536,
+           "attn_prompt_cache: d / B / P");
+  WN_CHECK(N >= 1 && N <= 64, "attn_prompt_cache: beam_size must be in [1, 64]");
+  return attn_prompt_cache_store(qkv, d, B, P, N, cache, (hipStream_t)stream);
+}
+
+int wn_op_beam_init(int32_t B, int32_t N, int32_t max_len, int32_t sos, const int32_t* prompt,
+                    int32_t P, float* score, int32_t* end, int32_t* tok, int32_t* path,
+                    int32_t* last_tok, void* stream) {
+  WN_CHECK(score && end && tok && path && last_tok, "beam_init: null argument");
+  WN_CHECK(B >= 1 && B <= 65536, "beam_init: B outside [1, 65536]");
+  WN_CHECK(N >= 1 && N <= 64, "beam_init: beam_size must be in [1, 64]");
+  WN_CHECK(max_len >= 1, "beam_init: max_len");
+  if (prompt) {
+    WN_CHECK(P >= 1 && P <= max_len, "beam_init: prompt length outside [1, max_len]");
+    return attn_beam_init_prompt(B * N, N, max_len, prompt, P, score, end, tok, path, last_tok,
+                                 (hipStream_t)stream);
+  }
+  return attn_beam_init(B * N, N, max_len, sos, score, end, tok, path, last_tok,
+                        (hipStream_t)stream);
+}
+
+int wn_op_beam_update(int32_t B, int32_t N, int32_t step, int32_t max_len, int32_t eos,
+                      int32_t V, const float* topv, const int32_t* topi, const float* score_in,
+                      const int32_t* end_in, const int32_t* tok_in, const int32_t* path_in,
+                      float* score_out, int32_t* end_out, int32_t* tok_out, int32_t* path_out,
+                      int32_t* last_tok, int32_t shared_row, int32_t* n_done_host, void* stream) {
+  WN_CHECK(topv && topi && score_in && end_in && tok_in && path_in && score_out && end_out &&
+               tok_out && path_out && last_tok && n_done_host, "beam_update: null argument");
+  WN_CHECK(B >= 1 && B <= 65536, "beam_update: B outside [1, 65536]");
+  WN_CHECK(N >= 1 && N <= 64, "beam_update: beam_size must be in [1, 64]");
+  WN_CHECK(step >= 1 && step + 1 <= max_len, "beam_update: step outside [1, max_len - 1]");
+  WN_CHECK(V >= 1 && eos >= 0 && eos < V, "beam_update: eos outside the vocabulary");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf done;
+  WN_TRY(done.ensure(sizeof(int)));
+  WN_HIP(hipMemsetAsync(done.p, 0, sizeof(int), s));
+  WN_TRY(attn_beam_update(B, N, step, max_len, eos, V, topv, topi, score_in, end_in, tok_in,
+                          path_in, score_out, end_out, tok_out, path_out, last_tok,
+                          done.as<int>(), s, shared_row != 0));
+  WN_HIP(hipMemcpyAsync(n_done_host, done.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_op_beam_finish(int32_t B, int32_t N, int32_t len, int32_t max_len, int32_t eos,
+                      float length_penalty, const float* score, const int32_t* tok,
+                      int32_t* out_tok, int32_t* out_len, int32_t prefix, void* stream) {
+  WN_CHECK(score && tok && out_tok && out_len, "beam_finish: null argument");
+  WN_CHECK(B >= 1 && B <= 65536, "beam_finish: B outside [1, 65536]");
+  WN_CHECK(N >= 1 && N <= 64, "beam_finish: beam_size must be in [1, 64]");
+  WN_CHECK(prefix >= 0 && prefix <= len && len <= max_len,
+           "beam_finish: need 0 <= prefix <= len <= max_len");
+  return attn_beam_finish(B, N, len, max_len, eos, length_penalty, score, tok, out_tok, out_len,
+                          (hipStream_t)stream, prefix);
 }
 
 }  // extern "C"
