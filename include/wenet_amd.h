@@ -818,6 +818,38 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
                                 int32_t* tok_lens_host, int32_t max_len, int32_t* steps_out,
                                 void* stream);
 
+/* RNN-T prefix beam search over the handle's CURRENT batch: PrefixBeamSearch.prefix_beam_search
+ * (wenet/models/transducer/search/prefix_beam_search.py:42-148, reached through
+ * Transducer.beam_search, transducer.py:216-260), which the reference runs one utterance at a
+ * time, for the whole batch in lock-step, one frame per step and at most one symbol per frame.
+ * Per frame and live hypothesis: log_softmax of the joint row, the shallow fusion
+ * log(transducer_weight exp(logp) + ctc_weight exp(ctc_logp)) in fp32, its `beam` largest
+ * entries (lower index on equal values), candidate scores float32(score) + value held as
+ * doubles, prefix fusion by token sequence with log_add in fp64 (the reference's call passes a
+ * list to a function that takes its values one by one and raises; this is the evident intent),
+ * a stable sort by score, the best `beam` kept.  A slot keeps the predictor state reached after
+ * its whole hypothesis, so only the hypotheses that appended a token run the LSTM step.  Always
+ * fp32 / fp64, whatever the handle's precision; ctc_weight == 0 does not run the CTC head.
+ * `longest T'` steps are issued without a look at the device in between.
+ *   beam              1..16 and at most the vocabulary
+ *   ctc_weight, transducer_weight   >= 0, not both 0
+ *   n_hyps_host       (B) hypotheses of each utterance (>= 1), in rank order
+ *   hyp_lens_host     (B, beam); hyp_tokens_host (B, beam, max_len), without the leading blank
+ *   hyp_scores_host   (B, beam) fp64; -inf beyond n_hyps
+ *   max_len           row pitch of hyp_tokens_host; -1 with a message if a hypothesis is longer
+ *                     (a hypothesis has at most T' tokens)
+ * Returns -1 with a wn_last_error text on a handle that wn_model_create_transducer did not
+ * build (no transducer weights). */
+int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
+                              float transducer_weight, int32_t* n_hyps_host,
+                              int32_t* hyp_lens_host, int32_t* hyp_tokens_host,
+                              double* hyp_scores_host, int32_t max_len, void* stream);
+
+/* Of the handle's last wn_transducer_beam_search: the steps it issued (the longest T') and the
+ * joint rows that ran the predictor's LSTM step, summed over the steps (the others copied their
+ * state).  Either pointer may be NULL. */
+int wn_transducer_beam_stats(wn_model* m, int32_t* steps_out, int64_t* advance_rows_out);
+
 /* Test hook, handle-less: one predictor step (RNNPredictor.forward_step, predictor.py:185-206,
  * without the embedding lookup).  x_dev (B, E): the embedding rows; w_host: 4 device pointers
  * per layer (weight_ih (4H, E or H), weight_hh (4H, H), bias_ih, bias_hh; gate order i, f, g, o);
@@ -841,6 +873,45 @@ int wn_op_joint_argmax(const float* enc_proj_dev, int32_t enc_rows, const float*
                        const int32_t* row_pred_host, const float* w_dev, const float* bias_dev,
                        int32_t M, int32_t J, int32_t V, int32_t* idx_host, float* max_host,
                        void* stream);
+
+/* Test hook, handle-less: the joint network with a full-row epilogue, the transducer / CTC
+ * fusion and the top-k of the beam search.  The first eleven arguments are those of
+ * wn_op_joint_argmax.  ctc_logp_dev (ctc_rows, V): CTC log-probs, row row_ctc_host[m] for joint
+ * row m (row_ctc_host NULL: row row_enc_host[m]); not read, and may be NULL, with
+ * ctc_weight == 0.  val_host / idx_host (M, k): the k largest fused values
+ * log(transducer_weight exp(logp) + ctc_weight exp(ctc)) (exp / log in fp64, rounded to fp32
+ * once) and their columns, larger value
+ * first, the lower index on equal values, a NaN ranked and returned as -inf -- so the indices
+ * of a live row are always distinct columns in [0, V).  Rows with row_enc_host[m] < 0 answer
+ * (-inf, -1).  fused_host (M, V), may be NULL: the fused rows (zeros for inert rows).
+ * k in 1..16 and at most V; the weights >= 0 and not both 0. */
+int wn_op_joint_fuse_topk(const float* enc_proj_dev, int32_t enc_rows, const float* pred_proj_dev,
+                          int32_t pred_rows, const int32_t* row_enc_host,
+                          const int32_t* row_pred_host, const float* w_dev, const float* bias_dev,
+                          int32_t M, int32_t J, int32_t V, const float* ctc_logp_dev,
+                          int32_t ctc_rows, const int32_t* row_ctc_host, float ctc_weight,
+                          float transducer_weight, int32_t k, float* val_host, int32_t* idx_host,
+                          float* fused_host, void* stream);
+
+/* Test hook, handle-less: one frame of the beam step of wn_transducer_beam_search on
+ * caller-given slots; every array is on the host.  In: lens_host (B) frames of each utterance,
+ * n_live_host (B), scores_host (B, beam) fp64, tok_lens_host (B, beam), tokens_host
+ * (B, beam, max_tok) (hypotheses without the leading blank), top_val_host / top_idx_host
+ * (B, beam, beam) the top-k pairs of each slot's fused row.  Out: the new slots in rank order
+ * (n_live_out, scores_out, tok_lens_out, tokens_out; token entries past a length are -1), and per
+ * new slot src_out (the slot b x beam + j whose predictor state it takes; -1: none, also when the
+ * utterance has no further frame), tok_out (the token it appended, else blank), advance_out
+ * (the predictor steps on it) and row_enc_out (its joint row of the next frame, the utterances'
+ * rows packed in order; -1: inert).  An utterance with frame >= its length moves on unchanged.
+ * Live counts, token counts and top-k indices are range-checked before the launch. */
+int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                         const int32_t* lens_host, int32_t max_tok, const int32_t* n_live_host,
+                         const double* scores_host, const int32_t* tok_lens_host,
+                         const int32_t* tokens_host, const float* top_val_host,
+                         const int32_t* top_idx_host, int32_t* n_live_out, double* scores_out,
+                         int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
+                         int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
+                         void* stream);
 
 #ifdef __cplusplus
 }

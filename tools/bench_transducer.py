@@ -16,6 +16,17 @@ lock-step steps, time per step; then `greedy_search()` as a whole (encoder + sea
 of audio per second, and `decode(['ctc_prefix_beam_search'], beam 10)` of the same model and
 batch beside it for scale.
 
+    python tools/bench_transducer.py --beam              # the prefix beam search instead
+
+--beam times the batched prefix beam search (wn_transducer_beam_search) on the same model, batch
+and fixed encoder output and writes profiles/transducer_beam.json: beam 5 and 10 with
+(ctc_weight, transducer_weight) = (0.3, 0.7) and (0.0, 1.0), the settings alternating, median of
+--repeats; per setting the search time, the time per step (a step is one frame: `longest T'`
+steps), the launches per step (2 per LSTM layer, the projection, joint.pred_ffn, the joint, the
+fusion + top-k, the beam step, the state gather) and the rows per step that ran the LSTM step
+(`advance`) against the B x beam rows rnnt_linear_kernel walks.  Beside it, in the same process:
+the greedy search at its shipped lookahead and decode(['ctc_prefix_beam_search'], beam 10).
+
 The per-kernel split (enc_proj / predictor / joint / advance) comes from a kernel trace in a run
 of its own, because the handle's launch brackets (wn_profile_enable) time the GEMM launchers
 only and a traced run is not a timed one:
@@ -49,8 +60,12 @@ def main(argv=None):
     p.add_argument('--blank-bias', type=float, nargs='+', default=[8.5, 8.0, 9.0, 7.0, 6.0])
     p.add_argument('--searches-only', type=int, default=0,
                    help='profiler runs: N searches per lookahead, no JSON')
-    p.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'transducer_greedy.json'))
+    p.add_argument('--beam', action='store_true', help='time the prefix beam search')
+    p.add_argument('--out', default=None)
     args = p.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'transducer_beam.json' if args.beam
+                                else 'transducer_greedy.json')
 
     import torch
     if not torch.cuda.is_available():
@@ -82,6 +97,8 @@ def main(argv=None):
         if picked['in_range']:
             break
     ref_tokens = basic_greedy_search(model, enc, enc_lens, args.n_steps)
+    if args.beam:
+        return bench_beam(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked)
 
     def one_search(F):
         model.tune('rnnt_lookahead', F)
@@ -139,6 +156,92 @@ def main(argv=None):
                method='host clock around calls that end in a device synchronise; settings '
                       'alternate in one process; median of --repeats')
     print(json.dumps(out['greedy_search']), json.dumps(out['ctc_prefix_beam_search_beam10']))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+    print('wrote', args.out)
+    return 0
+
+
+BEAM_SETTINGS = ((5, 0.3, 0.7), (5, 0.0, 1.0), (10, 0.3, 0.7), (10, 0.0, 1.0))
+
+
+def bench_beam(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked):
+    import torch
+    from wenet_amd.transducer import basic_greedy_search, prefix_beam_search
+    sync = torch.cuda.synchronize
+    B = int(feats.shape[0])
+    n_layers = configs['predictor_conf']['num_layers']
+    launches = 2 * n_layers + 6
+
+    def one(setting):
+        beam, cw, tw = setting
+        sync()
+        t0 = time.perf_counter()
+        nbest = prefix_beam_search(model, enc, enc_lens, beam, cw, tw)
+        dt = time.perf_counter() - t0
+        return dt, nbest
+
+    first, stats = {}, {}
+    for s in BEAM_SETTINGS:          # warm up every shape
+        first[s] = one(s)[1]
+        stats[s] = (model.last_rnnt_steps, model.last_rnnt_advance_rows)
+    if args.searches_only:
+        for _ in range(args.searches_only):
+            for s in BEAM_SETTINGS:
+                one(s)
+        return 0
+    times = {s: [] for s in BEAM_SETTINGS}
+    for _ in range(args.repeats):
+        for s in BEAM_SETTINGS:
+            dt, nbest = one(s)
+            assert nbest == first[s], f'{s}: another result on a repeat'
+            times[s].append(dt)
+    table = []
+    for s in BEAM_SETTINGS:
+        beam, cw, tw = s
+        med = statistics.median(times[s])
+        steps, adv = stats[s]
+        row = dict(beam=beam, ctc_weight=cw, transducer_weight=tw,
+                   search_ms=dict(median=med * 1e3, min=min(times[s]) * 1e3,
+                                  max=max(times[s]) * 1e3),
+                   steps=steps, us_per_step=med * 1e6 / max(steps, 1), launches_per_step=launches,
+                   rows=B * beam, advancing_rows_per_step=adv / max(steps, 1),
+                   mean_best_len=sum(len(u[0][0]) for u in first[s]) / B)
+        table.append(row)
+        print(f'beam {beam:2d} ({cw}, {tw}): {med * 1e3:8.2f} ms  ({steps} steps, '
+              f"{row['us_per_step']:.1f} us / step, {launches} launches / step, "
+              f"{row['advancing_rows_per_step']:.1f} of {B * beam} rows advance)", flush=True)
+
+    def timed(fn):
+        fn(); sync()
+        ts = []
+        for _ in range(args.repeats):
+            sync()
+            t0 = time.perf_counter()
+            fn()
+            sync()
+            ts.append(time.perf_counter() - t0)
+        return statistics.median(ts)
+
+    F = model.tune('rnnt_lookahead')
+    t_greedy = timed(lambda: basic_greedy_search(model, enc, enc_lens, args.n_steps))
+    greedy_steps = model.last_rnnt_steps
+    t_ctc = timed(lambda: model.decode(['ctc_prefix_beam_search'], feats, lens, beam_size=10))
+    t_e2e = timed(lambda: model.beam_search(feats, lens, beam_size=10))
+    out = dict(config=args.config, encoder_blocks=configs['encoder_conf']['num_blocks'], batch=B,
+               audio_seconds=audio_s, weights=picked, beam_search=table,
+               greedy_search_on_the_same_encoder_output=dict(
+                   lookahead=F, search_ms=t_greedy * 1e3, steps=greedy_steps,
+                   us_per_step=t_greedy * 1e6 / max(greedy_steps, 1)),
+               beam_search_beam10_with_encoder=dict(seconds=t_e2e, audio_s_per_s=audio_s / t_e2e),
+               ctc_prefix_beam_search_beam10_with_encoder=dict(seconds=t_ctc,
+                                                               audio_s_per_s=audio_s / t_ctc),
+               method='host clock around calls that end in a device synchronise; settings '
+                      'alternate in one process; median of --repeats')
+    print(json.dumps(out['greedy_search_on_the_same_encoder_output']),
+          json.dumps(out['beam_search_beam10_with_encoder']),
+          json.dumps(out['ctc_prefix_beam_search_beam10_with_encoder']))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)

@@ -76,7 +76,8 @@ EXPORTS = [
     'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
     'wn_stream_advance', 'wn_stream_advance_encoded',
     'wn_model_create_transducer', 'wn_transducer_greedy_search', 'wn_op_lstm_step',
-    'wn_op_joint_argmax',
+    'wn_op_joint_argmax', 'wn_transducer_beam_search', 'wn_op_joint_fuse_topk',
+    'wn_op_rnnt_beam_step', 'wn_transducer_beam_stats',
     'wn_op_attn_self_step', 'wn_op_attn_step_embed', 'wn_op_attn_prompt_cache', 'wn_op_beam_init',
     'wn_op_beam_update', 'wn_op_beam_finish',
 ]
@@ -195,6 +196,14 @@ def lib():
                                   i32, vp]
     L.wn_op_joint_argmax.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, pi32,
                                      POINTER(f32), vp]
+    L.wn_transducer_beam_search.argtypes = [vp, i32, f32, f32, pi32, pi32, pi32, pf64, i32, vp]
+    L.wn_transducer_beam_stats.argtypes = [vp, pi32, POINTER(i64)]
+    L.wn_op_joint_fuse_topk.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, vp,
+                                        i32, pi32, f32, f32, i32, POINTER(f32), pi32,
+                                        POINTER(f32), vp]
+    L.wn_op_rnnt_beam_step.argtypes = [i32, i32, i32, i32, i32, pi32, i32, pi32, pf64, pi32, pi32,
+                                       POINTER(f32), pi32, pi32, pf64, pi32, pi32, pi32, pi32,
+                                       pi32, pi32, vp]
     L.wn_op_attn_self_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
     L.wn_op_attn_step_embed.argtypes = [vp, i32, vp, i32, vp, i32, f32, i32, i32, vp, vp]
     L.wn_op_attn_prompt_cache.argtypes = [vp, i32, i32, i32, i32, vp, vp]

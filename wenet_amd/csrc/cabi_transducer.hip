@@ -1,6 +1,7 @@
 // C ABI (include/wenet_amd.h), hybrid transducer: the batched RNN-T greedy search with frame
-// lookahead over the handle's current batch (kernels: transducer.hip) and the two operator hooks
-// of its predictor step and joint + arg-max.
+// lookahead and the batched prefix beam search over the handle's current batch (kernels:
+// transducer.hip, transducer_beam.hip) and the operator hooks of the predictor step, the joint +
+// arg-max, the joint + fusion + top-k and the beam step.
 #include <algorithm>
 
 #include "model_state.h"
@@ -174,6 +175,181 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
   return 0;
 }
 
+int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
+                              float transducer_weight, int32_t* n_hyps_host,
+                              int32_t* hyp_lens_host, int32_t* hyp_tokens_host,
+                              double* hyp_scores_host, int32_t max_len, void* stream) {
+  WN_CHECK(m, "wn_transducer_beam_search: null handle");
+  WN_CHECK(m->tr.on && m->data->j_out.w,
+           "wn_transducer_beam_search: this model has no transducer weights (predictor / "
+           "joint); it was not built by wn_model_create_transducer");
+  WN_ENTER(m);
+  WN_CHECK(m->B > 0 && m->enc.p,
+           "wn_transducer_beam_search: no current batch (call wn_encode / wn_set_encoder_out)");
+  WN_CHECK(n_hyps_host && hyp_lens_host && hyp_tokens_host && hyp_scores_host && max_len >= 0,
+           "wn_transducer_beam_search: null output");
+  const wn_config& c = m->cfg;
+  const int V = c.vocab;
+  WN_CHECK(beam >= 1 && beam <= 16, "wn_transducer_beam_search: beam must be in [1, 16]");
+  WN_CHECK(beam <= V, "wn_transducer_beam_search: beam is larger than the vocabulary");
+  WN_CHECK(ctc_weight >= 0.f && transducer_weight >= 0.f,
+           "wn_transducer_beam_search: the weights must be >= 0");
+  WN_CHECK(ctc_weight > 0.f || transducer_weight > 0.f,
+           "wn_transducer_beam_search: ctc_weight and transducer_weight are both 0");
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  const ModelData& W = *m->data;
+  WN_CHECK(ctc_weight == 0.f || W.ctc.w, "wn_transducer_beam_search: ctc_weight > 0 on a handle "
+                                         "without a CTC head");
+  const int B = m->B, rows = m->rows, d = c.d_model;
+  const wn_transducer_config& tc = m->tr.c;
+  const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
+  const int J = tc.join_dim, blank = tc.blank;
+  int longest = 0;
+  for (int b = 0; b < B; ++b) longest = std::max(longest, m->len[b]);
+  const int max_tok = std::max(longest, 1);     // one symbol per frame at most
+  const int64_t M64 = (int64_t)B * beam;
+  const int ldl = (V + 31) / 32 * 32;
+  WN_CHECK(M64 * std::max(max_tok, ldl) <= ((int64_t)1 << 28),
+           "wn_transducer_beam_search: B x beam rows do not fit the workspace");
+  const int M = (int)M64;
+
+  // ---- workspace, sized by B x beam -----------------------------------------------------------
+  WN_TRY(m->tr_enc.ensure((size_t)std::max(rows, 1) * J * sizeof(float)));
+  const size_t n_state = up64((size_t)L * M * H), n_pp = up64((size_t)M * J), um = up64(M),
+               ub = up64(B);
+  const size_t o_h = 0, o_c = 2 * n_state, o_gates = 4 * n_state,
+               o_pout = o_gates + up64((size_t)M * 4 * H), o_pp = o_pout + up64((size_t)M * P),
+               o_logits = o_pp + 2 * n_pp, o_topv = o_logits + up64((size_t)M * ldl),
+               o_score = o_topv + up64((size_t)M * beam), n_f32 = o_score + 4 * um;
+  WN_TRY(m->tr_f32.ensure(n_f32 * sizeof(float)));
+  const size_t o_topi = 2 * ub + 7 * um, o_stat = o_topi + up64((size_t)M * beam),
+               n_i32 = o_stat + 64;
+  WN_TRY(m->tr_i32.ensure(n_i32 * sizeof(int)));
+  WN_TRY(m->tr_tok.ensure((size_t)2 * M * max_tok * sizeof(int)));
+  float* f = m->tr_f32.as<float>();
+  int* ip = m->tr_i32.as<int>();
+  float* enc_proj = m->tr_enc.as<float>();
+  float *gates = f + o_gates, *pout = f + o_pout, *logits = f + o_logits, *topv = f + o_topv;
+  RnntBeamSlots slots[2];
+  for (int i = 0; i < 2; ++i) {
+    slots[i].n_live = ip + i * ub;
+    slots[i].tok_len = ip + 2 * ub + i * um;
+    slots[i].score = reinterpret_cast<double*>(f + o_score) + i * um;
+    slots[i].tokens = m->tr_tok.as<int>() + (size_t)i * M * max_tok;
+  }
+  int* src = ip + 2 * ub + 2 * um;
+  int *last_tok = src + um, *advance = src + 2 * um, *row_enc = src + 3 * um,
+      *row_pred = src + 4 * um, *topi = ip + o_topi;
+  const int* off = m->d_off.as<int>();
+  const int* len = m->d_len.as<int>();
+
+  // ---- once per batch: enc_proj, the CTC log-prob rows (cw > 0 only), zero LSTM state ----------
+  const float* ctc = nullptr;
+  {
+    const int saved = t_gemm_prec;      // always the fp32 GEMMs, whatever the handle's precision
+    t_gemm_prec = PREC_F32;
+    int r = rows > 0 ? linear(W.j_enc, m->enc.as<float>(), d, enc_proj, J, rows, s) : 0;
+    if (r == 0 && ctc_weight != 0.f && rows > 0) {
+      r = m->tr_ctc.ensure(((size_t)rows * ldl + 2 * (size_t)rows) * sizeof(float));
+      if (r == 0) r = linear(W.ctc, m->enc.as<float>(), d, m->tr_ctc.as<float>(), ldl, rows, s);
+    }
+    t_gemm_prec = saved;
+    WN_TRY(r);
+  }
+  if (ctc_weight != 0.f && rows > 0) {
+    CtcRowArgs r;       // normalised in place; its top-1 is not used
+    r.logits = m->tr_ctc.as<float>(); r.ld = ldl; r.M = rows; r.V = V; r.k = 1;
+    r.blank = blank; r.blank_penalty = 0.f;
+    r.topk_val = m->tr_ctc.as<float>() + (size_t)rows * ldl;
+    r.topk_idx = reinterpret_cast<int*>(r.topk_val + rows);
+    r.logp = m->tr_ctc.as<float>(); r.ld_out = ldl;
+    WN_TRY(ctc_logsoftmax_topk(r, s));
+    ctc = m->tr_ctc.as<float>();
+  }
+  WN_HIP(hipMemsetAsync(f + o_h, 0, 4 * n_state * sizeof(float), s));
+  WN_HIP(hipMemsetAsync(ip + o_stat, 0, sizeof(int), s));
+  WN_TRY(rnnt_beam_init(slots[0], last_tok, advance, row_enc, row_pred, off, len, B, beam, blank, s));
+
+  // ---- exactly `longest` steps, stream-ordered, no look at the device in between ---------------
+  for (int i = 0; i < longest; ++i) {
+    const int cur = i & 1, nxt = cur ^ 1;
+    float *h = f + o_h + cur * n_state, *cst = f + o_c + cur * n_state, *pp = f + o_pp + cur * n_pp;
+    WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
+                          gates, pout, advance, nullptr, M, H, s));
+    RnntLinearArgs q;   // joint.pred_ffn
+    q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
+    q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
+    WN_TRY(rnnt_linear(q, s));
+    RnntJointArgs ja;
+    ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pp; ja.ldp = J;
+    ja.row_enc = row_enc; ja.row_pred = row_pred;
+    ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
+    ja.logits = logits; ja.ldl = ldl;
+    WN_TRY(rnnt_joint_rows(ja, s));
+    RnntFuseArgs fa;
+    fa.logits = logits; fa.ldl = ldl; fa.row_enc = row_enc; fa.ctc = ctc; fa.ldc = ldl;
+    fa.cw = ctc_weight; fa.tw = transducer_weight; fa.M = M; fa.V = V; fa.k = beam;
+    fa.val = topv; fa.idx = topi;
+    WN_TRY(rnnt_fuse_topk(fa, s));
+    RnntBeamStepArgs ba;
+    ba.in = slots[cur]; ba.out = slots[nxt]; ba.max_tok = max_tok;
+    ba.top_val = topv; ba.top_idx = topi; ba.off = off; ba.len = len;
+    ba.frame = i; ba.B = B; ba.beam = beam; ba.blank = blank; ba.V = V;
+    ba.src = src; ba.last_tok = last_tok; ba.advance = advance; ba.row_enc = row_enc;
+    ba.n_advance = ip + o_stat;
+    WN_TRY(rnnt_beam_step(ba, s));
+    WN_TRY(rnnt_beam_gather(src, h, cst, pp, f + o_h + nxt * n_state, f + o_c + nxt * n_state,
+                            f + o_pp + nxt * n_pp, M, L, H, J, s));
+  }
+
+  // ---- results: counts | lengths | scores | token rows into pinned memory, one wait ------------
+  const RnntBeamSlots& fin = slots[longest & 1];
+  const size_t p_len = up64(B) * sizeof(int), p_sc = p_len + um * sizeof(int),
+               p_tok = p_sc + um * sizeof(double),
+               p_stat = p_tok + up64((size_t)M * max_tok) * sizeof(int);
+  WN_TRY(m->tr_host.ensure(p_stat + 64));
+  char* hp = m->tr_host.p;
+  WN_HIP(hipMemcpyAsync(hp, fin.n_live, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(hp + p_len, fin.tok_len, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(hp + p_sc, fin.score, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(hp + p_tok, fin.tokens, (size_t)M * max_tok * sizeof(int),
+                        hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(hp + p_stat, ip + o_stat, sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(stream_wait(s));
+  m->tr_beam_steps = longest;
+  m->tr_beam_advance = *reinterpret_cast<const int*>(hp + p_stat);
+  for (int b = 0; b < B; ++b) m->tr_beam_advance += m->len[b] > 0;    // the first step's rows
+  const int* nl = reinterpret_cast<const int*>(hp);
+  const int* tl = reinterpret_cast<const int*>(hp + p_len);
+  const double* sc = reinterpret_cast<const double*>(hp + p_sc);
+  const int* tk = reinterpret_cast<const int*>(hp + p_tok);
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(nl[b] >= 1 && nl[b] <= beam, "wn_transducer_beam_search: an utterance ended without "
+                                          "a hypothesis");
+    n_hyps_host[b] = nl[b];
+    for (int k = 0; k < beam; ++k) {
+      const int g = b * beam + k;
+      const int n = k < nl[b] ? tl[g] : 0;
+      WN_CHECK(n >= 0 && n <= max_tok, "wn_transducer_beam_search: token row overflow");
+      WN_CHECK(n <= max_len, "wn_transducer_beam_search: max_len is smaller than the longest "
+                             "result (" + std::to_string(n) + " tokens)");
+      hyp_lens_host[g] = n;
+      hyp_scores_host[g] = k < nl[b] ? sc[g] : -INFINITY;
+      std::copy(tk + (size_t)g * max_tok, tk + (size_t)g * max_tok + n,
+                hyp_tokens_host + (size_t)g * max_len);
+    }
+  }
+  return 0;
+}
+
+int wn_transducer_beam_stats(wn_model* m, int32_t* steps_out, int64_t* advance_rows_out) {
+  WN_CHECK(m, "wn_transducer_beam_stats: null handle");
+  if (steps_out) *steps_out = m->tr_beam_steps;
+  if (advance_rows_out) *advance_rows_out = m->tr_beam_advance;
+  return 0;
+}
+
 int wn_op_lstm_step(const float* x_dev, const float* const* w_host, int32_t n_layers,
                     const float* proj_w_dev, const float* proj_b_dev, float* h_dev, float* c_dev,
                     const int32_t* advance_dev, float* out_dev, int32_t B, int32_t E, int32_t H,
@@ -227,6 +403,152 @@ int wn_op_joint_argmax(const float* enc_proj_dev, int32_t enc_rows, const float*
   WN_TRY(rnnt_reduce_partials(ja.part_max, ja.part_idx, ncb, M, out_max, out_idx, s));
   WN_HIP(hipMemcpyAsync(max_host, out_max, (size_t)M * sizeof(float), hipMemcpyDeviceToHost, s));
   WN_HIP(hipMemcpyAsync(idx_host, out_idx, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_op_joint_fuse_topk(const float* enc_proj_dev, int32_t enc_rows, const float* pred_proj_dev,
+                          int32_t pred_rows, const int32_t* row_enc_host,
+                          const int32_t* row_pred_host, const float* w_dev, const float* bias_dev,
+                          int32_t M, int32_t J, int32_t V, const float* ctc_logp_dev,
+                          int32_t ctc_rows, const int32_t* row_ctc_host, float ctc_weight,
+                          float transducer_weight, int32_t k, float* val_host, int32_t* idx_host,
+                          float* fused_host, void* stream) {
+  WN_CHECK(enc_proj_dev && pred_proj_dev && row_enc_host && row_pred_host && w_dev && bias_dev &&
+           val_host && idx_host, "wn_op_joint_fuse_topk: null argument");
+  WN_CHECK(M >= 1 && V >= 1 && enc_rows >= 1 && pred_rows >= 1, "wn_op_joint_fuse_topk: empty");
+  WN_CHECK(k >= 1 && k <= 16, "wn_op_joint_fuse_topk: k must be in [1, 16]");
+  WN_CHECK(k <= V, "wn_op_joint_fuse_topk: k is larger than the vocabulary");
+  WN_CHECK(ctc_weight >= 0.f && transducer_weight >= 0.f,
+           "wn_op_joint_fuse_topk: the weights must be >= 0");
+  WN_CHECK(ctc_weight > 0.f || transducer_weight > 0.f,
+           "wn_op_joint_fuse_topk: ctc_weight and transducer_weight are both 0");
+  WN_CHECK(ctc_weight == 0.f || (ctc_logp_dev && ctc_rows >= 1),
+           "wn_op_joint_fuse_topk: ctc_weight > 0 without CTC log-probs");
+  WN_CHECK((int64_t)M * V <= ((int64_t)1 << 28), "wn_op_joint_fuse_topk: M x V is too large");
+  for (int i = 0; i < M; ++i) {
+    WN_CHECK(row_enc_host[i] < enc_rows && row_pred_host[i] >= 0 && row_pred_host[i] < pred_rows,
+             "wn_op_joint_fuse_topk: row map outside its matrix");
+    if (ctc_weight != 0.f && row_enc_host[i] >= 0) {
+      const int rc = row_ctc_host ? row_ctc_host[i] : row_enc_host[i];
+      WN_CHECK(rc >= 0 && rc < ctc_rows, "wn_op_joint_fuse_topk: CTC row map outside its matrix");
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf map, rowsb, out;
+  WN_TRY(map.ensure((size_t)3 * M * sizeof(int)));
+  WN_TRY(rowsb.ensure((size_t)2 * M * V * sizeof(float)));
+  WN_TRY(out.ensure((size_t)2 * M * k * sizeof(float)));
+  int* mp = map.as<int>();
+  WN_HIP(hipMemcpyAsync(mp, row_enc_host, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
+  WN_HIP(hipMemcpyAsync(mp + M, row_pred_host, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
+  if (row_ctc_host)
+    WN_HIP(hipMemcpyAsync(mp + 2 * M, row_ctc_host, (size_t)M * sizeof(int), hipMemcpyHostToDevice, s));
+  float* logits = rowsb.as<float>();
+  float* fused = logits + (size_t)M * V;
+  if (fused_host) WN_HIP(hipMemsetAsync(fused, 0, (size_t)M * V * sizeof(float), s));
+  RnntJointArgs ja;
+  ja.enc_proj = enc_proj_dev; ja.lde = J; ja.pred_proj = pred_proj_dev; ja.ldp = J;
+  ja.row_enc = mp; ja.row_pred = mp + M;
+  ja.W = w_dev; ja.bias = bias_dev; ja.M = M; ja.J = J; ja.V = V;
+  ja.logits = logits; ja.ldl = V;
+  WN_TRY(rnnt_joint_rows(ja, s));
+  RnntFuseArgs fa;
+  fa.logits = logits; fa.ldl = V; fa.row_enc = mp;
+  fa.ctc = ctc_weight != 0.f ? ctc_logp_dev : nullptr; fa.ldc = V;
+  fa.row_ctc = row_ctc_host ? mp + 2 * M : nullptr;
+  fa.cw = ctc_weight; fa.tw = transducer_weight; fa.M = M; fa.V = V; fa.k = k;
+  fa.val = out.as<float>(); fa.idx = out.as<int>() + (size_t)M * k;
+  if (fused_host) { fa.fused = fused; fa.ldf = V; }
+  WN_TRY(rnnt_fuse_topk(fa, s));
+  WN_HIP(hipMemcpyAsync(val_host, fa.val, (size_t)M * k * sizeof(float), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(idx_host, fa.idx, (size_t)M * k * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (fused_host)
+    WN_HIP(hipMemcpyAsync(fused_host, fused, (size_t)M * V * sizeof(float), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                         const int32_t* lens_host, int32_t max_tok, const int32_t* n_live_host,
+                         const double* scores_host, const int32_t* tok_lens_host,
+                         const int32_t* tokens_host, const float* top_val_host,
+                         const int32_t* top_idx_host, int32_t* n_live_out, double* scores_out,
+                         int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
+                         int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
+                         void* stream) {
+  WN_CHECK(lens_host && n_live_host && scores_host && tok_lens_host && tokens_host &&
+           top_val_host && top_idx_host && n_live_out && scores_out && tok_lens_out &&
+           tokens_out && src_out && tok_out && advance_out && row_enc_out,
+           "wn_op_rnnt_beam_step: null argument");
+  WN_CHECK(beam >= 1 && beam <= 16, "wn_op_rnnt_beam_step: beam must be in [1, 16]");
+  WN_CHECK(B >= 1 && V >= 1 && max_tok >= 1 && frame >= 0 && blank >= 0 && blank < V &&
+           (int64_t)B * beam * max_tok <= ((int64_t)1 << 28),
+           "wn_op_rnnt_beam_step: empty or too large, or a blank outside the vocabulary");
+  std::vector<int> off(B);
+  int rows = 0;
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(lens_host[b] >= 0, "wn_op_rnnt_beam_step: negative length");
+    off[b] = rows;
+    rows += lens_host[b];
+    WN_CHECK(n_live_host[b] >= 0 && n_live_host[b] <= beam,
+             "wn_op_rnnt_beam_step: live count outside [0, beam]");
+    for (int j = 0; j < n_live_host[b]; ++j) {
+      const int g = b * beam + j;
+      // a live slot of an unfinished utterance may append one token
+      const int room = frame < lens_host[b] ? max_tok - 1 : max_tok;
+      WN_CHECK(tok_lens_host[g] >= 0 && tok_lens_host[g] <= room,
+               "wn_op_rnnt_beam_step: token count outside its row");
+      if (frame < lens_host[b])
+        for (int r = 0; r < beam; ++r)
+          WN_CHECK(top_idx_host[(size_t)g * beam + r] >= 0 && top_idx_host[(size_t)g * beam + r] < V,
+                   "wn_op_rnnt_beam_step: top-k index outside the vocabulary");
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int M = B * beam;
+  const size_t um = up64(M), ub = up64(B);
+  static thread_local DevBuf ibuf, fbuf;
+  const size_t o_tok = 4 * ub + 6 * um + 2 * up64((size_t)M * beam);
+  WN_TRY(ibuf.ensure((o_tok + 2 * (size_t)M * max_tok) * sizeof(int)));
+  WN_TRY(fbuf.ensure(2 * um * sizeof(double)));
+  int* ip = ibuf.as<int>();
+  RnntBeamStepArgs a;
+  int *d_off = ip, *d_len = ip + ub;
+  a.in.n_live = ip + 2 * ub; a.out.n_live = ip + 3 * ub;
+  int* q = ip + 4 * ub;
+  a.in.tok_len = q; a.out.tok_len = q + um; a.src = q + 2 * um; a.last_tok = q + 3 * um;
+  a.advance = q + 4 * um; a.row_enc = q + 5 * um;
+  int* d_topi = q + 6 * um;
+  float* d_topv = reinterpret_cast<float*>(d_topi + up64((size_t)M * beam));
+  a.in.tokens = ip + o_tok; a.out.tokens = a.in.tokens + (size_t)M * max_tok;
+  a.in.score = fbuf.as<double>(); a.out.score = a.in.score + um;
+  auto up = [&](void* dst, const void* srcp, size_t bytes) {
+    return hipMemcpyAsync(dst, srcp, bytes, hipMemcpyHostToDevice, s);
+  };
+  WN_HIP(up(d_off, off.data(), (size_t)B * sizeof(int)));
+  WN_HIP(up(d_len, lens_host, (size_t)B * sizeof(int)));
+  WN_HIP(up(a.in.n_live, n_live_host, (size_t)B * sizeof(int)));
+  WN_HIP(up(a.in.tok_len, tok_lens_host, (size_t)M * sizeof(int)));
+  WN_HIP(up(a.in.tokens, tokens_host, (size_t)M * max_tok * sizeof(int)));
+  WN_HIP(up(a.in.score, scores_host, (size_t)M * sizeof(double)));
+  WN_HIP(up(d_topi, top_idx_host, (size_t)M * beam * sizeof(int)));
+  WN_HIP(up(d_topv, top_val_host, (size_t)M * beam * sizeof(float)));
+  WN_HIP(hipMemsetAsync(a.out.tokens, 0xff, (size_t)M * max_tok * sizeof(int), s));   // -1
+  a.max_tok = max_tok; a.top_val = d_topv; a.top_idx = d_topi; a.off = d_off; a.len = d_len;
+  a.frame = frame; a.B = B; a.beam = beam; a.blank = blank; a.V = V;
+  WN_TRY(rnnt_beam_step(a, s));
+  auto down = [&](void* dst, const void* srcp, size_t bytes) {
+    return hipMemcpyAsync(dst, srcp, bytes, hipMemcpyDeviceToHost, s);
+  };
+  WN_HIP(down(n_live_out, a.out.n_live, (size_t)B * sizeof(int)));
+  WN_HIP(down(scores_out, a.out.score, (size_t)M * sizeof(double)));
+  WN_HIP(down(tok_lens_out, a.out.tok_len, (size_t)M * sizeof(int)));
+  WN_HIP(down(tokens_out, a.out.tokens, (size_t)M * max_tok * sizeof(int)));
+  WN_HIP(down(src_out, a.src, (size_t)M * sizeof(int)));
+  WN_HIP(down(tok_out, a.last_tok, (size_t)M * sizeof(int)));
+  WN_HIP(down(advance_out, a.advance, (size_t)M * sizeof(int)));
+  WN_HIP(down(row_enc_out, a.row_enc, (size_t)M * sizeof(int)));
   WN_HIP(hipStreamSynchronize(s));
   return 0;
 }

@@ -517,9 +517,13 @@ struct RnntJointArgs {
   int M = 0, J = 0, V = 0;
   float* part_max = nullptr; int* part_idx = nullptr;
   const int* n_active = nullptr;
+  float* logits = nullptr; int ldl = 0;   // rnnt_joint_rows: the (M, V) logits of the live rows
 };
 int rnnt_joint_col_blocks(int V);
 int rnnt_joint_argmax(const RnntJointArgs& a, hipStream_t s);
+// the same GEMM with a full-row epilogue: logits[m][:V] of every row with row_enc[m] >= 0 (the
+// others are left as they are); part_* are not used
+int rnnt_joint_rows(const RnntJointArgs& a, hipStream_t s);
 // search state of a batch, device arrays of B entries unless noted
 struct RnntState {
   int* t; int* cnt; int* last_tok; int* advance; int* done; int* n_tok;
@@ -534,5 +538,48 @@ int rnnt_advance(const float* part_max, const int* part_idx, int ncb, int V, con
 // the advance kernel's reduction of the column-block partials alone: out_*[m] of M rows
 int rnnt_reduce_partials(const float* part_max, const int* part_idx, int ncb, int M,
                          float* out_max, int* out_idx, hipStream_t s);
+
+// RNN-T prefix beam search (transducer_beam.hip), fp32 rows and fp64 scores.
+// Per live row (row_enc[m] >= 0): lse of the logits, f[v] = log(tw exp(l[v] - lse) +
+// cw exp(ctc[row_enc[m]][v])) (fp64 exp / log, one rounding to fp32) and the k largest (value, index), larger value first, the lower
+// index on equal values, a NaN as -inf.  Inert rows answer (-inf, -1).  cw == 0: ctc is not read.
+struct RnntFuseArgs {
+  const float* logits = nullptr; int ldl = 0;   // [M][V]
+  const int* row_enc = nullptr;
+  const float* ctc = nullptr; int ldc = 0;      // CTC log-probs by encoder row, or null
+  const int* row_ctc = nullptr;                 // the CTC row of joint row m (null: row_enc[m])
+  float cw = 0.f, tw = 1.f;
+  int M = 0, V = 0, k = 0;
+  float* val = nullptr; int* idx = nullptr;     // [M][k]
+  float* fused = nullptr; int ldf = 0;          // optional: the fused rows [M][V]
+};
+int rnnt_fuse_topk(const RnntFuseArgs& a, hipStream_t s);
+// the slots of a batch: beam per utterance, the first n_live[b] of them live, in rank order
+struct RnntBeamSlots {
+  int* n_live = nullptr;       // [B]
+  double* score = nullptr;     // [B x beam]
+  int* tok_len = nullptr;      // [B x beam]
+  int* tokens = nullptr;       // [B x beam][max_tok], without the leading blank
+};
+struct RnntBeamStepArgs {
+  RnntBeamSlots in, out;
+  int max_tok = 0;
+  const float* top_val = nullptr; const int* top_idx = nullptr;   // [B x beam][beam]
+  const int* off = nullptr; const int* len = nullptr;             // [B] encoder rows
+  int frame = 0, B = 0, beam = 0, blank = 0, V = 0;
+  // of the new slots, [B x beam]: the slot (of the whole batch) whose predictor state the slot
+  // takes (-1: none), the token it appended (else blank), whether the predictor steps on it,
+  // and its joint row of the next frame (-1: inert)
+  int* src = nullptr; int* last_tok = nullptr; int* advance = nullptr; int* row_enc = nullptr;
+  int* n_advance = nullptr;    // optional [1]: += the new slots that set `advance`
+};
+// one hypothesis [blank], score 0.0, per utterance; row_pred[g] = g
+int rnnt_beam_init(const RnntBeamSlots& st, int* last_tok, int* advance, int* row_enc,
+                   int* row_pred, const int* off, const int* len, int B, int beam, int blank, hipStream_t s);
+int rnnt_beam_step(const RnntBeamStepArgs& a, hipStream_t s);
+// rows src[g] of h_in / c_in [L][M][H] and pp_in [M][J] into rows g of the out buffers (src < 0: skip)
+int rnnt_beam_gather(const int* src, const float* h_in, const float* c_in, const float* pp_in,
+                     float* h_out, float* c_out, float* pp_out, int M, int L, int H, int J,
+                     hipStream_t s);
 
 }  // namespace wn

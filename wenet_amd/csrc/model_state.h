@@ -307,6 +307,9 @@ struct wn_model {
   // wn_transducer_greedy_search: enc_proj | predictor state and outputs | joint partials |
   // search state and tokens; the pinned n_active slots the host loop polls one group late
   DevBuf tr_enc, tr_f32, tr_i32, tr_tok;
+  DevBuf tr_ctc;          // wn_transducer_beam_search: the CTC log-prob rows it fuses with
+  int tr_beam_steps = 0;            // ... its last call: steps issued,
+  int64_t tr_beam_advance = 0;      // rows that ran the LSTM step, summed over the steps
   PinnedBuf tr_host;
   hipEvent_t tr_ev[2] = {nullptr, nullptr};
   ~wn_model() { for (hipEvent_t e : tr_ev) if (e) (void)hipEventDestroy(e); }

@@ -14,7 +14,8 @@
 //    the advancing rows; the others keep h and c bit for bit;
 //  * rnnt_joint_kernel    tanh(enc_proj[row] + pred_proj[b]) built on its way into LDS, times
 //    ffn_out.weight^T on v_mfma_f32_32x32x2_f32, 32 rows x 128 columns per block; the epilogue
-//    keeps a (max, index) per row and column block -- the (M, V) logits are never written.
+//    keeps a (max, index) per row and column block -- the (M, V) logits are never written (the
+//    beam search's instantiation, rnnt_joint_rows, writes them instead: transducer_beam.hip).
 //    Every row is summed in one fixed order in every block (four interleaved fmaf chains over
 //    ascending k -- the f32 MFMA is an fmaf chain per output element -- added in a fixed order;
 //    no K split across blocks), so a row's logits depend neither on M nor on the row's place in
@@ -116,6 +117,10 @@ __device__ __forceinline__ void rnnt_reduce_row(const float* __restrict__ part_m
   }
 }
 
+// FULL: the epilogue keeps the logits of every live row (p.logits, pitch p.ldl) instead of a
+// (max, index) per column block -- the beam search's instantiation.  The GEMM body is the one
+// text for both, so a row's logits are the same bits in either.
+template <bool FULL>
 __global__ __launch_bounds__(256) void rnnt_joint_kernel(RnntJointArgs p) {
   if (p.n_active && *p.n_active == 0) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -172,6 +177,15 @@ __global__ __launch_bounds__(256) void rnnt_joint_kernel(RnntJointArgs p) {
   // C / D layout: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int col = n0 + (lane & 31);
   const float bias = col < p.V ? p.bias[col] : 0.0f;
+  if constexpr (FULL) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (m < p.M && col < p.V && p.row_enc[m] >= 0)
+        p.logits[(int64_t)m * p.ldl + col] = acc[r] + bias;
+    }
+    return;
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     float v = col < p.V ? acc[r] + bias : -INFINITY;
@@ -327,9 +341,24 @@ int rnnt_joint_argmax(const RnntJointArgs& a, hipStream_t s) {
            "rnnt_joint_argmax: join_dim must be a multiple of 32 in [32, 1024]");
   WN_CHECK(a.lde % 4 == 0 && a.ldp % 4 == 0, "rnnt_joint_argmax: row pitches must be multiples of 4");
   const size_t lds = (size_t)JT_ROWS * (a.J * 4 + 16);
-  WN_MAX_DYN_LDS(rnnt_joint_kernel, lds);
-  hipLaunchKernelGGL(rnnt_joint_kernel, dim3(cdiv(a.V, JT_COLS), cdiv(a.M, JT_ROWS)), dim3(256),
-                     lds, s, a);
+  WN_MAX_DYN_LDS(rnnt_joint_kernel<false>, lds);
+  hipLaunchKernelGGL(rnnt_joint_kernel<false>, dim3(cdiv(a.V, JT_COLS), cdiv(a.M, JT_ROWS)),
+                     dim3(256), lds, s, a);
+  WN_HIP(hipGetLastError());
+  return 0;
+}
+
+int rnnt_joint_rows(const RnntJointArgs& a, hipStream_t s) {
+  WN_CHECK(a.enc_proj && a.pred_proj && a.row_enc && a.row_pred && a.W && a.bias && a.logits,
+           "rnnt_joint_rows: null operand");
+  WN_CHECK(a.M >= 1 && a.V >= 1 && a.ldl >= a.V, "rnnt_joint_rows: empty, or a pitch below V");
+  WN_CHECK(a.J >= 32 && a.J % 32 == 0 && a.J <= 1024,
+           "rnnt_joint_rows: join_dim must be a multiple of 32 in [32, 1024]");
+  WN_CHECK(a.lde % 4 == 0 && a.ldp % 4 == 0, "rnnt_joint_rows: row pitches must be multiples of 4");
+  const size_t lds = (size_t)JT_ROWS * (a.J * 4 + 16);
+  WN_MAX_DYN_LDS(rnnt_joint_kernel<true>, lds);
+  hipLaunchKernelGGL(rnnt_joint_kernel<true>, dim3(cdiv(a.V, JT_COLS), cdiv(a.M, JT_ROWS)),
+                     dim3(256), lds, s, a);
   WN_HIP(hipGetLastError());
   return 0;
 }
