@@ -674,6 +674,26 @@ int wn_op_conv1(const float* feats, const float* mean, const float* istd, const 
                 const float* bias, float* out, const int32_t* t1_off, const int32_t* t1_len,
                 int32_t B, int32_t T, int32_t F, int32_t C, int32_t out_rows,
                 int32_t plane_image, void* stream);
+/* The Conformer front end alone -- GlobalCMVN + Conv2dSubsampling4 + the sqrt(d) scale, what
+ * wn_encode runs in front of layer 0 (at position 0), under the handle's precision and tuning
+ * set -- and copies of what it left, each optional (NULL), DEVICE arrays, complete on return:
+ *   c1 [sum t1_len][F1][d]  the conv1 activations conv2 read (t1_len = 2 l2 + 1 per utterance
+ *                           with l2 > 0; the plane-image form is unpacked to fp32 first)
+ *   c2 [M][F2][d]           conv2 + ReLU, M = sum l2
+ *   x  [M][d]               the packed rows layer 0 reads
+ * enc_lens_host [B] (or NULL) = l2.  *route_out = what ran, 0 if M == 0, else
+ *   1 << 16 | linear_x6 << 13 | projection << 12 | slices << 8 | tile << 4 | kind
+ *   kind        0 conv2 as the gathered-row v_mfma_f32 GEMM, 1 six-product with the fp32 gather,
+ *               2 six-product gathering from conv1's plane image
+ *   tile        (kinds 1, 2) 0 one launch of 128-row tiles, 1 one launch of 256-row tiles,
+ *               2 256-row tiles + the remainder as 128-row tiles, 3 256-row tiles + the
+ *               remainder as `slices` K slices
+ *   projection  1 K slices + ffn_reduce_ln (with layer 0's first LayerNorm), 0 linear();
+ *               linear_x6: that linear() went through the split pass + six-product GEMM
+ * Refuses Conv1dSubsampling2 handles, T < 7 and lengths outside [0, T]. */
+int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host,
+                  int32_t B, int32_t T, float* c1, float* c2, float* x,
+                  int32_t* enc_lens_host, int32_t* route_out, void* stream);
 /* CTC head tail: blank penalty, log-softmax, top-k (logp NULL: the top-k only). */
 int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_t k,
                    int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,

@@ -12,7 +12,11 @@ Further down: the kernels of the `attention` decode mode (csrc/attn_search.hip; 
 tests/test_kernel_refs.py, GPU tests in tests/test_gpu_attn_search.py) -- the self-attention step
 as ref_attention on the rows gathered through the paths, the beam state kernels restated in NumPy.
 
-No GPU and no oracle import in here.
+Behind conv1: the rest of the Conformer front end (conv2, the output projection) and the Whisper
+front end, for tests/test_gpu_frontend.py; their whole-chain references call the oracle's own
+functions (imported inside those functions only).
+
+No GPU in here.
 """
 import math
 
@@ -358,6 +362,159 @@ def conv1_refs(c):
     e = max([(p - r).abs().max().item() for p, r in zip(plain, ref) if r.numel()] + [0.0])
     s = max([r.abs().max().item() for r in ref if r.numel()] + [0.0])
     return ref, e, s
+
+
+# ---------------------------------------------------------------------------------------------
+# the rest of Conv2dSubsampling4: conv2 + ReLU, Linear(d * F2 -> d) * sqrt(d)
+
+
+def ref_conv2(c1_b, w, bias, fp32=False):
+    """c1_b (t1_len, F1, C): ONE utterance's conv1 activations, channels last; w (C, C, 3, 3), the
+    reference's weight.  relu(Conv2d(C, C, 3, stride 2)) (subsampling.py:191-192) -> (t2_len, F2,
+    C) fp64, t2_len = (t1_len - 3) // 2 + 1."""
+    dt = torch.float32 if fp32 else torch.float64
+    x = c1_b.to(dt).permute(2, 0, 1).unsqueeze(0)                      # (1, C, t1, F1)
+    y = F.relu(F.conv2d(x, w.to(dt), bias.to(dt), stride=2))[0]        # (C, t2, F2)
+    return y.permute(1, 2, 0).double()
+
+
+def ref_sub_out(c2_b, w_out, b_out, d, fp32=False):
+    """c2_b (t2_len, F2, C) -> sqrt(d) * Linear(C * F2 -> d) over the reference's column order
+    c * F2 + f (x.transpose(1, 2).view(b, t, c * f), subsampling.py:225-226; xscale,
+    embedding.py:144).  Returns (t2_len, d) fp64."""
+    dt = torch.float32 if fp32 else torch.float64
+    t2, F2, C = c2_b.shape
+    x = c2_b.to(dt).permute(0, 2, 1).reshape(t2, C * F2)
+    return (F.linear(x, w_out.to(dt), b_out.to(dt)) * math.sqrt(d)).double()
+
+
+def sub4_lens(lens):
+    """Output frames of Conv2dSubsampling4 for utterances of `lens` feature frames: the mask
+    [:, :, 2::2][:, :, 2::2] (subsampling.py:228) keeps the frames 6 + 4 k < L."""
+    return [(int(n) - 7) // 4 + 1 if int(n) > 6 else 0 for n in lens]
+
+
+def ref_frontend_chain(feats, lens, sd, d, fp32=False):
+    """GlobalCMVN + Conv2dSubsampling4 + xscale through the oracle's own functions, one utterance
+    at a time on its first 4 l2 + 3 frames (everything its l2 kept output frames read).  Returns
+    a list of (l2, d) fp64 tensors."""
+    from oracle import wenet_oracle as O
+    dt = torch.float32 if fp32 else torch.float64
+    pfx = 'encoder.embed.'
+    sdd = {k: v.to(dt) for k, v in sd.items()
+           if k.startswith(pfx + 'conv.') or k.startswith(pfx + 'out.')}
+    sdd[pfx + 'pos_enc.pe'] = torch.zeros(1, 1, d, dtype=dt)     # (the table is not used here)
+    mean, istd = sd.get('encoder.global_cmvn.mean'), sd.get('encoder.global_cmvn.istd')
+    outs = []
+    for b, l2 in enumerate(sub4_lens(lens)):
+        if l2 == 0:
+            outs.append(torch.zeros(0, d, dtype=torch.float64))
+            continue
+        n = 4 * l2 + 3
+        x = feats[b, :n].to(dt).unsqueeze(0)
+        if mean is not None:
+            x = O.global_cmvn(x, mean.to(dt), istd.to(dt))
+        y, _, m = O.conv2d_subsampling4(x, torch.ones(1, 1, n, dtype=torch.bool), sdd, pfx, d)
+        assert y.shape[1] == l2 and int(m.sum()) == l2
+        outs.append(y[0].double())
+    return outs
+
+
+def _err_scale(plain, ref):
+    e = max([(p - r).abs().max().item() for p, r in zip(plain, ref) if r.numel()] + [0.0])
+    s = max([r.abs().max().item() for r in ref if r.numel()] + [0.0])
+    return e, s
+
+
+def frontend_refs(feats, lens, sd, d, c1, c2, utts=None):
+    """The three comparisons of the front-end tests.  c1 / c2: the GPU's own conv1 / conv2
+    activations as lists per utterance ((2 l2 + 1, F1, d) and (l2, F2, d) fp32); utts: the
+    utterances to evaluate (None: all).  Returns {'c2': ..., 'x_proj': ..., 'x_chain': ...}, each
+    (list of fp64 references per evaluated utterance, e_plain, scale):
+      c2       ref_conv2 of the GPU's c1                   -- conv2 alone
+      x_proj   ref_sub_out of the GPU's c2                 -- the projection alone
+      x_chain  ref_frontend_chain of the features          -- everything from the features on
+    e_plain: the fp32 CPU evaluation of the same step on the same inputs against the fp64 one."""
+    pfx = 'encoder.embed.'
+    w2, b2 = sd[pfx + 'conv.2.weight'], sd[pfx + 'conv.2.bias']
+    wo, bo = sd[pfx + 'out.0.weight'], sd[pfx + 'out.0.bias']
+    l2 = sub4_lens(lens)
+    utts = [b for b in (range(len(l2)) if utts is None else utts) if l2[b] > 0]
+    out = {}
+    ref = [ref_conv2(c1[b], w2, b2) for b in utts]
+    plain = [ref_conv2(c1[b], w2, b2, fp32=True) for b in utts]
+    out['c2'] = (ref, ) + _err_scale(plain, ref)
+    ref = [ref_sub_out(c2[b], wo, bo, d) for b in utts]
+    plain = [ref_sub_out(c2[b], wo, bo, d, fp32=True) for b in utts]
+    out['x_proj'] = (ref, ) + _err_scale(plain, ref)
+    sub_f = torch.stack([feats[b] for b in utts]) if utts else feats[:0]
+    sub_l = [lens[b] for b in utts]
+    ref = ref_frontend_chain(sub_f, sub_l, sd, d)
+    plain = ref_frontend_chain(sub_f, sub_l, sd, d, fp32=True)
+    out['x_chain'] = (ref, ) + _err_scale(plain, ref)
+    return out, utts
+
+
+def frontend_model_parts(F_in, d, whisper=False, seed=0):
+    """(configs, state dict) of a one-block model with `F_in` feature bins and width `d`: a copy
+    of the synthetic configuration tiny_lite (whisper: whisper_tiny_like), d / 64 heads."""
+    from wenet_amd import synthetic as S
+    configs = S.make_configs('whisper_tiny_like' if whisper else 'tiny_lite')
+    configs['input_dim'] = F_in
+    ec = configs['encoder_conf']
+    ec['output_size'], ec['attention_heads'], ec['num_blocks'] = d, d // 64, 1
+    if configs.get('decoder_conf'):
+        configs['decoder_conf']['attention_heads'] = d // 64
+    return configs, S.make_state_dict(configs, seed)
+
+
+def make_frontend_feats(lens, F_in, seed=0, T=None, poison=True):
+    """(B, T, F_in) fbank-like features (mean 11, std 3) for utterances of `lens` frames, T =
+    max(lens) unless given.  poison: the frames at and beyond 4 l2 + 3 of every utterance -- what
+    none of its l2 kept output frames reads -- hold POISON; else the frames beyond the length are
+    zeros, as the reference's padding() leaves them."""
+    g = torch.Generator().manual_seed(seed)
+    T = max(lens) if T is None else T
+    feats = torch.randn(len(lens), T, F_in, generator=g) * 3.0 + 11.0
+    for b, (n, l2) in enumerate(zip(lens, sub4_lens(lens))):
+        if poison:
+            feats[b, (4 * l2 + 3 if l2 else 0):] = POISON
+        else:
+            feats[b, n:] = 0.0
+    return feats
+
+
+# ---------------------------------------------------------------------------------------------
+# Conv1dSubsampling2 + WhisperPositionalEncoding (the Whisper front end)
+
+
+def sub2_lens(lens, T):
+    """Output frames of Conv1dSubsampling2 on a (B, T, F) batch: the mask [:, :, (T + 1) % 2::2]
+    (subsampling.py:171) keeps t' with 2 t' + (T + 1) % 2 < L."""
+    par = (T + 1) % 2
+    return [(int(n) - par + 1) // 2 if int(n) > par else 0 for n in lens]
+
+
+def ref_whisper_frontend(feats, lens, sd, fp32=False):
+    """The oracle's conv1d_subsampling2 on the whole zero-padded batch (the reference reads the
+    padding frames: they stay zeros, processor.py:526-577), cut to the frames its mask keeps.
+    Returns a list of (l2, d) fp64 tensors."""
+    from oracle import wenet_oracle as O
+    dt = torch.float32 if fp32 else torch.float64
+    pfx = 'encoder.embed.'
+    sdd = {k: v.to(dt) for k, v in sd.items() if k.startswith(pfx)}
+    T = feats.shape[1]
+    mask = ~O.make_pad_mask(torch.as_tensor(lens), T).unsqueeze(1)
+    y, _, m = O.conv1d_subsampling2(feats.to(dt), mask, sdd, pfx)
+    keep = m.squeeze(1).sum(1).tolist()
+    assert keep == sub2_lens(lens, T), (keep, sub2_lens(lens, T))
+    return [y[b, :n].double() for b, n in enumerate(keep)]
+
+
+def whisper_frontend_refs(feats, lens, sd):
+    ref = ref_whisper_frontend(feats, lens, sd)
+    plain = ref_whisper_frontend(feats, lens, sd, fp32=True)
+    return (ref, ) + _err_scale(plain, ref)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -88,7 +88,8 @@ def tune(**kw):
 
 def record(name, err, e_plain, scale, bf16=False):
     """Prints the figures of a case, appends its ratio err / bound to the file
-    WN_KERNEL_OPS_RATIOS names (profiles/r21a_kernel_ops_error_ratios.txt is one such run), then
+    WN_KERNEL_OPS_RATIOS names (profiles/r21a_kernel_ops_error_ratios.txt is one such run,
+    r23a_frontend_error_ratios.txt one of tests/test_gpu_frontend.py), then
     asserts the cap on the yardstick and the bound."""
     b = KR.bound(e_plain, scale, bf16)
     ratio = err / b if b > 0 else (0.0 if err == 0 else float('inf'))

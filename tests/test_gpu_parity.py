@@ -186,7 +186,11 @@ def test_encoder_layers_vs_oracle(config, B, frames, chunk, left):
                 err = (enc[b, :nb] - layers[n][b, :nb]).abs().max().item() \
                     if nb else 0.0
                 scale = max(layers[n][b, :nb].abs().max().item(), 1.0) if nb else 1.0
-                assert err < 1e-3 * scale, (config, 'layer', n, 'utt', b, err)
+                # n == 0 is the front end's output against the fp32 oracle: a coarse check of
+                # the wiring only.  tests/test_gpu_frontend.py holds conv2, the projection and
+                # the whole chain to fp32 rounding of an fp64 reference, on every route
+                assert err < 1e-3 * scale, (config, 'layer', n, 'utt', b, err,
+                                            'front end: see test_gpu_frontend.py' if n == 0 else '')
     finally:
         L.wn_debug_set(model._h, b'n_layers', -1)
         L.wn_debug_set(model._h, b'skip_after_norm', 0)

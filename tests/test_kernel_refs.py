@@ -545,3 +545,103 @@ def test_self_step_regime_caps(regime, length):
     if regime[0] == 'tied':
         mean = case['vg'].double().view(case['n'], length, -1).mean(1)
         assert (ref - mean).abs().max().item() <= 1e-12 * scale
+
+
+# ---------------------------------------------------------------------------------------------
+# the front ends behind conv1 (tests/test_gpu_frontend.py)
+
+
+@pytest.mark.parametrize('F_in,d', [(23, 64), (81, 64), (80, 128)])
+def test_frontend_steps_compose_to_the_oracle_chain(F_in, d):
+    """ref_conv1 -> ref_conv2 -> ref_sub_out, the three plain steps, against the oracle's
+    global_cmvn + conv2d_subsampling4 on the same utterances."""
+    _, sd = KR.frontend_model_parts(F_in, d)
+    lens = [7, 6, 10, 11, 0, 75, 40]
+    feats = KR.make_frontend_feats(lens, F_in, seed=3)
+    l2 = KR.sub4_lens(lens)
+    pfx = 'encoder.embed.'
+    c1 = KR.ref_conv1(feats, sd['encoder.global_cmvn.mean'], sd['encoder.global_cmvn.istd'],
+                      sd[pfx + 'conv.0.weight'], sd[pfx + 'conv.0.bias'],
+                      [2 * n + 1 if n else 0 for n in l2])
+    want = KR.ref_frontend_chain(feats, lens, sd, d)
+    for b, n in enumerate(l2):
+        assert want[b].shape == (n, d)
+        if n == 0:
+            continue
+        c2 = KR.ref_conv2(c1[b], sd[pfx + 'conv.2.weight'], sd[pfx + 'conv.2.bias'])
+        assert c2.shape == (n, ((F_in - 1) // 2 - 1) // 2, d)
+        _close(KR.ref_sub_out(c2, sd[pfx + 'out.0.weight'], sd[pfx + 'out.0.bias'], d), want[b])
+
+
+@pytest.mark.parametrize('F_in,d', [(23, 64), (80, 64)])
+def test_frontend_chain_per_utterance_equals_the_padded_batch(F_in, d):
+    """The per-utterance evaluation on the first 4 l2 + 3 frames against conv2d_subsampling4 on
+    the whole batch, padded as the reference pads it (sorted by length, zeros behind), at the
+    frames its mask keeps: the kept frames read nothing at or beyond frame 4 l2 + 3."""
+    _, sd = KR.frontend_model_parts(F_in, d)
+    g = torch.Generator().manual_seed(5)
+    raw = [(torch.randn(n, F_in, generator=g) * 3.0 + 11.0).numpy()
+           for n in (7, 9, 10, 11, 12, 30, 61, 8)]
+    padded, lens, _ = O.padding(raw)
+    T = padded.shape[1]
+    sd64 = {k: v.double() for k, v in sd.items() if v.is_floating_point()}
+    mask = ~O.make_pad_mask(lens, T).unsqueeze(1)
+    x = O.global_cmvn(padded.double(), sd64['encoder.global_cmvn.mean'],
+                      sd64['encoder.global_cmvn.istd'])
+    want, _, m = O.conv2d_subsampling4(x, mask, sd64, 'encoder.embed.', d)
+    keep = m.squeeze(1).sum(1).tolist()
+    assert keep == KR.sub4_lens(lens.tolist())
+    got = KR.ref_frontend_chain(padded, lens.tolist(), sd, d)
+    # ... and the frames behind 4 l2 + 3 may hold anything
+    poisoned = padded.clone()
+    for b, n in enumerate(keep):
+        poisoned[b, 4 * n + 3:] = KR.POISON
+    got_p = KR.ref_frontend_chain(poisoned, lens.tolist(), sd, d)
+    for b, n in enumerate(keep):
+        _close(got[b], want[b, :n])
+        assert torch.equal(got[b], got_p[b])
+
+
+def test_sub4_lens_is_the_reference_mask():
+    lens = torch.arange(0, 40)
+    m = ~O.make_pad_mask(lens, 40).unsqueeze(1)
+    assert m[:, :, 2::2][:, :, 2::2].squeeze(1).sum(1).tolist() == KR.sub4_lens(lens.tolist())
+
+
+@pytest.mark.parametrize('F_in,d', [(23, 64), (80, 256)])
+def test_frontend_yardstick_is_inside_the_cap(F_in, d):
+    """frontend_refs on CPU stand-ins for the GPU's c1 / c2 (the fp32 evaluation of the previous
+    step): e_plain of all three comparisons inside the cap, and far inside (< 1e-5 of the
+    scale: what makes these tests three orders tighter than the whole-encoder ones)."""
+    _, sd = KR.frontend_model_parts(F_in, d)
+    lens = [7, 6, 10, 11, 0, 75, 120]
+    feats = KR.make_frontend_feats(lens, F_in, seed=4)
+    l2 = KR.sub4_lens(lens)
+    pfx = 'encoder.embed.'
+    c1 = KR.ref_conv1(feats, sd['encoder.global_cmvn.mean'], sd['encoder.global_cmvn.istd'],
+                      sd[pfx + 'conv.0.weight'], sd[pfx + 'conv.0.bias'],
+                      [2 * n + 1 if n else 0 for n in l2], fp32=True)
+    c1 = [t.float() for t in c1]
+    c2 = [KR.ref_conv2(t, sd[pfx + 'conv.2.weight'], sd[pfx + 'conv.2.bias'], fp32=True).float()
+          if t.numel() else torch.zeros(0) for t in c1]
+    refs, utts = KR.frontend_refs(feats, lens, sd, d, c1, c2)
+    assert utts == [0, 2, 3, 5, 6]
+    for name in ('c2', 'x_proj', 'x_chain'):
+        ref, e, s = refs[name]
+        assert [r.shape[0] for r in ref] == [l2[b] for b in utts]
+        assert s > 0 and KR.cap_ok(e, s) and 0 < e < 1e-5 * s, (name, e, s)
+
+
+@pytest.mark.parametrize('F_in,T', [(80, 12), (128, 13)])
+def test_whisper_frontend_reference(F_in, T):
+    """sub2_lens against the reference's mask (asserted inside ref_whisper_frontend), the shapes
+    and the cap on the yardstick."""
+    _, sd = KR.frontend_model_parts(F_in, 384, whisper=True)
+    lens = [T, 0, 1, 2, 3, T - 1, 7]
+    g = torch.Generator().manual_seed(6)
+    feats = torch.randn(len(lens), T, F_in, generator=g)
+    for b, n in enumerate(lens):
+        feats[b, n:] = 0.0
+    ref, e, s = KR.whisper_frontend_refs(feats, lens, sd)
+    assert [r.shape[0] for r in ref] == KR.sub2_lens(lens, T)
+    assert s > 0 and KR.cap_ok(e, s)

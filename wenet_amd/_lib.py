@@ -71,6 +71,7 @@ EXPORTS = [
     'wn_ctc_logprobs', 'wn_set_ctc_probs', 'wn_ctc_greedy_search', 'wn_ctc_force_align',
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
     'wn_op_layernorm', 'wn_op_log_add', 'wn_op_attention', 'wn_op_dwconv', 'wn_op_conv1',
+    'wn_op_conv2d4',
     'wn_op_ctc_rows', 'wn_debug_set', 'wn_profile_enable',
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
     'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
@@ -182,6 +183,7 @@ def lib():
                                i32, i32, i32, i32, f32, vp]
     L.wn_op_conv1.argtypes = [vp, vp, vp, vp, vp, vp, pi32, pi32, i32, i32, i32, i32, i32, i32,
                               vp]
+    L.wn_op_conv2d4.argtypes = [vp, vp, pi32, i32, i32, vp, vp, vp, pi32, pi32, vp]
     L.wn_op_ctc_rows.argtypes = [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp]
     L.wn_debug_set.argtypes = [vp, c_char_p, i32]
     L.wn_tune_set.argtypes = [c_char_p, i32]

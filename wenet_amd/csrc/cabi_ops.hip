@@ -512,6 +512,53 @@ int wn_op_conv1(const float* feats, const float* mean, const float* istd, const 
   return cmvn_conv1_relu(a, s);
 }
 
+int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
+                  int32_t T, float* c1, float* c2, float* x, int32_t* enc_lens_host,
+                  int32_t* route_out, void* stream) {
+  WN_CHECK(m && feats_dev && feat_lens_host && route_out, "wn_op_conv2d4: null argument");
+  WN_ENTER(m);
+  // (the encode gate is one-shot, as in wn_encode)
+  struct GateDrop { wn_model* m; ~GateDrop() { m->enc_gate = nullptr; } } gate_drop{m};
+  m->pb_valid = false;
+  PrecisionScope prec_scope(m);
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0,
+           "wn_op_conv2d4: needs a Conformer encoder");
+  WN_CHECK(B > 0, "wn_encode: empty batch");
+  WN_CHECK(B < 65536, "wn_op_conv2d4: more than 65535 utterances");
+  WN_CHECK(T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  WN_TRY(subsample_conv2d4(m, feats_dev, feat_lens_host, B, T, enc_lens_host, 0, s));
+  WN_TRY(encode_gate_wait(m, s));
+  *route_out = m->front_route;
+  const int M = m->rows, d = m->cfg.d_model, F1 = m->F1(), F2 = m->F2();
+  if (M > 0) {
+    int M1 = 0, max_t1 = 0;
+    for (int b = 0; b < B; ++b) {
+      const int l1 = m->len[b] > 0 ? 2 * m->len[b] + 1 : 0;
+      M1 += l1;
+      max_t1 = std::max(max_t1, l1);
+    }
+    if (c1 && (m->front_route & 15) == CONV2_X6_PLANES) {
+      hipLaunchKernelGGL(conv1_image_unpack_kernel, dim3(cdiv(max_t1 * F1 * (d / 8), 256), B),
+                         dim3(256), 0, s, m->c1.as<char>(), cdiv(M1 * F1, 32),
+                         m->d_off1.as<int>(), m->d_len1.as<int>(), F1, d, c1);
+      WN_HIP(hipGetLastError());
+    } else if (c1) {
+      WN_HIP(hipMemcpyAsync(c1, m->c1.p, (size_t)M1 * F1 * d * sizeof(float),
+                            hipMemcpyDeviceToDevice, s));
+    }
+    if (c2)
+      WN_HIP(hipMemcpyAsync(c2, m->c2.p, (size_t)M * F2 * d * sizeof(float),
+                            hipMemcpyDeviceToDevice, s));
+    if (x)
+      WN_HIP(hipMemcpyAsync(x, m->x.p, (size_t)M * d * sizeof(float), hipMemcpyDeviceToDevice,
+                            s));
+  }
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
 int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_t k,
                    int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,
                    float* logp, int32_t ld_out, void* stream) {

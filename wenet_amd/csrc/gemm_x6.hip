@@ -569,6 +569,53 @@ int gemm_x6_bm(int M, int N, int ksplit) {
   return half_rounds_128 < 2 * cdiv(t256, 256) ? 128 : 256;
 }
 
+// The tile form gemm_x6() runs the gathered-A GEMM (the subsampling conv2) in, under the calling
+// thread's tune(): the launch code switches on it, and wn_op_conv2d4 reports it to the tests.
+X6ConvForm gemm_x6_conv_form(const X6Args& a) {
+  X6ConvForm f;
+  const bool af32 = a.A != nullptr;
+  // One 256-row tile per CU and round: when the last round would be less than half
+  // full, its rows go to a second launch of 128-row tiles (half as long) instead --
+  // 589 tiles at config 2 = 2.3 rounds become 2 rounds + 154 half tiles.
+  // (rounds cut for fewer CUs, with the prefix beam search of the batch in front confined to
+  // its own few CUs by a CU-masked stream, were measured in round 4: 39-44 k against 44 k
+  // audio-s/s on the same box, profiles/r06b_cu_mask.txt -- removed)
+  const int ncu = 256;
+  const int t256 = cdiv(a.M, 256), full = t256 / ncu * ncu;
+  // tune().x6_conv_bm = 128 (round 5, the default): the WHOLE conv2 as ONE launch of 128-row
+  // tiles on four waves, two blocks per CU.  With two decodes in flight conv2 runs beside the
+  // previous decode's prefix beam search, which holds 32 CUs for ~0.9 ms: the 256-row form's
+  // second launch below -- the last round as K slices, 231 blocks meant for 256 free CUs --
+  // then spills into a second round and doubles, its full rounds lose 12.5 %; the finer tiles
+  // of one launch lose 51 us where the three launches lose ~137 (r12l: +2.3 % per step).  Alone
+  // the one-launch form is 3 % slower (844 vs 822 us: -0.4 % on a plain decode()); it is the
+  // default for every caller so that DecodePipeline and decode() return the same bits (the
+  // K-slice tail sums in another order).  0 = the 256-row form (A/B).
+  if (a.bm == 0 && tune().x6_conv_bm == 128 && !af32) { f.tile = X6CONV_128; return f; }
+  if (a.bm == 0 && a.N <= XBN && full > 0 && t256 - full > 0 && t256 - full <= ncu / 2) {
+    f.full = full;
+    // round 3: the remaining t256 - full tiles as K SLICES of 256-row tiles when tiles x
+    // slices still fit one round -- 77 tiles x 3 slices at config 2: a third of a round
+    // (+ a 60-MB reduction) instead of 154 half-height tiles that each take a whole tile's
+    // time on a wave per SIMD (207 us, r05e)
+    const int rem = t256 - full, nkb = a.K / 16;
+    int S = 0;
+    for (int t = std::min(4, ncu / rem); t >= 2; --t)
+      if (nkb % t == 0) { S = t; break; }
+    const int rows = a.M - full * 256;
+    if (!af32 && S >= 2 && a.part &&
+        a.part_bytes >= (size_t)S * rows * a.N * sizeof(float) && a.N % 4 == 0) {
+      f.tile = X6CONV_256_KTAIL; f.slices = S;
+      return f;
+    }
+    f.tile = X6CONV_256_REM128;
+    return f;
+  }
+  const int bm = a.bm ? a.bm : gemm_x6_bm(a.M, a.N, a.ksplit);
+  f.tile = bm == 256 ? X6CONV_256 : X6CONV_128;
+  return f;
+}
+
 int gemm_x6(const X6Args& args, hipStream_t s) {
   X6Args a = args;
   if (tune().x6_probe) a.probe = tune().x6_probe;      // ablation knob (tools/bench_x6.py --probe)
@@ -590,46 +637,29 @@ int gemm_x6(const X6Args& args, hipStream_t s) {
     WN_CHECK(a.epi == 0 && a.act == ACT_RELU && a.conv_kbc > 0 && (af32 || a.a_tiles > 0) &&
                  (a.K / 16) % a.conv_kbc == 0 && a.K / 16 / a.conv_kbc <= 9,
              "gemm_x6: gathered A operand");
-    // One 256-row tile per CU and round: when the last round would be less than half
-    // full, its rows go to a second launch of 128-row tiles (half as long) instead --
-    // 589 tiles at config 2 = 2.3 rounds become 2 rounds + 154 half tiles.
-    // (rounds cut for fewer CUs, with the prefix beam search of the batch in front confined to
-    // its own few CUs by a CU-masked stream, were measured in round 4: 39-44 k against 44 k
-    // audio-s/s on the same box, profiles/r06b_cu_mask.txt -- removed)
-    const int ncu = 256;
-    const int t256 = cdiv(a.M, 256), full = t256 / ncu * ncu;
     auto run = [&](const X6Args& x, int rows) {
       if (af32) return rows == 256 ? launch_x6<256, 0, ACT_RELU, true, true>(x, s)
                                    : launch_x6<128, 0, ACT_RELU, true, true>(x, s);
       return rows == 256 ? launch_x6<256, 0, ACT_RELU, true>(x, s)
                          : launch_x6<128, 0, ACT_RELU, true, false, 4>(x, s);
     };
-    // tune().x6_conv_bm = 128 (round 5, the default): the WHOLE conv2 as ONE launch of 128-row
-    // tiles on four waves, two blocks per CU.  With two decodes in flight conv2 runs beside the
-    // previous decode's prefix beam search, which holds 32 CUs for ~0.9 ms: the 256-row form's
-    // second launch below -- the last round as K slices, 231 blocks meant for 256 free CUs --
-    // then spills into a second round and doubles, its full rounds lose 12.5 %; the finer tiles
-    // of one launch lose 51 us where the three launches lose ~137 (r12l: +2.3 % per step).  Alone
-    // the one-launch form is 3 % slower (844 vs 822 us: -0.4 % on a plain decode()); it is the
-    // default for every caller so that DecodePipeline and decode() return the same bits (the
-    // K-slice tail sums in another order).  0 = the 256-row form (A/B).
-    if (a.bm == 0 && tune().x6_conv_bm == 128 && !af32) return run(a, 128);
-    if (a.bm == 0 && a.N <= XBN && full > 0 && t256 - full > 0 && t256 - full <= ncu / 2) {
-      X6Args main = a, rest = a;
-      main.M = full * 256;
-      rest.row0 = full * 256;
-      if (run(main, 256) != 0) return -1;
-      // round 3: the remaining t256 - full tiles as K SLICES of 256-row tiles when tiles x
-      // slices still fit one round -- 77 tiles x 3 slices at config 2: a third of a round
-      // (+ a 60-MB reduction) instead of 154 half-height tiles that each take a whole tile's
-      // time on a wave per SIMD (207 us, r05e)
-      const int rem = t256 - full, nkb = a.K / 16;
-      int S = 0;
-      for (int t = std::min(4, ncu / rem); t >= 2; --t)
-        if (nkb % t == 0) { S = t; break; }
-      const int rows = a.M - full * 256;
-      if (!af32 && S >= 2 && a.part &&
-          a.part_bytes >= (size_t)S * rows * a.N * sizeof(float) && a.N % 4 == 0) {
+    const X6ConvForm f = gemm_x6_conv_form(a);
+    const int full = f.full;
+    switch (f.tile) {
+      case X6CONV_128: return run(a, 128);
+      case X6CONV_256: return run(a, 256);
+      case X6CONV_256_REM128: {
+        X6Args main = a, rest = a;
+        main.M = full * 256;
+        rest.row0 = full * 256;
+        if (run(main, 256) != 0) return -1;
+        return run(rest, 128);
+      }
+      case X6CONV_256_KTAIL: {
+        X6Args main = a;
+        main.M = full * 256;
+        if (run(main, 256) != 0) return -1;
+        const int S = f.slices, rows = a.M - full * 256;
         X6Args r = a;
         r.a_pix = a.a_pix + (size_t)full * 256;
         r.M = rows; r.row0 = 0; r.epi = 1; r.ksplit = S; r.C = a.part; r.bm = 256;
@@ -641,9 +671,10 @@ int gemm_x6(const X6Args& args, hipStream_t s) {
         WN_HIP(hipGetLastError());
         return 0;
       }
-      return run(rest, 128);
+      default: break;
     }
-    return run(a, bm);
+    set_error("gemm_x6: unknown conv2 tile form");
+    return -1;
   }
 #define WN_X6(BM, AF)                                          \
   switch (a.epi) {                                             \

@@ -202,6 +202,21 @@ size_t x6_bytes(int R, int K);
 int x6_split(const float* src, int R, int K, int ld, void* dst, hipStream_t s);
 int gemm_x6_bm(int M, int N, int ksplit);
 int gemm_x6(const X6Args& a, hipStream_t s);
+// The tile form gemm_x6() runs a gathered-A GEMM (a.a_pix: the subsampling conv2) in under the
+// calling thread's tune(): its launch code switches on this, wn_op_conv2d4 reports it.
+enum X6ConvTile {
+  X6CONV_128 = 0,          // one launch of 128-row tiles
+  X6CONV_256 = 1,          // one launch of 256-row tiles
+  X6CONV_256_REM128 = 2,   // `full` 256-row tiles, the rows behind them as 128-row tiles
+  X6CONV_256_KTAIL = 3     // `full` 256-row tiles, the rows behind them as `slices` K slices of
+                           // 256-row tiles into a.part + conv_tail_reduce_kernel
+};
+struct X6ConvForm {
+  int tile = X6CONV_128;
+  int full = 0;            // 256-row tiles of the first launch (the two-launch forms)
+  int slices = 0;          // K slices of the tail (X6CONV_256_KTAIL)
+};
+X6ConvForm gemm_x6_conv_form(const X6Args& a);
 // Fused six-product feed-forward module (ffn_x6f.hip): hidden tensor in registers, d_model 256.
 struct FfnX6Args {
   const float* X = nullptr;    // X = LayerNorm(x): [M][ldx] fp32 (split into planes in registers)

@@ -469,6 +469,27 @@ int encode_gate_wait(wn_model* m, hipStream_t s) {
   return 0;
 }
 
+// How subsample_conv2d4 runs conv2 for M output frames / M1 conv1 frames under the calling
+// thread's precision and tune() (the function switches on this, wn_op_conv2d4 reports it);
+// *w6: the plane image of conv2's weight for the two six-product kinds.
+int conv2_kind(const wn_model* m, int M, int M1, const void** w6) {
+  const ModelData& W = *m->data;
+  const int d = m->cfg.d_model, F1 = m->F1(), F2 = m->F2();
+  // fp32 on the bf16 matrix cores (gemm_x6.hip): conv1 writes the plane image of its
+  // output, conv2 gathers its rows from it
+  *w6 = nullptr;
+  if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && d % 32 == 0 &&
+      F1 <= 64 &&
+      (M * F2 >= 4096 || tune().gemm_x6 == 2)) {
+    auto it = W.x6_at.find(W.conv2.w);
+    if (it != W.x6_at.end()) *w6 = it->second;
+  }
+  if (*w6 && (tune().x6_af32 != 0 || tune().x6_conv_af32 != 0) &&
+      (int64_t)M1 * F1 * d * 4 < ((int64_t)1 << 31))
+    return CONV2_X6_AF32;
+  return *w6 ? CONV2_X6_PLANES : CONV2_GEMM_F32;
+}
+
 int subsample_conv2d4(wn_model* m, const float* feats_dev,
                       const int32_t* feat_lens_host, int B, int T,
                       int32_t* enc_lens_host, int pos0, hipStream_t s) {
@@ -477,6 +498,7 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
   const int d = c.d_model, F1 = m->F1(), F2 = m->F2();
   const int Tp = ((T - 1) / 2 - 1) / 2;
   m->ln0_done = false;
+  m->front_route = 0;
   WN_CHECK(pos0 + Tp <= c.max_pos, "utterance longer than the positional table");
   std::vector<int> off2(B), len2(B), off1(B), len1(B);
   int M = 0, M1 = 0, max_t1 = 0;
@@ -510,17 +532,9 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
     WN_TRY(m->hbuf.ensure((size_t)M * c.ffn_dim * sizeof(float)));
     WN_TRY(m->qkv.ensure((size_t)M * 3 * d * sizeof(float)));
     WN_TRY(m->d_a_row_off.ensure((size_t)M * F2 * sizeof(int64_t)));
-    // fp32 on the bf16 matrix cores (gemm_x6.hip): conv1 writes the plane image of its
-    // output, conv2 gathers its rows from it
     const void* w6 = nullptr;
-    if (t_gemm_prec == PREC_F32 && tune().gemm_x6 != 0 && d % 32 == 0 &&
-        F1 <= 64 &&
-        (M * F2 >= 4096 || tune().gemm_x6 == 2)) {
-      auto it = W.x6_at.find(W.conv2.w);
-      if (it != W.x6_at.end()) w6 = it->second;
-    }
-    if (w6 && (tune().x6_af32 != 0 || tune().x6_conv_af32 != 0) &&
-        (int64_t)M1 * F1 * d * 4 < ((int64_t)1 << 31)) {
+    const int kind = conv2_kind(m, M, M1, &w6);
+    if (kind == CONV2_X6_AF32) {
       // conv1 as always (fp32, channels last); conv2 gathers its A rows from it, 64 B per
       // pixel and k block, and splits them in registers
       WN_TRY(m->c1.ensure((size_t)M1 * F1 * d * sizeof(float)));
@@ -542,12 +556,14 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       g.a_pix = pix; g.conv_kbc = d / 16;
       for (int ky = 0; ky < 3; ++ky)
         for (int kx = 0; kx < 3; ++kx) g.tap_delta[ky * 3 + kx] = ky * F1 + kx;
+      const X6ConvForm form = gemm_x6_conv_form(g);
       WN_TRY(gemm_x6(g, s));
       WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                     s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
+      m->front_route = front_route_code(kind, form, false, t_linear_took_x6);
       return 0;
     }
-    if (w6) {
+    if (kind == CONV2_X6_PLANES) {
       const int tiles = cdiv(M1 * F1, 32);
       WN_TRY(m->c1.ensure(x6_bytes(M1 * F1, d)));
       Conv1Args c1;
@@ -586,12 +602,14 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
         g.tap_delta[ky * 3 + 1] = ky * F1 + ne;       // f1 = 2 f2 + 1 (odd, position ne + f2)
         g.tap_delta[ky * 3 + 2] = ky * F1 + 1;        // f1 = 2 f2 + 2 (even, position f2 + 1)
       }
+      const X6ConvForm form = gemm_x6_conv_form(g);
       WN_TRY(gemm_x6(g, s));
       const int r = sub_out_linear(m, M, F2, s);
       if (r < 0) return r;
       if (r == 0)
         WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                       s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
+      m->front_route = front_route_code(kind, form, r != 0, r == 0 && t_linear_took_x6);
       return 0;
     }
     // GlobalCMVN + conv1 + ReLU                        encoder.py:155, subsampling.py:188
@@ -616,6 +634,7 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
     // Linear(d*F2 -> d) * sqrt(d)                      subsampling.py:225-226, embedding.py:144
     WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,
                   s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
+    m->front_route = front_route_code(kind, X6ConvForm(), false, t_linear_took_x6);
   }
   return 0;
 }

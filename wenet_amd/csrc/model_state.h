@@ -277,6 +277,7 @@ struct wn_model {
   int ctc_rows = 0, ctc_k = 0;
   bool ctc_valid = false;
   bool ln0_done = false;   // t1 already holds layer 0's norm_ff_macaron(x) (sub_out_linear)
+  int front_route = 0;     // front_route_code() of the last subsample_conv2d4 (0: no rows)
   DevBuf logits, topk_val, topk_idx;
   // searches
   DevBuf pb_dbg;
@@ -470,6 +471,19 @@ int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
 int subsample_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, int32_t* enc_lens_host, int pos0, hipStream_t s);
 int encode_gate_wait(wn_model* m, hipStream_t s);
+// How subsample_conv2d4 ran (wn_model::front_route, wn_op_conv2d4's route_out).
+enum Conv2Kind {
+  CONV2_GEMM_F32 = 0,    // conv1 fp32, conv2 as the gathered-row v_mfma_f32 GEMM (gemm_f32)
+  CONV2_X6_AF32 = 1,     // conv1 fp32, conv2 six-product with the fp32 gather
+  CONV2_X6_PLANES = 2    // conv1 writes its plane image, conv2 six-product gathers from it
+};
+int conv2_kind(const wn_model* m, int M, int M1, const void** w6);
+// bit 16: set (rows ran) | bit 13: linear() took the six-product kernel | bit 12: the projection
+// ran as sub_out_linear | bits 8-11: K slices of conv2's tail | bits 4-7: X6ConvTile |
+// bits 0-3: Conv2Kind
+inline int front_route_code(int kind, const X6ConvForm& f, bool sub_out, bool linear_x6) {
+  return kind | f.tile << 4 | f.slices << 8 | (int)sub_out << 12 | (int)linear_x6 << 13 | 1 << 16;
+}
 // (conformer.hip: the Conformer layers and the feed-forward routing)
 int ffn_module(wn_model* m, const Norm& nrm, const Linear& w1, const Linear& w2, int act,
                float alpha, bool ln_done, bool h16, hipStream_t s);
