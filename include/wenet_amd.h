@@ -870,6 +870,80 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
  * state).  Either pointer may be NULL. */
 int wn_transducer_beam_stats(wn_model* m, int32_t* steps_out, int64_t* advance_rows_out);
 
+/* Teacher-forced transducer score of host n-bests over the handle's CURRENT batch: per
+ * hypothesis log P(y | x) = -RNN-T loss, what Transducer._cal_transducer_score
+ * (wenet/models/transducer/transducer.py:161-186) takes from torchaudio's rnnt_loss for one
+ * utterance at a time: Graves' forward algorithm over the log-softmax of the joint logits,
+ *   alpha(t, u) = log_add(alpha(t-1, u) + lp_blank(t-1, u), alpha(t, u-1) + lp_label(t, u-1)),
+ *   score = alpha(T'-1, U) + lp_blank(T'-1, U).
+ * The (beam, T', U + 1, V) logits are never built: the hypotheses of an utterance go into a
+ * prefix trie, the predictor runs once per trie node, the joint GEMM has one row per (frame,
+ * node) and keeps only a row's log-sum-exp and its log-probs at the blank and at the tokens of
+ * the node's children; the lattices run in fp64.  Always fp32 / fp64, whatever the handle's
+ * precision; a hypothesis' score is the same bits alone or in any batch.  The hypothesis arrays
+ * are laid out as for wn_rescore:
+ *   beam              1..16
+ *   n_hyps_host       (B), each in [1, beam]
+ *   hyp_lens_host     (B, beam), each in [0, max_len]; hyp_tokens_host (B, beam, max_len),
+ *                     tokens in [0, vocab), without the leading blank; max_len <= 4095.  As in
+ *                     wn_rescore, the entries of hypotheses k >= n_hyps[b] are never read
+ *   td_scores_host    (B, beam) fp64; -inf beyond n_hyps.  An utterance of ZERO frames scores
+ *                     -inf for every hypothesis (no path ends in a blank of a frame).
+ * Returns -1 with a wn_last_error text for a handle without transducer weights, a beam outside
+ * 1..16, a token outside the vocabulary, a length outside [0, max_len], n_hyps outside
+ * [1, beam]. */
+int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
+                        const int32_t* hyp_lens_host, const int32_t* hyp_tokens_host,
+                        int32_t max_len, double* td_scores_host, void* stream);
+
+/* Of the handle's last wn_transducer_score: the joint GEMM rows it computed (frames x trie
+ * nodes, summed over the utterances), the rows without prefix sharing (frames x (len + 1),
+ * summed over the hypotheses) and the trie nodes of the batch.  Any pointer may be NULL. */
+int wn_transducer_score_stats(wn_model* m, int64_t* rows_out, int64_t* rows_unshared_out,
+                              int32_t* nodes_out);
+
+/* Measurement (tools/bench_transducer.py --rescore): of the handle's last wn_transducer_score
+ * made under wn_profile_enable(m, 1), device time in milliseconds between events on the call's
+ * stream: ms_out[0] joint.enc_ffn of the encoder output, [1] the predictor over the trie with
+ * joint.pred_ffn, [2] the joint log-prob gather GEMM, [3] the lattices.  Without profiling the
+ * call records no events and the four values are 0. */
+int wn_transducer_score_times(wn_model* m, float* ms_out);
+
+/* Test hook, handle-less and HOST ONLY (no device is touched): the prefix trie of one
+ * utterance's n_hyps (1..16) hypotheses (hyp_lens_host (n_hyps), hyp_tokens_host (n_hyps,
+ * max_len)).  Node 0 is the empty prefix (parent -1, token `blank`, depth 0); nodes come in
+ * level order, within a level in order of first appearance over the hypotheses in their given
+ * order.  parent_out / token_out / depth_out: room for 1 + n_hyps * max_len entries,
+ * *n_nodes_out are filled.  path_out (n_hyps, max_len + 1): the node of every prefix of a
+ * hypothesis, len + 1 entries, then -1.  col_off_out (nodes + 1) / cols_out (2 nodes - 1): per
+ * node the joint columns it is read at, `blank` first, then its children's tokens in node
+ * order. */
+int wn_op_rnnt_trie(int32_t n_hyps, const int32_t* hyp_lens_host, const int32_t* hyp_tokens_host,
+                    int32_t max_len, int32_t blank, int32_t* n_nodes_out, int32_t* parent_out,
+                    int32_t* token_out, int32_t* depth_out, int32_t* path_out,
+                    int32_t* col_off_out, int32_t* cols_out);
+
+/* Test hook, handle-less: the joint network with a gathering log-softmax epilogue.  The first
+ * eleven arguments are those of wn_op_joint_argmax.  Row m lists the columns
+ * cols_host[col_off_host[m] .. col_off_host[m + 1]) (at most 17, each in [0, V); col_off_host
+ * has M + 1 entries from 0); logp_host gets, one float per list entry,
+ * logit[col] - logsumexp(row).  Entries of rows with row_enc_host[m] < 0 are not written by the
+ * kernel and come back as NaN. */
+int wn_op_joint_logp_gather(const float* enc_proj_dev, int32_t enc_rows,
+                            const float* pred_proj_dev, int32_t pred_rows,
+                            const int32_t* row_enc_host, const int32_t* row_pred_host,
+                            const float* w_dev, const float* bias_dev, int32_t M, int32_t J,
+                            int32_t V, const int32_t* col_off_host, const int32_t* cols_host,
+                            float* logp_host, void* stream);
+
+/* Test hook, handle-less: N RNN-T lattices by the forward algorithm in fp64.  Lattice n has
+ * T_host[n] frames and U_host[n] labels (U <= 4095); lp_blank_host holds its T x (U + 1) blank
+ * log-probs (t major), lp_label_host its T x U label log-probs, the lattices back to back.
+ * scores_host (N): log P; -inf for T == 0.  -inf entries never give NaN. */
+int wn_op_rnnt_lattice(int32_t N, const int32_t* T_host, const int32_t* U_host,
+                       const float* lp_blank_host, const float* lp_label_host,
+                       double* scores_host, void* stream);
+
 /* Test hook, handle-less: one predictor step (RNNPredictor.forward_step, predictor.py:185-206,
  * without the embedding lookup).  x_dev (B, E): the embedding rows; w_host: 4 device pointers
  * per layer (weight_ih (4H, E or H), weight_hh (4H, H), bias_ih, bias_hh; gate order i, f, g, o);

@@ -27,6 +27,17 @@ fusion + top-k, the beam step, the state gather) and the rows per step that ran 
 (`advance`) against the B x beam rows rnnt_linear_kernel walks.  Beside it, in the same process:
 the greedy search at its shipped lookahead and decode(['ctc_prefix_beam_search'], beam 10).
 
+    python tools/bench_transducer.py --rescore           # transducer + attention rescoring
+
+--rescore times the parts of Transducer.transducer_attention_rescoring on the same model, batch and
+fixed encoder output and writes profiles/transducer_rescore.json: beams 5 and 10, search weights
+(0.3, 0.7), rescoring weights (ctc 0.3, attn 0.4, transducer 0.3, reverse 0.3), the beams
+alternating, median of --repeats.  Per beam: the search, wn_transducer_score (and, from a call of
+their own under wn_profile_enable, by events on its stream: joint.enc_ffn, the predictor over the
+trie, the gather GEMM and the lattices), the attention scores (wn_rescore); the GEMM rows computed
+against the rows without prefix sharing; `transducer_attention_rescoring()` as a whole in seconds
+of audio per second beside `beam_search()`.
+
 The per-kernel split (enc_proj / predictor / joint / advance) comes from a kernel trace in a run
 of its own, because the handle's launch brackets (wn_profile_enable) time the GEMM launchers
 only and a traced run is not a timed one:
@@ -61,10 +72,13 @@ def main(argv=None):
     p.add_argument('--searches-only', type=int, default=0,
                    help='profiler runs: N searches per lookahead, no JSON')
     p.add_argument('--beam', action='store_true', help='time the prefix beam search')
+    p.add_argument('--rescore', action='store_true',
+                   help='time transducer + attention rescoring')
     p.add_argument('--out', default=None)
     args = p.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'transducer_beam.json' if args.beam
+        args.out = os.path.join(ROOT, 'profiles', 'transducer_rescore.json' if args.rescore
+                                else 'transducer_beam.json' if args.beam
                                 else 'transducer_greedy.json')
 
     import torch
@@ -99,6 +113,8 @@ def main(argv=None):
     ref_tokens = basic_greedy_search(model, enc, enc_lens, args.n_steps)
     if args.beam:
         return bench_beam(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked)
+    if args.rescore:
+        return bench_rescore(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked)
 
     def one_search(F):
         model.tune('rnnt_lookahead', F)
@@ -242,6 +258,109 @@ def bench_beam(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked
     print(json.dumps(out['greedy_search_on_the_same_encoder_output']),
           json.dumps(out['beam_search_beam10_with_encoder']),
           json.dumps(out['ctc_prefix_beam_search_beam10_with_encoder']))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+    print('wrote', args.out)
+    return 0
+
+
+RESCORE_BEAMS = (5, 10)
+RESCORE_SEARCH = (0.3, 0.7)                  # (ctc, transducer) of the search
+RESCORE_WEIGHTS = (0.3, 0.4, 0.3, 0.3)       # (ctc, attn, transducer, reverse) of the rescoring
+
+
+def bench_rescore(args, model, configs, feats, lens, enc, enc_lens, audio_s, picked):
+    import ctypes
+    import torch
+    from wenet_amd import _lib
+    from wenet_amd import transducer as T
+    sync = torch.cuda.synchronize
+    B = int(feats.shape[0])
+    cw, aw, tw, rw = RESCORE_WEIGHTS
+
+    def clock(fn):
+        sync()
+        t0 = time.perf_counter()
+        out = fn()
+        sync()
+        return time.perf_counter() - t0, out
+
+    def one(beam):
+        t_search, nbest = clock(lambda: T.prefix_beam_search(model, enc, enc_lens, beam,
+                                                             *RESCORE_SEARCH))
+        hyps = [[t for t, _ in u] for u in nbest]
+        t_score, td = clock(lambda: T._score_current(model, hyps))
+        rows_stat = model.last_rnnt_score_rows
+        # the stages, in a call of their own under the handle's launch brackets (event marks
+        # inside wn_transducer_score); the timed call above records none
+        _lib.check(model._L.wn_profile_enable(model._h, 1), 'wn_profile_enable')
+        try:
+            td_marked = T._score_current(model, hyps)
+            ms = (ctypes.c_float * 4)()
+            _lib.check(model._L.wn_transducer_score_times(model._h, ms),
+                       'wn_transducer_score_times')
+        finally:
+            _lib.check(model._L.wn_profile_enable(model._h, 0), 'wn_profile_enable')
+        assert td_marked == td
+        t_attn, attn = clock(lambda: T._attn_scores_current(model, hyps, rw))
+        return dict(search=t_search, score=t_score, attn=t_attn, enc_proj=ms[0] * 1e-3,
+                    predictor=ms[1] * 1e-3, gather=ms[2] * 1e-3, lattice=ms[3] * 1e-3), \
+            (nbest, td, attn, rows_stat)
+
+    first = {beam: one(beam)[1] for beam in RESCORE_BEAMS}      # warm up every shape
+    if args.searches_only:
+        for _ in range(args.searches_only):
+            for beam in RESCORE_BEAMS:
+                one(beam)
+        return 0
+    times = {beam: [] for beam in RESCORE_BEAMS}
+    for _ in range(args.repeats):
+        for beam in RESCORE_BEAMS:
+            t, got = one(beam)
+            assert got[:3] == first[beam][:3], f'beam {beam}: another result on a repeat'
+            times[beam].append(t)
+
+    def timed(fn):
+        fn(); sync()
+        ts = [clock(fn)[0] for _ in range(args.repeats)]
+        return statistics.median(ts)
+
+    J, V = configs['joint_conf']['join_dim'], configs['output_dim']
+    table = []
+    for beam in RESCORE_BEAMS:
+        med = {k: statistics.median(t[k] for t in times[beam]) for k in times[beam][0]}
+        nbest, _, _, (rows, unshared, nodes) = first[beam]
+        t_e2e = timed(lambda: model.transducer_attention_rescoring(
+            feats, lens, beam, reverse_weight=rw, ctc_weight=cw, attn_weight=aw,
+            transducer_weight=tw, search_ctc_weight=RESCORE_SEARCH[0],
+            search_transducer_weight=RESCORE_SEARCH[1]))
+        t_bs = timed(lambda: model.beam_search(feats, lens, beam_size=beam,
+                                               ctc_weight=RESCORE_SEARCH[0],
+                                               transducer_weight=RESCORE_SEARCH[1]))
+        row = dict(beam=beam, ms={k: v * 1e3 for k, v in med.items()},
+                   rows=rows, rows_unshared=unshared, trie_nodes=nodes,
+                   gather_tflops=rows * 2.0 * J * V / max(med['gather'], 1e-9) * 1e-12,
+                   mean_hyp_len=sum(len(t) for u in nbest for t, _ in u)
+                   / max(sum(len(u) for u in nbest), 1),
+                   transducer_attention_rescoring=dict(seconds=t_e2e, audio_s_per_s=audio_s / t_e2e),
+                   beam_search=dict(seconds=t_bs, audio_s_per_s=audio_s / t_bs))
+        table.append(row)
+        print(f"beam {beam:2d}: search {med['search'] * 1e3:7.2f} ms, score {med['score'] * 1e3:7.2f} "
+              f"ms (enc_proj {med['enc_proj'] * 1e3:.2f}, predictor {med['predictor'] * 1e3:.2f}, "
+              f"gather {med['gather'] * 1e3:.2f}, "
+              f"lattice {med['lattice'] * 1e3:.2f}), attention "
+              f"{med['attn'] * 1e3:7.2f} ms; rows {rows} of {unshared} unshared, "
+              f"{row['gather_tflops']:.1f} TFLOP/s; rescoring {audio_s / t_e2e:.0f} audio-s/s, "
+              f'beam_search {audio_s / t_bs:.0f}', flush=True)
+    out = dict(config=args.config, encoder_blocks=configs['encoder_conf']['num_blocks'], batch=B,
+               audio_seconds=audio_s, weights=picked, search_weights=list(RESCORE_SEARCH),
+               rescore_weights=dict(ctc=cw, attn=aw, transducer=tw, reverse=rw), rescoring=table,
+               method='host clock around calls that end in a device synchronise (search, score, '
+                      'attention, the whole calls); enc_proj / predictor / gather / lattice: '
+                      'device time between events inside a wn_transducer_score call of their '
+                      'own under wn_profile_enable; beams alternate '
+                      'in one process; median of --repeats')
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)

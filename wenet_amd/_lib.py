@@ -79,6 +79,9 @@ EXPORTS = [
     'wn_model_create_transducer', 'wn_transducer_greedy_search', 'wn_op_lstm_step',
     'wn_op_joint_argmax', 'wn_transducer_beam_search', 'wn_op_joint_fuse_topk',
     'wn_op_rnnt_beam_step', 'wn_transducer_beam_stats',
+    'wn_transducer_score', 'wn_transducer_score_stats', 'wn_transducer_score_times',
+    'wn_op_rnnt_trie',
+    'wn_op_joint_logp_gather', 'wn_op_rnnt_lattice',
     'wn_op_attn_self_step', 'wn_op_attn_step_embed', 'wn_op_attn_prompt_cache', 'wn_op_beam_init',
     'wn_op_beam_update', 'wn_op_beam_finish',
 ]
@@ -206,6 +209,14 @@ def lib():
     L.wn_op_rnnt_beam_step.argtypes = [i32, i32, i32, i32, i32, pi32, i32, pi32, pf64, pi32, pi32,
                                        POINTER(f32), pi32, pi32, pf64, pi32, pi32, pi32, pi32,
                                        pi32, pi32, vp]
+    L.wn_transducer_score.argtypes = [vp, i32, pi32, pi32, pi32, i32, pf64, vp]
+    L.wn_transducer_score_stats.argtypes = [vp, POINTER(i64), POINTER(i64), pi32]
+    L.wn_transducer_score_times.argtypes = [vp, POINTER(f32)]
+    L.wn_op_rnnt_trie.argtypes = [i32, pi32, pi32, i32, i32, pi32, pi32, pi32, pi32, pi32, pi32,
+                                  pi32]
+    L.wn_op_joint_logp_gather.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32,
+                                          pi32, pi32, POINTER(f32), vp]
+    L.wn_op_rnnt_lattice.argtypes = [i32, pi32, pi32, POINTER(f32), POINTER(f32), pf64, vp]
     L.wn_op_attn_self_step.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
     L.wn_op_attn_step_embed.argtypes = [vp, i32, vp, i32, vp, i32, f32, i32, i32, vp, vp]
     L.wn_op_attn_prompt_cache.argtypes = [vp, i32, i32, i32, i32, vp, vp]

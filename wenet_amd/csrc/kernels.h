@@ -597,4 +597,37 @@ int rnnt_beam_gather(const int* src, const float* h_in, const float* c_in, const
                      float* h_out, float* c_out, float* pp_out, int M, int L, int H, int J,
                      hipStream_t s);
 
+// Teacher-forced transducer score (transducer_score.hip): fp32 rows, fp64 lattice.
+// Per row m with row_enc[m] >= 0, for every entry e of its column list
+// [col_off[m], col_off[m + 1]): logp[e] = logit[cols[e]] - logsumexp(row), the logits of
+// rnnt_joint_kernel (its own A tile and k loop, rnnt_joint_tile.h: the same bits).  Inert rows write nothing.  ent_row[e] is
+// the row that entry e belongs to.  Nothing of size (M, V) is written.
+struct RnntGatherArgs {
+  const float* enc_proj = nullptr; int lde = 0;
+  const float* pred_proj = nullptr; int ldp = 0;
+  const int* row_enc = nullptr; const int* row_pred = nullptr;
+  const float* W = nullptr; const float* bias = nullptr;   // [V][J], [V]
+  int M = 0, J = 0, V = 0;
+  const int* col_off = nullptr;     // [M + 1]
+  const int* cols = nullptr; const int* ent_row = nullptr;   // [col_off[M]]
+  float* logp = nullptr;            // [col_off[M]]
+};
+int rnnt_joint_logp_gather(const RnntGatherArgs& a, hipStream_t s);
+// rows r0 .. r0 + n of h / c [L][stride / H][H] take the rows parent[r0 + i] (< 0: left alone)
+int rnnt_trie_gather(const int* parent, float* h, float* c, int r0, int n, int L,
+                     int64_t layer_stride, int H, hipStream_t s);
+// N lattices: score[n] = log P(y | x) by the forward algorithm, fp64.  lp_blank(t, u) =
+// blank[blank_base[n] + t blank_stride[n] + ub[u_off[n] + u]] (u <= U), lp_label(t, u) =
+// label[label_base[n] + t label_stride[n] + ul[u_off[n] + u]] (u < U).  T[n] <= 0: -inf.
+struct RnntLatticeArgs {
+  const float* blank = nullptr; const float* label = nullptr;
+  const int* T = nullptr; const int* U = nullptr;
+  const int64_t* blank_base = nullptr; const int64_t* label_base = nullptr;
+  const int* blank_stride = nullptr; const int* label_stride = nullptr;
+  const int* u_off = nullptr; const int* ub = nullptr; const int* ul = nullptr;
+  double* score = nullptr;
+  int N = 0, max_U = 0;
+};
+int rnnt_lattice(const RnntLatticeArgs& a, hipStream_t s);
+
 }  // namespace wn

@@ -311,9 +311,19 @@ struct wn_model {
   DevBuf tr_ctc;          // wn_transducer_beam_search: the CTC log-prob rows it fuses with
   int tr_beam_steps = 0;            // ... its last call: steps issued,
   int64_t tr_beam_advance = 0;      // rows that ran the LSTM step, summed over the steps
+  // wn_transducer_score, its last call: GEMM rows (frames x trie nodes), what they would have
+  // been without the trie (frames x sum of len + 1), trie nodes
+  int64_t tr_score_rows = 0, tr_score_unshared = 0;
+  int tr_score_nodes = 0;
+  DevBuf tr_sc_f32, tr_sc_i32, tr_sc_logp;
+  hipEvent_t tr_sc_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // its stage marks
+  float tr_score_ms[4] = {0.f, 0.f, 0.f, 0.f};   // enc_proj, predictor, gather GEMM, lattice
   PinnedBuf tr_host;
   hipEvent_t tr_ev[2] = {nullptr, nullptr};
-  ~wn_model() { for (hipEvent_t e : tr_ev) if (e) (void)hipEventDestroy(e); }
+  ~wn_model() {
+    for (hipEvent_t e : tr_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : tr_sc_ev) if (e) (void)hipEventDestroy(e);
+  }
   bool ab_truncated = false;   // the last prompted search stopped at the positional table
   bool mem_cache_valid = false;
 

@@ -25,14 +25,12 @@
 //    rnnt_reduce_kernel runs on its own for the operator hook), scans the window in frame order, applies the emission
 //    rule, appends tokens and writes the next step's row map, `advance`, `done`, `n_active`.
 // Plain stream-ordered launches; every kernel of a finished batch returns on n_active == 0.
-#include "kernels.h"
+#include "rnnt_joint_tile.h"
 
 namespace wn {
 namespace {
 
 constexpr int RL_KC = 16;          // 64-lane chunks of a weight row kept in registers: K <= 1024
-constexpr int JT_ROWS = 32;        // rows per block of the joint kernel
-constexpr int JT_COLS = 128;       // columns per block (four waves x 32)
 
 __global__ __launch_bounds__(256) void rnnt_linear_kernel(RnntLinearArgs p) {
   if (p.n_active && *p.n_active == 0) return;
@@ -128,51 +126,12 @@ __global__ __launch_bounds__(256) void rnnt_joint_kernel(RnntJointArgs p) {
   __shared__ int red_i[4][JT_ROWS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.y * JT_ROWS;
-  const int pitch = p.J * 4 + 16;             // bytes per LDS row (conflict-free ds_read_b128)
-  const int j4 = p.J / 4;
-  // A rows of this block: tanh(enc_proj + pred_proj); rows past M and inert rows are zeros
-  for (int c = tid; c < JT_ROWS * j4; c += 256) {
-    const int row = c / j4, kc = c - row * j4;
-    const int m = m0 + row;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (m < p.M) {
-      const int re = p.row_enc[m];
-      if (re >= 0) {
-        const f32x4 e = *reinterpret_cast<const f32x4*>(p.enc_proj + (int64_t)re * p.lde + kc * 4);
-        const f32x4 q = *reinterpret_cast<const f32x4*>(
-            p.pred_proj + (int64_t)p.row_pred[m] * p.ldp + kc * 4);
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4) v[e4] = tanhf(e[e4] + q[e4]);
-      }
-    }
-    *reinterpret_cast<f32x4*>(smem + row * pitch + kc * 16) = v;
-  }
+  // A rows of this block and this wave's 32 x 32 logits without the bias (rnnt_joint_tile.h)
+  rnnt_joint_stage_a(smem, p.enc_proj, p.lde, p.pred_proj, p.ldp, p.row_enc, p.row_pred, p.M, p.J,
+                     m0, tid);
   __syncthreads();
-
   const int n0 = blockIdx.x * JT_COLS + wave * 32;
-  const int wrow = min(n0 + (lane & 31), p.V - 1);   // columns past V: a copy, never kept
-  const float* w_ptr = p.W + (int64_t)wrow * p.J + (lane >> 5) * 4;
-  const char* a_ptr = smem + (lane & 31) * pitch + (lane >> 5) * 16;
-  // four accumulators, one per k mod 4 class (each an fmaf chain over J / 4 terms in ascending
-  // k), summed as (0 + 1) + (2 + 3): a fixed order, shorter chains, less rounding error
-  f32x16 acc4[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc4[e][r] = 0.0f;
-  // 8 k per round: lanes 0..31 hold k0 + 0..3, lanes 32..63 k0 + 4..7 of their row / column
-  const int nk8 = p.J / 8;
-#pragma unroll 4
-  for (int k8 = 0; k8 < nk8; ++k8) {
-    const f32x4 w = *reinterpret_cast<const f32x4*>(w_ptr + k8 * 8);
-    const f32x4 a = *reinterpret_cast<const f32x4*>(a_ptr + k8 * 32);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      acc4[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], w[e], acc4[e], 0, 0, 0);
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = (acc4[0][r] + acc4[1][r]) + (acc4[2][r] + acc4[3][r]);
+  const f32x16 acc = rnnt_joint_tile_sums(smem, p.W, p.J, p.V, n0, lane);
 
   // C / D layout: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
   const int col = n0 + (lane & 31);

@@ -725,9 +725,11 @@ class ASRModel:
     def _decode_begin(self, methods, speech, speech_lengths, beam_size=1,
                       decoding_chunk_size=-1, num_decoding_left_chunks=-1,
                       simulate_streaming=False, context_graph=None, blank_id=0,
-                      blank_penalty=0.0):
+                      blank_penalty=0.0, ctc_topk=None):
         """First half of decode(): argument checks, then the encoder and the
-        CTC head are queued on the current stream (no host sync)."""
+        CTC head are queued on the current stream (no host sync).  `ctc_topk`: the
+        CTC head keeps at least that many entries per row (a caller that runs a
+        prefix beam search of its own on the batch)."""
         assert speech.shape[0] == speech_lengths.shape[0]
         assert decoding_chunk_size != 0
         self._use_context_graph(context_graph)
@@ -740,6 +742,8 @@ class ASRModel:
         need_beam = ('ctc_prefix_beam_search' in methods
                      or 'attention_rescoring' in methods)
         k = beam_size if need_beam else 1
+        if ctc_topk is not None:
+            k = max(k, ctc_topk)
         _lib.check(
             self._L.wn_ctc_logprobs(self._h, k, blank_id, blank_penalty, None,
                                     Tp, _stream_ptr(self.device)),

@@ -5,6 +5,8 @@ Mirrors (reference file:line):
   * basic_greedy_search                       wenet/models/transducer/search/greedy_search.py:6-54
   * Transducer.beam_search                    wenet/models/transducer/transducer.py:216-260
   * PrefixBeamSearch.prefix_beam_search       transducer/search/prefix_beam_search.py:42-148
+  * Transducer.transducer_attention_rescoring wenet/models/transducer/transducer.py:262-396
+  * _cal_transducer_score / _cal_attn_score   wenet/models/transducer/transducer.py:161-214
   * RNNPredictor / TransducerJoint            transducer/predictor.py:60-206, joint.py:62-92
   * how init_model builds the model           wenet/utils/init_model.py:137-154
 
@@ -29,6 +31,7 @@ from wenet_amd.search import DecodeResult, _stream_ptr
 
 RNNT_METHOD = 'rnnt_greedy_search'   # wenet/bin/recognize.py:86
 RNNT_BEAM_METHOD = 'rnnt_beam_search'
+RNNT_RESCORE_METHOD = 'rnnt_beam_attn_rescoring'
 
 
 def _refuse(key, got, want):
@@ -154,6 +157,151 @@ def _beam_results(nbest) -> List[DecodeResult]:
                          nbest_scores=[s for _, s in u]) for u in nbest]
 
 
+def _hyp_arrays(hyps: List[List[List[int]]]):
+    """Per-utterance lists of token lists -> (beam, n_hyps, hyp_lens, hyp_tokens, max_len) laid
+    out as wn_rescore / wn_transducer_score read them."""
+    B = len(hyps)
+    beam = max(max((len(u) for u in hyps), default=0), 1)
+    max_len = max(max((len(h) for u in hyps for h in u), default=0), 1)
+    n_hyps = np.zeros((B, ), dtype=np.int32)
+    lens = np.zeros((B, beam), dtype=np.int32)
+    tokens = np.zeros((B, beam, max_len), dtype=np.int32)
+    for b, u in enumerate(hyps):
+        n_hyps[b] = len(u)
+        for i, h in enumerate(u):
+            lens[b, i] = len(h)
+            tokens[b, i, :len(h)] = np.asarray(h, dtype=np.int32).reshape(-1)
+    return beam, n_hyps, lens, tokens, max_len
+
+
+def _score_current(model, hyps: List[List[List[int]]]) -> List[List[float]]:
+    """wn_transducer_score on the handle's current batch: per utterance the -RNN-T loss of each
+    of its hypotheses (fp64)."""
+    beam, n_hyps, lens, tokens, max_len = _hyp_arrays(hyps)
+    td = np.empty((len(hyps), beam), dtype=np.float64)
+    _lib.check(
+        model._L.wn_transducer_score(model._h, beam, _lib.i32p(n_hyps), _lib.i32p(lens),
+                                     _lib.i32p(tokens), max_len, _lib.f64p(td),
+                                     _stream_ptr(model.device)), 'wn_transducer_score')
+    rows, unshared, nodes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+    _lib.check(model._L.wn_transducer_score_stats(model._h, ctypes.byref(rows),
+                                                  ctypes.byref(unshared), ctypes.byref(nodes)),
+               'wn_transducer_score_stats')
+    model.last_rnnt_score_rows = (int(rows.value), int(unshared.value), int(nodes.value))
+    return [td[b, :n_hyps[b]].tolist() for b in range(len(hyps))]
+
+
+def transducer_score(model, encoder_out: torch.Tensor, encoder_out_lens,
+                     hyps: List[List[List[int]]]) -> List[List[float]]:
+    """Transducer._cal_transducer_score (transducer.py:161-186) on a caller's padded (B, T', d)
+    encoder output, any B: per utterance the -RNN-T loss of each of its hypotheses (token lists
+    without the leading blank), fp64.  An utterance of zero frames scores -inf."""
+    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
+    B, _ = model._set_encoder_out(encoder_out, lens)
+    if len(hyps) != B:
+        raise ValueError(f'transducer_score: {len(hyps)} n-bests for a batch of {B} utterances')
+    return _score_current(model, hyps)
+
+
+def _attn_scores_current(model, hyps: List[List[List[int]]], reverse_weight: float):
+    """The attention decoder's score of every hypothesis (transducer.py:188-214 + :376-387)
+    through wn_rescore with explicit host hypotheses and ctc_weight = 0: its all_scores."""
+    beam, n_hyps, lens, tokens, max_len = _hyp_arrays(hyps)
+    B = len(hyps)
+    best = np.zeros((B, ), dtype=np.int32)
+    score = np.zeros((B, ), dtype=np.float32)
+    all_scores = np.zeros((B, beam), dtype=np.float32)
+    zeros = np.zeros((B, beam), dtype=np.float64)
+    null_d = ctypes.POINTER(ctypes.c_double)()
+    _lib.check(
+        model._L.wn_rescore(model._h, beam, _lib.i32p(n_hyps), _lib.i32p(lens), _lib.i32p(tokens),
+                            _lib.f64p(zeros), max_len, 0.0, float(reverse_weight),
+                            _lib.i32p(best), _lib.f32p(score), null_d, null_d,
+                            _lib.f32p(all_scores), _stream_ptr(model.device)), 'wn_rescore')
+    return [all_scores[b, :n_hyps[b]].astype(np.float64).tolist() for b in range(B)]
+
+
+def combine_scores(attn, beam_score, td, attn_weight: float, ctc_weight: float,
+                   transducer_weight: float):
+    """transducer.py:389-394 for one utterance, in fp64: (index of the winner, the rescored
+    score of every hypothesis).  The first maximum wins; a NaN never wins (`score > best` is
+    false for it, as in the reference)."""
+    scores, best, best_score = [], 0, -float('inf')
+    for i in range(len(attn)):
+        s = float(attn[i]) * attn_weight + float(beam_score[i]) * ctc_weight
+        if transducer_weight != 0.0:
+            s += float(td[i]) * transducer_weight
+        scores.append(s)
+        if s > best_score:
+            best, best_score = i, s
+    return best, scores
+
+
+BEAM_SEARCH_TYPES = ('transducer', 'ctc')
+
+
+def _check_search_type(beam_search_type):
+    if beam_search_type not in BEAM_SEARCH_TYPES:
+        raise ValueError(f'beam_search_type={beam_search_type!r}: expected one of '
+                         f'{BEAM_SEARCH_TYPES}')
+
+
+def _rescore_current(model, nbest, reverse_weight, ctc_weight, attn_weight, transducer_weight
+                     ) -> List[DecodeResult]:
+    """Steps 2.1 - 2.2 and the combination of transducer_attention_rescoring on the handle's
+    current batch, for an n-best [(tokens, score), ...] per utterance."""
+    hyps = [[list(t) for t, _ in u] for u in nbest]
+    # the transducer score first: it reads the encoder output as the search left it
+    td = _score_current(model, hyps) if transducer_weight != 0.0 else [None] * len(hyps)
+    attn = _attn_scores_current(model, hyps, reverse_weight)
+    out = []
+    for b, u in enumerate(nbest):
+        best, scores = combine_scores(attn[b], [s for _, s in u], td[b], attn_weight, ctc_weight,
+                                      transducer_weight)
+        r = DecodeResult(hyps[b][best], score=scores[best], nbest=hyps[b], nbest_scores=scores)
+        r.attn_scores, r.td_scores = attn[b], td[b]     # extra: the parts of every score
+        out.append(r)
+    return out
+
+
+def _ctc_nbest_current(model, B: int, Tp: int, max_frames: int, beam_size: int, blank_id: int,
+                       head: bool):
+    """This project's CTC prefix beam search on the handle's current batch as
+    [(tokens, score), ...] per utterance.  `head`: run the CTC head first (top-k = beam_size);
+    otherwise its rows are in place already."""
+    from wenet_amd.search import _prefix_beam
+    if head:
+        _lib.check(model._L.wn_ctc_logprobs(model._h, beam_size, blank_id, 0.0, None, Tp,
+                                            _stream_ptr(model.device)), 'wn_ctc_logprobs')
+    res, _ = _prefix_beam(model._h, B, max_frames, beam_size, blank_id, model.device)
+    return [[(list(t), float(s)) for t, s in zip(r.nbest, r.nbest_scores)] for r in res]
+
+
+def attention_rescoring(model, encoder_out: torch.Tensor, encoder_out_lens, beam_size: int,
+                        reverse_weight: float = 0.0, ctc_weight: float = 0.0,
+                        attn_weight: float = 0.0, transducer_weight: float = 0.0,
+                        search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0,
+                        beam_search_type: str = 'transducer') -> List[DecodeResult]:
+    """transducer.py:316-396 on a caller's padded (B, T', d) encoder output, any B: one record
+    per utterance with `tokens`, `score`, `nbest` (in search order) and `nbest_scores` (the
+    rescored score of each).  Every utterance needs at least one encoder frame: the attention
+    scores come from wn_rescore, which refuses an utterance without frames (only
+    `transducer_score` serves that case, with -inf)."""
+    _check_search_type(beam_search_type)
+    if reverse_weight > 0.0:
+        assert model._cfg.dec_r_layers > 0
+    lens = torch.as_tensor(encoder_out_lens).reshape(-1)
+    B, Tp = model._set_encoder_out(encoder_out, lens)
+    max_frames = int(lens.max()) if B > 0 else 0
+    if beam_search_type == 'transducer':
+        nbest = _beam_current(model, B, max_frames, beam_size, search_ctc_weight,
+                              search_transducer_weight)
+    else:
+        nbest = _ctc_nbest_current(model, B, Tp, max_frames, beam_size, model.blank, True)
+    return _rescore_current(model, nbest, reverse_weight, ctc_weight, attn_weight,
+                            transducer_weight)
+
+
 class Transducer(ASRModel):
     """Hybrid transducer + CTC + attention model with the reference's inference API."""
 
@@ -162,6 +310,8 @@ class Transducer(ASRModel):
         self.blank = self._tcfg.blank
         self.last_rnnt_steps = 0     # lock-step steps of the last transducer search
         self.last_rnnt_advance_rows = 0   # beam search: rows that ran the LSTM step, all steps
+        # transducer score: (joint rows computed, rows without prefix sharing, trie nodes)
+        self.last_rnnt_score_rows = (0, 0, 0)
 
     def _config(self, configs: dict) -> _lib.WnConfig:
         cfg, self._tcfg = transducer_config_from_yaml(configs)
@@ -202,23 +352,74 @@ class Transducer(ASRModel):
                               transducer_weight)
         return [u[0][0] for u in nbest], [u[0][1] for u in nbest]
 
+    def transducer_attention_rescoring(
+            self, speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int,
+            decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+            simulate_streaming: bool = False, reverse_weight: float = 0.0,
+            ctc_weight: float = 0.0, attn_weight: float = 0.0, transducer_weight: float = 0.0,
+            search_ctc_weight: float = 1.0, search_transducer_weight: float = 0.0,
+            beam_search_type: str = 'transducer') -> Tuple[List[List[int]], List[float]]:
+        """transducer.py:262-396, for any batch size: (token lists, scores), one entry per
+        utterance.  One encoder pass; the n-best of the RNN-T prefix beam search with the search
+        weights ('transducer') or of the CTC prefix beam search ('ctc'); per hypothesis
+        `attn * attn_weight + beam_score * ctc_weight + td * transducer_weight` in fp64, where
+        td = -RNN-T loss (wn_transducer_score, skipped when transducer_weight == 0) and attn the
+        attention decoder's score (blended with the right-to-left decoder's by reverse_weight).
+        The reference takes one utterance; with B == 1 its pair is `(out[0][0], out[1][0])`.
+        Every utterance needs at least one encoder frame (wn_rescore refuses one without)."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        if reverse_weight > 0.0:
+            # decoder should be a bitransformer decoder if reverse_weight > 0.0
+            assert self._cfg.dec_r_layers > 0
+        _check_search_type(beam_search_type)
+        _ = simulate_streaming
+        speech, lens = self._prep(speech, speech_lengths)
+        B = speech.shape[0]
+        _, enc_lens, Tp = self._encode(speech, lens, decoding_chunk_size,
+                                       num_decoding_left_chunks, False)
+        max_frames = int(enc_lens.max()) if B > 0 else 0
+        if beam_search_type == 'transducer':
+            nbest = _beam_current(self, B, max_frames, beam_size, search_ctc_weight,
+                                  search_transducer_weight)
+        else:
+            nbest = _ctc_nbest_current(self, B, Tp, max_frames, beam_size, self.blank, True)
+        res = _rescore_current(self, nbest, reverse_weight, ctc_weight, attn_weight,
+                               transducer_weight)
+        return [list(r.tokens) for r in res], [r.score for r in res]
+
     def decode(self, methods: List[str], speech: torch.Tensor, speech_lengths: torch.Tensor,
                beam_size: int = 1, decoding_chunk_size: int = -1,
                num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                simulate_streaming: bool = False, reverse_weight: float = 0.0,
                context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0,
                length_penalty: float = 0.0, infos=None, n_steps: int = 64,
-               search_ctc_weight: float = 0.3, search_transducer_weight: float = 0.7
-               ) -> Dict[str, List[DecodeResult]]:
-        """ASRModel.decode, which additionally knows 'rnnt_greedy_search' and 'rnnt_beam_search':
-        one encoder pass serves every requested mode.  The beam search takes `beam_size` and its
-        fusion weights `search_ctc_weight` / `search_transducer_weight`; `ctc_weight` stays the
-        rescoring weight and is not read by it.  Its results carry `tokens`, `score`, `nbest`
-        and `nbest_scores`."""
-        others = [m for m in methods if m not in (RNNT_METHOD, RNNT_BEAM_METHOD)]
+               search_ctc_weight: float = 0.3, search_transducer_weight: float = 0.7,
+               attn_weight: float = 0.0, transducer_weight: float = 0.0,
+               beam_search_type: str = 'transducer') -> Dict[str, List[DecodeResult]]:
+        """ASRModel.decode, which additionally knows 'rnnt_greedy_search', 'rnnt_beam_search' and
+        'rnnt_beam_attn_rescoring': one encoder pass serves every requested mode.  The beam
+        search takes `beam_size` and its fusion weights `search_ctc_weight` /
+        `search_transducer_weight`; `ctc_weight` stays the rescoring weight and is not read by
+        it.  Its results carry `tokens`, `score`, `nbest` and `nbest_scores`.
+        'rnnt_beam_attn_rescoring' (transducer_attention_rescoring) rescores the n-best of that
+        search (computed once when both modes are asked for), or with beam_search_type='ctc' of
+        the CTC prefix beam search, with `attn_weight`, `ctc_weight`, `transducer_weight` and
+        `reverse_weight`; its results carry `tokens`, `score`, `nbest` in search order and
+        `nbest_scores`, the rescored score of each."""
+        rescoring = RNNT_RESCORE_METHOD in methods
+        if rescoring:
+            _check_search_type(beam_search_type)
+            if reverse_weight > 0.0:
+                assert self._cfg.dec_r_layers > 0
+        ctc_nbest = rescoring and beam_search_type == 'ctc'
+        others = [m for m in methods
+                  if m not in (RNNT_METHOD, RNNT_BEAM_METHOD, RNNT_RESCORE_METHOD)]
+        # (the CTC n-best of the rescoring needs the CTC head's top-k at beam_size)
         st = self._decode_begin(others, speech, speech_lengths, beam_size, decoding_chunk_size,
                                 num_decoding_left_chunks, simulate_streaming, context_graph,
-                                blank_id, blank_penalty)
+                                blank_id, blank_penalty,
+                                ctc_topk=beam_size if ctc_nbest else None)
         results = {}
         if RNNT_METHOD in methods:
             # first: the search reads the encoder output, which the non-blank filter of
@@ -226,10 +427,22 @@ class Transducer(ASRModel):
             B, enc_lens = st['B'], st['enc_lens']
             toks = _search_current(self, B, int(enc_lens.max()) if B > 0 else 0, n_steps)
             results[RNNT_METHOD] = [DecodeResult(t) for t in toks]
+        nbest = None
         if RNNT_BEAM_METHOD in methods:      # (before _decode_end, for the same reason)
             B, enc_lens = st['B'], st['enc_lens']
-            results[RNNT_BEAM_METHOD] = _beam_results(_beam_current(
-                self, B, int(enc_lens.max()) if B > 0 else 0, beam_size, search_ctc_weight,
-                search_transducer_weight))
+            nbest = _beam_current(self, B, int(enc_lens.max()) if B > 0 else 0, beam_size,
+                                  search_ctc_weight, search_transducer_weight)
+            results[RNNT_BEAM_METHOD] = _beam_results(nbest)
+        if rescoring:                        # (likewise: it reads the encoder output)
+            B, enc_lens = st['B'], st['enc_lens']
+            max_frames = int(enc_lens.max()) if B > 0 else 0
+            if ctc_nbest:
+                nbest = _ctc_nbest_current(self, B, st['Tp'], max_frames, beam_size,
+                                           st['blank_id'], False)
+            elif nbest is None:
+                nbest = _beam_current(self, B, max_frames, beam_size, search_ctc_weight,
+                                      search_transducer_weight)
+            results[RNNT_RESCORE_METHOD] = _rescore_current(
+                self, nbest, reverse_weight, ctc_weight, attn_weight, transducer_weight)
         results.update(self._decode_end(st, ctc_weight, reverse_weight, length_penalty, infos))
         return results
