@@ -736,6 +736,44 @@ int wn_op_beam_finish(int32_t B, int32_t N, int32_t len, int32_t max_len, int32_
                       float length_penalty, const float* score_dev, const int32_t* tok_dev,
                       int32_t* out_tok_dev, int32_t* out_len_dev, int32_t prefix, void* stream);
 
+/* Operator hooks of the kernels that own a complete row (test infrastructure): thin wrappers of
+ * the launchers the encoder calls, every argument checked on the host BEFORE anything is launched
+ * (null pointers, M > 0, a width the launcher has a case for, row strides >= the width and
+ * multiples of 4 elements, pitch >= M, S >= 1, mode in 0..2), so that no accepted call reads or
+ * writes outside the caller's buffers.  Every array is a DEVICE array; eps sits inside the square
+ * root (torch.nn.LayerNorm).
+ *   layernorm_ex    y = LN(x; w, b); x (M, ldx), y (M, ldy) fp32 or, y_bf16 != 0, bf16 (ldy in
+ *                   bf16 elements); y may be x.  D in {64, 128, 192, 256, 384, 512, 640, 768, 1024,
+ *                   1280}
+ *   layernorm2      y1 = LN(x; w1, b1), y2 = LN(y1; w2, b2) (fp32 or bf16) on dense (M, D) rows;
+ *                   y1 may be x.  D in {64, 128, 256, 512, 768, 1024, 1280}
+ *   layernorm_mx    LN(x) as MXFP8: q (M, D) e4m3 bytes, scale dwords [D/128][pitch] (byte
+ *                   (c >> 5) & 3 of dword [c >> 7][row] for column c).  D in {256, ..., 1280} step 256
+ *   ffn_reduce_ln   x_new = x + alpha (sum_s P[s] + b2), P [S][M][D], D in {256, 512}.  mode 0:
+ *                   x <- x_new, y = LN(x_new; w, b); mode 1: x <- LN(x_new; w, b), y = LN(x; w2,
+ *                   bb2); mode 2: x <- LN(x_new; w, b) only (y unused).  y3 != NULL: mode 1 with y
+ *                   leaving as its plane image (csrc/x6.h) in y3 instead, y3_bytes >= the image of
+ *                   M rows rounded up to 32: (D / 16) * ceil(M / 32) * 3072
+ *   gemm_rowln      x_out = resid + alpha (A W^T + bias), y = LN(x_out; ln_w, ln_b); W (256, K),
+ *                   K % 32 == 0, K >= 96, lda >= K, ldr / ldx / ldy >= 256; bias / resid may be
+ *                   NULL, resid may be x_out, y may be A.  Calls the kernel whatever the
+ *                   `gemm_rowln` tune switch says */
+int wn_op_layernorm_ex(const float* x, int32_t ldx, const float* w, const float* b, void* y,
+                       int32_t ldy, int32_t M, int32_t D, float eps, int32_t y_bf16, void* stream);
+int wn_op_layernorm2(const float* x, const float* w1, const float* b1, const float* w2,
+                     const float* b2, float* y1, void* y2, int32_t M, int32_t D, float eps,
+                     int32_t y2_bf16, void* stream);
+int wn_op_layernorm_mx(const float* x, int32_t ldx, const float* w, const float* b, void* q,
+                       void* scale, int32_t pitch, int32_t M, int32_t D, float eps, void* stream);
+int wn_op_ffn_reduce_ln(float* x, const float* P, int32_t S, const float* b2, float alpha,
+                        const float* w, const float* b, const float* w2, const float* bb2, float* y,
+                        void* y3, int64_t y3_bytes, int32_t M, int32_t D, float eps, int32_t mode,
+                        void* stream);
+int wn_op_gemm_rowln(const float* A, int32_t lda, const float* W, const float* bias,
+                     const float* resid, int32_t ldr, float alpha, float* x_out, int32_t ldx,
+                     const float* ln_w, const float* ln_b, float eps, float* y, int32_t ldy,
+                     int32_t M, int32_t K, void* stream);
+
 /* Measurement hook for bench.py: bracket launches of the dominant kernel (the
  * FFN w_1 GEMM, positionwise_feed_forward.py:58; every 6th launch, because each
  * event pair idles the GPU for ~10 us) with HIP events on the launch stream.  wn_profile_collect waits for them and returns the number of

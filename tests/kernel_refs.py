@@ -16,6 +16,10 @@ Behind conv1: the rest of the Conformer front end (conv2, the output projection)
 front end, for tests/test_gpu_frontend.py; their whole-chain references call the oracle's own
 functions (imported inside those functions only).
 
+At the end: the kernels that own a complete row -- LayerNorm, the FFN slice reduce, the row-LN GEMM
+-- as written-out formulas, a decoder of the plane image (csrc/x6.h) and the row regimes, for
+tests/test_gpu_rows.py.
+
 No GPU in here.
 """
 import math
@@ -769,6 +773,162 @@ def beam_finish_margin_ok(s_row, same=()):
         return bool(np.all(np.isneginf(s_row)))           # every row -inf: the first wins
     others = [s_row[i] for i in range(len(s_row)) if i != w and i not in same]
     return all(s_row[w] - o > 4 * ULP32 * abs(s_row[w]) for o in others)
+
+
+# ---------------------------------------------------------------------------------------------
+# the kernels that own a complete row: the LayerNorm family (csrc/encoder_kernels.hip), the FFN
+# reduce (csrc/ffn_fused.hip), the row-LN GEMM (csrc/gemm_rowln.hip); GPU tests in
+# tests/test_gpu_rows.py
+
+
+def ref_layernorm(x, w, b, eps, fp32=False):
+    """torch.nn.LayerNorm over the last dim, written out: mean, centred second moment (biased),
+    (x - mean) / sqrt(var + eps) * w + b.  Returns fp64."""
+    dt = torch.float32 if fp32 else torch.float64
+    x, w, b = x.to(dt), w.to(dt), b.to(dt)
+    D = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / D
+    d = x - mean
+    var = (d * d).sum(-1, keepdim=True) / D
+    return (d / torch.sqrt(var + eps) * w + b).double()
+
+
+def ref_ffn_reduce(x, P, b2, alpha, w, b, w2, bb2, eps, mode, fp32=False):
+    """x (M, D), P (S, M, D).  x_new = x + alpha * (sum_s P[s] + b2), the slices added one by one.
+    mode 0: (x_new, LN(x_new; w, b)); mode 1: (x1 = LN(x_new; w, b), LN(x1; w2, bb2)); mode 2:
+    (LN(x_new; w, b), None).  Returns (new x, y) in fp64."""
+    dt = torch.float32 if fp32 else torch.float64
+    acc = torch.zeros(P.shape[1:], dtype=dt)
+    for s in range(P.shape[0]):
+        acc = acc + P[s].to(dt)
+    x_new = (x.to(dt) + alpha * (acc + b2.to(dt))).double()
+    if mode == 0:
+        return x_new, ref_layernorm(x_new, w, b, eps, fp32)
+    x1 = ref_layernorm(x_new, w, b, eps, fp32)
+    if mode == 1:
+        return x1, ref_layernorm(x1, w2, bb2, eps, fp32)
+    return x1, None
+
+
+def ref_gemm_rowln(A, W, bias, resid, alpha, ln_w, ln_b, eps, fp32=False):
+    """A (M, K), W (256, K); bias / resid may be None.  x_out = resid + alpha * (A W^T + bias),
+    y = LN(x_out; ln_w, ln_b).  Returns (x_out, y) in fp64."""
+    dt = torch.float32 if fp32 else torch.float64
+    acc = A.to(dt) @ W.to(dt).t()
+    if bias is not None:
+        acc = acc + bias.to(dt)
+    x_out = alpha * acc
+    if resid is not None:
+        x_out = resid.to(dt) + x_out
+    x_out = x_out.double()
+    return x_out, ref_layernorm(x_out, ln_w, ln_b, eps, fp32)
+
+
+def x3_offsets(M, D):
+    """Byte offsets (3, M, D) of the bf16 elements of a plane image of M rows x D columns
+    (csrc/x6.h): for plane pl, k block kb, half h and row, the 16 bytes at
+    ((kb * tiles + (row >> 5)) * 3072 + pl * 1024 + h * 512 + (row & 31) * 16 hold the columns
+    16 kb + 8 h .. + 7; tiles = ceil(M / 32)."""
+    tiles = (M + 31) // 32
+    pl = np.arange(3).reshape(3, 1, 1)
+    row = np.arange(M).reshape(1, M, 1)
+    col = np.arange(D).reshape(1, 1, D)
+    kb, h, e = col // 16, (col // 8) % 2, col % 8
+    return ((kb * tiles + (row >> 5)) * 3072 + pl * 1024 + h * 512 + (row & 31) * 16) + 2 * e
+
+
+def x3_image_bytes(M, D):
+    return (D // 16) * ((M + 31) // 32) * 3072
+
+
+def x3_decode(buf, M, D):
+    """buf: the bytes of a plane image (uint8, at least x3_image_bytes(M, D)).  Returns the three
+    bf16 planes as a (3, M, D) float32 array."""
+    buf = np.asarray(buf, dtype=np.uint8)
+    off = x3_offsets(M, D)
+    u16 = buf[off].astype(np.uint32) | (buf[off + 1].astype(np.uint32) << 8)
+    return (u16 << 16).view(np.float32)
+
+
+ROW_REGIMES = ('unit', 'offset', 'cols', 'small', 'outlier')
+ROWS_EPS = 1e-5
+
+
+def make_rows_case(regime, M, D, seed=0):
+    """Rows for the LayerNorm family.  unit: 3 randn + 1; offset: 30 + randn (a one-pass variance
+    cancels); cols: randn times a per-column logspace(-3, 3); small: 1e-4 randn, variance far below
+    eps (eps outside the root shows); outlier: randn with the last column at 1e4.  w, b (and w2,
+    b2 of a second norm) distinct per column."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(M, D, generator=g)
+    if regime == 'unit':
+        x = 3.0 * x + 1.0
+    elif regime == 'offset':
+        x = 30.0 + x
+    elif regime == 'cols':
+        x = x * torch.logspace(-3, 3, D)
+    elif regime == 'small':
+        x = 1e-4 * x
+    elif regime == 'outlier':
+        x[:, -1] = 1e4
+    else:
+        raise ValueError(regime)
+    return dict(x=x.contiguous(), w=1.0 + 0.2 * torch.randn(D, generator=g),
+                b=0.1 * torch.randn(D, generator=g), w2=1.0 + 0.2 * torch.randn(D, generator=g),
+                b2=0.1 * torch.randn(D, generator=g), eps=ROWS_EPS, M=M, D=D)
+
+
+def rows_refs(c):
+    """(fp64 LN(x), e_plain, scale) of a make_rows_case."""
+    ref = ref_layernorm(c['x'], c['w'], c['b'], c['eps'])
+    plain = ref_layernorm(c['x'], c['w'], c['b'], c['eps'], fp32=True)
+    return ref, (plain - ref).abs().max().item(), ref.abs().max().item()
+
+
+def rows2_refs(c):
+    """(fp64 LN(LN(x; w, b); w2, b2), e_plain, scale) of a make_rows_case."""
+    def two(fp32):
+        y1 = ref_layernorm(c['x'], c['w'], c['b'], c['eps'], fp32)
+        return ref_layernorm(y1, c['w2'], c['b2'], c['eps'], fp32)
+    ref, plain = two(False), two(True)
+    return ref, (plain - ref).abs().max().item(), ref.abs().max().item()
+
+
+def make_ffn_reduce_case(M, D, S, alpha, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    c = make_rows_case('unit', M, D, seed + 1)
+    c.update(P=torch.randn(S, M, D, generator=g), fb2=0.3 * torch.randn(D, generator=g),
+             alpha=alpha, S=S)
+    return c
+
+
+def ffn_reduce_refs(c, mode):
+    """((x, y) fp64, (e_plain, scale) of x, (e_plain, scale) of y or None)."""
+    args = (c['x'], c['P'], c['fb2'], c['alpha'], c['w'], c['b'], c['w2'], c['b2'], c['eps'], mode)
+    ref = ref_ffn_reduce(*args)
+    plain = ref_ffn_reduce(*args, fp32=True)
+    out = [ref]
+    for r, p in zip(ref, plain):
+        out.append(None if r is None else ((p - r).abs().max().item(), r.abs().max().item()))
+    return tuple(out)
+
+
+def make_gemm_rowln_case(M, K, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return dict(A=torch.randn(M, K, generator=g), W=torch.randn(256, K, generator=g) / math.sqrt(K),
+                bias=0.3 * torch.randn(256, generator=g), resid=torch.randn(M, 256, generator=g),
+                ln_w=1.0 + 0.2 * torch.randn(256, generator=g),
+                ln_b=0.1 * torch.randn(256, generator=g), eps=ROWS_EPS, M=M, K=K)
+
+
+def gemm_rowln_refs(c, bias=True, resid=True, alpha=1.0):
+    """((x_out, y) fp64, (e_plain, scale) of x_out, (e_plain, scale) of y)."""
+    args = (c['A'], c['W'], c['bias'] if bias else None, c['resid'] if resid else None, alpha,
+            c['ln_w'], c['ln_b'], c['eps'])
+    ref = ref_gemm_rowln(*args)
+    plain = ref_gemm_rowln(*args, fp32=True)
+    return (ref, ) + tuple(((p - r).abs().max().item(), r.abs().max().item())
+                           for r, p in zip(ref, plain))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -59,6 +59,25 @@ def test_argument_validation_without_a_device():
         assert L.wn_tune_set(b'ffn_x6f_var', 0) == 0 and L.wn_tune_set(b'x6_probe', 0) == 0
 
 
+@pytest.mark.parametrize('hook', ['layernorm_ex', 'layernorm2', 'layernorm_mx', 'ffn_reduce_ln',
+                                  'gemm_rowln'])
+def test_row_hooks_check_their_arguments_before_any_device_call(hook):
+    """The refusals tests/test_gpu_rows.py runs on the GPU need no device: every one of them is
+    decided on the host, with a message that names the argument."""
+    from wenet_amd import _lib
+    from test_gpu_rows import rejection_calls
+    L = _lib.lib()
+    host = ctypes.create_string_buffer(64)
+    calls = rejection_calls(L, ctypes.addressof(host))[hook]
+    assert len(calls) >= 10
+    for what, call, words in calls:
+        assert call() != 0, f'{hook}: {what} was accepted'
+        msg = L.wn_last_error().decode()
+        # refused by the hook itself (csrc/cabi_ops.hip), not further down by a launcher
+        assert 'cabi_ops.hip' in msg and words in msg, f'{hook}: {what}: "{msg}"'
+    assert host.raw == bytes(64)
+
+
 def test_tune_table_defaults_and_process_default_round_trip():
     """wn_tune_set writes the process default, wn_tune_get(NULL, ...) reads it; every key of
     csrc/tune.h's table is reachable and starts at its documented default."""

@@ -645,3 +645,155 @@ def test_whisper_frontend_reference(F_in, T):
     ref, e, s = KR.whisper_frontend_refs(feats, lens, sd)
     assert [r.shape[0] for r in ref] == KR.sub2_lens(lens, T)
     assert s > 0 and KR.cap_ok(e, s)
+
+
+# ---- the kernels that own a complete row (tests/test_gpu_rows.py) ------------------------------
+
+# every width of the layernorm launcher; the GPU tests run all five regimes at 192, 256, 640
+LN_WIDTHS = [64, 128, 192, 256, 384, 512, 640, 768, 1024, 1280]
+
+
+def _ln_f32(x, w, b, eps, form):
+    """fp32 restatements of a LayerNorm row kernel.  'recip': the kernel's own arithmetic (sum
+    times 1.0f / D, 1.0f / sqrtf); 'one_pass': variance as E[x^2] - mean^2; 'eps_outside': eps
+    added to the standard deviation instead of the variance."""
+    x, w, b = x.float(), w.float(), b.float()
+    D = x.shape[-1]
+    inv = torch.tensor(1.0 / D, dtype=torch.float32)
+    mean = x.sum(-1, keepdim=True) * inv
+    d = x - mean
+    if form == 'one_pass':
+        var = (x * x).sum(-1, keepdim=True) * inv - mean * mean
+    else:
+        var = (d * d).sum(-1, keepdim=True) * inv
+    if form == 'eps_outside':
+        rstd = 1.0 / (torch.sqrt(var) + eps)
+    else:
+        rstd = 1.0 / torch.sqrt(var + eps)
+    return (d * rstd * w + b).double()
+
+
+def test_ref_layernorm_is_torch_layer_norm():
+    c = KR.make_rows_case('unit', 9, 192, seed=3)
+    want = torch.nn.functional.layer_norm(c['x'].double(), (192, ), c['w'].double(),
+                                          c['b'].double(), c['eps'])
+    _close(KR.ref_layernorm(c['x'], c['w'], c['b'], c['eps']), want)
+
+
+@pytest.mark.parametrize('D', LN_WIDTHS)
+@pytest.mark.parametrize('regime', KR.ROW_REGIMES)
+def test_rows_regime_caps_and_reciprocal_form(regime, D):
+    """The yardstick is inside its cap for every regime, width and row count of the GPU tests,
+    and a correct fp32 kernel -- the reciprocal form the kernels use -- is inside the bound."""
+    for M in (1, 4, 5, 37):
+        c = KR.make_rows_case(regime, M, D, seed=D + M)
+        ref, e, scale = KR.rows_refs(c)
+        assert torch.isfinite(ref).all() and scale > 0 and KR.cap_ok(e, scale), (M, e / scale)
+        err = (_ln_f32(c['x'], c['w'], c['b'], c['eps'], 'recip') - ref).abs().max().item()
+        assert err <= KR.bound(e, scale), (M, err, KR.bound(e, scale))
+        ref2, e2, scale2 = KR.rows2_refs(c)
+        assert KR.cap_ok(e2, scale2), (M, e2 / scale2)
+
+
+@pytest.mark.parametrize('D', [64, 192, 256, 640, 1280])
+def test_rows_offset_regime_catches_a_one_pass_variance(D):
+    c = KR.make_rows_case('offset', 37, D, seed=D)
+    ref, e, scale = KR.rows_refs(c)
+    err = (_ln_f32(c['x'], c['w'], c['b'], c['eps'], 'one_pass') - ref).abs().max().item()
+    assert not err <= KR.bound(e, scale), (err, KR.bound(e, scale))
+
+
+@pytest.mark.parametrize('D', [64, 192, 256, 640, 1280])
+def test_rows_small_regime_catches_eps_outside_the_root(D):
+    c = KR.make_rows_case('small', 37, D, seed=D)
+    ref, e, scale = KR.rows_refs(c)
+    err = (_ln_f32(c['x'], c['w'], c['b'], c['eps'], 'eps_outside') - ref).abs().max().item()
+    assert not err <= KR.bound(e, scale), (err, KR.bound(e, scale))
+
+
+@pytest.mark.parametrize('D', [256, 512])
+def test_x3_decode_returns_the_planes_of_an_image(D):
+    """An image laid out record by record from the layout's text (csrc/x6.h: records of 32 rows x
+    16 k per (k block, row tile, plane), halves of 8 k, 16 bytes per row and half), filled with
+    the oracle's planes."""
+    M = 37
+    g = torch.Generator().manual_seed(D)
+    x = torch.randn(M, D, generator=g) * 3.0
+    planes = [p.numpy() for p in O.x6_planes(x)]
+    tiles = (M + 31) // 32
+    img = np.full(KR.x3_image_bytes(M, D), 0xA5, np.uint8)
+    assert img.size == (D // 16) * tiles * 3 * 1024
+    for kb in range(D // 16):
+        for tile in range(tiles):
+            for pl in range(3):
+                rec = ((kb * tiles + tile) * 3 + pl) * 1024
+                for h in range(2):
+                    for r in range(32):
+                        row = tile * 32 + r
+                        if row >= M:
+                            continue
+                        v = planes[pl][row, 16 * kb + 8 * h:16 * kb + 8 * h + 8]
+                        u16 = (v.view(np.uint32) >> 16).astype(np.uint16)
+                        assert ((v.view(np.uint32) & 0xffff) == 0).all()     # bf16 values
+                        at = rec + h * 512 + r * 16
+                        img[at:at + 16] = u16.view(np.uint8)
+    got = KR.x3_decode(img, M, D)
+    for pl in range(3):
+        np.testing.assert_array_equal(got[pl].view(np.uint32), planes[pl].view(np.uint32))
+    # the offsets name every byte of the rows < M once and nothing else
+    off = KR.x3_offsets(M, D)
+    owned = np.zeros(img.size, np.int32)
+    np.add.at(owned, off.reshape(-1), 1)
+    np.add.at(owned, off.reshape(-1) + 1, 1)
+    assert owned.max() == 1 and owned.sum() == 3 * M * D * 2
+    assert (img[owned == 0] == 0xA5).all()
+
+
+@pytest.mark.parametrize('D', [256, 512])
+def test_ref_ffn_reduce_modes(D):
+    c = KR.make_ffn_reduce_case(5, D, 9, 0.5, seed=D)
+    args = (c['x'], c['P'], c['fb2'], c['alpha'], c['w'], c['b'], c['w2'], c['b2'], c['eps'])
+    x_new = c['x'].double() + 0.5 * (c['P'].double().sum(0) + c['fb2'].double())
+    x0, y0 = KR.ref_ffn_reduce(*args, 0)
+    _close(x0, x_new)
+    _close(y0, KR.ref_layernorm(x_new, c['w'], c['b'], c['eps']))
+    x1, y1 = KR.ref_ffn_reduce(*args, 1)
+    assert torch.equal(x1, KR.ref_layernorm(x0, c['w'], c['b'], c['eps']))
+    assert torch.equal(y1, KR.ref_layernorm(KR.ref_layernorm(x0, c['w'], c['b'], c['eps']),
+                                            c['w2'], c['b2'], c['eps']))
+    x2, y2 = KR.ref_ffn_reduce(*args, 2)
+    assert torch.equal(x2, x1) and y2 is None
+
+
+@pytest.mark.parametrize('D', [256, 512])
+@pytest.mark.parametrize('alpha', [0.5, 16.0])
+def test_ffn_reduce_caps(D, alpha):
+    for S in (1, 9, 32):
+        c = KR.make_ffn_reduce_case(9, D, S, alpha, seed=D + S)
+        for mode in (0, 1, 2):
+            _, ex, ey = KR.ffn_reduce_refs(c, mode)
+            assert KR.cap_ok(*ex) and (ey is None or KR.cap_ok(*ey)), (S, mode, ex, ey)
+
+
+@pytest.mark.parametrize('K', [96, 128, 256, 512])
+def test_gemm_rowln_caps(K):
+    c = KR.make_gemm_rowln_case(95, K, seed=K)
+    for bias, resid, alpha in ((True, True, 0.5), (False, True, 1.0), (True, False, 1.0),
+                               (False, False, 0.5)):
+        (x, y), ex, ey = KR.gemm_rowln_refs(c, bias, resid, alpha)
+        assert x.shape == y.shape == (95, 256)
+        assert KR.cap_ok(*ex) and KR.cap_ok(*ey), (bias, resid, alpha, ex, ey)
+    want = c['resid'].double() + 0.5 * (c['A'].double() @ c['W'].double().t() + c['bias'].double())
+    (x, y), _, _ = KR.gemm_rowln_refs(c, True, True, 0.5)
+    _close(x, want)
+    _close(y, KR.ref_layernorm(want, c['ln_w'], c['ln_b'], c['eps']))
+
+
+def test_oracle_defines_the_scale_of_an_all_zero_mx_block():
+    """What test_gpu_rows.py's zero-block case of layernorm_mx relies on: amax = 0 gives the scale
+    byte 0 and zero elements."""
+    x = torch.randn(3, 256)
+    x[:, 64:96] = 0.0
+    q, E = O.mx_quantize(x)
+    assert (E[:, 2] == 0).all() and (q.view(torch.uint8)[:, 64:96] == 0).all()
+    assert (E[:, [0, 1, 3]] > 0).all()

@@ -84,6 +84,8 @@ EXPORTS = [
     'wn_op_joint_logp_gather', 'wn_op_rnnt_lattice',
     'wn_op_attn_self_step', 'wn_op_attn_step_embed', 'wn_op_attn_prompt_cache', 'wn_op_beam_init',
     'wn_op_beam_update', 'wn_op_beam_finish',
+    'wn_op_layernorm_ex', 'wn_op_layernorm2', 'wn_op_layernorm_mx', 'wn_op_ffn_reduce_ln',
+    'wn_op_gemm_rowln',
 ]
 
 _lib = None
@@ -224,6 +226,13 @@ def lib():
     L.wn_op_beam_update.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, i32, pi32, vp]
     L.wn_op_beam_finish.argtypes = [i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
+    L.wn_op_layernorm_ex.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, f32, i32, vp]
+    L.wn_op_layernorm2.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, vp]
+    L.wn_op_layernorm_mx.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, vp]
+    L.wn_op_ffn_reduce_ln.argtypes = [vp, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, i64, i32, i32,
+                                      f32, i32, vp]
+    L.wn_op_gemm_rowln.argtypes = [vp, i32, vp, vp, vp, i32, f32, vp, i32, vp, vp, f32, vp, i32,
+                                   i32, i32, vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

@@ -63,6 +63,11 @@ int device_ints_in_range(const int32_t* dev, int rows, int ld, int cols, int hi,
   return 0;
 }
 
+// the widths a row kernel's launcher has a case for
+bool width_in(int D, std::initializer_list<int> widths) {
+  return std::find(widths.begin(), widths.end(), D) != widths.end();
+}
+
 }  // namespace
 }  // namespace wn
 
@@ -662,6 +667,85 @@ int wn_op_beam_finish(int32_t B, int32_t N, int32_t len, int32_t max_len, int32_
            "beam_finish: need 0 <= prefix <= len <= max_len");
   return attn_beam_finish(B, N, len, max_len, eos, length_penalty, score, tok, out_tok, out_len,
                           (hipStream_t)stream, prefix);
+}
+
+// ---- the kernels that own a complete row: LayerNorm family, FFN reduce, row-LN GEMM ----------
+
+int wn_op_layernorm_ex(const float* x, int32_t ldx, const float* w, const float* b, void* y,
+                       int32_t ldy, int32_t M, int32_t D, float eps, int32_t y_bf16, void* stream) {
+  WN_CHECK(x && w && b && y, "layernorm: null argument");
+  WN_CHECK(M > 0, "layernorm: empty");
+  WN_CHECK(width_in(D, {64, 128, 192, 256, 384, 512, 640, 768, 1024, 1280}),
+           "layernorm: unsupported width " + std::to_string(D));
+  WN_CHECK(ldx >= D && ldy >= D && ldx % 4 == 0 && ldy % 4 == 0,
+           "layernorm: a row stride is smaller than the width or no multiple of 4");
+  return layernorm(x, ldx, w, b, reinterpret_cast<float*>(y), ldy, M, D, eps,
+                   (hipStream_t)stream, y_bf16 != 0);
+}
+
+int wn_op_layernorm2(const float* x, const float* w1, const float* b1, const float* w2,
+                     const float* b2, float* y1, void* y2, int32_t M, int32_t D, float eps,
+                     int32_t y2_bf16, void* stream) {
+  WN_CHECK(x && w1 && b1 && w2 && b2 && y1 && y2, "layernorm2: null argument");
+  WN_CHECK(M > 0, "layernorm2: empty");
+  WN_CHECK(width_in(D, {64, 128, 256, 512, 768, 1024, 1280}),
+           "layernorm2: unsupported width " + std::to_string(D));
+  return layernorm2(x, w1, b1, w2, b2, y1, reinterpret_cast<float*>(y2), M, D, eps,
+                    (hipStream_t)stream, y2_bf16 != 0);
+}
+
+int wn_op_layernorm_mx(const float* x, int32_t ldx, const float* w, const float* b, void* q,
+                       void* scale, int32_t pitch, int32_t M, int32_t D, float eps, void* stream) {
+  WN_CHECK(x && w && b && q && scale, "layernorm_mx: null argument");
+  WN_CHECK(M > 0, "layernorm_mx: empty");
+  WN_CHECK(width_in(D, {256, 512, 768, 1024, 1280}),
+           "layernorm_mx: unsupported width " + std::to_string(D));
+  WN_CHECK(ldx >= D && ldx % 4 == 0,
+           "layernorm_mx: the row stride is smaller than the width or no multiple of 4");
+  WN_CHECK(pitch >= M, "layernorm_mx: scale pitch smaller than M");
+  return layernorm_mx(x, ldx, w, b, q, reinterpret_cast<unsigned*>(scale), pitch, M, D, eps,
+                      (hipStream_t)stream);
+}
+
+int wn_op_ffn_reduce_ln(float* x, const float* P, int32_t S, const float* b2, float alpha,
+                        const float* w, const float* b, const float* w2, const float* bb2, float* y,
+                        void* y3, int64_t y3_bytes, int32_t M, int32_t D, float eps, int32_t mode,
+                        void* stream) {
+  WN_CHECK(x && P && b2 && w && b, "ffn_reduce_ln: null argument");
+  WN_CHECK(M > 0, "ffn_reduce_ln: empty");
+  WN_CHECK(D == 256 || D == 512, "ffn_reduce_ln: unsupported width " + std::to_string(D));
+  WN_CHECK(S >= 1, "ffn_reduce_ln: S must be at least 1");
+  WN_CHECK(mode >= 0 && mode <= 2, "ffn_reduce_ln: mode outside 0..2");
+  WN_CHECK(mode != 1 || (w2 && bb2), "ffn_reduce_ln: null argument (mode 1 needs w2 and bb2)");
+  if (y3) {
+    WN_CHECK(mode == 1, "ffn_reduce_ln: the plane image form is mode 1");
+    WN_CHECK(y3_bytes >= 0 && (uint64_t)y3_bytes >= x6_bytes(M, D),
+             "ffn_reduce_ln: y3_bytes is smaller than the plane image");
+    return ffn_reduce_ln_img(x, P, S, b2, alpha, w, b, w2, bb2, y3, M, D, eps,
+                             (hipStream_t)stream);
+  }
+  WN_CHECK(mode == 2 || y, "ffn_reduce_ln: null argument (modes 0 and 1 write y)");
+  return ffn_reduce_ln(x, P, S, b2, alpha, w, b, w2, bb2, y, M, D, eps, mode,
+                       (hipStream_t)stream);
+}
+
+int wn_op_gemm_rowln(const float* A, int32_t lda, const float* W, const float* bias,
+                     const float* resid, int32_t ldr, float alpha, float* x_out, int32_t ldx,
+                     const float* ln_w, const float* ln_b, float eps, float* y, int32_t ldy,
+                     int32_t M, int32_t K, void* stream) {
+  WN_CHECK(A && W && x_out && y && ln_w && ln_b, "gemm_rowln: null argument");
+  WN_CHECK(M > 0, "gemm_rowln: empty");
+  WN_CHECK(K % 32 == 0 && K >= 96, "gemm_rowln: K must be a multiple of 32, at least 96");
+  WN_CHECK(lda >= K && lda % 4 == 0, "gemm_rowln: lda is smaller than K or no multiple of 4");
+  WN_CHECK(ldr >= 256 && ldx >= 256 && ldy >= 256, "gemm_rowln: ldr / ldx / ldy below 256");
+  // (the kernel addresses A and W with 32-bit byte offsets)
+  WN_CHECK((int64_t)M * lda * 4 < ((int64_t)1 << 31) && (int64_t)256 * K * 4 < ((int64_t)1 << 31),
+           "gemm_rowln: A or W is 2 GiB or more");
+  RowLnArgs a;
+  a.A = A; a.lda = lda; a.W = W; a.bias = bias; a.resid = resid; a.ldr = ldr; a.alpha = alpha;
+  a.x_out = x_out; a.ldx = ldx; a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps; a.y = y; a.ldy = ldy;
+  a.M = M; a.N = 256; a.K = K;
+  return gemm_rowln(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -13,32 +13,22 @@ namespace {
 
 // (RowRegs / ln_inplace: rowregs.h)
 
-// One wave per row; with RPW = 2 a wave owns two adjacent rows and issues both
-// row loads before the first reduction (twice the bytes in flight per CU).
-// Measured r01f: 3.9 vs 4.1 us isolated on 7932 x 256 (4.2 TB/s, cache
-// resident), 11.1 vs 10.8 us on 15800 x 512, no change of the decode step ->
-// RPW = 1 stays the default, RPW = 2 is wn_tune_set("ln_rows", 2).
-template <int E, int RPW>
+// One wave per row.  (History: a form in which a wave owned two adjacent rows and issued both
+// row loads before the first reduction -- twice the bytes in flight per CU -- measured, r01f,
+// 3.9 vs 4.1 us isolated on 7932 x 256 (4.2 TB/s, cache resident), 11.1 vs 10.8 us on
+// 15800 x 512, no change of the decode step; it was dropped.)
+template <int E>
 __global__ __launch_bounds__(256) void layernorm_kernel(
     const float* __restrict__ x, int ldx, const float* __restrict__ w,
     const float* __restrict__ b, float* __restrict__ y, int ldy, int M,
     float eps) {
   const int lane = threadIdx.x & 63;
-  const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
-  if (row0 >= M) return;
-  RowRegs<E> r[RPW];
-#pragma unroll
-  for (int i = 0; i < RPW; ++i) {
-    const int row = min(row0 + i, M - 1);
-    r[i].load(x + (int64_t)row * ldx, lane);
-  }
-#pragma unroll
-  for (int i = 0; i < RPW; ++i) {
-    if (row0 + i < M) {
-      ln_inplace<E>(r[i], w, b, lane, eps);
-      r[i].store(y + (int64_t)(row0 + i) * ldy, lane);
-    }
-  }
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  RowRegs<E> r;
+  r.load(x + (int64_t)row * ldx, lane);
+  ln_inplace<E>(r, w, b, lane, eps);
+  r.store(y + (int64_t)row * ldy, lane);
 }
 
 // y1 = LN(x; w1, b1); y2 = LN(y1; w2, b2): norm_final of layer i followed by
@@ -864,7 +854,7 @@ int layernorm(const float* x, int ldx, const float* w, const float* b, float* y,
   dim3 g(cdiv(M, 4)), t(256);
 #define WN_LN(E)                                                                 \
   case E * 64:                                                                   \
-    hipLaunchKernelGGL((layernorm_kernel<E, 1>), g, t, 0, s, x, ldx, w, b, y,    \
+    hipLaunchKernelGGL((layernorm_kernel<E>), g, t, 0, s, x, ldx, w, b, y,       \
                        ldy, M, eps);                                             \
     break;
   switch (D) {
