@@ -876,6 +876,75 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
                                 int32_t* tok_lens_host, int32_t max_len, int32_t* steps_out,
                                 void* stream);
 
+/* ---- streaming transducer sessions: resumable RNN-T greedy search ---------- */
+/* wn_transducer_greedy_search for sessions that receive their encoder frames chunk by chunk (the
+ * reference has no such entry point: its greedy search is one-shot, transducer.py:427 "TODO
+ * forward chunk by chunk").  A set of `n_slots` independent sessions whose search state -- the
+ * LSTM's h / c, the projected predictor output, the last token, the tokens with the encoder
+ * frame of each, the frame counters -- lives in HBM between calls.  Feeding a session its frames
+ * in any pieces gives the token list the one-shot search gives for all of them at once, and
+ * after every call the list it gives for the frames so far; a session's state is bit for bit the
+ * same whatever the pieces, the window (tune key "rnnt_lookahead"), its slot and the other
+ * sessions of a call.  Every call names the sessions it touches by slot id; calls on one set must
+ * be ordered (one stream, or events between streams).  A set belongs to the handle it was created
+ * on and must be destroyed before it; its workspace is its own, so other searches on the handle
+ * between two calls leave the sessions alone.  Always fp32, as the one-shot search. */
+typedef struct wn_rnnt_stream_set wn_rnnt_stream_set;
+
+/* Where wn_rnnt_stream_advance_encoded puts its results (all HOST arrays, the n sessions of the
+ * call in call order): tok_lens (n) the tokens each session holds after the call; tokens, times
+ * (n, max_len) the whole list so far and the absolute encoder frame of each token
+ * (non-decreasing, at most n_steps equal entries), of each row the first tok_lens entries
+ * written; frames_decoded (n) the frames the session has consumed; trailing_blank (n) the frames
+ * consumed behind the frame of its last token, or all of them if it has none (this project's
+ * definition: the reference has no RNN-T endpointing).  max_len must be >= what a session's
+ * token count may become in the call: min(tokens before + n_t * n_steps, max_tokens).  steps:
+ * the lock-step steps of the call, may be NULL. */
+typedef struct wn_rnnt_stream_result {
+  int32_t* tok_lens;
+  int32_t* tokens;
+  int32_t* times;
+  int32_t* frames_decoded;
+  int32_t* trailing_blank;
+  int32_t max_len;
+  int32_t* steps;
+} wn_rnnt_stream_result;
+
+/* Allocate the state of n_slots sessions (1..256), once: at most max_frames encoder frames and
+ * max_tokens stored tokens per session, n_steps symbols per frame at most (the reference's
+ * n_steps, 64).  Every slot starts reset.  -1 with a wn_last_error text on a handle that
+ * wn_model_create_transducer did not build (no transducer weights). */
+int wn_rnnt_stream_create(wn_model* m, int32_t n_slots, int32_t max_frames, int32_t max_tokens,
+                          int32_t n_steps, wn_rnnt_stream_set** out, void* stream);
+int wn_rnnt_stream_destroy(wn_rnnt_stream_set* set);
+
+/* Zero predictor state, last token = blank, no tokens, counters to zero for the n sessions in
+ * slot_ids (host); the other sessions keep their state bit for bit. */
+int wn_rnnt_stream_reset(wn_rnnt_stream_set* set, int32_t n, const int32_t* slot_ids,
+                         void* stream);
+
+/* The search on the next frames of n sessions: enc_out_dev is the (n, chunk, d_model) encoder
+ * output of wn_encode_chunk_batch on the device, session i consumes its first n_t_host[i] rows
+ * (0 <= n_t <= chunk; 0 leaves the session's state bit for bit).  joint.enc_ffn runs once over the
+ * n x chunk rows, then the lock-step loop of wn_transducer_greedy_search over the call's frames:
+ * groups of 8 steps, at most chunk x (n_steps + 1) + 1 of them.  A token that the n_steps cap
+ * emits on a call's last frame leaves its predictor step to the next call with frames.
+ * Refused on the host, before any launch, with -1 and a wn_last_error text that names the
+ * argument: n outside [1, n_slots]; a slot id out of range; the same slot twice in one call; n_t
+ * outside [0, chunk]; a call that would take a session past max_frames; a max_len smaller than
+ * stated above.  A refused call changes no session.
+ * A session whose tokens pass max_tokens keeps counting and stops storing: the call returns -1
+ * with "token buffer overflow" (the other sessions of the call did advance), and that session
+ * must be reset. */
+int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int32_t* slot_ids,
+                                   const float* enc_out_dev, const int32_t* n_t_host,
+                                   int32_t chunk, const wn_rnnt_stream_result* out, void* stream);
+
+/* Test hook: one slot's h, c (layers x H each), pred_proj (join_dim) and
+ * {last_tok, stale, n_tok, frames, trailing_blank} copied to the host. */
+int wn_rnnt_stream_state(wn_rnnt_stream_set* set, int32_t slot, float* h, float* c,
+                         float* pred_proj, int32_t* scalars5, void* stream);
+
 /* RNN-T prefix beam search over the handle's CURRENT batch: PrefixBeamSearch.prefix_beam_search
  * (wenet/models/transducer/search/prefix_beam_search.py:42-148, reached through
  * Transducer.beam_search, transducer.py:216-260), which the reference runs one utterance at a

@@ -22,6 +22,16 @@ sessions have that much audio behind them when the measurement starts (the searc
 brought there first).  `--requadratic`: also time what a caller had to do before the
 resumable search existed to get a partial after every chunk -- search.ctc_prefix_beam_search
 over ALL log-probs received so far (`rerun_step_ms_*`).
+
+--rnnt: the same question for the hybrid transducer's streaming sessions.  Model
+`aishell_u2pp_rnnt` (conformer_u2pp_rnnt.yaml at full width), N sessions with 5 s of audio
+behind them (put back there before every block of the resumable search), chunk 16, the window `rnnt_lookahead` 1 / 4 / 16 set on the handle.  Per N and
+window the step latency of (a) the encoder chunk alone, (b) the chunk + the resumable RNN-T
+greedy search (wenet_amd.streaming.RnntStreamSearch.advance_encoded) and (c) the chunk + the
+one-shot wn_transducer_greedy_search over the 5 s of history and the new chunk -- what a caller
+had to run for a partial before the sessions existed; blocks of 10 steps of each kind in turn.
+Host clock around work that ends in a device synchronise.  Writes
+profiles/streaming_rnnt_sessions.json (or --out).
 """
 import argparse
 import json
@@ -53,7 +63,12 @@ def main():
     ap.add_argument('--requadratic', action='store_true',
                     help='--search: also time the one-shot search over everything so far')
     ap.add_argument('--nbest', action='store_true', help='--search: n-best partials')
+    ap.add_argument('--rnnt', action='store_true',
+                    help='streaming transducer sessions: resumable vs one-shot RNN-T greedy search')
+    ap.add_argument('--lookahead', default='1,4,16', help='--rnnt: rnnt_lookahead values')
     args = ap.parse_args()
+    if args.rnnt:
+        return rnnt_main(args)
     from wenet_amd import synthetic as S
     from wenet_amd.model import ASRModel
     dev = torch.device('cuda', 0)
@@ -165,6 +180,106 @@ def search_rows(args, model, dev, n, xs, att, cnn, offsets, req, secs):
         out[names[k] + '_p99'] = round(float(np.percentile(a, 99)), 3)
     out['search_minus_step_ms'] = round(out['search_step_ms_median'] - out['step_ms_median'], 3)
     return out
+
+
+def rnnt_main(args):
+    from wenet_amd import Transducer
+    from wenet_amd import synthetic as S
+    from wenet_amd.streaming import RnntStreamSearch
+    from wenet_amd.transducer import basic_greedy_search
+    dev = torch.device('cuda', 0)
+    config = 'aishell_u2pp_rnnt' if args.config == 'wenetspeech_u2pp' else args.config
+    configs = S.make_configs(config)
+    model = Transducer(configs, S.make_state_dict(configs, 0), device=dev)
+    tc = model._tcfg
+    chunk = args.chunk
+    window = (chunk - 1) * 4 + 7
+    req = chunk * args.left if args.left >= 0 else -1
+    secs = float(args.utt_seconds.split(',')[0])
+    hist = int(round(secs / 0.04))
+    n_hist = (hist + chunk - 1) // chunk
+    n_steps = 64
+    rows = []
+    for n in [int(x) for x in args.sessions.split(',')]:
+        feats, _ = S.make_features(n, window, seed=5, feat_dim=configs['input_dim'])
+        xs = feats.to(dev)
+        for F in [int(x) for x in args.lookahead.split(',')]:
+            assert model.tune('rnnt_lookahead', F) == F
+            att, cnn, offsets = [None] * n, [None] * n, [0] * n
+            total = chunk * (n_hist + max(args.warmup // 2, 3) + 12)
+            rs = RnntStreamSearch(model._h, dev, n, total, total * n_steps, n_steps,
+                                  dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
+            slots = list(range(n))
+            past = []
+            for _ in range(n_hist):            # the sessions' history: 5 s of encoder output
+                ys, att, cnn = model.forward_encoder_chunk_batch(xs, offsets, req, att, cnn)
+                offsets = [o + chunk for o in offsets]
+                rs.advance_encoded(slots, ys)
+                past.append(ys)
+            past_chunks = past
+            past = torch.cat(past, 1)[:, -hist:].contiguous()
+            state = dict(att=att, cnn=cnn, offsets=offsets, steps=[], rerun_steps=[])
+
+            def step(kind):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ys, state['att'], state['cnn'] = model.forward_encoder_chunk_batch(
+                    xs, state['offsets'], req, state['att'], state['cnn'])
+                if kind == 'search':
+                    state['steps'].append(rs.advance_encoded(slots, ys).steps)
+                elif kind == 'rerun':
+                    sofar = torch.cat([past, ys], 1)
+                    basic_greedy_search(model, sofar, [sofar.size(1)] * n, n_steps)
+                    state['rerun_steps'].append(model.last_rnnt_steps)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0      # (the offset stays at 5 s, as in --search)
+                if args.left < 0 and state['att'][0].size(2) > args.max_cache:
+                    state['att'] = [a[:, :, -args.max_cache:].contiguous() for a in state['att']]
+                return dt
+
+            kinds = ['none', 'search', 'rerun']
+            lat = {k: [] for k in kinds}
+            for k in kinds:
+                for _ in range(max(args.warmup // 2, 3)):
+                    step(k)
+            state['steps'], state['rerun_steps'] = [], []
+            for _ in range(max(args.steps // 10, 1)):
+                for k in kinds:
+                    if k == 'search':      # back to 5 s of audio behind every session (untimed)
+                        rs.reset(slots)
+                        for ys in past_chunks:
+                            rs.advance_encoded(slots, ys)
+                    for _ in range(10):
+                        lat[k].append(step(k))
+            row = dict(sessions=n, chunk=chunk, left_chunks=args.left, rnnt_lookahead=F,
+                       history_frames=hist, n_steps=n_steps,
+                       tokens_per_session=round(float(np.mean(rs.n_tok)), 1),
+                       frames_per_session=int(rs.frames[0]),
+                       lockstep_steps_per_call=round(float(np.mean(state['steps'])), 1),
+                       rerun_lockstep_steps=round(float(np.mean(state['rerun_steps'])), 1))
+            names = dict(none='step_ms', search='stream_step_ms', rerun='rerun_step_ms')
+            for k in kinds:
+                a = np.asarray(lat[k]) * 1e3
+                row[names[k] + '_median'] = round(float(np.median(a)), 3)
+                row[names[k] + '_p99'] = round(float(np.percentile(a, 99)), 3)
+            row['stream_minus_step_ms'] = round(row['stream_step_ms_median'] - row['step_ms_median'], 3)
+            row['rerun_minus_step_ms'] = round(row['rerun_step_ms_median'] - row['step_ms_median'], 3)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            rs.close()
+            model.tune('rnnt_lookahead', 'inherit')
+    out = args.out or os.path.join(ROOT, 'profiles', 'streaming_rnnt_sessions.json')
+    with open(out, 'w') as f:
+        json.dump(dict(
+            model=config, steps=args.steps, warmup=args.warmup,
+            note='step latency, host clock around a device synchronise, one MI355X; blocks of 10 '
+                 'steps of each kind in turn',
+            step_ms='(a) encoder chunk forward for all sessions',
+            stream_step_ms='(b) encoder chunk + wn_rnnt_stream_advance_encoded (joint.enc_ffn over '
+                           'the chunk + resumable greedy search, tokens and times to the host)',
+            rerun_step_ms='(c) encoder chunk + wn_transducer_greedy_search over the history and '
+                          'the new chunk (history_frames + chunk frames per session)',
+            rows=rows), f, indent=1)
 
 
 if __name__ == '__main__':

@@ -45,6 +45,15 @@ class WnStreamResult(Structure):
                 ('trailing_blank', POINTER(c_int32)), ('max_len', c_int32)]
 
 
+class WnRnntStreamResult(Structure):
+    """wn_rnnt_stream_result: where wn_rnnt_stream_advance_encoded puts a call's results (host
+    arrays)."""
+    _fields_ = [('tok_lens', POINTER(c_int32)), ('tokens', POINTER(c_int32)),
+                ('times', POINTER(c_int32)), ('frames_decoded', POINTER(c_int32)),
+                ('trailing_blank', POINTER(c_int32)), ('max_len', c_int32),
+                ('steps', POINTER(c_int32))]
+
+
 class WnAttentionOp(Structure):
     """wn_attention_op: the arguments of wn_op_attention."""
     _fields_ = [('Q', c_void_p), ('K', c_void_p), ('V', c_void_p),
@@ -79,6 +88,8 @@ EXPORTS = [
     'wn_model_create_transducer', 'wn_transducer_greedy_search', 'wn_op_lstm_step',
     'wn_op_joint_argmax', 'wn_transducer_beam_search', 'wn_op_joint_fuse_topk',
     'wn_op_rnnt_beam_step', 'wn_transducer_beam_stats',
+    'wn_rnnt_stream_create', 'wn_rnnt_stream_destroy', 'wn_rnnt_stream_reset',
+    'wn_rnnt_stream_advance_encoded', 'wn_rnnt_stream_state',
     'wn_transducer_score', 'wn_transducer_score_stats', 'wn_transducer_score_times',
     'wn_op_rnnt_trie',
     'wn_op_joint_logp_gather', 'wn_op_rnnt_lattice',
@@ -199,6 +210,13 @@ def lib():
     L.wn_model_create_transducer.argtypes = [POINTER(WnConfig), POINTER(WnTransducerConfig),
                                              POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_transducer_greedy_search.argtypes = [vp, i32, pi32, pi32, i32, pi32, vp]
+    L.wn_rnnt_stream_create.argtypes = [vp, i32, i32, i32, i32, POINTER(vp), vp]
+    L.wn_rnnt_stream_destroy.argtypes = [vp]
+    L.wn_rnnt_stream_reset.argtypes = [vp, i32, pi32, vp]
+    L.wn_rnnt_stream_advance_encoded.argtypes = [vp, i32, pi32, vp, pi32, i32,
+                                                 POINTER(WnRnntStreamResult), vp]
+    L.wn_rnnt_stream_state.argtypes = [vp, i32, POINTER(f32), POINTER(f32), POINTER(f32), pi32,
+                                       vp]
     L.wn_op_lstm_step.argtypes = [vp, POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, i32, i32,
                                   i32, vp]
     L.wn_op_joint_argmax.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, pi32,

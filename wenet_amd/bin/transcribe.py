@@ -44,6 +44,10 @@ def get_args(argv=None):
                    help='decode through a streaming session, printing partial results')
     p.add_argument('--chunk', type=int, default=16,
                    help='decoding_chunk_size of --stream (encoder frames per step)')
+    p.add_argument('--search', default='ctc_prefix_beam_search',
+                   choices=['ctc_prefix_beam_search', 'rnnt_greedy_search'],
+                   help='the search of --stream; rnnt_greedy_search needs a transducer model '
+                        'and does no attention rescoring')
     p.add_argument('--align', action='store_true',
                    help='force align the input audio and transcript')
     p.add_argument('--label', type=str, default=None, help='the input label to align')
@@ -69,13 +73,14 @@ def align_file(model, audio_file, label, out=print):
     return r
 
 
-def stream_file(model, audio_file, chunk, beam_size=10, out=print):
+def stream_file(model, audio_file, chunk, beam_size=10, out=print,
+                search='ctc_prefix_beam_search'):
     """One streaming session over the file; `out` gets each changed partial, then the final
     result's text.  Returns the final DecodeResult."""
     from wenet_amd.streaming import StreamingRecognizer
     speech = model.compute_feature(audio_file).to(model.device)
     rec = StreamingRecognizer(model, 1, chunk, beam_size=beam_size,
-                              max_seconds=speech.size(0) / 100.0 + 1.0)
+                              max_seconds=speech.size(0) / 100.0 + 1.0, search=search)
     sid = rec.open()
     piece = chunk * model.subsampling_rate()
     shown = None
@@ -103,7 +108,8 @@ def main(argv=None):
     if args.stream:
         if args.context_path is not None:
             raise SystemExit('--stream does not support --context_path')
-        result = stream_file(model, args.audio_file, args.chunk, args.beam or 10)
+        result = stream_file(model, args.audio_file, args.chunk, args.beam or 10,
+                             search=args.search)
     elif args.beam is None and args.context_path is None and args.task is None \
             and args.lang is None:
         result = model.transcribe(args.audio_file)      # asr_model.py:345-358

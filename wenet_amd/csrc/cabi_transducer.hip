@@ -5,45 +5,7 @@
 #include <algorithm>
 
 #include "model_state.h"
-
-namespace wn {
-namespace {
-
-constexpr int RNNT_GROUP = 8;     // steps issued between two looks at n_active
-
-// one predictor step for the advancing rows: LSTM layers in place on h / c [L][B][H], then the
-// projection into out [B][P] (proj.w == nullptr: none)
-int predictor_step(const float* x, int ldx, const int* x_rows, int E,
-                   const ModelData::LstmLayer* layers, int L, const Linear& proj, float* h,
-                   float* c, float* gates, float* out, const int* advance, const int* n_active,
-                   int B, int H, hipStream_t s) {
-  for (int l = 0; l < L; ++l) {
-    float* hl = h + (size_t)l * B * H;
-    RnntLinearArgs g;
-    if (l == 0) { g.x1 = x; g.ldx1 = ldx; g.x1_rows = x_rows; g.K1 = E; }
-    else { g.x1 = h + (size_t)(l - 1) * B * H; g.ldx1 = H; g.K1 = H; }
-    g.W1 = layers[l].w_ih; g.b1 = layers[l].b_ih;
-    g.x2 = hl; g.ldx2 = H; g.W2 = layers[l].w_hh; g.K2 = H; g.b2 = layers[l].b_hh;
-    g.y = gates; g.ldy = 4 * H; g.N = 4 * H; g.B = B;
-    g.advance = advance; g.n_active = n_active;
-    WN_TRY(rnnt_linear(g, s));
-    WN_TRY(rnnt_cell(gates, hl, c + (size_t)l * B * H, advance, B, H, n_active, s));
-  }
-  if (proj.w) {
-    RnntLinearArgs g;
-    g.x1 = h + (size_t)(L - 1) * B * H; g.ldx1 = H; g.K1 = H;
-    g.W1 = proj.w; g.b1 = proj.b;
-    g.y = out; g.ldy = proj.out; g.N = proj.out; g.B = B;
-    g.advance = advance; g.n_active = n_active;
-    WN_TRY(rnnt_linear(g, s));
-  }
-  return 0;
-}
-
-size_t up64(size_t n) { return (n + 63) / 64 * 64; }
-
-}  // namespace
-}  // namespace wn
+#include "rnnt_predictor.h"
 
 extern "C" {
 

@@ -554,6 +554,45 @@ int rnnt_advance(const float* part_max, const int* part_idx, int ncb, int V, con
 int rnnt_reduce_partials(const float* part_max, const int* part_idx, int ncb, int M,
                          float* out_max, int* out_idx, hipStream_t s);
 
+// Resumable RNN-T greedy search (transducer_stream.hip): the state of a set of sessions, one
+// slot each, that stays in HBM between calls.  Arrays of n_slots entries unless noted.
+struct RnntStreamSlots {
+  float* h; float* c;               // [n_slots][L][H]
+  float* pred_proj;                 // [n_slots][J]
+  int* last_tok; int* stale;        // stale: pred_proj does not belong to last_tok yet
+  int* n_tok; int* frames;          // tokens emitted (counts on past max_tok), frames consumed
+  int* trailing_blank;              // frames consumed behind the frame of the last token
+  int* last_time;                   // the absolute frame of the last token, -1: none
+  int* tokens; int* times; int max_tok;   // [n_slots][max_tok]
+  int L, H, J;
+};
+// The compact batch of one call over n sessions: what rnnt_linear / rnnt_cell / rnnt_joint_argmax
+// run on unchanged.  Device arrays of n entries unless noted.
+struct RnntStreamCall {
+  const int* slot; const int* n_t;  // the call's sessions and the frames each consumes
+  float* h; float* c;               // [L][n][H]
+  float* pred_proj;                 // [n][J]
+  int* last_tok; int* advance; int* done; int* t; int* cnt;
+  int* row_enc; int* row_pred;      // [n x F] rows of the next joint launch (enc row i chunk + t)
+  int* n_active; int* steps;        // [1]
+  // results of the call, compact: n_tok | frames | trailing_blank [3][n], tokens | times
+  // [2][n][ld_out], of each row the first min(n_tok, max_tok) entries
+  int* out_stat; int* out_tok; int ld_out;
+};
+// gather the sessions' state into the compact batch; advance = stale && n_t > 0, done = n_t <= 0,
+// the first row map, n_active, steps = 0
+int rnnt_stream_begin(const RnntStreamSlots& sl, const RnntStreamCall& c, int n, int chunk, int F,
+                      hipStream_t s);
+// rnnt_advance's rule on the call's frames; tokens and their absolute frames go to the slot's
+// own buffers; a token that the n_steps cap emits on the call's last frame sets `stale`
+int rnnt_stream_advance(const float* part_max, const int* part_idx, int ncb, int V,
+                        const RnntStreamSlots& sl, const RnntStreamCall& c, int n, int chunk,
+                        int F, int blank, int n_steps, hipStream_t s);
+// scatter the compact state back, frames += n_t, the call's results into out_*
+int rnnt_stream_end(const RnntStreamSlots& sl, const RnntStreamCall& c, int n, hipStream_t s);
+// zero state, last_tok = blank, stale = 1, counters 0 for the n slots in `slot` (device)
+int rnnt_stream_reset(const RnntStreamSlots& sl, const int* slot, int n, int blank, hipStream_t s);
+
 // RNN-T prefix beam search (transducer_beam.hip), fp32 rows and fp64 scores.
 // Per live row (row_enc[m] >= 0): lse of the logits, f[v] = log(tw exp(l[v] - lse) +
 // cw exp(ctc[row_enc[m]][v])) (fp64 exp / log, one rounding to fp32) and the k largest (value, index), larger value first, the lower

@@ -25,6 +25,7 @@
 //    rnnt_reduce_kernel runs on its own for the operator hook), scans the window in frame order, applies the emission
 //    rule, appends tokens and writes the next step's row map, `advance`, `done`, `n_active`.
 // Plain stream-ordered launches; every kernel of a finished batch returns on n_active == 0.
+#include "rnnt_argmax.h"
 #include "rnnt_joint_tile.h"
 
 namespace wn {
@@ -88,32 +89,7 @@ __global__ __launch_bounds__(256) void rnnt_cell_kernel(const float* __restrict_
   h[idx] = go * tanhf(cn);
 }
 
-// (value, index) maximum, the lower index on equal values.  A NaN counts as the largest value,
-// as in torch.argmax (the first NaN of a row wins): a merge that never accepted one would leave
-// the caller's start index in place, which need not be a column of the matrix.
-__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
-  const bool on = ov != ov, vn = v != v;
-  const bool gt = ov > v || (on && !vn);
-  const bool eq = ov == v || (on && vn);
-  if (gt || (eq && oi < i)) { v = ov; i = oi; }
-}
-
-// one wave: (max, index) of a row's ncb column-block partials, the same pair in every lane.
-// Starts from the row's first partial, so the index is always one that the joint kernel wrote:
-// a column in [0, V), or -1 for an inert row.
-__device__ __forceinline__ void rnnt_reduce_row(const float* __restrict__ part_max,
-                                                const int* __restrict__ part_idx, int64_t base,
-                                                int ncb, int lane, float& v, int& i) {
-  v = part_max[base];
-  i = part_idx[base];
-  for (int cb = lane; cb < ncb; cb += 64) argmax_merge(v, i, part_max[base + cb], part_idx[base + cb]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, 64);
-    const int oi = __shfl_xor(i, o, 64);
-    argmax_merge(v, i, ov, oi);
-  }
-}
+// argmax_merge, rnnt_reduce_row: rnnt_argmax.h
 
 // FULL: the epilogue keeps the logits of every live row (p.logits, pitch p.ldl) instead of a
 // (max, index) per column block -- the beam search's instantiation.  The GEMM body is the one

@@ -15,7 +15,9 @@ Layers, bottom up:
   in pieces;
 * `CtcEndpointConfig` / `CtcEndpointRule` / `endpoint_rule`: the reference's endpoint rules
   evaluated on the host from the two counters the search kernel keeps;
-* `StreamingRecognizer`: open / accept / step / finish / close.
+* `RnntStreamSearch`: the same for a hybrid transducer -- resumable RNN-T greedy searches
+  (`wn_rnnt_stream_create`, csrc/transducer_stream.hip), advanced by encoder output;
+* `StreamingRecognizer`: open / accept / step / finish / close, with either search.
 """
 import ctypes
 from typing import Dict, List, Optional, Tuple
@@ -241,6 +243,116 @@ class _Results(list):
     raw = None
 
 
+class RnntStreamSearch:
+    """`n_slots` resumable RNN-T greedy searches on the device (wn_rnnt_stream_create; the
+    handle must be a `wenet_amd.Transducer`'s).
+
+    `advance_encoded(slots, enc_out, n_t)` feeds session slots[i] the first n_t[i] frames of
+    enc_out[i] and returns one DecodeResult per session for everything that session has
+    consumed so far -- what `transducer.basic_greedy_search` returns for those frames in one
+    call: `tokens`, `times` (the encoder frame of each token) and the extra attributes
+    `frames_decoded`, `trailing_blank`; `.raw` of the returned list holds the call's arrays and
+    `.steps` its lock-step steps.  `dims` = (predictor layers, hidden size, join_dim) is what
+    `state(slot)` needs to size its arrays."""
+
+    def __init__(self, handle: int, device, n_slots: int, max_frames: int, max_tokens: int,
+                 n_steps: int = 64, dims=None):
+        self._L = _lib.lib()
+        self.device = device
+        self.n_slots, self.max_frames, self.max_tokens = n_slots, max_frames, max_tokens
+        self.n_steps, self.dims = n_steps, dims
+        self.frames = [0] * n_slots         # frames every slot has consumed
+        self.n_tok = [0] * n_slots          # tokens every slot has emitted
+        self._set = None
+        h = ctypes.c_void_p()
+        _lib.check(self._L.wn_rnnt_stream_create(handle, n_slots, max_frames, max_tokens,
+                                                 n_steps, ctypes.byref(h), self._stream()),
+                   'wn_rnnt_stream_create')
+        self._set = h
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def close(self):
+        if self._set is not None:
+            self._L.wn_rnnt_stream_destroy(self._set)
+            self._set = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def reset(self, slots):
+        ids = np.asarray(list(slots), dtype=np.int32)
+        _lib.check(self._L.wn_rnnt_stream_reset(self._set, len(ids), _lib.i32p(ids),
+                                                self._stream()), 'wn_rnnt_stream_reset')
+        for s in ids.tolist():
+            self.frames[s] = self.n_tok[s] = 0
+
+    def advance_encoded(self, slots, enc_out, n_t=None, max_len=None):
+        """enc_out: (n, chunk, d_model) float32 encoder output on the device.  `max_len`: the
+        row pitch of the result arrays (default: what the call can need)."""
+        assert enc_out.is_cuda and enc_out.dim() == 3 and enc_out.size(0) == len(slots)
+        import torch
+        from wenet_amd.search import DecodeResult
+        enc_out = enc_out.detach().to(torch.float32).contiguous()
+        ids = np.asarray(list(slots), dtype=np.int32)
+        nt = np.asarray(list(n_t) if n_t is not None else [enc_out.size(1)] * len(ids),
+                        dtype=np.int32)
+        assert len(ids) == len(nt)
+        n = len(ids)
+        if max_len is None:
+            max_len = max([min(self.n_tok[s] + max(int(t), 0) * self.n_steps, self.max_tokens)
+                           for s, t in zip(ids.tolist(), nt.tolist())
+                           if 0 <= s < self.n_slots] + [1])
+        a = dict(tok_lens=np.zeros((n, ), np.int32), tokens=np.zeros((n, max_len), np.int32),
+                 times=np.zeros((n, max_len), np.int32),
+                 frames_decoded=np.zeros((n, ), np.int32),
+                 trailing_blank=np.zeros((n, ), np.int32), max_len=max_len,
+                 steps=np.zeros((1, ), np.int32))
+        r = _lib.WnRnntStreamResult(_lib.i32p(a['tok_lens']), _lib.i32p(a['tokens']),
+                                    _lib.i32p(a['times']), _lib.i32p(a['frames_decoded']),
+                                    _lib.i32p(a['trailing_blank']), max_len, _lib.i32p(a['steps']))
+        st = self._L.wn_rnnt_stream_advance_encoded(
+            self._set, n, _lib.i32p(ids), enc_out.data_ptr(), _lib.i32p(nt), enc_out.size(1),
+            ctypes.byref(r), self._stream())
+        if st != 0 and b'token buffer overflow' in self._L.wn_last_error():
+            # the sessions did advance; the device keeps counting past max_tokens
+            for s, t in zip(ids.tolist(), nt.tolist()):
+                self.frames[s] += int(t)
+                self.n_tok[s] = self.max_tokens
+        _lib.check(st, 'wn_rnnt_stream_advance_encoded')
+        out = _Results()
+        for b, s in enumerate(ids.tolist()):
+            self.frames[s] = int(a['frames_decoded'][b])
+            self.n_tok[s] = nl = int(a['tok_lens'][b])
+            res = DecodeResult(tokens=tuple(a['tokens'][b, :nl].tolist()),
+                               times=a['times'][b, :nl].tolist())
+            res.frames_decoded = int(a['frames_decoded'][b])
+            res.trailing_blank = int(a['trailing_blank'][b])
+            out.append(res)
+        out.raw = a
+        out.steps = int(a['steps'][0])
+        return out
+
+    def state(self, slot: int):
+        """wn_rnnt_stream_state: (h, c (layers, H), pred_proj (J), dict of the counters)."""
+        assert self.dims is not None, 'RnntStreamSearch.state needs dims=(layers, hidden, join_dim)'
+        L_, H, J = self.dims
+        h = np.zeros((L_, H), np.float32)
+        c = np.zeros((L_, H), np.float32)
+        pp = np.zeros((J, ), np.float32)
+        sc = np.zeros((5, ), np.int32)
+        _lib.check(self._L.wn_rnnt_stream_state(self._set, slot, _lib.f32p(h), _lib.f32p(c),
+                                                _lib.f32p(pp), _lib.i32p(sc), self._stream()),
+                   'wn_rnnt_stream_state')
+        names = ('last_tok', 'stale', 'n_tok', 'frames', 'trailing_blank')
+        return h, c, pp, dict(zip(names, sc.tolist()))
+
+
 # --------------------------------------------------------------------------- recognizer
 class _Session:
     __slots__ = ('slot', 'win', 'feats', 'base', 'att', 'cnn', 'offset', 'enc', 'last')
@@ -268,14 +380,35 @@ class StreamingRecognizer:
     `step()` advances every session that has a full window by one chunk in ONE
     `forward_encoder_chunk_batch` and ONE search call; its results carry `is_endpoint`
     (the endpoint rule that fired, or None) next to the search's counters.  Only causal,
-    chunk-trained Conformers are accepted (`ASRModel._check_simulate_streaming`)."""
+    chunk-trained Conformers are accepted (`ASRModel._check_simulate_streaming`).
+
+    `search='ctc_prefix_beam_search'` (default) is the CTC prefix beam search above.
+    `search='rnnt_greedy_search'` needs a `wenet_amd.Transducer` and runs the resumable RNN-T
+    greedy search (`RnntStreamSearch`, at most `n_steps` symbols per frame): partial and final
+    results are the greedy token lists with `times`; `beam_size` and `nbest` are not read,
+    and attention `rescoring` is NOT applied in this mode (finish() ignores it).  The endpoint
+    rules are fed with that search's counters: `trailing_blank` counts the frames consumed
+    behind the frame of the last token (this project's definition: the reference has no RNN-T
+    endpointing).  A session may store `max_tokens` tokens (default: 8 per encoder frame of
+    `max_seconds`, fewer if n_steps is smaller); one that emits more raises and must be closed."""
+
+    SEARCHES = ('ctc_prefix_beam_search', 'rnnt_greedy_search')
 
     def __init__(self, model, n_sessions: int, decoding_chunk_size: int,
                  num_decoding_left_chunks: int = -1, beam_size: int = 10,
                  max_seconds: float = 60.0, endpoint: Optional[CtcEndpointConfig] = None,
-                 blank_id: int = 0):
+                 blank_id: int = 0, search: str = 'ctc_prefix_beam_search', n_steps: int = 64,
+                 max_tokens: Optional[int] = None):
         import torch
         assert decoding_chunk_size > 0, 'decoding_chunk_size must be positive'
+        if search not in self.SEARCHES:
+            raise ValueError(f'search={search!r}: expected one of {self.SEARCHES}')
+        self.rnnt = search == 'rnnt_greedy_search'
+        if self.rnnt:
+            from wenet_amd.transducer import Transducer
+            if not isinstance(model, Transducer):
+                raise TypeError("search='rnnt_greedy_search' needs a wenet_amd.Transducer, got "
+                                f'{type(model).__name__}')
         model._check_simulate_streaming(torch.empty((1, 0, 0)))
         ctx = getattr(model, '_ctx_graph', None)
         if ctx is not None:
@@ -289,9 +422,17 @@ class StreamingRecognizer:
         self.endpoint = endpoint or CtcEndpointConfig(blank=blank_id)
         self.frame_shift_ms = 10 * self.subsampling
         max_frames = int(np.ceil(max_seconds * 1000.0 / self.frame_shift_ms)) + decoding_chunk_size
-        self.search = StreamSearch(model._h, model.device, n_sessions, beam_size, max_frames,
-                                   blank_id, self.endpoint.blank_threshold,
-                                   self.endpoint.blank_scale)
+        if self.rnnt:
+            tc = model._tcfg
+            if max_tokens is None:
+                max_tokens = max_frames * min(n_steps, 8)
+            self.search = RnntStreamSearch(model._h, model.device, n_sessions, max_frames,
+                                           max_tokens, n_steps,
+                                           dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
+        else:
+            self.search = StreamSearch(model._h, model.device, n_sessions, beam_size, max_frames,
+                                       blank_id, self.endpoint.blank_threshold,
+                                       self.endpoint.blank_scale)
         self._free = list(range(n_sessions - 1, -1, -1))
         self._sessions: Dict[int, _Session] = {}
         self._next_sid = 0
@@ -330,7 +471,10 @@ class StreamingRecognizer:
         ys, att, cnn = self.model.forward_encoder_chunk_batch(
             xs, [s.offset for s in ss], self.required, [s.att for s in ss],
             [s.cnn for s in ss])
-        res = self.search.advance_encoded([s.slot for s in ss], ys, nbest=nbest)
+        if self.rnnt:
+            res = self.search.advance_encoded([s.slot for s in ss], ys)
+        else:
+            res = self.search.advance_encoded([s.slot for s in ss], ys, nbest=nbest)
         for b, s in enumerate(ss):
             s.att, s.cnn = att[b], cnn[b]
             s.offset += ys.size(1)
@@ -367,13 +511,23 @@ class StreamingRecognizer:
         """No more frames for `sid`: run the windows that are left (the last may be shorter),
         return the n-best like `ctc_prefix_beam_search`, attention-rescored when asked for and
         the model has a decoder.  The session stays open (closed by `close`) but takes no more
-        frames."""
+        frames.  With search='rnnt_greedy_search' the result is the greedy token list of the
+        whole utterance; rescoring is not applied."""
         import torch
         from wenet_amd import search
         s = self._sessions[sid]
         res = None
         for w in s.win.flush():
             res = self._run([sid], [w], True)[0]
+        if self.rnnt:
+            if res is None:
+                # nothing left to run: what has been consumed (an n_t = 0 advance)
+                d = self.model._cfg.d_model
+                res = self.search.advance_encoded(
+                    [s.slot], torch.zeros((1, 1, d), dtype=torch.float32,
+                                          device=self.model.device), [0])[0]
+                res.is_endpoint = s.last.is_endpoint if s.last is not None else None
+            return res
         if res is None:
             # nothing left to run: the n-best of what has been consumed (an n_t = 0 advance)
             V = self.model.vocab_size
