@@ -945,6 +945,81 @@ int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int
 int wn_rnnt_stream_state(wn_rnnt_stream_set* set, int32_t slot, float* h, float* c,
                          float* pred_proj, int32_t* scalars5, void* stream);
 
+/* ---- streaming transducer sessions: resumable RNN-T prefix beam search ---------- */
+/* wn_transducer_beam_search (below) for sessions that receive their encoder frames chunk by chunk
+ * (no counterpart in the reference: its prefix beam search is one-shot).  A set of `n_slots`
+ * sessions of `beam` slots each; a session's state -- n_live and frames, per slot the fp64 score,
+ * the token row (at most one symbol per frame), the last token, whether the predictor step on it
+ * is still owed (`pending`), the absolute frame of its last token, the LSTM's h / c and the
+ * projected predictor output -- lives in HBM between calls.  The search is causal: after every
+ * call a session's beam is the beam the one-shot search gives for the frames it has consumed, and
+ * its stored state is bit for bit the same whatever the pieces, its slot and the other sessions
+ * of a call.  (The scores equal the one-shot search's bit for bit where both runs take the same
+ * GEMM route for joint.enc_ffn and the CTC head; a one-shot batch of >= 512 rows may take the
+ * six-product GEMM for the CTC head, a chunk does not.)  The beam, the fusion weights and
+ * max_frames are fixed when the set is created.  Calls on one set must be ordered; the set
+ * belongs to the handle it was created on and must be destroyed before it; its workspace is its
+ * own, so other searches on the handle between two calls leave the sessions alone.  Always
+ * fp32 / fp64, as the one-shot search. */
+typedef struct wn_rnnt_beam_stream_set wn_rnnt_beam_stream_set;
+
+/* Where wn_rnnt_beam_stream_advance_encoded puts its results (all HOST arrays, the n sessions of
+ * the call in call order): n_hyps (n) the live hypotheses of each session, best first; hyp_lens
+ * (n, beam); hyp_tokens (n, beam, max_len), of each row the first hyp_lens entries written, tokens
+ * without the leading blank; hyp_scores (n, beam) fp64, -inf beyond n_hyps; frames_decoded (n) the
+ * frames the session has consumed; trailing_blank (n) the frames consumed behind the frame of the
+ * best hypothesis' last token, or all of them if it has none (this project's definition: the
+ * reference has no RNN-T endpointing).  max_len must be >= the frames any session of the call has
+ * consumed after it (a hypothesis holds at most one token per frame). */
+typedef struct wn_rnnt_beam_stream_result {
+  int32_t* n_hyps;
+  int32_t* hyp_lens;
+  int32_t* hyp_tokens;
+  double* hyp_scores;
+  int32_t* frames_decoded;
+  int32_t* trailing_blank;
+  int32_t max_len;
+} wn_rnnt_beam_stream_result;
+
+/* Allocate the state of n_slots sessions (1..256), once; every slot starts reset.  Refused with
+ * -1 and a wn_last_error text: a handle that wn_model_create_transducer did not build; beam
+ * outside [1, 16] or above the vocabulary; max_frames < 1 or n_slots x beam x max_frames > 2^28;
+ * a negative weight, both weights 0; ctc_weight > 0 on a handle without a CTC head. */
+int wn_rnnt_beam_stream_create(wn_model* m, int32_t n_slots, int32_t beam, int32_t max_frames,
+                               float ctc_weight, float transducer_weight,
+                               wn_rnnt_beam_stream_set** out, void* stream);
+int wn_rnnt_beam_stream_destroy(wn_rnnt_beam_stream_set* set);
+
+/* The state the one-shot search starts an utterance from -- one live hypothesis [], score 0.0,
+ * last token = blank with its predictor step owed, zero LSTM state, counters 0 -- for the n
+ * sessions in slot_ids (host); the other sessions keep their state bit for bit. */
+int wn_rnnt_beam_stream_reset(wn_rnnt_beam_stream_set* set, int32_t n, const int32_t* slot_ids,
+                              void* stream);
+
+/* The search on the next frames of n sessions: enc_out_dev is the (n, chunk, d_model) encoder
+ * output of wn_encode_chunk_batch on the device, session i consumes its first n_t_host[i] rows
+ * (0 <= n_t <= chunk; 0 leaves the session's state bit for bit and returns its current beam).
+ * joint.enc_ffn -- and with ctc_weight > 0 the CTC head and its log-softmax -- run once over the
+ * n x chunk rows, then exactly max(n_t) lock-step steps of wn_transducer_beam_search's frame
+ * without a look at the device in between, then one copy of the results.  A token appended on a
+ * session's last frame of the call leaves its predictor step to the next call with frames.
+ * Refused on the host, before any launch, with -1 and a wn_last_error text that names the
+ * argument: n outside [1, n_slots]; a slot id out of range; the same slot twice in one call; n_t
+ * outside [0, chunk]; a call that would take a session past max_frames; a max_len smaller than
+ * stated above.  A refused call changes no session. */
+int wn_rnnt_beam_stream_advance_encoded(wn_rnnt_beam_stream_set* set, int32_t n,
+                                        const int32_t* slot_ids, const float* enc_out_dev,
+                                        const int32_t* n_t_host, int32_t chunk,
+                                        const wn_rnnt_beam_stream_result* out, void* stream);
+
+/* Test hook: one session's whole state copied to the host: counters2 = {n_live, frames}; scores
+ * (beam) fp64; slot_ints (4, beam) = tok_len | last_tok | pending | last_time; tokens
+ * (beam, max_frames), -1 behind tok_len; h, c (beam, layers, H); pred_proj (beam, join_dim).
+ * Slots beyond n_live hold one fixed form (-inf, blank, -1, zeros). */
+int wn_rnnt_beam_stream_state(wn_rnnt_beam_stream_set* set, int32_t slot, int32_t* counters2,
+                              double* scores, int32_t* slot_ints, int32_t* tokens, float* h,
+                              float* c, float* pred_proj, void* stream);
+
 /* RNN-T prefix beam search over the handle's CURRENT batch: PrefixBeamSearch.prefix_beam_search
  * (wenet/models/transducer/search/prefix_beam_search.py:42-148, reached through
  * Transducer.beam_search, transducer.py:216-260), which the reference runs one utterance at a
@@ -1113,6 +1188,27 @@ int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int3
                          int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
                          int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
                          void* stream);
+
+/* The same frame in the carry mode of the resumable search (wn_rnnt_beam_stream_*): lens_host are
+ * the frames of the CALL, frame0_host (B) the frames each utterance consumed before it.  In,
+ * additionally, per slot (B, beam): last_time_host, pending_host and last_tok_host as the step
+ * finds them.  On an utterance's last frame of the call src_out is written as on any other frame,
+ * a token-appending slot reports pending_out = 1 with advance_out = 0, and row_enc_out stays -1.
+ * An utterance with frame >= its length moves on with src_out[g] = g and keeps its tok_out (the
+ * last_tok it came with) and pending_out.  last_time_out: frame0 + frame for a slot that
+ * appended a token, else its source slot's last_time (a fused entry: the blank candidate's
+ * slot); -1 for an empty slot. */
+int wn_op_rnnt_beam_step_carry(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                               const int32_t* lens_host, int32_t max_tok,
+                               const int32_t* n_live_host, const double* scores_host,
+                               const int32_t* tok_lens_host, const int32_t* tokens_host,
+                               const float* top_val_host, const int32_t* top_idx_host,
+                               const int32_t* frame0_host, const int32_t* last_time_host,
+                               const int32_t* pending_host, const int32_t* last_tok_host,
+                               int32_t* n_live_out, double* scores_out, int32_t* tok_lens_out,
+                               int32_t* tokens_out, int32_t* src_out, int32_t* tok_out,
+                               int32_t* advance_out, int32_t* row_enc_out, int32_t* pending_out,
+                               int32_t* last_time_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,13 @@ one-shot wn_transducer_greedy_search over the 5 s of history and the new chunk -
 had to run for a partial before the sessions existed; blocks of 10 steps of each kind in turn.
 Host clock around work that ends in a device synchronise.  Writes
 profiles/streaming_rnnt_sessions.json (or --out).
+
+--rnnt-beam: the same for the resumable RNN-T prefix beam search
+(wenet_amd.streaming.RnntBeamStreamSearch.advance_encoded, fusion weights 0.3 / 0.7) at the beams
+of --beams (5,10): (a) the encoder chunk alone, (b) the chunk + the session step, (c) the chunk +
+the one-shot transducer.prefix_beam_search over the 5 s of history and the new chunk, on the same
+process and encoder output; plus the kernel launches of one session step, counted from the
+model's shape.  Writes profiles/streaming_rnnt_beam_sessions.json (or --out).
 """
 import argparse
 import json
@@ -66,7 +73,13 @@ def main():
     ap.add_argument('--rnnt', action='store_true',
                     help='streaming transducer sessions: resumable vs one-shot RNN-T greedy search')
     ap.add_argument('--lookahead', default='1,4,16', help='--rnnt: rnnt_lookahead values')
+    ap.add_argument('--rnnt-beam', action='store_true',
+                    help='streaming transducer sessions: resumable vs one-shot RNN-T prefix beam '
+                         'search')
+    ap.add_argument('--beams', default='5,10', help='--rnnt-beam: beam sizes')
     args = ap.parse_args()
+    if args.rnnt_beam:
+        return rnnt_beam_main(args)
     if args.rnnt:
         return rnnt_main(args)
     from wenet_amd import synthetic as S
@@ -279,6 +292,112 @@ def rnnt_main(args):
                            'the chunk + resumable greedy search, tokens and times to the host)',
             rerun_step_ms='(c) encoder chunk + wn_transducer_greedy_search over the history and '
                           'the new chunk (history_frames + chunk frames per session)',
+            rows=rows), f, indent=1)
+
+
+def rnnt_beam_main(args):
+    from wenet_amd import Transducer
+    from wenet_amd import synthetic as S
+    from wenet_amd.streaming import RnntBeamStreamSearch
+    from wenet_amd.transducer import prefix_beam_search
+    dev = torch.device('cuda', 0)
+    config = 'aishell_u2pp_rnnt' if args.config == 'wenetspeech_u2pp' else args.config
+    configs = S.make_configs(config)
+    model = Transducer(configs, S.make_state_dict(configs, 0), device=dev)
+    tc = model._tcfg
+    chunk = args.chunk
+    window = (chunk - 1) * 4 + 7
+    req = chunk * args.left if args.left >= 0 else -1
+    secs = float(args.utt_seconds.split(',')[0])
+    hist = int(round(secs / 0.04))
+    n_hist = (hist + chunk - 1) // chunk
+    cw, tw = 0.3, 0.7
+    # one session step: joint.enc_ffn, the CTC head, its log-softmax, begin, end, and per frame
+    # two launches per LSTM layer, the projection, joint.pred_ffn, the joint rows, the fusion +
+    # top-k, the beam step and the gather
+    per_frame = 2 * tc.pred_layers + 6
+    launches = 5 + chunk * per_frame
+    rows = []
+    for n in [int(x) for x in args.sessions.split(',')]:
+        feats, _ = S.make_features(n, window, seed=5, feat_dim=configs['input_dim'])
+        xs = feats.to(dev)
+        for beam in [int(x) for x in args.beams.split(',')]:
+            att, cnn, offsets = [None] * n, [None] * n, [0] * n
+            total = chunk * (n_hist + max(args.warmup // 2, 3) + 12)
+            rs = RnntBeamStreamSearch(model._h, dev, n, beam, total, cw, tw,
+                                      dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
+            slots = list(range(n))
+            past = []
+            for _ in range(n_hist):            # the sessions' history: 5 s of encoder output
+                ys, att, cnn = model.forward_encoder_chunk_batch(xs, offsets, req, att, cnn)
+                offsets = [o + chunk for o in offsets]
+                rs.advance_encoded(slots, ys)
+                past.append(ys)
+            past_chunks = past
+            past = torch.cat(past, 1)[:, -hist:].contiguous()
+            state = dict(att=att, cnn=cnn, offsets=offsets, tokens=[])
+
+            def step(kind):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ys, state['att'], state['cnn'] = model.forward_encoder_chunk_batch(
+                    xs, state['offsets'], req, state['att'], state['cnn'])
+                if kind == 'search':
+                    res = rs.advance_encoded(slots, ys)
+                    state['tokens'].append(float(np.mean([len(r.tokens) for r in res])))
+                elif kind == 'rerun':
+                    sofar = torch.cat([past, ys], 1)
+                    prefix_beam_search(model, sofar, [sofar.size(1)] * n, beam, cw, tw)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0      # (the offset stays at 5 s, as in --search)
+                if args.left < 0 and state['att'][0].size(2) > args.max_cache:
+                    state['att'] = [a[:, :, -args.max_cache:].contiguous() for a in state['att']]
+                return dt
+
+            kinds = ['none', 'search', 'rerun']
+            lat = {k: [] for k in kinds}
+            for k in kinds:
+                for _ in range(max(args.warmup // 2, 3)):
+                    step(k)
+            state['tokens'] = []
+            for _ in range(max(args.steps // 10, 1)):
+                for k in kinds:
+                    if k == 'search':      # back to 5 s of audio behind every session (untimed)
+                        rs.reset(slots)
+                        for ys in past_chunks:
+                            rs.advance_encoded(slots, ys)
+                    for _ in range(10):
+                        lat[k].append(step(k))
+            row = dict(sessions=n, chunk=chunk, left_chunks=args.left, beam=beam,
+                       ctc_weight=cw, transducer_weight=tw, history_frames=hist,
+                       best_tokens_per_session=round(float(np.mean(state['tokens'])), 1),
+                       frames_per_session=int(rs.frames[0]),
+                       lockstep_steps_per_call=chunk, launches_per_step=launches,
+                       launches_per_frame=per_frame, rerun_lockstep_steps=hist + chunk)
+            names = dict(none='step_ms', search='stream_step_ms', rerun='rerun_step_ms')
+            for k in kinds:
+                a = np.asarray(lat[k]) * 1e3
+                row[names[k] + '_median'] = round(float(np.median(a)), 3)
+                row[names[k] + '_p99'] = round(float(np.percentile(a, 99)), 3)
+            row['stream_minus_step_ms'] = round(row['stream_step_ms_median'] - row['step_ms_median'], 3)
+            row['rerun_minus_step_ms'] = round(row['rerun_step_ms_median'] - row['step_ms_median'], 3)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            rs.close()
+    out = args.out or os.path.join(ROOT, 'profiles', 'streaming_rnnt_beam_sessions.json')
+    with open(out, 'w') as f:
+        json.dump(dict(
+            model=config, steps=args.steps, warmup=args.warmup,
+            note='step latency, host clock around a device synchronise, one MI355X; blocks of 10 '
+                 'steps of each kind in turn',
+            step_ms='(a) encoder chunk forward for all sessions',
+            stream_step_ms='(b) encoder chunk + wn_rnnt_beam_stream_advance_encoded (joint.enc_ffn '
+                           'and the CTC head over the chunk + resumable prefix beam search, the '
+                           'n-best to the host)',
+            rerun_step_ms='(c) encoder chunk + wn_transducer_beam_search over the history and '
+                          'the new chunk (history_frames + chunk frames per session)',
+            launches_per_step='kernel launches of one session step, counted from the model shape: '
+                              '5 + chunk x (2 x LSTM layers + 6)',
             rows=rows), f, indent=1)
 
 

@@ -8,7 +8,7 @@ include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
 __all__ = ["load_model", "ASRModel", "Transducer", "DecodeResult", "StreamingRecognizer",
-           "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
+           "RnntBeamStreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
            "force_align_batch"]
 
 
@@ -22,7 +22,8 @@ def __getattr__(name):
     if name == "DecodeResult":
         from wenet_amd.search import DecodeResult
         return DecodeResult
-    if name in ("StreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule"):
+    if name in ("StreamingRecognizer", "RnntBeamStreamingRecognizer", "CtcEndpointConfig",
+                "CtcEndpointRule"):
         from wenet_amd import streaming as _s
         return getattr(_s, name)
     if name in ("AlignResult", "force_align", "force_align_batch"):

@@ -54,6 +54,15 @@ class WnRnntStreamResult(Structure):
                 ('steps', POINTER(c_int32))]
 
 
+class WnRnntBeamStreamResult(Structure):
+    """wn_rnnt_beam_stream_result: where wn_rnnt_beam_stream_advance_encoded puts a call's
+    results (host arrays)."""
+    _fields_ = [('n_hyps', POINTER(c_int32)), ('hyp_lens', POINTER(c_int32)),
+                ('hyp_tokens', POINTER(c_int32)), ('hyp_scores', POINTER(c_double)),
+                ('frames_decoded', POINTER(c_int32)), ('trailing_blank', POINTER(c_int32)),
+                ('max_len', c_int32)]
+
+
 class WnAttentionOp(Structure):
     """wn_attention_op: the arguments of wn_op_attention."""
     _fields_ = [('Q', c_void_p), ('K', c_void_p), ('V', c_void_p),
@@ -90,6 +99,9 @@ EXPORTS = [
     'wn_op_rnnt_beam_step', 'wn_transducer_beam_stats',
     'wn_rnnt_stream_create', 'wn_rnnt_stream_destroy', 'wn_rnnt_stream_reset',
     'wn_rnnt_stream_advance_encoded', 'wn_rnnt_stream_state',
+    'wn_rnnt_beam_stream_create', 'wn_rnnt_beam_stream_destroy', 'wn_rnnt_beam_stream_reset',
+    'wn_rnnt_beam_stream_advance_encoded', 'wn_rnnt_beam_stream_state',
+    'wn_op_rnnt_beam_step_carry',
     'wn_transducer_score', 'wn_transducer_score_stats', 'wn_transducer_score_times',
     'wn_op_rnnt_trie',
     'wn_op_joint_logp_gather', 'wn_op_rnnt_lattice',
@@ -217,6 +229,17 @@ def lib():
                                                  POINTER(WnRnntStreamResult), vp]
     L.wn_rnnt_stream_state.argtypes = [vp, i32, POINTER(f32), POINTER(f32), POINTER(f32), pi32,
                                        vp]
+    L.wn_rnnt_beam_stream_create.argtypes = [vp, i32, i32, i32, f32, f32, POINTER(vp), vp]
+    L.wn_rnnt_beam_stream_destroy.argtypes = [vp]
+    L.wn_rnnt_beam_stream_reset.argtypes = [vp, i32, pi32, vp]
+    L.wn_rnnt_beam_stream_advance_encoded.argtypes = [vp, i32, pi32, vp, pi32, i32,
+                                                      POINTER(WnRnntBeamStreamResult), vp]
+    L.wn_rnnt_beam_stream_state.argtypes = [vp, i32, pi32, pf64, pi32, pi32, POINTER(f32),
+                                            POINTER(f32), POINTER(f32), vp]
+    L.wn_op_rnnt_beam_step_carry.argtypes = [i32, i32, i32, i32, i32, pi32, i32, pi32, pf64, pi32,
+                                             pi32, POINTER(f32), pi32, pi32, pi32, pi32, pi32,
+                                             pi32, pf64, pi32, pi32, pi32, pi32, pi32, pi32, pi32,
+                                             pi32, vp]
     L.wn_op_lstm_step.argtypes = [vp, POINTER(vp), i32, vp, vp, vp, vp, vp, vp, i32, i32, i32,
                                   i32, vp]
     L.wn_op_joint_argmax.argtypes = [vp, i32, vp, i32, pi32, pi32, vp, vp, i32, i32, i32, pi32,

@@ -45,9 +45,18 @@ def get_args(argv=None):
     p.add_argument('--chunk', type=int, default=16,
                    help='decoding_chunk_size of --stream (encoder frames per step)')
     p.add_argument('--search', default='ctc_prefix_beam_search',
-                   choices=['ctc_prefix_beam_search', 'rnnt_greedy_search'],
+                   choices=['ctc_prefix_beam_search', 'rnnt_greedy_search',
+                            'rnnt_prefix_beam_search'],
                    help='the search of --stream; rnnt_greedy_search needs a transducer model '
-                        'and does no attention rescoring')
+                        'and does no attention rescoring; rnnt_prefix_beam_search needs one '
+                        'too and keeps an n-best per chunk (--beam_size, --search_ctc_weight, '
+                        '--search_transducer_weight)')
+    p.add_argument('--beam_size', type=int, default=5,
+                   help='beam of --search rnnt_prefix_beam_search')
+    p.add_argument('--search_ctc_weight', type=float, default=0.3,
+                   help='CTC weight of the shallow fusion in --search rnnt_prefix_beam_search')
+    p.add_argument('--search_transducer_weight', type=float, default=0.7,
+                   help='transducer weight of that fusion')
     p.add_argument('--align', action='store_true',
                    help='force align the input audio and transcript')
     p.add_argument('--label', type=str, default=None, help='the input label to align')
@@ -74,13 +83,20 @@ def align_file(model, audio_file, label, out=print):
 
 
 def stream_file(model, audio_file, chunk, beam_size=10, out=print,
-                search='ctc_prefix_beam_search'):
+                search='ctc_prefix_beam_search', search_ctc_weight=0.3,
+                search_transducer_weight=0.7):
     """One streaming session over the file; `out` gets each changed partial, then the final
     result's text.  Returns the final DecodeResult."""
-    from wenet_amd.streaming import StreamingRecognizer
+    from wenet_amd.streaming import RnntBeamStreamingRecognizer, StreamingRecognizer
     speech = model.compute_feature(audio_file).to(model.device)
-    rec = StreamingRecognizer(model, 1, chunk, beam_size=beam_size,
-                              max_seconds=speech.size(0) / 100.0 + 1.0, search=search)
+    if search == RnntBeamStreamingRecognizer.SEARCH:
+        rec = RnntBeamStreamingRecognizer(model, 1, chunk, beam_size=beam_size,
+                                          search_ctc_weight=search_ctc_weight,
+                                          search_transducer_weight=search_transducer_weight,
+                                          max_seconds=speech.size(0) / 100.0 + 1.0)
+    else:
+        rec = StreamingRecognizer(model, 1, chunk, beam_size=beam_size,
+                                  max_seconds=speech.size(0) / 100.0 + 1.0, search=search)
     sid = rec.open()
     piece = chunk * model.subsampling_rate()
     shown = None
@@ -108,8 +124,13 @@ def main(argv=None):
     if args.stream:
         if args.context_path is not None:
             raise SystemExit('--stream does not support --context_path')
-        result = stream_file(model, args.audio_file, args.chunk, args.beam or 10,
-                             search=args.search)
+        if args.search == 'rnnt_prefix_beam_search':
+            result = stream_file(model, args.audio_file, args.chunk, args.beam or args.beam_size,
+                                 search=args.search, search_ctc_weight=args.search_ctc_weight,
+                                 search_transducer_weight=args.search_transducer_weight)
+        else:
+            result = stream_file(model, args.audio_file, args.chunk, args.beam or 10,
+                                 search=args.search)
     elif args.beam is None and args.context_path is None and args.task is None \
             and args.lang is None:
         result = model.transcribe(args.audio_file)      # asr_model.py:345-358

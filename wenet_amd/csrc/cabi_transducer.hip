@@ -1,7 +1,7 @@
 // C ABI (include/wenet_amd.h), hybrid transducer: the batched RNN-T greedy search with frame
 // lookahead and the batched prefix beam search over the handle's current batch (kernels:
 // transducer.hip, transducer_beam.hip) and the operator hooks of the predictor step, the joint +
-// arg-max, the joint + fusion + top-k and the beam step.
+// arg-max, the joint + fusion + top-k and the beam step (plain and in carry mode).
 #include <algorithm>
 
 #include "model_state.h"
@@ -431,14 +431,19 @@ int wn_op_joint_fuse_topk(const float* enc_proj_dev, int32_t enc_rows, const flo
   return 0;
 }
 
-int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
-                         const int32_t* lens_host, int32_t max_tok, const int32_t* n_live_host,
-                         const double* scores_host, const int32_t* tok_lens_host,
-                         const int32_t* tokens_host, const float* top_val_host,
-                         const int32_t* top_idx_host, int32_t* n_live_out, double* scores_out,
-                         int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
-                         int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
-                         void* stream) {
+// the body of wn_op_rnnt_beam_step; `cy` non-null: the carry mode (wn_op_rnnt_beam_step_carry)
+struct BeamStepCarry {
+  const int32_t* frame0; const int32_t* last_time; const int32_t* pending; const int32_t* last_tok;
+  int32_t* pending_out; int32_t* last_time_out;
+};
+static int beam_step_op(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                        const int32_t* lens_host, int32_t max_tok, const int32_t* n_live_host,
+                        const double* scores_host, const int32_t* tok_lens_host,
+                        const int32_t* tokens_host, const float* top_val_host,
+                        const int32_t* top_idx_host, int32_t* n_live_out, double* scores_out,
+                        int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
+                        int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
+                        const BeamStepCarry* cy, void* stream) {
   WN_CHECK(lens_host && n_live_host && scores_host && tok_lens_host && tokens_host &&
            top_val_host && top_idx_host && n_live_out && scores_out && tok_lens_out &&
            tokens_out && src_out && tok_out && advance_out && row_enc_out,
@@ -470,8 +475,9 @@ int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int3
   hipStream_t s = (hipStream_t)stream;
   const int M = B * beam;
   const size_t um = up64(M), ub = up64(B);
-  static thread_local DevBuf ibuf, fbuf;
+  static thread_local DevBuf ibuf, fbuf, cbuf;
   const size_t o_tok = 4 * ub + 6 * um + 2 * up64((size_t)M * beam);
+  if (cy) WN_TRY(cbuf.ensure((ub + 3 * um) * sizeof(int)));
   WN_TRY(ibuf.ensure((o_tok + 2 * (size_t)M * max_tok) * sizeof(int)));
   WN_TRY(fbuf.ensure(2 * um * sizeof(double)));
   int* ip = ibuf.as<int>();
@@ -499,10 +505,24 @@ int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int3
   WN_HIP(hipMemsetAsync(a.out.tokens, 0xff, (size_t)M * max_tok * sizeof(int), s));   // -1
   a.max_tok = max_tok; a.top_val = d_topv; a.top_idx = d_topi; a.off = d_off; a.len = d_len;
   a.frame = frame; a.B = B; a.beam = beam; a.blank = blank; a.V = V;
+  if (cy) {
+    int* cp = cbuf.as<int>();
+    int *d_f0 = cp, *d_lt_in = cp + ub, *d_lt_out = d_lt_in + um, *d_pend = d_lt_in + 2 * um;
+    WN_HIP(up(d_f0, cy->frame0, (size_t)B * sizeof(int)));
+    WN_HIP(up(d_lt_in, cy->last_time, (size_t)M * sizeof(int)));
+    WN_HIP(up(d_pend, cy->pending, (size_t)M * sizeof(int)));
+    WN_HIP(up(a.last_tok, cy->last_tok, (size_t)M * sizeof(int)));
+    WN_HIP(hipMemsetAsync(d_lt_out, 0xff, (size_t)M * sizeof(int), s));
+    a.frame0 = d_f0; a.last_time_in = d_lt_in; a.last_time_out = d_lt_out; a.pending = d_pend;
+  }
   WN_TRY(rnnt_beam_step(a, s));
   auto down = [&](void* dst, const void* srcp, size_t bytes) {
     return hipMemcpyAsync(dst, srcp, bytes, hipMemcpyDeviceToHost, s);
   };
+  if (cy) {
+    WN_HIP(down(cy->pending_out, a.pending, (size_t)M * sizeof(int)));
+    WN_HIP(down(cy->last_time_out, a.last_time_out, (size_t)M * sizeof(int)));
+  }
   WN_HIP(down(n_live_out, a.out.n_live, (size_t)B * sizeof(int)));
   WN_HIP(down(scores_out, a.out.score, (size_t)M * sizeof(double)));
   WN_HIP(down(tok_lens_out, a.out.tok_len, (size_t)M * sizeof(int)));
@@ -512,6 +532,50 @@ int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int3
   WN_HIP(down(advance_out, a.advance, (size_t)M * sizeof(int)));
   WN_HIP(down(row_enc_out, a.row_enc, (size_t)M * sizeof(int)));
   WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_op_rnnt_beam_step(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                         const int32_t* lens_host, int32_t max_tok, const int32_t* n_live_host,
+                         const double* scores_host, const int32_t* tok_lens_host,
+                         const int32_t* tokens_host, const float* top_val_host,
+                         const int32_t* top_idx_host, int32_t* n_live_out, double* scores_out,
+                         int32_t* tok_lens_out, int32_t* tokens_out, int32_t* src_out,
+                         int32_t* tok_out, int32_t* advance_out, int32_t* row_enc_out,
+                         void* stream) {
+  return beam_step_op(B, beam, blank, V, frame, lens_host, max_tok, n_live_host, scores_host,
+                      tok_lens_host, tokens_host, top_val_host, top_idx_host, n_live_out,
+                      scores_out, tok_lens_out, tokens_out, src_out, tok_out, advance_out,
+                      row_enc_out, nullptr, stream);
+}
+
+int wn_op_rnnt_beam_step_carry(int32_t B, int32_t beam, int32_t blank, int32_t V, int32_t frame,
+                               const int32_t* lens_host, int32_t max_tok,
+                               const int32_t* n_live_host, const double* scores_host,
+                               const int32_t* tok_lens_host, const int32_t* tokens_host,
+                               const float* top_val_host, const int32_t* top_idx_host,
+                               const int32_t* frame0_host, const int32_t* last_time_host,
+                               const int32_t* pending_host, const int32_t* last_tok_host,
+                               int32_t* n_live_out, double* scores_out, int32_t* tok_lens_out,
+                               int32_t* tokens_out, int32_t* src_out, int32_t* tok_out,
+                               int32_t* advance_out, int32_t* row_enc_out, int32_t* pending_out,
+                               int32_t* last_time_out, void* stream) {
+  WN_CHECK(frame0_host && last_time_host && pending_host && last_tok_host && pending_out &&
+           last_time_out, "wn_op_rnnt_beam_step_carry: null argument");
+  const BeamStepCarry cy = {frame0_host, last_time_host, pending_host, last_tok_host, pending_out,
+                            last_time_out};
+  if (beam_step_op(B, beam, blank, V, frame, lens_host, max_tok, n_live_host, scores_host,
+                   tok_lens_host, tokens_host, top_val_host, top_idx_host, n_live_out, scores_out,
+                   tok_lens_out, tokens_out, src_out, tok_out, advance_out, row_enc_out, &cy,
+                   stream) != 0) {
+    // the shared body names the plain hook in its refusals
+    std::string e = wn_last_error();
+    const std::string from = "wn_op_rnnt_beam_step:";
+    const size_t at = e.find(from);
+    if (at != std::string::npos) e.replace(at, from.size(), "wn_op_rnnt_beam_step_carry:");
+    set_error(e);
+    return -1;
+  }
   return 0;
 }
 

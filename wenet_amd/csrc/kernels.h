@@ -626,6 +626,17 @@ struct RnntBeamStepArgs {
   // and its joint row of the next frame (-1: inert)
   int* src = nullptr; int* last_tok = nullptr; int* advance = nullptr; int* row_enc = nullptr;
   int* n_advance = nullptr;    // optional [1]: += the new slots that set `advance`
+  // Carry mode (pending != nullptr; the resumable search, transducer_beam_stream.hip): `len` is
+  // the frames of this CALL and another call may follow.  On an utterance's last frame of the
+  // call `src` is written as on any other frame (the gather carries the state), a token-appending
+  // slot's owed predictor step goes to pending[g] (advance stays 0) and row_enc stays -1.  On a
+  // later step (frame >= len) the utterance's slots move on as they are with src[g] = g: both
+  // buffer parities hold them, last_tok and pending are left alone.  last_time_out[g]: frame0[b]
+  // + frame if the new slot appended a token, else last_time_in of its source slot.  All null:
+  // the kernel does exactly what the one-shot search needs.
+  int* pending = nullptr;                      // [B x beam]
+  const int* last_time_in = nullptr; int* last_time_out = nullptr;   // [B x beam]
+  const int* frame0 = nullptr;                 // [B] frames consumed before this call
 };
 // one hypothesis [blank], score 0.0, per utterance; row_pred[g] = g
 int rnnt_beam_init(const RnntBeamSlots& st, int* last_tok, int* advance, int* row_enc,
@@ -635,6 +646,46 @@ int rnnt_beam_step(const RnntBeamStepArgs& a, hipStream_t s);
 int rnnt_beam_gather(const int* src, const float* h_in, const float* c_in, const float* pp_in,
                      float* h_out, float* c_out, float* pp_out, int M, int L, int H, int J,
                      hipStream_t s);
+
+// Resumable RNN-T prefix beam search (transducer_beam_stream.hip): the state of n_slots sessions
+// of `beam` slots each that stays in HBM between calls.  Slot q = session * beam + j.
+struct RnntBeamStreamSlots {
+  int* n_live; int* frames;         // [n_slots]: live hypotheses, frames consumed
+  double* score;                    // [n_slots x beam]
+  int* tok_len; int* last_tok;      // [n_slots x beam]
+  int* pending;                     // the predictor step on last_tok is still owed
+  int* last_time;                   // the absolute frame of the slot's last token, -1: none
+  int* tokens; int max_tok;         // [n_slots x beam][max_tok = max_frames]; -1 behind tok_len
+  float* h; float* c;               // [n_slots x beam][L][H]
+  float* pred_proj;                 // [n_slots x beam][J]
+  int beam, L, H, J;
+};
+// The compact batch of one call over n sessions, M = n x beam rows: what predictor_step,
+// rnnt_linear, rnnt_joint_rows, rnnt_fuse_topk, rnnt_beam_step (carry mode) and rnnt_beam_gather
+// run on.  `st`, h, c, pred_proj, last_time: the buffer of one parity.
+struct RnntBeamStreamCall {
+  const int* slot; const int* n_t;  // [n] the call's sessions and the frames each consumes
+  RnntBeamSlots st; int max_tok;    // token rows [M][max_tok]
+  float* h; float* c;               // [L][M][H]
+  float* pred_proj;                 // [M][J]
+  int* last_time;                   // [M]
+  int* last_tok; int* pending; int* advance; int* row_enc; int* row_pred;   // [M]
+  int* off; int* len; int* frame0;  // [n]: i * chunk, n_t[i], frames before the call
+  // results (rnnt_beam_stream_end): n_live | frames | trailing_blank [3][n], tok_len [M],
+  // score [M], token rows [M][ld_out] (the first tok_len entries of each)
+  int* out_stat; int* out_len; double* out_score; int* out_tok; int ld_out;
+};
+// slots -> the compact batch (parity 0): advance = pending && n_t > 0 (pending is consumed then),
+// row_enc = i * chunk for the live slots of a session with n_t > 0, else -1
+int rnnt_beam_stream_begin(const RnntBeamStreamSlots& sl, const RnntBeamStreamCall& c, int n,
+                           int chunk, hipStream_t s);
+// the compact batch (the parity the call ended in) -> slots, frames += n_t, the call's results.
+// Dead slots are stored in one canonical form (zero state, -inf, blank, -1).
+int rnnt_beam_stream_end(const RnntBeamStreamSlots& sl, const RnntBeamStreamCall& c, int n,
+                         int blank, hipStream_t s);
+// the state rnnt_beam_init gives an utterance, for the n sessions in `slot` (device)
+int rnnt_beam_stream_reset(const RnntBeamStreamSlots& sl, const int* slot, int n, int blank,
+                           hipStream_t s);
 
 // Teacher-forced transducer score (transducer_score.hip): fp32 rows, fp64 lattice.
 // Per row m with row_enc[m] >= 0, for every entry e of its column list

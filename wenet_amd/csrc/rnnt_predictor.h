@@ -1,6 +1,6 @@
 // The predictor step of the RNN-T searches on the host side, shared by cabi_transducer.hip (the
-// one-shot greedy and beam searches, wn_op_lstm_step) and cabi_transducer_stream.hip (the
-// resumable greedy search): the launches of one LSTM time step + projection for the advancing
+// one-shot greedy and beam searches, wn_op_lstm_step), cabi_transducer_stream.hip and
+// cabi_transducer_beam_stream.hip (the resumable greedy and beam searches): the launches of one LSTM time step + projection for the advancing
 // rows of a batch.
 #pragma once
 #include "model_state.h"

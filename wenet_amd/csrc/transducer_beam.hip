@@ -31,6 +31,10 @@
 //    double buffered.
 // No kernel waits for another workgroup; the host issues `longest T'` steps without looking at
 // the device.  Rows of empty slots and finished utterances are inert (row_enc < 0).
+// The resumable search (transducer_beam_stream.hip) runs the same kernels on a compact batch of
+// sessions; rnnt_beam_step_kernel's carry mode (RnntBeamStepArgs::pending != nullptr, kernels.h)
+// is what differs on a session's last frame of a call and behind it.  Without those pointers the
+// kernel does what it did before they existed.
 #include "kernels.h"
 
 namespace wn {
@@ -170,12 +174,19 @@ __global__ __launch_bounds__(BS_THREADS) void rnnt_beam_step_kernel(RnntBeamStep
   const int len = a.len[b];
   const int64_t mt = a.max_tok;
 
+  const bool carry = a.pending != nullptr;     // the resumable search (kernels.h)
   if (a.frame >= len) {      // finished (or empty): the slots move on as they are, inert
     if (tid < beam) {
       const int g = g0 + tid;
       a.out.score[g] = tid < n ? a.in.score[g] : -INFINITY;
       a.out.tok_len[g] = tid < n ? min(max(a.in.tok_len[g], 0), a.max_tok) : 0;
-      a.src[g] = -1; a.last_tok[g] = a.blank; a.advance[g] = 0; a.row_enc[g] = -1;
+      a.advance[g] = 0; a.row_enc[g] = -1;
+      if (carry) {           // the state goes along in both parities; last_tok / pending stay
+        a.src[g] = tid < n ? g : -1;
+        a.last_time_out[g] = tid < n ? a.last_time_in[g] : -1;
+      } else {
+        a.src[g] = -1; a.last_tok[g] = a.blank;
+      }
     }
     if (tid == 0) a.out.n_live[b] = n;
     for (int s = 0; s < n; ++s) {
@@ -262,10 +273,14 @@ __global__ __launch_bounds__(BS_THREADS) void rnnt_beam_step_kernel(RnntBeamStep
       const int c = w_cand[tid], sj = c_src[c], t = c_tok[c];
       a.out.score[g] = c_sc[c];
       a.out.tok_len[g] = min(s_len[sj] + (t >= 0 ? 1 : 0), a.max_tok);
-      a.src[g] = more ? g0 + sj : -1;
+      a.src[g] = (more || carry) ? g0 + sj : -1;
       a.last_tok[g] = t >= 0 ? t : a.blank;
       const int adv = (t >= 0 && more) ? 1 : 0;
       a.advance[g] = adv;
+      if (carry) {           // the step behind a token on the call's last frame is owed
+        a.pending[g] = (t >= 0 && !more) ? 1 : 0;
+        a.last_time_out[g] = t >= 0 ? a.frame0[b] + a.frame : a.last_time_in[g0 + sj];
+      }
       if (adv && a.n_advance) atomicAdd(a.n_advance, 1);     // (a statistic: rows of LSTM steps)
       a.row_enc[g] = more ? a.off[b] + a.frame + 1 : -1;
       if (t >= 0 && s_len[sj] < a.max_tok) a.out.tokens[g * mt + s_len[sj]] = t;
@@ -273,6 +288,7 @@ __global__ __launch_bounds__(BS_THREADS) void rnnt_beam_step_kernel(RnntBeamStep
       a.out.score[g] = -INFINITY;
       a.out.tok_len[g] = 0;
       a.src[g] = -1; a.last_tok[g] = a.blank; a.advance[g] = 0; a.row_enc[g] = -1;
+      if (carry) { a.pending[g] = 0; a.last_time_out[g] = -1; }
     }
   }
   if (tid == 0) a.out.n_live[b] = n_new;
@@ -331,6 +347,8 @@ int rnnt_beam_step(const RnntBeamStepArgs& a, hipStream_t s) {
            a.len && a.src && a.last_tok && a.advance && a.row_enc, "rnnt_beam_step: null operand");
   WN_CHECK(a.B >= 1 && a.beam >= 1 && a.beam <= BS_MAX_BEAM, "rnnt_beam_step: beam must be in [1, 16]");
   WN_CHECK(a.max_tok >= 1 && a.V >= 1 && a.frame >= 0, "rnnt_beam_step: empty");
+  WN_CHECK(!a.pending || (a.last_time_in && a.last_time_out && a.frame0),
+           "rnnt_beam_step: carry mode needs last_time_in / last_time_out / frame0");
   hipLaunchKernelGGL(rnnt_beam_step_kernel, dim3(a.B), dim3(BS_THREADS), 0, s, a);
   WN_HIP(hipGetLastError());
   return 0;

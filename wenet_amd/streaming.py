@@ -17,7 +17,11 @@ Layers, bottom up:
   evaluated on the host from the two counters the search kernel keeps;
 * `RnntStreamSearch`: the same for a hybrid transducer -- resumable RNN-T greedy searches
   (`wn_rnnt_stream_create`, csrc/transducer_stream.hip), advanced by encoder output;
-* `StreamingRecognizer`: open / accept / step / finish / close, with either search.
+* `RnntBeamStreamSearch`: resumable RNN-T prefix beam searches (`wn_rnnt_beam_stream_create`,
+  csrc/transducer_beam_stream.hip): an n-best per session after every chunk;
+* `StreamingRecognizer`: open / accept / step / finish / close, with either search;
+* `RnntBeamStreamingRecognizer`: the same on the resumable RNN-T prefix beam search, with the
+  transducer + attention rescoring of the final beam in `finish`.
 """
 import ctypes
 from typing import Dict, List, Optional, Tuple
@@ -353,6 +357,120 @@ class RnntStreamSearch:
         return h, c, pp, dict(zip(names, sc.tolist()))
 
 
+class RnntBeamStreamSearch:
+    """`n_slots` resumable RNN-T prefix beam searches on the device
+    (wn_rnnt_beam_stream_create; the handle must be a `wenet_amd.Transducer`'s).  The beam and
+    the fusion weights of `transducer.prefix_beam_search` are fixed for the set.
+
+    `advance_encoded(slots, enc_out, n_t)` feeds session slots[i] the first n_t[i] frames of
+    enc_out[i] and returns one DecodeResult per session for everything that session has
+    consumed so far -- what `transducer.prefix_beam_search` returns for those frames in one
+    call: `tokens` and `score` of the best hypothesis, `nbest`, `nbest_scores`, and the extra
+    attributes `frames_decoded`, `trailing_blank` (frames consumed behind the last token of the
+    best hypothesis: this project's definition); `.raw` of the returned list holds the call's
+    arrays.  `dims` = (predictor layers, hidden size, join_dim) is what `state(slot)` needs to
+    size its arrays."""
+
+    def __init__(self, handle: int, device, n_slots: int, beam_size: int, max_frames: int,
+                 ctc_weight: float = 0.3, transducer_weight: float = 0.7, dims=None):
+        self._L = _lib.lib()
+        self.device = device
+        self.n_slots, self.beam, self.max_frames = n_slots, int(beam_size), max_frames
+        self.ctc_weight, self.transducer_weight = float(ctc_weight), float(transducer_weight)
+        self.dims = dims
+        self.frames = [0] * n_slots         # frames every slot has consumed
+        self._set = None
+        h = ctypes.c_void_p()
+        _lib.check(self._L.wn_rnnt_beam_stream_create(
+            handle, n_slots, self.beam, max_frames, self.ctc_weight, self.transducer_weight,
+            ctypes.byref(h), self._stream()), 'wn_rnnt_beam_stream_create')
+        self._set = h
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def close(self):
+        if self._set is not None:
+            self._L.wn_rnnt_beam_stream_destroy(self._set)
+            self._set = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def reset(self, slots):
+        ids = np.asarray(list(slots), dtype=np.int32)
+        _lib.check(self._L.wn_rnnt_beam_stream_reset(self._set, len(ids), _lib.i32p(ids),
+                                                     self._stream()), 'wn_rnnt_beam_stream_reset')
+        for s in ids.tolist():
+            self.frames[s] = 0
+
+    def advance_encoded(self, slots, enc_out, n_t=None, max_len=None):
+        """enc_out: (n, chunk, d_model) float32 encoder output on the device.  `max_len`: the
+        row pitch of the result arrays (default: what the call can need)."""
+        assert enc_out.is_cuda and enc_out.dim() == 3 and enc_out.size(0) == len(slots)
+        import torch
+        from wenet_amd.search import DecodeResult
+        enc_out = enc_out.detach().to(torch.float32).contiguous()
+        ids = np.asarray(list(slots), dtype=np.int32)
+        nt = np.asarray(list(n_t) if n_t is not None else [enc_out.size(1)] * len(ids),
+                        dtype=np.int32)
+        assert len(ids) == len(nt)
+        n, beam = len(ids), self.beam
+        if max_len is None:
+            max_len = max([self.frames[s] + max(int(t), 0) for s, t in zip(ids.tolist(), nt.tolist())
+                           if 0 <= s < self.n_slots] + [1])
+        a = dict(n_hyps=np.zeros((n, ), np.int32), hyp_lens=np.zeros((n, beam), np.int32),
+                 hyp_tokens=np.zeros((n, beam, max(max_len, 1)), np.int32),
+                 hyp_scores=np.full((n, beam), -np.inf, np.float64),
+                 frames_decoded=np.zeros((n, ), np.int32),
+                 trailing_blank=np.zeros((n, ), np.int32), max_len=max_len)
+        r = _lib.WnRnntBeamStreamResult(
+            _lib.i32p(a['n_hyps']), _lib.i32p(a['hyp_lens']), _lib.i32p(a['hyp_tokens']),
+            _lib.f64p(a['hyp_scores']), _lib.i32p(a['frames_decoded']),
+            _lib.i32p(a['trailing_blank']), max_len)
+        _lib.check(self._L.wn_rnnt_beam_stream_advance_encoded(
+            self._set, n, _lib.i32p(ids), enc_out.data_ptr(), _lib.i32p(nt), enc_out.size(1),
+            ctypes.byref(r), self._stream()), 'wn_rnnt_beam_stream_advance_encoded')
+        out = _Results()
+        for b, s in enumerate(ids.tolist()):
+            self.frames[s] = int(a['frames_decoded'][b])
+            nbest = [a['hyp_tokens'][b, k, :a['hyp_lens'][b, k]].tolist()
+                     for k in range(int(a['n_hyps'][b]))]
+            scores = a['hyp_scores'][b, :len(nbest)].tolist()
+            res = DecodeResult(nbest[0], score=scores[0], nbest=nbest, nbest_scores=scores)
+            res.frames_decoded = int(a['frames_decoded'][b])
+            res.trailing_blank = int(a['trailing_blank'][b])
+            out.append(res)
+        out.raw = a
+        return out
+
+    def state(self, slot: int):
+        """wn_rnnt_beam_stream_state: the session's whole state as a dict of host arrays:
+        n_live, frames, score (beam), tok_len / last_tok / pending / last_time (beam), tokens
+        (beam, max_frames), h / c (beam, layers, H), pred_proj (beam, J)."""
+        assert self.dims is not None, 'RnntBeamStreamSearch.state needs dims=(layers, hidden, join_dim)'
+        L_, H, J = self.dims
+        beam = self.beam
+        cnt = np.zeros((2, ), np.int32)
+        score = np.zeros((beam, ), np.float64)
+        ints = np.zeros((4, beam), np.int32)
+        tokens = np.zeros((beam, self.max_frames), np.int32)
+        h = np.zeros((beam, L_, H), np.float32)
+        c = np.zeros((beam, L_, H), np.float32)
+        pp = np.zeros((beam, J), np.float32)
+        _lib.check(self._L.wn_rnnt_beam_stream_state(
+            self._set, slot, _lib.i32p(cnt), _lib.f64p(score), _lib.i32p(ints), _lib.i32p(tokens),
+            _lib.f32p(h), _lib.f32p(c), _lib.f32p(pp), self._stream()),
+            'wn_rnnt_beam_stream_state')
+        return dict(n_live=int(cnt[0]), frames=int(cnt[1]), score=score, tok_len=ints[0],
+                    last_tok=ints[1], pending=ints[2], last_time=ints[3], tokens=tokens, h=h, c=c,
+                    pred_proj=pp)
+
+
 # --------------------------------------------------------------------------- recognizer
 class _Session:
     __slots__ = ('slot', 'win', 'feats', 'base', 'att', 'cnn', 'offset', 'enc', 'last')
@@ -399,15 +517,33 @@ class StreamingRecognizer:
                  max_seconds: float = 60.0, endpoint: Optional[CtcEndpointConfig] = None,
                  blank_id: int = 0, search: str = 'ctc_prefix_beam_search', n_steps: int = 64,
                  max_tokens: Optional[int] = None):
-        import torch
-        assert decoding_chunk_size > 0, 'decoding_chunk_size must be positive'
         if search not in self.SEARCHES:
             raise ValueError(f'search={search!r}: expected one of {self.SEARCHES}')
         self.rnnt = search == 'rnnt_greedy_search'
+        max_frames = self._setup(model, n_sessions, decoding_chunk_size, num_decoding_left_chunks,
+                                 max_seconds, endpoint, blank_id, search if self.rnnt else None)
         if self.rnnt:
+            tc = model._tcfg
+            if max_tokens is None:
+                max_tokens = max_frames * min(n_steps, 8)
+            self.search = RnntStreamSearch(model._h, model.device, n_sessions, max_frames,
+                                           max_tokens, n_steps,
+                                           dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
+        else:
+            self.search = StreamSearch(model._h, model.device, n_sessions, beam_size, max_frames,
+                                       blank_id, self.endpoint.blank_threshold,
+                                       self.endpoint.blank_scale)
+
+    def _setup(self, model, n_sessions, decoding_chunk_size, num_decoding_left_chunks,
+               max_seconds, endpoint, blank_id, transducer_search):
+        """Everything of __init__ but the search object; returns max_frames.
+        transducer_search: the name of a search that needs a `wenet_amd.Transducer`, or None."""
+        import torch
+        assert decoding_chunk_size > 0, 'decoding_chunk_size must be positive'
+        if transducer_search is not None:
             from wenet_amd.transducer import Transducer
             if not isinstance(model, Transducer):
-                raise TypeError("search='rnnt_greedy_search' needs a wenet_amd.Transducer, got "
+                raise TypeError(f"search='{transducer_search}' needs a wenet_amd.Transducer, got "
                                 f'{type(model).__name__}')
         model._check_simulate_streaming(torch.empty((1, 0, 0)))
         ctx = getattr(model, '_ctx_graph', None)
@@ -421,21 +557,10 @@ class StreamingRecognizer:
         self.right_context = model.right_context()
         self.endpoint = endpoint or CtcEndpointConfig(blank=blank_id)
         self.frame_shift_ms = 10 * self.subsampling
-        max_frames = int(np.ceil(max_seconds * 1000.0 / self.frame_shift_ms)) + decoding_chunk_size
-        if self.rnnt:
-            tc = model._tcfg
-            if max_tokens is None:
-                max_tokens = max_frames * min(n_steps, 8)
-            self.search = RnntStreamSearch(model._h, model.device, n_sessions, max_frames,
-                                           max_tokens, n_steps,
-                                           dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
-        else:
-            self.search = StreamSearch(model._h, model.device, n_sessions, beam_size, max_frames,
-                                       blank_id, self.endpoint.blank_threshold,
-                                       self.endpoint.blank_scale)
         self._free = list(range(n_sessions - 1, -1, -1))
         self._sessions: Dict[int, _Session] = {}
         self._next_sid = 0
+        return int(np.ceil(max_seconds * 1000.0 / self.frame_shift_ms)) + decoding_chunk_size
 
     # ---- session life cycle
     def open(self) -> int:
@@ -541,5 +666,77 @@ class StreamingRecognizer:
                 self.model, [res], enc, torch.tensor([enc.size(1)], dtype=torch.int32),
                 ctc_weight, reverse_weight)[0]
             out.is_endpoint = res.is_endpoint
+            return out
+        return res
+
+
+class RnntBeamStreamingRecognizer(StreamingRecognizer):
+    """`StreamingRecognizer` on the resumable RNN-T prefix beam search (`RnntBeamStreamSearch`):
+    the same open / accept / step / finish / close / encoder_out on a `wenet_amd.Transducer`.
+
+        rec = RnntBeamStreamingRecognizer(model, n_sessions=16, decoding_chunk_size=16,
+                                          beam_size=5)
+
+    Every partial result is the n-best `transducer.prefix_beam_search` gives for the frames so
+    far (`tokens`, `score`, `nbest`, `nbest_scores`), fused with the CTC head's log-probs by
+    `search_ctc_weight` / `search_transducer_weight`.  The endpoint rules read
+    `trailing_blank` = the frames consumed behind the last token of the best hypothesis (this
+    project's definition: the reference has no RNN-T endpointing).  A separate class, not a
+    third entry of `StreamingRecognizer.SEARCHES`: the constructor and `finish` take the
+    transducer's arguments."""
+
+    SEARCH = 'rnnt_prefix_beam_search'
+
+    def __init__(self, model, n_sessions: int, decoding_chunk_size: int,
+                 num_decoding_left_chunks: int = -1, beam_size: int = 5,
+                 search_ctc_weight: float = 0.3, search_transducer_weight: float = 0.7,
+                 max_seconds: float = 60.0, endpoint: Optional[CtcEndpointConfig] = None,
+                 blank_id: int = 0):
+        self.rnnt = True          # (_run: the search takes no `nbest` switch)
+        max_frames = self._setup(model, n_sessions, decoding_chunk_size, num_decoding_left_chunks,
+                                 max_seconds, endpoint, blank_id, self.SEARCH)
+        tc = model._tcfg
+        self.beam_size = int(beam_size)
+        self.search_ctc_weight = float(search_ctc_weight)
+        self.search_transducer_weight = float(search_transducer_weight)
+        self.search = RnntBeamStreamSearch(model._h, model.device, n_sessions, self.beam_size,
+                                           max_frames, self.search_ctc_weight,
+                                           self.search_transducer_weight,
+                                           dims=(tc.pred_layers, tc.pred_hidden, tc.join_dim))
+
+    def finish(self, sid: int, rescoring: bool = True, attn_weight: float = 0.0,
+               transducer_weight: float = 0.0, ctc_weight: float = 0.0,
+               reverse_weight: float = 0.0):
+        """No more frames for `sid`: run the windows that are left (the last may be shorter) and
+        return the final beam.  With `rescoring` on a model with a decoder, the beam is rescored
+        as `Transducer.transducer_attention_rescoring` rescores the one-shot search's (per
+        hypothesis attn * attn_weight + beam score * ctc_weight + td * transducer_weight; the
+        defaults are that method's) on the session's encoder output, WITHOUT running the search
+        again: `tokens` / `score` of the winner, `nbest` in search order, `nbest_scores` the
+        rescored score of each.  The session stays open (closed by `close`) but takes no more
+        frames."""
+        import torch
+        from wenet_amd import transducer
+        s = self._sessions[sid]
+        res = None
+        for w in s.win.flush():
+            res = self._run([sid], [w], True)[0]
+        if res is None:
+            # nothing left to run: the beam of what has been consumed (an n_t = 0 advance)
+            d = self.model._cfg.d_model
+            res = self.search.advance_encoded(
+                [s.slot], torch.zeros((1, 1, d), dtype=torch.float32, device=self.model.device),
+                [0])[0]
+            res.is_endpoint = s.last.is_endpoint if s.last is not None else None
+        if rescoring and self.model._cfg.dec_layers > 0 and s.offset > 0:
+            if reverse_weight > 0.0:
+                assert self.model._cfg.dec_r_layers > 0
+            enc = self.encoder_out(sid)
+            self.model._set_encoder_out(enc, torch.tensor([enc.size(1)], dtype=torch.int32))
+            out = transducer._rescore_current(
+                self.model, [list(zip(res.nbest, res.nbest_scores))], reverse_weight, ctc_weight,
+                attn_weight, transducer_weight)[0]
+            out.is_endpoint = res.is_endpoint
+            out.frames_decoded, out.trailing_blank = res.frames_decoded, res.trailing_blank
             return out
         return res
