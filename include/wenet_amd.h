@@ -854,6 +854,47 @@ int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config*
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out);
 
+/* The reference's two stateless predictors (predictor.py:209-495): EmbeddingPredictor, a
+ * multi-head, position-weighted mix of the last history_size + 1 token embeddings -> ffn ->
+ * LayerNorm -> activation, and ConvPredictor, a depthwise conv over the same window -> LayerNorm
+ * -> activation.  Like wn_transducer_config, a struct and an entry point of their own: nothing
+ * an existing caller passes changes. */
+typedef struct {
+  int32_t kind;              /* 1 embedding, 2 conv */
+  int32_t context;           /* predictor_conf.history_size + 1, 1..16 */
+  int32_t heads;             /* predictor_conf.n_head, 1..16; conv: 1 */
+  int32_t activation;        /* 0 swish, 1 relu */
+  int32_t conv_bias;         /* conv only: predictor.conv.bias exists */
+  float norm_eps;            /* predictor_conf.layer_norm_epsilon */
+} wn_stateless_predictor_config;
+
+/* wn_model_create_transducer for a stateless predictor: tcfg->pred_embed == tcfg->pred_out ==
+ * embed_size (the reference asserts embed_size == output_size), tcfg->pred_layers == 0 and
+ * tcfg->pred_hidden == 0.  Ingests predictor.{embed.weight, norm.*}, for an embedding predictor
+ * predictor.{pos_embed.weight, ffn.*} (pos_embed.bias may be present and is not read: neither
+ * forward nor forward_step of the reference reads it), for a conv predictor
+ * predictor.conv.weight (and .bias with conv_bias), and joint.{enc_ffn, pred_ffn, ffn_out}.*.
+ * Every transducer entry point works on the handle: a predictor advance is one launch of
+ * rnnt_stateless_step (csrc/transducer_stateless.hip), whose window is the tail of the token row
+ * the search keeps anyway, so such a handle has no h / c: the streaming state hooks write
+ * nothing to their h / c arguments.  Results do not depend on the batch, the lookahead, the slot
+ * or how a session's frames are split into calls, as for an LSTM handle. */
+int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
+                                         const wn_stateless_predictor_config* scfg,
+                                         const wn_tensor* weights, int32_t n_weights,
+                                         int32_t device, wn_model** out);
+
+/* Operator hook: one advance of a stateless predictor + joint.pred_ffn for M rows
+ * (rnnt_stateless_step).  ctx_host (M, context) holds the window ids of every row, oldest first,
+ * each in [-1, V) (-1: the zero vector).  w_dev, device pointers: embed.weight [V][E], then for
+ * kind 1 pos_embed.weight [heads][E][context], ffn.weight, ffn.bias, for kind 2 conv.weight
+ * [E][context], conv.bias (or NULL); then norm.weight, norm.bias, joint.pred_ffn.weight [J][E],
+ * joint.pred_ffn.bias: 8 pointers for kind 1, 7 for kind 2.  advance_host (M) or NULL (all
+ * rows): the rows with a zero are not written.  out_dev: (M, J). */
+int wn_op_stateless_step(const wn_stateless_predictor_config* scfg, const int32_t* ctx_host,
+                         const float* const* w_dev, const int32_t* advance_host, float* out_dev,
+                         int32_t M, int32_t V, int32_t E, int32_t J, void* stream);
+
 /* RNN-T greedy search over the handle's CURRENT batch (after wn_encode / wn_encode_chunk* /
  * wn_set_encoder_out): basic_greedy_search (wenet/models/transducer/search/greedy_search.py:6-54,
  * reached through Transducer.greedy_search, transducer.py:398-442), which the reference runs one
@@ -941,7 +982,8 @@ int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int
                                    int32_t chunk, const wn_rnnt_stream_result* out, void* stream);
 
 /* Test hook: one slot's h, c (layers x H each), pred_proj (join_dim) and
- * {last_tok, stale, n_tok, frames, trailing_blank} copied to the host. */
+ * {last_tok, stale, n_tok, frames, trailing_blank} copied to the host.  A handle with a
+ * stateless predictor has no h / c (0 layers): nothing is written to them. */
 int wn_rnnt_stream_state(wn_rnnt_stream_set* set, int32_t slot, float* h, float* c,
                          float* pred_proj, int32_t* scalars5, void* stream);
 
@@ -1015,7 +1057,8 @@ int wn_rnnt_beam_stream_advance_encoded(wn_rnnt_beam_stream_set* set, int32_t n,
 /* Test hook: one session's whole state copied to the host: counters2 = {n_live, frames}; scores
  * (beam) fp64; slot_ints (4, beam) = tok_len | last_tok | pending | last_time; tokens
  * (beam, max_frames), -1 behind tok_len; h, c (beam, layers, H); pred_proj (beam, join_dim).
- * Slots beyond n_live hold one fixed form (-inf, blank, -1, zeros). */
+ * Slots beyond n_live hold one fixed form (-inf, blank, -1, zeros).  A handle with a stateless
+ * predictor has no h / c (0 layers): nothing is written to them. */
 int wn_rnnt_beam_stream_state(wn_rnnt_beam_stream_set* set, int32_t slot, int32_t* counters2,
                               double* scores, int32_t* slot_ints, int32_t* tokens, float* h,
                               float* c, float* pred_proj, void* stream);

@@ -38,6 +38,21 @@ trie, the gather GEMM and the lattices), the attention scores (wn_rescore); the 
 against the rows without prefix sharing; `transducer_attention_rescoring()` as a whole in seconds
 of audio per second beside `beam_search()`.
 
+    python tools/bench_transducer.py --predictor embedding     # a stateless predictor
+
+--predictor embedding | conv times the searches of a model with a stateless predictor
+(`aishell_u2pp_rnnt_embed`: examples/aishell/rnnt/conf/example_embedding_predictor.yaml's 320 /
+320, 4 heads, history 5, join 320; conv: the same widths with a ConvPredictor) and of the LSTM
+model (`aishell_u2pp_rnnt`) beside it in the same process, on the same batch, each on its own
+fixed encoder output, and writes profiles/transducer_stateless.json: the greedy search at
+lookahead 1 / 4 / 16 and the prefix beam search with beam 5 / 10 at (0.3, 0.7), the models and
+settings alternating, median of --repeats; per setting the search time, the steps, the time per
+step and the launches per step (beam: 2 per LSTM layer + 6 = 10 for the LSTM model; one
+rnnt_stateless_step, the joint, the fusion + top-k, the beam step and the gather = 5 for a
+stateless one).  Each model gets the first blank bias of --blank-bias with 30-60 symbols per
+utterance (for the stateless model 10.0 .. 12.0 are tried after them: a random joint emits
+more under such a predictor).
+
 The per-kernel split (enc_proj / predictor / joint / advance) comes from a kernel trace in a run
 of its own, because the handle's launch brackets (wn_profile_enable) time the GEMM launchers
 only and a traced run is not a timed one:
@@ -74,8 +89,12 @@ def main(argv=None):
     p.add_argument('--beam', action='store_true', help='time the prefix beam search')
     p.add_argument('--rescore', action='store_true',
                    help='time transducer + attention rescoring')
+    p.add_argument('--predictor', choices=('rnn', 'embedding', 'conv'), default='rnn',
+                   help='embedding / conv: time a stateless predictor beside the LSTM model')
     p.add_argument('--out', default=None)
     args = p.parse_args(argv)
+    if args.predictor != 'rnn':
+        return bench_stateless(args)
     if args.out is None:
         args.out = os.path.join(ROOT, 'profiles', 'transducer_rescore.json' if args.rescore
                                 else 'transducer_beam.json' if args.beam
@@ -172,6 +191,113 @@ def main(argv=None):
                method='host clock around calls that end in a device synchronise; settings '
                       'alternate in one process; median of --repeats')
     print(json.dumps(out['greedy_search']), json.dumps(out['ctc_prefix_beam_search_beam10']))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+    print('wrote', args.out)
+    return 0
+
+
+STATELESS_LOOKAHEADS = (1, 4, 16)
+STATELESS_BEAMS = ((5, 0.3, 0.7), (10, 0.3, 0.7))
+
+
+def bench_stateless(args):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_transducer: needs the GPU (no CPU fallback)')
+    from wenet_amd import Transducer
+    from wenet_amd import synthetic as S
+    from wenet_amd.transducer import basic_greedy_search, prefix_beam_search
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'transducer_stateless.json')
+    sync = torch.cuda.synchronize
+    feats, lens = S.make_bench_group('config2')
+    feats = feats.cuda()
+    B = int(feats.shape[0])
+    audio_s = float(lens.sum()) * 0.01
+    if args.predictor == 'embedding':
+        stateless = S.make_configs('aishell_u2pp_rnnt_embed')
+    else:
+        S.CONFIGS['aishell_u2pp_rnnt_conv'] = S._rnnt_stateless(
+            'aishell_u2pp_rnnt', 'conv', 320, 320, history_size=5, activation='relu', bias=True)
+        stateless = S.make_configs('aishell_u2pp_rnnt_conv')
+    models = {}
+    for kind, configs in (('rnn', S.make_configs('aishell_u2pp_rnnt')), (args.predictor, stateless)):
+        if args.layers is not None:
+            configs['encoder_conf']['num_blocks'] = args.layers
+        # (a random joint emits more under a stateless predictor: larger biases are tried too)
+        for bias in list(args.blank_bias) + ([] if kind == 'rnn' else [10.0, 10.5, 11.0, 11.5, 12.0]):
+            model = Transducer(configs, S.make_state_dict(configs, 0, rnnt_blank_bias=bias),
+                               device='cuda')
+            enc, mask = model._forward_encoder(feats, lens)
+            enc_lens = mask.squeeze(1).sum(1).cpu()
+            toks = basic_greedy_search(model, enc, enc_lens, args.n_steps)
+            mean = sum(len(u) for u in toks) / len(toks)
+            print(f'{kind}: blank bias {bias}: {mean:.1f} symbols per utterance', flush=True)
+            picked = dict(blank_bias=bias, mean_symbols=mean, in_range=30 <= mean <= 60)
+            if picked['in_range']:
+                break
+        layers = configs['predictor_conf'].get('num_layers', 0)
+        models[kind] = dict(model=model, enc=enc, enc_lens=enc_lens, weights=picked, tokens=toks,
+                            beam_launches=2 * layers + 6 if kind == 'rnn' else 5,
+                            greedy_launches=2 * layers + 4 if kind == 'rnn' else 3)
+
+    def greedy(kind, F):
+        m = models[kind]
+        m['model'].tune('rnnt_lookahead', F)
+        sync()
+        t0 = time.perf_counter()
+        toks = basic_greedy_search(m['model'], m['enc'], m['enc_lens'], args.n_steps)
+        dt = time.perf_counter() - t0
+        assert toks == m['tokens'], f'{kind}: lookahead {F} decodes other tokens'
+        return dt, m['model'].last_rnnt_steps
+
+    def beam(kind, setting):
+        m = models[kind]
+        sync()
+        t0 = time.perf_counter()
+        nbest = prefix_beam_search(m['model'], m['enc'], m['enc_lens'], *setting)
+        dt = time.perf_counter() - t0
+        return dt, m['model'].last_rnnt_steps, nbest
+
+    runs = [(kind, 'greedy', F) for F in STATELESS_LOOKAHEADS for kind in models] + \
+        [(kind, 'beam', s) for s in STATELESS_BEAMS for kind in models]
+    first = {}
+    for r in runs:                    # warm up every shape
+        first[r] = greedy(r[0], r[2]) if r[1] == 'greedy' else beam(r[0], r[2])
+    times = {r: [] for r in runs}
+    for _ in range(args.repeats):
+        for r in runs:
+            got = greedy(r[0], r[2]) if r[1] == 'greedy' else beam(r[0], r[2])
+            assert r[1] == 'greedy' or got[2] == first[r][2], f'{r}: another result on a repeat'
+            times[r].append(got[0])
+    out = dict(batch=B, audio_seconds=audio_s, n_steps=args.n_steps, models={},
+               method='host clock around calls that end in a device synchronise; models and '
+                      'settings alternate in one process; median of --repeats')
+    for kind, m in models.items():
+        table = dict(weights=m['weights'], greedy={}, beam=[])
+        for r in runs:
+            if r[0] != kind:
+                continue
+            med = statistics.median(times[r])
+            steps = first[r][1]
+            row = dict(search_ms=dict(median=med * 1e3, min=min(times[r]) * 1e3,
+                                      max=max(times[r]) * 1e3),
+                       steps=steps, us_per_step=med * 1e6 / max(steps, 1))
+            if r[1] == 'greedy':
+                row['launches_per_step'] = m['greedy_launches']
+                table['greedy'][str(r[2])] = row
+                what = f'greedy lookahead {r[2]:2d}'
+            else:
+                row.update(beam=r[2][0], ctc_weight=r[2][1], transducer_weight=r[2][2],
+                           launches_per_step=m['beam_launches'], rows=B * r[2][0])
+                table['beam'].append(row)
+                what = f'beam {r[2][0]:2d} {r[2][1:]}'
+            print(f"{kind:9s} {what}: {med * 1e3:8.2f} ms  ({steps} steps, "
+                  f"{row['us_per_step']:.1f} us / step, {row['launches_per_step']} launches / step)",
+                  flush=True)
+        out['models'][kind] = table
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)

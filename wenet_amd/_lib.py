@@ -31,6 +31,12 @@ class WnTransducerConfig(Structure):
                                        'join_dim', 'blank')]
 
 
+class WnStatelessPredictorConfig(Structure):
+    """wn_stateless_predictor_config: an embedding (kind 1) or conv (kind 2) predictor."""
+    _fields_ = [(n, c_int32) for n in ('kind', 'context', 'heads', 'activation', 'conv_bias')] + [
+        ('norm_eps', c_float)]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -109,6 +115,7 @@ EXPORTS = [
     'wn_op_beam_update', 'wn_op_beam_finish',
     'wn_op_layernorm_ex', 'wn_op_layernorm2', 'wn_op_layernorm_mx', 'wn_op_ffn_reduce_ln',
     'wn_op_gemm_rowln',
+    'wn_model_create_transducer_stateless', 'wn_op_stateless_step',
 ]
 
 _lib = None
@@ -221,6 +228,11 @@ def lib():
     L.wn_profile_collect.argtypes = [vp, pi32, pf64, pf64]
     L.wn_model_create_transducer.argtypes = [POINTER(WnConfig), POINTER(WnTransducerConfig),
                                              POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_model_create_transducer_stateless.argtypes = [
+        POINTER(WnConfig), POINTER(WnTransducerConfig), POINTER(WnStatelessPredictorConfig),
+        POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_stateless_step.argtypes = [POINTER(WnStatelessPredictorConfig), pi32, POINTER(vp),
+                                       pi32, vp, i32, i32, i32, i32, vp]
     L.wn_transducer_greedy_search.argtypes = [vp, i32, pi32, pi32, i32, pi32, vp]
     L.wn_rnnt_stream_create.argtypes = [vp, i32, i32, i32, i32, POINTER(vp), vp]
     L.wn_rnnt_stream_destroy.argtypes = [vp]

@@ -20,6 +20,7 @@ LIB = os.path.join(HERE, 'libwenet_amd.so')
 SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_bf16s.hip', 'gemm_bf16p.hip', 'gemm_skinny.hip', 'ffn_fused.hip', 'gemm_rowln.hip', 'gemm_x6.hip', 'ffn_x6f.hip', 'gemm_x6r.hip', 'gemm_x6r512.hip', 'attn_search.hip', 'encoder_kernels.hip', 'attention_bf16.hip', 'attention_x6.hip', 'ctc.hip', 'ctc_align.hip', 'fbank.hip',
            'logmel.hip', 'model.hip', 'conformer.hip', 'cabi_model.hip', 'cabi_encode.hip', 'cabi_ctc.hip', 'cabi_align.hip',
            'cabi_decoder.hip', 'cabi_ops.hip', 'transducer.hip', 'transducer_beam.hip',
+           'transducer_stateless.hip',
            'cabi_transducer.hip', 'transducer_score.hip', 'cabi_transducer_score.hip',
            'transducer_stream.hip', 'cabi_transducer_stream.hip',
            'transducer_beam_stream.hip', 'cabi_transducer_beam_stream.hip']

@@ -128,10 +128,11 @@ extern "C" {
 const char* wn_last_error(void) { return last_error_cstr(); }
 const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 
-// wn_model_create / wn_model_create_transducer (tcfg == nullptr: no predictor / joint)
+// wn_model_create / wn_model_create_transducer (tcfg == nullptr: no predictor / joint) /
+// wn_model_create_transducer_stateless (scfg != nullptr: a stateless predictor, no LSTM)
 static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
-                        const wn_tensor* weights, int32_t n_weights, int32_t device,
-                        wn_model** out) {
+                        const wn_stateless_predictor_config* scfg, const wn_tensor* weights,
+                        int32_t n_weights, int32_t device, wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && c.d_model / c.n_heads == 64,
@@ -154,6 +155,7 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
   m->cfg = c;
   m->device = device;
   if (tcfg) { m->tr.on = true; m->tr.c = *tcfg; }
+  if (tcfg && scfg) m->tr.sp = *scfg;
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -383,14 +385,47 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     const wn_transducer_config& tc = *tcfg;
     const int E = tc.pred_embed, H = tc.pred_hidden, P = tc.pred_out, J = tc.join_dim;
     WN_CHECK(!tf, "transducer: Conformer encoders only");
-    WN_CHECK(E >= 1 && E <= 1024 && H >= 1 && H <= 1024 && P >= 1 && P <= 1024 &&
-             tc.pred_layers >= 1 && tc.pred_layers <= 8,
-             "transducer: predictor widths must be in [1, 1024], 1 to 8 LSTM layers");
+    if (scfg) {
+      const wn_stateless_predictor_config& sc = *scfg;
+      WN_CHECK(sc.kind == 1 || sc.kind == 2,
+               "stateless predictor: kind must be 1 (embedding) or 2 (conv)");
+      WN_CHECK(E >= 1 && E <= 1024 && P == E && H == 0 && tc.pred_layers == 0,
+               "stateless predictor: pred_embed == pred_out in [1, 1024], pred_hidden == "
+               "pred_layers == 0");
+      WN_CHECK(sc.context >= 1 && sc.context <= 16 && sc.heads >= 1 && sc.heads <= 16,
+               "stateless predictor: context and heads must be in [1, 16]");
+      WN_CHECK(sc.kind == 1 || sc.heads == 1,
+               "stateless predictor: a conv predictor has heads == 1");
+      WN_CHECK(sc.activation == 0 || sc.activation == 1,
+               "stateless predictor: activation 0 (swish) or 1 (relu)");
+      WN_CHECK(sc.norm_eps > 0.f, "stateless predictor: norm_eps must be > 0");
+    } else {
+      WN_CHECK(E >= 1 && E <= 1024 && H >= 1 && H <= 1024 && P >= 1 && P <= 1024 &&
+               tc.pred_layers >= 1 && tc.pred_layers <= 8,
+               "transducer: predictor widths must be in [1, 1024], 1 to 8 LSTM layers");
+    }
     WN_CHECK(J >= 32 && J <= 1024 && J % 32 == 0,
              "transducer: join_dim must be a multiple of 32 in [32, 1024]");
     WN_CHECK(tc.blank >= 0 && tc.blank < V, "transducer: blank id outside the vocabulary");
     WN_GET(emb, "predictor.embed.weight", (int64_t)V * E);
     hs.add("predictor.embed.weight", emb, (size_t)V * E);
+    if (scfg) {
+      const int C = scfg->context;
+      WN_TRY(stage_norm(src, hs, "predictor.norm", E));
+      if (scfg->kind == 1) {
+        // (pos_embed.bias, present with `bias: true`, is read by neither forward nor forward_step)
+        WN_GET(pos, "predictor.pos_embed.weight", (int64_t)scfg->heads * E * C);
+        hs.add("predictor.pos_embed.weight", pos, (size_t)scfg->heads * E * C);
+        WN_TRY(stage_linear(src, hs, "predictor.ffn", E, E));
+      } else {
+        WN_GET(cw, "predictor.conv.weight", (int64_t)E * C);
+        hs.add("predictor.conv.weight", cw, (size_t)E * C);
+        if (scfg->conv_bias) {
+          WN_GET(cb, "predictor.conv.bias", E);
+          hs.add("predictor.conv.bias", cb, E);
+        }
+      }
+    }
     for (int l = 0; l < tc.pred_layers; ++l) {
       const std::string sfx = "_l" + std::to_string(l);
       const int in = l == 0 ? E : H;
@@ -403,7 +438,7 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
       hs.add("predictor.rnn.bias_ih" + sfx, bi, 4 * H);
       hs.add("predictor.rnn.bias_hh" + sfx, bh, 4 * H);
     }
-    WN_TRY(stage_linear(src, hs, "predictor.projection", P, H));
+    if (!scfg) { WN_TRY(stage_linear(src, hs, "predictor.projection", P, H)); }
     WN_TRY(stage_linear(src, hs, "joint.enc_ffn", J, d));
     WN_TRY(stage_linear(src, hs, "joint.pred_ffn", J, P));
     WN_TRY(stage_linear(src, hs, "joint.ffn_out", V, J));
@@ -533,7 +568,17 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
       W.pred_rnn[l] = {P("predictor.rnn.weight_ih" + sfx), P("predictor.rnn.weight_hh" + sfx),
                        P("predictor.rnn.bias_ih" + sfx), P("predictor.rnn.bias_hh" + sfx)};
     }
-    W.pred_proj = LIN("predictor.projection", tc.pred_out, tc.pred_hidden);
+    if (!scfg) W.pred_proj = LIN("predictor.projection", tc.pred_out, tc.pred_hidden);
+    if (scfg) {
+      W.pred_norm = NORM("predictor.norm");
+      if (scfg->kind == 1) {
+        W.pred_pos = P("predictor.pos_embed.weight");
+        W.pred_ffn = LIN("predictor.ffn", tc.pred_embed, tc.pred_embed);
+      } else {
+        W.pred_conv_w = P("predictor.conv.weight");
+        if (scfg->conv_bias) W.pred_conv_b = P("predictor.conv.bias");
+      }
+    }
     W.j_enc = LIN("joint.enc_ffn", tc.join_dim, d);
     W.j_pred = LIN("joint.pred_ffn", tc.join_dim, tc.pred_out);
     W.j_out = LIN("joint.ffn_out", V, tc.join_dim);
@@ -546,14 +591,22 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
 
 int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
                     int32_t n_weights, int32_t device, wn_model** out) {
-  return create_model(cfg, nullptr, weights, n_weights, device, out);
+  return create_model(cfg, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out) {
   WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
-  return create_model(cfg, tcfg, weights, n_weights, device, out);
+  return create_model(cfg, tcfg, nullptr, weights, n_weights, device, out);
+}
+
+int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
+                                         const wn_stateless_predictor_config* scfg,
+                                         const wn_tensor* weights, int32_t n_weights,
+                                         int32_t device, wn_model** out) {
+  WN_CHECK(tcfg && scfg, "wn_model_create_transducer_stateless: null argument");
+  return create_model(cfg, tcfg, scfg, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -564,7 +617,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   std::unique_ptr<wn_model> m(new wn_model());
   m->data = src->data;      // weights, views and tables are read-only: shared
   m->cfg = src->cfg;
-  m->tr.on = src->tr.on; m->tr.c = src->tr.c;
+  m->tr.on = src->tr.on; m->tr.c = src->tr.c; m->tr.sp = src->tr.sp;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;

@@ -29,6 +29,7 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
   const wn_transducer_config& tc = m->tr.c;
   const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
   const int J = tc.join_dim, V = c.vocab, blank = tc.blank;
+  const bool stateless = m->tr.sp.kind != 0;
   const int F = std::min(std::max(tune().rnnt_lookahead, 1), 16);
   int longest = 0;
   for (int b = 0; b < B; ++b) longest = std::max(longest, m->len[b]);
@@ -76,7 +77,7 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
     t_gemm_prec = saved;
     WN_TRY(r);
   }
-  WN_HIP(hipMemsetAsync(h, 0, 2 * n_state * sizeof(float), s));
+  if (n_state > 0) WN_HIP(hipMemsetAsync(h, 0, 2 * n_state * sizeof(float), s));
   WN_TRY(rnnt_init(st, B, F, blank, s));
 
   // ---- the lock-step loop: groups of steps, n_active looked at one group late -----------------
@@ -86,13 +87,19 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
   for (int g = 0; issued < bound; ++g) {
     const int n = (int)std::min<int64_t>(RNNT_GROUP, bound - issued);
     for (int i = 0; i < n; ++i) {
-      WN_TRY(predictor_step(W.pred_embed, E, st.last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h,
-                            cst, gates, pout, st.advance, st.n_active, B, H, s));
-      RnntLinearArgs q;   // joint.pred_ffn
-      q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-      q.y = pproj; q.ldy = J; q.N = J; q.B = B;
-      q.advance = st.advance; q.n_active = st.n_active;
-      WN_TRY(rnnt_linear(q, s));
+      if (stateless) {    // the window: the tail of the utterance's token row up to n_tok
+        StatelessWindow sw;
+        sw.tokens = st.tokens; sw.ld_tok = max_tok; sw.tok_len = st.n_tok;
+        WN_TRY(stateless_step(m, sw, pproj, st.advance, st.n_active, B, s));
+      } else {
+        WN_TRY(predictor_step(W.pred_embed, E, st.last_tok, E, W.pred_rnn.data(), L, W.pred_proj,
+                              h, cst, gates, pout, st.advance, st.n_active, B, H, s));
+        RnntLinearArgs q;   // joint.pred_ffn
+        q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
+        q.y = pproj; q.ldy = J; q.N = J; q.B = B;
+        q.advance = st.advance; q.n_active = st.n_active;
+        WN_TRY(rnnt_linear(q, s));
+      }
       RnntJointArgs ja;
       ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pproj; ja.ldp = J;
       ja.row_enc = st.row_enc; ja.row_pred = st.row_pred;
@@ -167,6 +174,7 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
   const wn_transducer_config& tc = m->tr.c;
   const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
   const int J = tc.join_dim, blank = tc.blank;
+  const bool stateless = m->tr.sp.kind != 0;
   int longest = 0;
   for (int b = 0; b < B; ++b) longest = std::max(longest, m->len[b]);
   const int max_tok = std::max(longest, 1);     // one symbol per frame at most
@@ -229,7 +237,7 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
     WN_TRY(ctc_logsoftmax_topk(r, s));
     ctc = m->tr_ctc.as<float>();
   }
-  WN_HIP(hipMemsetAsync(f + o_h, 0, 4 * n_state * sizeof(float), s));
+  if (n_state > 0) WN_HIP(hipMemsetAsync(f + o_h, 0, 4 * n_state * sizeof(float), s));
   WN_HIP(hipMemsetAsync(ip + o_stat, 0, sizeof(int), s));
   WN_TRY(rnnt_beam_init(slots[0], last_tok, advance, row_enc, row_pred, off, len, B, beam, blank, s));
 
@@ -237,12 +245,18 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
   for (int i = 0; i < longest; ++i) {
     const int cur = i & 1, nxt = cur ^ 1;
     float *h = f + o_h + cur * n_state, *cst = f + o_c + cur * n_state, *pp = f + o_pp + cur * n_pp;
-    WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
-                          gates, pout, advance, nullptr, M, H, s));
-    RnntLinearArgs q;   // joint.pred_ffn
-    q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-    q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
-    WN_TRY(rnnt_linear(q, s));
+    if (stateless) {    // the window: the tail of the slot's token row in the parity just written
+      StatelessWindow sw;
+      sw.tokens = slots[cur].tokens; sw.ld_tok = max_tok; sw.tok_len = slots[cur].tok_len;
+      WN_TRY(stateless_step(m, sw, pp, advance, nullptr, M, s));
+    } else {
+      WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
+                            gates, pout, advance, nullptr, M, H, s));
+      RnntLinearArgs q;   // joint.pred_ffn
+      q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
+      q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
+      WN_TRY(rnnt_linear(q, s));
+    }
     RnntJointArgs ja;
     ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pp; ja.ldp = J;
     ja.row_enc = row_enc; ja.row_pred = row_pred;
@@ -332,6 +346,50 @@ int wn_op_lstm_step(const float* x_dev, const float* const* w_host, int32_t n_la
   proj.w = proj_w_dev; proj.b = proj_b_dev; proj.out = P; proj.in = H;
   return predictor_step(x_dev, E, nullptr, E, layers.data(), n_layers, proj, h_dev, c_dev,
                         gates.as<float>(), out_dev, advance_dev, nullptr, B, H, s);
+}
+
+int wn_op_stateless_step(const wn_stateless_predictor_config* scfg, const int32_t* ctx_host,
+                         const float* const* w_dev, const int32_t* advance_host, float* out_dev,
+                         int32_t M, int32_t V, int32_t E, int32_t J, void* stream) {
+  WN_CHECK(scfg && ctx_host && w_dev && out_dev, "wn_op_stateless_step: null argument");
+  const wn_stateless_predictor_config& sc = *scfg;
+  WN_CHECK(sc.kind == 1 || sc.kind == 2,
+           "wn_op_stateless_step: kind must be 1 (embedding) or 2 (conv)");
+  WN_CHECK(M >= 1 && M <= (1 << 20) && V >= 1, "wn_op_stateless_step: empty or too large");
+  WN_CHECK(E >= 1 && E <= 1024 && J >= 1 && J <= 1024,
+           "wn_op_stateless_step: widths must be in [1, 1024]");
+  WN_CHECK(sc.context >= 1 && sc.context <= 16 && sc.heads >= 1 && sc.heads <= 16,
+           "wn_op_stateless_step: context and heads must be in [1, 16]");
+  WN_CHECK(sc.activation == 0 || sc.activation == 1,
+           "wn_op_stateless_step: activation 0 (swish) or 1 (relu)");
+  const int C = sc.context, nw = sc.kind == 1 ? 8 : 7;
+  for (int i = 0; i < nw; ++i)
+    WN_CHECK(w_dev[i] || (sc.kind == 2 && i == 2), "wn_op_stateless_step: null weight");
+  for (int64_t i = 0; i < (int64_t)M * C; ++i)
+    WN_CHECK(ctx_host[i] >= -1 && ctx_host[i] < V,
+             "wn_op_stateless_step: context id outside [-1, vocabulary)");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf ids;
+  const size_t n_ctx = up64((size_t)M * C);
+  WN_TRY(ids.ensure((n_ctx + (size_t)M) * sizeof(int)));
+  WN_HIP(hipMemcpyAsync(ids.p, ctx_host, (size_t)M * C * sizeof(int), hipMemcpyHostToDevice, s));
+  if (advance_host)
+    WN_HIP(hipMemcpyAsync(ids.as<int>() + n_ctx, advance_host, (size_t)M * sizeof(int),
+                          hipMemcpyHostToDevice, s));
+  RnntStatelessArgs a;
+  a.kind = sc.kind; a.E = E; a.C = C; a.heads = sc.kind == 1 ? sc.heads : 1; a.J = J; a.V = V;
+  a.act = sc.activation; a.eps = sc.norm_eps;
+  a.embed = w_dev[0];
+  if (sc.kind == 1) { a.pos = w_dev[1]; a.ffn_w = w_dev[2]; a.ffn_b = w_dev[3]; }
+  else { a.conv_w = w_dev[1]; a.conv_b = w_dev[2]; }
+  const float* const* r = w_dev + (sc.kind == 1 ? 4 : 3);
+  a.norm_w = r[0]; a.norm_b = r[1]; a.pj_w = r[2]; a.pj_b = r[3];
+  a.ctx = ids.as<int>();
+  a.out = out_dev; a.ldo = J; a.M = M;
+  a.advance = advance_host ? ids.as<int>() + n_ctx : nullptr;
+  WN_TRY(rnnt_stateless_step(a, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
 }
 
 int wn_op_joint_argmax(const float* enc_proj_dev, int32_t enc_rows, const float* pred_proj_dev,

@@ -170,6 +170,7 @@ int wn_rnnt_beam_stream_advance_encoded(wn_rnnt_beam_stream_set* set, int32_t n,
   const int J = tc.join_dim, V = c.vocab, blank = tc.blank, d = c.d_model;
   const int beam = S->beam, max_tok = S->max_frames;
   const float cw = S->cw, tw = S->tw;
+  const bool stateless = m->tr.sp.kind != 0;
   const int M = n * beam, ldl = (V + 31) / 32 * 32;
   WN_CHECK((int64_t)n * chunk * std::max(J, ldl) <= ((int64_t)1 << 30) &&
                (int64_t)M * ldl <= ((int64_t)1 << 28),
@@ -266,12 +267,18 @@ int wn_rnnt_beam_stream_advance_encoded(wn_rnnt_beam_stream_set* set, int32_t n,
   for (int i = 0; i < longest; ++i) {
     const int cur = i & 1, nxt = cur ^ 1;
     float *h = f + o_h + cur * n_state, *cst = f + o_c + cur * n_state, *pp = f + o_pp + cur * n_pp;
-    WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
-                          gates, pout, advance, nullptr, M, H, s));
-    RnntLinearArgs q;   // joint.pred_ffn
-    q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-    q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
-    WN_TRY(rnnt_linear(q, s));
+    if (stateless) {    // the window: the tail of the slot's token row in the parity just written
+      StatelessWindow sw;
+      sw.tokens = slots[cur].tokens; sw.ld_tok = max_tok; sw.tok_len = slots[cur].tok_len;
+      WN_TRY(stateless_step(m, sw, pp, advance, nullptr, M, s));
+    } else {
+      WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
+                            gates, pout, advance, nullptr, M, H, s));
+      RnntLinearArgs q;   // joint.pred_ffn
+      q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
+      q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
+      WN_TRY(rnnt_linear(q, s));
+    }
     RnntJointArgs ja;
     ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pp; ja.ldp = J;
     ja.row_enc = row_enc; ja.row_pred = row_pred;

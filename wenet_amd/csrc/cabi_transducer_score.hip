@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "model_state.h"
+#include "rnnt_predictor.h"
 #include "rnnt_trie.h"
 
 namespace wn {
@@ -125,6 +126,10 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
     if (m->len[b] > 0)
       for (int k = 0; k < n_hyps_host[b]; ++k) n_u += (size_t)hyp_lens_host[(size_t)b * beam + k] + 1;
   const size_t o_ub = ip.add(n_u), o_ul = ip.add(n_u);
+  // a stateless predictor: the window of every node, (nodes, C), next to the trie
+  const bool stateless = m->tr.sp.kind != 0;
+  const int C = m->tr.sp.context;
+  const size_t o_ctx = stateless ? ip.add((size_t)n_tot * C) : 0;
   std::vector<int>& hi = ip.host;
   std::vector<int64_t> base(NH, 0);
   int max_u = 0;
@@ -136,6 +141,13 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
       for (int i = 0; i < Nb; ++i) {
         hi[o_par + gid[b][i]] = t.parent[i] < 0 ? -1 : gid[b][t.parent[i]];
         hi[o_tok + gid[b][i]] = t.token[i];
+      }
+      if (stateless && Nb > 0) {
+        std::vector<int> ctx((size_t)Nb * C);
+        rnnt_trie_context(t, C, ctx.data());
+        for (int i = 0; i < Nb; ++i)
+          std::copy(ctx.begin() + (size_t)i * C, ctx.begin() + (size_t)(i + 1) * C,
+                    hi.begin() + o_ctx + (size_t)gid[b][i] * C);
       }
       const int ent_base = ent;
       for (int f = 0; f < Tb; ++f)
@@ -212,9 +224,14 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
   WN_HIP(mark(1));
 
   // ---- the predictor over the trie, depth by depth: a node starts from its parent's state --------
-  WN_HIP(hipMemsetAsync(h, 0, 2 * n_state * sizeof(float), s));
+  if (n_state > 0) WN_HIP(hipMemsetAsync(h, 0, 2 * n_state * sizeof(float), s));
   const int64_t lstride = (int64_t)n_tot * H;
-  for (int dd = 0; dd <= depth_max; ++dd) {
+  if (stateless) {    // every node at once: its output is a function of its window alone
+    StatelessWindow sw;
+    sw.ctx = di + o_ctx;
+    WN_TRY(stateless_step(m, sw, pproj, nullptr, nullptr, n_tot, s));
+  }
+  for (int dd = 0; !stateless && dd <= depth_max; ++dd) {
     const int r0 = lvl_off[dd], n = lvl_off[dd + 1] - r0;
     if (n <= 0) continue;
     if (dd > 0) WN_TRY(rnnt_trie_gather(di + o_par, h, cst, r0, n, L, lstride, H, s));
@@ -232,14 +249,14 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
   }
   const float* top = h + (L - 1) * lstride;
   int ld_top = H, k_top = H;
-  if (W.pred_proj.w) {
+  if (!stateless && W.pred_proj.w) {
     RnntLinearArgs g;
     g.x1 = top; g.ldx1 = H; g.K1 = H; g.W1 = W.pred_proj.w; g.b1 = W.pred_proj.b;
     g.y = pout; g.ldy = P; g.N = P; g.B = n_tot;
     WN_TRY(rnnt_linear(g, s));
     top = pout; ld_top = P; k_top = P;
   }
-  {
+  if (!stateless) {
     RnntLinearArgs q;   // joint.pred_ffn
     q.x1 = top; q.ldx1 = ld_top; q.K1 = k_top; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
     q.y = pproj; q.ldy = J; q.N = J; q.B = n_tot;

@@ -157,6 +157,7 @@ int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int
   const int J = tc.join_dim, V = c.vocab, blank = tc.blank, d = c.d_model;
   const int F = std::min(std::max(tune().rnnt_lookahead, 1), 16);
   const int n_steps = S->n_steps;
+  const bool stateless = m->tr.sp.kind != 0;
   const int M = n * F, ncb = rnnt_joint_col_blocks(V), rows = n * chunk;
   int longest = 0;
   for (int i = 0; i < n; ++i) longest = std::max(longest, (int)n_t_host[i]);
@@ -214,13 +215,20 @@ int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int
   for (int g = 0; issued < bound; ++g) {
     const int k = (int)std::min<int64_t>(RNNT_GROUP, bound - issued);
     for (int i = 0; i < k; ++i) {
-      WN_TRY(predictor_step(W.pred_embed, E, cl.last_tok, E, W.pred_rnn.data(), L, W.pred_proj,
-                            cl.h, cl.c, gates, pout, cl.advance, cl.n_active, n, H, s));
-      RnntLinearArgs q;   // joint.pred_ffn
-      q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-      q.y = cl.pred_proj; q.ldy = J; q.N = J; q.B = n;
-      q.advance = cl.advance; q.n_active = cl.n_active;
-      WN_TRY(rnnt_linear(q, s));
+      if (stateless) {    // the window: the tail of the session's own token row up to n_tok
+        StatelessWindow sw;
+        sw.tokens = S->sl.tokens; sw.ld_tok = S->sl.max_tok; sw.tok_len = S->sl.n_tok;
+        sw.tok_row = cl.slot;
+        WN_TRY(stateless_step(m, sw, cl.pred_proj, cl.advance, cl.n_active, n, s));
+      } else {
+        WN_TRY(predictor_step(W.pred_embed, E, cl.last_tok, E, W.pred_rnn.data(), L, W.pred_proj,
+                              cl.h, cl.c, gates, pout, cl.advance, cl.n_active, n, H, s));
+        RnntLinearArgs q;   // joint.pred_ffn
+        q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
+        q.y = cl.pred_proj; q.ldy = J; q.N = J; q.B = n;
+        q.advance = cl.advance; q.n_active = cl.n_active;
+        WN_TRY(rnnt_linear(q, s));
+      }
       RnntJointArgs ja;
       ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = cl.pred_proj; ja.ldp = J;
       ja.row_enc = cl.row_enc; ja.row_pred = cl.row_pred;

@@ -554,6 +554,35 @@ int rnnt_advance(const float* part_max, const int* part_idx, int ncb, int V, con
 int rnnt_reduce_partials(const float* part_max, const int* part_idx, int ncb, int M,
                          float* out_max, int* out_idx, hipStream_t s);
 
+// One advance of a stateless predictor (transducer_stateless.hip), fp32: for the rows with
+// advance[m] != 0 (null: all rows) out[m][:J] = joint.pred_ffn(act(LayerNorm(mix(window of m)))).
+// kind 1 (EmbeddingPredictor): w[h][c] = sum_e x[c][e] pos[h][e][c], mix[e] = sum_c (sum_h w[h][c])
+// x[c][e] / (heads C), then ffn.  kind 2 (ConvPredictor): mix[e] = sum_c x[c][e] conv_w[e][c]
+// (+ conv_b[e]).  x[c] = embed[id[c]], the zero vector for an id outside [0, V).  The window of
+// row m, oldest first: ctx[m][:C], or (ctx == null) the last C entries of
+// [-1, ..., -1, blank, tokens[tr][0 .. tok_len[tr])] with tr = tok_row ? tok_row[m] : m; a
+// position at or past ld_tok reads as -1.  The other rows of `out` are left as they are.
+struct RnntStatelessArgs {
+  int kind = 0, E = 0, C = 0, heads = 1, J = 0, V = 0;
+  int act = 0;                      // 0 swish, 1 relu
+  float eps = 1e-5f;
+  const float* embed = nullptr;     // [V][E]
+  const float* pos = nullptr;       // [heads][E][C]
+  const float* ffn_w = nullptr; const float* ffn_b = nullptr;     // [E][E], [E]
+  const float* conv_w = nullptr; const float* conv_b = nullptr;   // [E][C], [E] or null
+  const float* norm_w = nullptr; const float* norm_b = nullptr;   // [E]
+  const float* pj_w = nullptr; const float* pj_b = nullptr;       // joint.pred_ffn [J][E], [J]
+  const int* ctx = nullptr;         // [M][C], or null: the token rows
+  const int* tokens = nullptr; int ld_tok = 0;
+  const int* tok_len = nullptr; const int* tok_row = nullptr;
+  int blank = 0;
+  float* out = nullptr; int ldo = 0;
+  int M = 0;
+  const int* advance = nullptr;
+  const int* n_active = nullptr;    // device flag: 0 = the batch is finished, return at once
+};
+int rnnt_stateless_step(const RnntStatelessArgs& a, hipStream_t s);
+
 // Resumable RNN-T greedy search (transducer_stream.hip): the state of a set of sessions, one
 // slot each, that stays in HBM between calls.  Arrays of n_slots entries unless noted.
 struct RnntStreamSlots {

@@ -224,6 +224,12 @@ struct ModelData {
   const float* pred_embed = nullptr;     // [V][pred_embed]
   std::vector<LstmLayer> pred_rnn;
   Linear pred_proj, j_enc, j_pred, j_out;
+  // stateless predictors (wn_model::tr.sp.kind != 0; no LSTM layers): EmbeddingPredictor's
+  // pos_embed.weight [heads][E][C] and ffn, ConvPredictor's conv [E][C] (+ bias), the LayerNorm
+  const float* pred_pos = nullptr;
+  const float* pred_conv_w = nullptr; const float* pred_conv_b = nullptr;
+  Linear pred_ffn;
+  Norm pred_norm;
   // fbank tables
   const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
   const float* fb_mel_w = nullptr;
@@ -253,7 +259,12 @@ struct ModelData {
 struct wn_model {
   wn_config cfg;
   // wn_model_create_transducer: the predictor / joint widths (tr.on == false: an asr_model)
-  struct { bool on = false; wn_transducer_config c = {}; } tr;
+  // sp.kind != 0: wn_model_create_transducer_stateless (c.pred_layers == 0, c.pred_hidden == 0)
+  struct {
+    bool on = false;
+    wn_transducer_config c = {};
+    wn_stateless_predictor_config sp = {};
+  } tr;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();

@@ -38,6 +38,33 @@ inline int predictor_step(const float* x, int ldx, const int* x_rows, int E,
   return 0;
 }
 
+// Where the window of a stateless predictor's row comes from: explicit ids [M][C], or the tail
+// of a token row the search keeps (kernels.h, RnntStatelessArgs).
+struct StatelessWindow {
+  const int* ctx = nullptr;
+  const int* tokens = nullptr; int ld_tok = 0;
+  const int* tok_len = nullptr; const int* tok_row = nullptr;
+};
+
+// One advance of a stateless handle's predictor for the advancing rows, joint.pred_ffn included:
+// pred_proj [M][J] in one launch (the LSTM route: predictor_step + the joint.pred_ffn launch).
+inline int stateless_step(const wn_model* m, const StatelessWindow& w, float* pred_proj,
+                          const int* advance, const int* n_active, int M, hipStream_t s) {
+  const ModelData& W = *m->data;
+  const wn_transducer_config& tc = m->tr.c;
+  const wn_stateless_predictor_config& sc = m->tr.sp;
+  RnntStatelessArgs a;
+  a.kind = sc.kind; a.E = tc.pred_embed; a.C = sc.context; a.heads = sc.heads; a.J = tc.join_dim;
+  a.V = m->cfg.vocab; a.act = sc.activation; a.eps = sc.norm_eps;
+  a.embed = W.pred_embed; a.pos = W.pred_pos; a.ffn_w = W.pred_ffn.w; a.ffn_b = W.pred_ffn.b;
+  a.conv_w = W.pred_conv_w; a.conv_b = W.pred_conv_b;
+  a.norm_w = W.pred_norm.w; a.norm_b = W.pred_norm.b; a.pj_w = W.j_pred.w; a.pj_b = W.j_pred.b;
+  a.ctx = w.ctx; a.tokens = w.tokens; a.ld_tok = w.ld_tok; a.tok_len = w.tok_len;
+  a.tok_row = w.tok_row; a.blank = tc.blank;
+  a.out = pred_proj; a.ldo = tc.join_dim; a.M = M; a.advance = advance; a.n_active = n_active;
+  return rnnt_stateless_step(a, s);
+}
+
 inline size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 
 }  // namespace wn

@@ -71,4 +71,14 @@ inline void rnnt_trie_build(const int* tokens, const int* lens, int n, int pitch
   }
 }
 
+// A stateless predictor's window of every node, ctx + node * C, oldest first: the last C entries
+// of [-1, ..., -1, blank, the path to the node] (node 0's token is the blank).
+inline void rnnt_trie_context(const RnntTrie& t, int C, int* ctx) {
+  for (int i = 0; i < t.nodes(); ++i) {
+    int c = C - 1;
+    for (int j = i; c >= 0 && j >= 0; j = t.parent[j]) ctx[(size_t)i * C + c--] = t.token[j];
+    for (; c >= 0; --c) ctx[(size_t)i * C + c] = -1;
+  }
+}
+
 }  // namespace wn

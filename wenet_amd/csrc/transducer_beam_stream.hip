@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void rnnt_beam_stream_reset_kernel(RnntBeamStr
 }
 
 bool beam_stream_dims_ok(const RnntBeamStreamSlots& sl) {
-  return sl.beam >= 1 && sl.beam <= 16 && sl.L >= 1 && sl.H >= 1 && sl.J >= 1 && sl.max_tok >= 1;
+  return sl.beam >= 1 && sl.beam <= 16 && sl.L >= 0 && sl.H >= 0 && sl.J >= 1 && sl.max_tok >= 1;
 }
 
 }  // namespace

@@ -388,6 +388,26 @@ CONFIGS['tiny_rnnt_wide'] = dict(CONFIGS['tiny_rnnt'], output_dim=8329)
 # examples/aishell/rnnt/conf/conformer_u2pp_rnnt.yaml:1-87 at full width (tools/bench_transducer.py)
 CONFIGS['aishell_u2pp_rnnt'] = _rnnt('aishell_u2pp', 256, 256, 256, 256, 512)
 
+
+# the reference's stateless predictors (predictor.py:209-495) in place of the LSTM: `kind`
+# 'embedding' (examples/aishell/rnnt/conf/example_embedding_predictor.yaml:24-43) or 'conv';
+# embed_size == output_size == joint_conf.pred_output_size
+def _rnnt_stateless(base: str, kind: str, embed: int, join: int, **conf) -> dict:
+    c = copy.deepcopy(CONFIGS[base])
+    c['predictor'] = kind
+    c['predictor_conf'] = dict(embed_size=embed, output_size=embed, embed_dropout=0.1, **conf)
+    c['joint_conf'] = dict(c['joint_conf'], pred_output_size=embed, join_dim=join)
+    return c
+
+
+CONFIGS['tiny_rnnt_embed'] = _rnnt_stateless('tiny_rnnt', 'embedding', 80, 160, n_head=4,
+                                             history_size=3, bias=False)
+CONFIGS['tiny_rnnt_conv'] = _rnnt_stateless('tiny_rnnt', 'conv', 96, 160, history_size=2,
+                                            activation='relu', bias=True)
+# example_embedding_predictor.yaml at full width (tools/bench_transducer.py --predictor embedding)
+CONFIGS['aishell_u2pp_rnnt_embed'] = _rnnt_stateless('aishell_u2pp_rnnt', 'embedding', 320, 320,
+                                                     n_head=4, history_size=5, bias=False)
+
 RNNT_BLANK_BIAS = 6.0    # make_state_dict's default bias of the joint's blank logit
 
 
@@ -452,7 +472,9 @@ def _add_transducer(sd, configs: dict, seed: int, blank_bias: float):
     frame group, 9 and more empties whole utterances."""
     pc, jc = configs['predictor_conf'], configs['joint_conf']
     V = configs['output_dim']
-    E, H, P, L = pc['embed_size'], pc['hidden_size'], pc['output_size'], pc['num_layers']
+    kind = configs.get('predictor', 'rnn')
+    E, P = pc['embed_size'], pc['output_size']
+    H, L = (pc['hidden_size'], pc['num_layers']) if kind == 'rnn' else (0, 0)
     J = jc['join_dim']
 
     def mat(name, out_f, in_f):
@@ -467,8 +489,26 @@ def _add_transducer(sd, configs: dict, seed: int, blank_bias: float):
         mat(f'predictor.rnn.weight_hh_l{l}', 4 * H, H)
         vec(f'predictor.rnn.bias_ih_l{l}', 4 * H)
         vec(f'predictor.rnn.bias_hh_l{l}', 4 * H)
-    for name, o, i in (('predictor.projection', P, H), ('joint.enc_ffn', J, jc['enc_output_size']),
-                       ('joint.pred_ffn', J, P), ('joint.ffn_out', V, J)):
+    linears = [('joint.enc_ffn', J, jc['enc_output_size']), ('joint.pred_ffn', J, P),
+               ('joint.ffn_out', V, J)]
+    if kind == 'rnn':
+        linears.insert(0, ('predictor.projection', P, H))
+    else:
+        # EmbeddingPredictor / ConvPredictor (predictor.py:218-242, :381-405)
+        C = pc.get('history_size', 2) + 1
+        if kind == 'embedding':
+            mat('predictor.pos_embed.weight', pc['n_head'], E * C)
+            if pc.get('bias', False):
+                vec('predictor.pos_embed.bias', pc['n_head'])   # (the reference never reads it)
+            linears.insert(0, ('predictor.ffn', E, E))
+        else:
+            sd['predictor.conv.weight'] = _normal(seed, 'predictor.conv.weight', (E, 1, C),
+                                                  3.0 / math.sqrt(C))
+            if pc.get('bias', False):
+                vec('predictor.conv.bias', E)
+        sd['predictor.norm.weight'] = _normal(seed, 'predictor.norm.weight', (E, ), 0.1, 1.0)
+        vec('predictor.norm.bias', E)
+    for name, o, i in linears:
         mat(name + '.weight', o, i)
         vec(name + '.bias', o)
     blank = ((configs.get('tokenizer_conf') or {}).get('special_tokens') or {}).get('<blank>', 0)

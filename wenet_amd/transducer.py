@@ -8,6 +8,7 @@ Mirrors (reference file:line):
   * Transducer.transducer_attention_rescoring wenet/models/transducer/transducer.py:262-396
   * _cal_transducer_score / _cal_attn_score   wenet/models/transducer/transducer.py:161-214
   * RNNPredictor / TransducerJoint            transducer/predictor.py:60-206, joint.py:62-92
+  * EmbeddingPredictor / ConvPredictor        transducer/predictor.py:209-495
   * how init_model builds the model           wenet/utils/init_model.py:137-154
 
 The reference decodes one utterance and one symbol at a time; here the whole batch runs in
@@ -91,6 +92,76 @@ def transducer_config_from_yaml(configs: dict):
     st = (configs.get('tokenizer_conf') or {}).get('special_tokens') or {}
     tc.blank = st.get('<blank>', (configs.get('ctc_conf') or {}).get('ctc_blank_id', 0))
     return c, tc
+
+
+STATELESS_PREDICTORS = {'embedding': 1, 'conv': 2}      # wn_stateless_predictor_config.kind
+
+
+def stateless_transducer_config_from_yaml(configs: dict):
+    """train.yaml dict of a `model: transducer` recipe with `predictor: embedding` or
+    `predictor: conv` (predictor.py:209-495) -> (wn_config, wn_transducer_config,
+    WnStatelessPredictorConfig).  The encoder / decoder keys and the joint are read as
+    `transducer_config_from_yaml` reads them; the handle has pred_embed == pred_out ==
+    embed_size and no LSTM layers.  Has kernels: swish or relu, a window of at most 16 tokens,
+    at most 16 heads, embed_size at most 1024; anything else is refused."""
+    model_type = configs.get('model', 'asr_model')
+    if model_type != 'transducer':
+        _refuse('model', model_type, 'transducer')
+    pred = configs.get('predictor', 'rnn')
+    if pred not in STATELESS_PREDICTORS:
+        _refuse('predictor', pred, 'embedding or conv')
+    joint = configs.get('joint', 'transducer_joint')
+    if joint != 'transducer_joint':
+        _refuse('joint', joint, 'transducer_joint')
+    pc = configs.get('predictor_conf') or {}
+    jc = configs.get('joint_conf') or {}
+    for k, want in (('joint_mode', 'add'), ('prejoin_linear', True), ('postjoin_linear', False),
+                    ('activation', 'tanh'), ('hat_joint', False)):   # TransducerJoint defaults
+        if jc.get(k, want) != want:
+            _refuse(f'joint_conf.{k}', jc.get(k), want)
+    for k in ('embed_size', 'output_size') + (('n_head', ) if pred == 'embedding' else ()):
+        if k not in pc:
+            raise KeyError(f'predictor_conf.{k}')
+    embed = pc['embed_size']
+    if pc['output_size'] != embed:      # predictor.py:230 / :392 assert it
+        _refuse('predictor_conf.output_size', pc['output_size'], embed)
+    if not 1 <= embed <= 1024:
+        _refuse('predictor_conf.embed_size', embed, 'at most 1024')
+    act = pc.get('activation', 'swish' if pred == 'embedding' else 'relu')
+    if act not in ('swish', 'relu'):
+        _refuse('predictor_conf.activation', act, 'swish or relu')
+    history = pc.get('history_size', 2)
+    if not 0 <= history <= 15:
+        _refuse('predictor_conf.history_size', history, 'at most 15 (a window of 16 tokens)')
+    heads = pc['n_head'] if pred == 'embedding' else 1
+    if not 1 <= heads <= 16:
+        _refuse('predictor_conf.n_head', heads, 'at most 16')
+    as_asr = copy.copy(configs)
+    as_asr['model'] = 'asr_model'
+    c = config_from_yaml(as_asr)
+    if c.encoder_type != 0:
+        _refuse('encoder', configs.get('encoder'), 'conformer')
+    if jc.get('enc_output_size', c.d_model) != c.d_model:
+        _refuse('joint_conf.enc_output_size', jc.get('enc_output_size'), c.d_model)
+    if jc.get('pred_output_size', embed) != embed:
+        _refuse('joint_conf.pred_output_size', jc.get('pred_output_size'), embed)
+    join_dim = jc['join_dim']
+    if join_dim % 32 != 0 or not 32 <= join_dim <= 1024:
+        _refuse('joint_conf.join_dim', join_dim, 'a multiple of 32 in [32, 1024]')
+    tc = _lib.WnTransducerConfig()
+    tc.pred_embed = tc.pred_out = embed
+    tc.pred_hidden = tc.pred_layers = 0
+    tc.join_dim = join_dim
+    st = (configs.get('tokenizer_conf') or {}).get('special_tokens') or {}
+    tc.blank = st.get('<blank>', (configs.get('ctc_conf') or {}).get('ctc_blank_id', 0))
+    sc = _lib.WnStatelessPredictorConfig()
+    sc.kind = STATELESS_PREDICTORS[pred]
+    sc.context = history + 1
+    sc.heads = heads
+    sc.activation = 0 if act == 'swish' else 1
+    sc.conv_bias = int(pred == 'conv' and bool(pc.get('bias', False)))
+    sc.norm_eps = pc.get('layer_norm_epsilon', 1e-5)
+    return c, tc, sc
 
 
 def _search_current(model, B: int, max_frames: int, n_steps: int):
@@ -314,10 +385,18 @@ class Transducer(ASRModel):
         self.last_rnnt_score_rows = (0, 0, 0)
 
     def _config(self, configs: dict) -> _lib.WnConfig:
-        cfg, self._tcfg = transducer_config_from_yaml(configs)
+        self._scfg = None       # WnStatelessPredictorConfig of an embedding / conv predictor
+        if configs.get('predictor', 'rnn') in STATELESS_PREDICTORS:
+            cfg, self._tcfg, self._scfg = stateless_transducer_config_from_yaml(configs)
+        else:
+            cfg, self._tcfg = transducer_config_from_yaml(configs)
         return cfg
 
     def _create(self, L, tensors, n: int, h) -> int:
+        if self._scfg is not None:
+            return L.wn_model_create_transducer_stateless(
+                ctypes.byref(self._cfg), ctypes.byref(self._tcfg), ctypes.byref(self._scfg),
+                tensors, n, self.device.index, ctypes.byref(h))
         return L.wn_model_create_transducer(ctypes.byref(self._cfg), ctypes.byref(self._tcfg),
                                             tensors, n, self.device.index, ctypes.byref(h))
 
