@@ -674,6 +674,29 @@ int wn_op_conv1(const float* feats, const float* mean, const float* istd, const 
                 const float* bias, float* out, const int32_t* t1_off, const int32_t* t1_len,
                 int32_t B, int32_t T, int32_t F, int32_t C, int32_t out_rows,
                 int32_t plane_image, void* stream);
+/* Self attention WITH the relative shift (FireRedASR's FiredRelPositionMultiHeadedAttention, the
+ * Transformer-XL form; csrc/firered.hip), fp32, d_k = 64, full context:
+ *   score(i, j) = ((q_i + u) . k_j + (q_i + v) . p_{i-j}) * scale, softmax over the sequence's keys.
+ * Q / K / V / O [rows][ld*]; off / len host [n_seq] (ascending, disjoint).  P [p_rows][ldp] holds
+ * the projected position row of DISTANCE r = i - j in row p_center - r (the row order of the
+ * reference's pos_emb); every |r| < max(len) must lie inside the table. */
+int wn_op_attention_relshift(const float* Q, const float* K, const float* V, int32_t ldq,
+                             int32_t ldk, int32_t ldv, int32_t rows, const float* P,
+                             int32_t ldp, int32_t p_rows, int32_t p_center, const float* bias_u,
+                             const float* bias_v, float* O, int32_t ldo, const int32_t* off,
+                             const int32_t* len, int32_t n_seq, int32_t n_heads, float scale,
+                             void* stream);
+/* The FireRedASR front end up to the output projection (FireRedConv2dSubsampling4): GlobalCMVN
+ * (mean NULL: none), six zero frames behind every utterance's own last frame, Conv2d(1, C, 3, 2)
+ * + ReLU, Conv2d(C, C, 3, 2) + ReLU.  feats (B, T, F); w1 [9][C] and w2 [9][C_in][C_out]
+ * tap-major; out [out_rows][ldo] with utterance b's frames from row out_off[b] (host [B]),
+ * column c * F2 + f2.  out_len (host [B], written) = ((len + 6 - 3) / 2 + 1 - 3) / 2 + 1, 0 for
+ * an empty utterance. */
+int wn_op_firered_frontend(const float* feats, const float* mean, const float* istd,
+                           const float* w1, const float* b1, const float* w2, const float* b2,
+                           float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,
+                           const int32_t* out_off, int32_t* out_len, int32_t B, int32_t T,
+                           int32_t F, int32_t C, void* stream);
 /* The Conformer front end alone -- GlobalCMVN + Conv2dSubsampling4 + the sqrt(d) scale, what
  * wn_encode runs in front of layer 0 (at position 0), under the handle's precision and tuning
  * set -- and copies of what it left, each optional (NULL), DEVICE arrays, complete on return:
@@ -883,6 +906,33 @@ int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transduc
                                          const wn_stateless_predictor_config* scfg,
                                          const wn_tensor* weights, int32_t n_weights,
                                          int32_t device, wn_model** out);
+
+/* FireRedASR-AED (`model: firered`, wenet/models/firered/): a Conformer-family encoder with the
+ * 32-channel FireRedConv2dSubsampling4 front end, Transformer-XL relative-position attention WITH
+ * the relative shift, three LayerNorms inside the attention (folded into the QKV weights on the
+ * host, in fp64), a conv module at conv_inner_factor 4 (LayerNorm over 2 d_model channels), no
+ * biases on linear_q/k/v/out and the convolutions, no after_norm.  Like wn_transducer_config, a
+ * struct and an entry point of their own: wn_config and wn_model_create are unchanged. */
+typedef struct {
+  int32_t sub_channels;       /* FireRedConv2dSubsampling4 odim: 32 */
+  int32_t conv_inner_factor;  /* encoder_conf.conv_inner_factor: 4 */
+  int32_t max_frames;         /* cap on an utterance's encoder frames T': every layer keeps
+                                 2 max_frames - 1 projected position rows */
+  float attn_norm_eps;        /* eps of layer_norm_q / k / v: torch's default 1e-5 */
+} wn_firered_config;
+
+/* wn_model_create for a `model: firered` state dict (the names init_model gives it).  cfg:
+ * encoder_type 0, input_layer 0, cnn_norm 0 (layer_norm), causal 0, no chunk sizes; the decoder
+ * fields as for any left-to-right `transformer` decoder.  On the handle, wn_encode runs the
+ * FireRed front end and layers -- every utterance as the reference encodes it ALONE: six zero
+ * frames behind its own last frame, T' = ((len + 6 - 3) / 2 + 1 - 3) / 2 + 1, the padded output
+ * has T' of the longest length T -- in fp32, full context only (chunk must be < 0); the CTC, the
+ * `attention` search and the rescoring entry points then work on the encoder output unchanged.
+ * wn_encode_chunk*, wn_stream_create, wn_op_conv2d4 and a bf16 / fp8 precision are refused on
+ * such a handle. */
+int wn_model_create_firered(const wn_config* cfg, const wn_firered_config* fcfg,
+                            const wn_tensor* weights, int32_t n_weights, int32_t device,
+                            wn_model** out);
 
 /* Operator hook: one advance of a stateless predictor + joint.pred_ffn for M rows
  * (rnnt_stateless_step).  ctx_host (M, context) holds the window ids of every row, oldest first,

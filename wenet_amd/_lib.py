@@ -37,6 +37,12 @@ class WnStatelessPredictorConfig(Structure):
         ('norm_eps', c_float)]
 
 
+class WnFireRedConfig(Structure):
+    """wn_firered_config: what a FireRedASR-AED encoder has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('sub_channels', 'conv_inner_factor', 'max_frames')] + [
+        ('attn_norm_eps', c_float)]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -116,6 +122,7 @@ EXPORTS = [
     'wn_op_layernorm_ex', 'wn_op_layernorm2', 'wn_op_layernorm_mx', 'wn_op_ffn_reduce_ln',
     'wn_op_gemm_rowln',
     'wn_model_create_transducer_stateless', 'wn_op_stateless_step',
+    'wn_op_attention_relshift', 'wn_op_firered_frontend', 'wn_model_create_firered',
 ]
 
 _lib = None
@@ -286,6 +293,12 @@ def lib():
                                       f32, i32, vp]
     L.wn_op_gemm_rowln.argtypes = [vp, i32, vp, vp, vp, i32, f32, vp, i32, vp, vp, f32, vp, i32,
                                    i32, i32, vp]
+    L.wn_model_create_firered.argtypes = [POINTER(WnConfig), POINTER(WnFireRedConfig),
+                                          POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_attention_relshift.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp,
+                                           vp, vp, i32, pi32, pi32, i32, i32, f32, vp]
+    L.wn_op_firered_frontend.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32,
+                                         pi32, i32, i32, i32, i32, vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

@@ -71,6 +71,16 @@ int wn_encode(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host
            "wn_encode: this handle has no weights");
   WN_CHECK(B > 0, "wn_encode: empty batch");
   WN_CHECK(chunk != 0, "decoding_chunk_size must not be 0 (asr_model.py:310)");
+  if (m->fr.on) {
+    WN_CHECK(chunk < 0, "chunk decoding is not implemented for the FireRed encoder (the "
+                        "reference: firedasr don't support streaming)");
+    WN_CHECK(m->prec == PREC_F32, "wn_encode: a FireRed handle stays fp32");
+    WN_CHECK(T >= 1, "wn_encode: empty features");
+    WN_HIP(hipSetDevice(m->device));
+    WN_TRY(encode_gate_wait(m, (hipStream_t)stream));
+    return encode_firered(m, feats_dev, feat_lens_host, B, T, enc_out_dev, enc_lens_host,
+                          (hipStream_t)stream);
+  }
   if (m->cfg.encoder_type == 1) {
     WN_CHECK(chunk < 0 && m->cfg.static_chunk_size <= 0,
              "chunk decoding is not implemented for the transformer encoder");
@@ -115,6 +125,7 @@ int wn_encode_chunk_batch(wn_model* m, int32_t n_sess, const float* feats_dev, i
   PrecisionScope prec_scope(m);
   WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0,
            "wn_encode_chunk: needs a Conformer encoder");
+  WN_CHECK(!m->fr.on, "wn_encode_chunk: the FireRed encoder does not stream");
   WN_CHECK(time >= 7, "wn_encode_chunk: at least 7 frames are needed by Conv2dSubsampling4");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));

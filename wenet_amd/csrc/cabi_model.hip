@@ -129,12 +129,33 @@ const char* wn_last_error(void) { return last_error_cstr(); }
 const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 
 // wn_model_create / wn_model_create_transducer (tcfg == nullptr: no predictor / joint) /
-// wn_model_create_transducer_stateless (scfg != nullptr: a stateless predictor, no LSTM)
-static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
-                        const wn_stateless_predictor_config* scfg, const wn_tensor* weights,
-                        int32_t n_weights, int32_t device, wn_model** out) {
+// wn_model_create_transducer_stateless (scfg != nullptr: a stateless predictor, no LSTM) /
+// wn_model_create_firered (fcfg != nullptr, cabi_firered.hip: the FireRedASR-AED encoder)
+}  // extern "C"
+
+int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
+                         const wn_stateless_predictor_config* scfg,
+                         const wn_firered_config* fcfg, const wn_tensor* weights,
+                         int32_t n_weights, int32_t device, wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
+  const bool fr = fcfg != nullptr;
+  if (fr) {
+    WN_CHECK(!tcfg, "firered: no transducer head");
+    WN_CHECK(c.encoder_type == 0 && c.input_layer == 0 && c.cnn_norm == 0 && c.causal == 0 &&
+             c.use_dynamic_chunk == 0 && c.static_chunk_size == 0 && c.activation == 0,
+             "firered: conformer layers, layer_norm conv module, full context, swish");
+    WN_CHECK(fcfg->sub_channels >= 1 && fcfg->sub_channels <= 256,
+             "firered: sub_channels must be in [1, 256]");
+    WN_CHECK(fcfg->conv_inner_factor == 4, "firered: conv_inner_factor must be 4");
+    WN_CHECK(fcfg->max_frames >= 1 && fcfg->max_frames <= 8192,
+             "firered: max_frames must be in [1, 8192]");
+    WN_CHECK(fcfg->attn_norm_eps > 0.f, "firered: attn_norm_eps must be > 0");
+    WN_CHECK(c.d_model == 64 || c.d_model == 128 || c.d_model == 256 || c.d_model == 512 ||
+                 c.d_model == 1280,
+             "firered: the depthwise conv over 2 d_model channels has kernels for d_model 64, "
+             "128, 256, 512 and 1280");
+  }
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && c.d_model / c.n_heads == 64,
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
@@ -156,6 +177,7 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
   m->device = device;
   if (tcfg) { m->tr.on = true; m->tr.c = *tcfg; }
   if (tcfg && scfg) m->tr.sp = *scfg;
+  if (fr) { m->fr.on = true; m->fr.c = *fcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -194,6 +216,25 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
         for (int k = 0; k < 3; ++k)
           t[(size_t)n * 3 * d + (size_t)k * d + ch] = w2[((size_t)n * d + ch) * 3 + k];
     hs.add("tconv2.b", b2, d);
+  } else if (fr) {
+    // FireRedConv2dSubsampling4 (firered/subsampling.py:42-49): C channels, direct kernels
+    const int C = fcfg->sub_channels;
+    WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)C * 9);
+    WN_GET(b0, "encoder.embed.conv.0.bias", C);
+    float* t = hs.alloc("fr.conv1.w", (size_t)9 * C);          // (C,1,3,3) -> [tap][c]
+    for (int ch = 0; ch < C; ++ch)
+      for (int k = 0; k < 9; ++k) t[k * C + ch] = w0[ch * 9 + k];
+    hs.add("fr.conv1.b", b0, C);
+    WN_GET(w2, "encoder.embed.conv.2.weight", (int64_t)C * C * 9);
+    WN_GET(b2, "encoder.embed.conv.2.bias", C);
+    t = hs.alloc("fr.conv2.w", (size_t)9 * C * C);             // (n,c,3,3) -> [tap][c][n]
+    for (int n = 0; n < C; ++n)
+      for (int ch = 0; ch < C; ++ch)
+        for (int k = 0; k < 9; ++k)
+          t[((size_t)k * C + ch) * C + n] = w2[((size_t)n * C + ch) * 9 + k];
+    hs.add("fr.conv2.b", b2, C);
+    // out Linear(C * F2 -> d): the kernels write the reference's own column order c * F2 + f
+    WN_TRY(stage_linear(src, hs, "encoder.embed.out.0", d, C * F2));
   } else {  // conv1 (d,1,3,3) -> [tap][c]
     WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)d * 9);
     WN_GET(b0, "encoder.embed.conv.0.bias", d);
@@ -275,7 +316,7 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
     hs.add("fbank.mel_w", wts.data(), wts.size());
   }
-  WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));
+  if (!fr) WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));   // (firered: final_norm false)
   const bool has_ctc = src.has("ctc.ctc_lo.weight");
   if (has_ctc) WN_TRY(stage_linear(src, hs, "ctc.ctc_lo", V, d));
   for (int i = 0; tf && i < c.n_layers; ++i) {
@@ -301,7 +342,88 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_1", F, d));
     WN_TRY(stage_linear(src, hs, p + ".feed_forward.w_2", d, F));
   }
-  for (int i = 0; !tf && i < c.n_layers; ++i) {
+  if (fr) {
+    // the plain normalisation in front of the folded QKV projection, and the relative position
+    // rows: row r of the (2 max_frames - 1)-row table is the sinusoid of the relative position
+    // max_frames - 1 - r (firered/attention.py:30-43, evaluated in fp32 like the module)
+    float* u = hs.alloc("fr.unit.weight", d);
+    for (int i = 0; i < d; ++i) u[i] = 1.0f;
+    hs.alloc("fr.unit.bias", d);
+    const int cap = fcfg->max_frames;
+    float* t = hs.alloc("fr.rel_pe", (size_t)(2 * cap - 1) * d);
+    for (int r = 0; r < 2 * cap - 1; ++r) {
+      const float pos = (float)(cap - 1 - r);
+      for (int i = 0; i < d; i += 2) {
+        const float div = expf((float)i * -(logf(10000.0f) / (float)d));
+        t[(size_t)r * d + i] = sinf(pos * div);
+        t[(size_t)r * d + i + 1] = cosf(pos * div);
+      }
+    }
+  }
+  for (int i = 0; fr && i < c.n_layers; ++i) {
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    const int d2 = 2 * d;
+    for (const char* n : {"norm_ff_macaron", "norm_conv", "norm_ff", "norm_final"})
+      WN_TRY(stage_norm(src, hs, p + "." + n, d));
+    WN_TRY(stage_norm(src, hs, p + ".conv_module.norm", d2));
+    for (const char* ff : {"feed_forward_macaron", "feed_forward"}) {
+      WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_1", F, d));
+      WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_2", d, F));
+    }
+    {  // layer_norm_q / k / v folded into the QKV projection, in fp64: the three LayerNorms
+       // normalise the same x, so LN(x; g, b) W^T = LN(x; 1, 0) (W diag(g))^T + W b
+      std::vector<float> w((size_t)3 * d * d), b((size_t)3 * d);
+      const char* parts[3] = {"q", "k", "v"};
+      for (int j = 0; j < 3; ++j) {
+        WN_GET(pw, p + ".self_attn.linear_" + parts[j] + ".weight", (int64_t)d * d);
+        WN_GET(g, p + ".self_attn.layer_norm_" + parts[j] + ".weight", d);
+        WN_GET(be, p + ".self_attn.layer_norm_" + parts[j] + ".bias", d);
+        for (int o = 0; o < d; ++o) {
+          double acc = 0.0;
+          for (int k = 0; k < d; ++k) {
+            w[((size_t)j * d + o) * d + k] = (float)((double)pw[(size_t)o * d + k] * (double)g[k]);
+            acc += (double)pw[(size_t)o * d + k] * (double)be[k];
+          }
+          b[(size_t)j * d + o] = (float)acc;
+        }
+      }
+      hs.add(p + ".qkv.weight", w.data(), w.size());
+      hs.add(p + ".qkv.bias", b.data(), b.size());
+    }
+    // (linear_out carries a bias only with query_bias, transformer/attention.py:77)
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d,
+                        src.has(p + ".self_attn.linear_out.bias")));
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_pos", d, d, false));
+    WN_GET(bu, p + ".self_attn.pos_bias_u", d);
+    WN_GET(bv, p + ".self_attn.pos_bias_v", d);
+    hs.add(p + ".pos_bias_u", bu, d);
+    hs.add(p + ".pos_bias_v", bv, d);
+    {  // pointwise_conv1 (4d, d, 1), no bias: GLU halves [0, 2d) | [2d, 4d), rows permuted per
+       // 64 as [32 a | 32 gate]; the GLU of a zero frame is 0 (cpad)
+      WN_GET(w1, p + ".conv_module.pointwise_conv1.weight", (int64_t)2 * d2 * d);
+      std::vector<float> w((size_t)2 * d2 * d);
+      for (int g = 0; g < d2 / 32; ++g)
+        for (int j = 0; j < 32; ++j) {
+          const int ch = g * 32 + j;
+          memcpy(&w[(size_t)(g * 64 + j) * d], &w1[(size_t)ch * d], sizeof(float) * d);
+          memcpy(&w[(size_t)(g * 64 + 32 + j) * d], &w1[(size_t)(d2 + ch) * d],
+                 sizeof(float) * d);
+        }
+      hs.add(p + ".pw1.weight", w.data(), w.size());
+      hs.alloc(p + ".pw1.bias", 2 * d2);
+      hs.alloc(p + ".cpad", d2);
+    }
+    {  // depthwise (2d,1,K), no bias -> [K][2d]
+      WN_GET(wd, p + ".conv_module.depthwise_conv.weight", (int64_t)d2 * K);
+      std::vector<float> w((size_t)K * d2);
+      for (int ch = 0; ch < d2; ++ch)
+        for (int k = 0; k < K; ++k) w[(size_t)k * d2 + ch] = wd[(size_t)ch * K + k];
+      hs.add(p + ".dw.weight", w.data(), w.size());
+      hs.alloc(p + ".dw.bias", d2);
+    }
+    WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d2, false));
+  }
+  for (int i = 0; !tf && !fr && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -464,6 +586,12 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.tconv1.out = d; W.tconv1.in = K1;
     W.tconv2.w = P("tconv2.w"); W.tconv2.b = P("tconv2.b");
     W.tconv2.out = d; W.tconv2.in = 3 * d;
+  } else if (fr) {
+    const int C = fcfg->sub_channels;
+    W.conv1_w = P("fr.conv1.w"); W.conv1_b = P("fr.conv1.b");
+    W.conv2.w = P("fr.conv2.w"); W.conv2.b = P("fr.conv2.b");
+    W.conv2.out = C; W.conv2.in = 9 * C;
+    W.sub_out = LIN("encoder.embed.out.0", d, C * F2);
   } else {
     W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
     W.conv2.w = P("conv2.w"); W.conv2.b = P("conv2.b");
@@ -483,7 +611,7 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_HIP(hipMemcpy(W.fb_tab_i.p, tab.data(), tab.size() * sizeof(int),
                      hipMemcpyHostToDevice));
   }
-  W.after_norm = NORM("encoder.after_norm");
+  if (!fr) W.after_norm = NORM("encoder.after_norm");
   if (has_ctc) W.ctc = LIN("ctc.ctc_lo", V, d);
   if (tf) {
     W.tf_layers.resize(c.n_layers);
@@ -496,11 +624,45 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
       L.ff1 = LIN(p + ".feed_forward.w_1", F, d);
       L.ff2 = LIN(p + ".feed_forward.w_2", d, F);
     }
+  } else if (fr) {
+    // p = linear_pos(pos_emb) depends on weights only: every layer's rows for all distances
+    // |r| < max_frames, projected once ((2 max_frames - 1) x d floats per layer)
+    const int rows = 2 * fcfg->max_frames - 1;
+    W.layers.resize(c.n_layers);
+    WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * rows * d * sizeof(float)));
+    for (int i = 0; i < c.n_layers; ++i) {
+      const std::string p = "encoder.encoders." + std::to_string(i);
+      EncLayer& L = W.layers[i];
+      L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
+      L.norm_mha = NORM("fr.unit");
+      L.norm_conv = NORM(p + ".norm_conv");
+      L.norm_ff = NORM(p + ".norm_ff");
+      L.norm_final = NORM(p + ".norm_final");
+      L.conv_norm = NORM(p + ".conv_module.norm");
+      L.ffm1 = LIN(p + ".feed_forward_macaron.w_1", F, d);
+      L.ffm2 = LIN(p + ".feed_forward_macaron.w_2", d, F);
+      L.ff1 = LIN(p + ".feed_forward.w_1", F, d);
+      L.ff2 = LIN(p + ".feed_forward.w_2", d, F);
+      L.qkv = LIN(p + ".qkv", 3 * d, d);
+      L.out = LIN(p + ".self_attn.linear_out", d, d,
+                  W.w.count(p + ".self_attn.linear_out.bias") != 0);
+      L.pw1 = LIN(p + ".pw1", 4 * d, d);
+      L.pw2 = LIN(p + ".conv_module.pointwise_conv2", d, 2 * d, false);
+      L.bias_u = P(p + ".pos_bias_u");
+      L.bias_v = P(p + ".pos_bias_v");
+      L.pos_w = P(p + ".self_attn.linear_pos.weight");
+      L.dw_wt = P(p + ".dw.weight");
+      L.dw_b = P(p + ".dw.bias");
+      L.cpad = P(p + ".cpad");
+      L.pos_tab = W.pos_tabs.as<float>() + (size_t)i * rows * d;
+      Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = d; lp.in = d;
+      WN_TRY(linear(lp, P("fr.rel_pe"), d, L.pos_tab, d, rows, 0));
+    }
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -583,22 +745,26 @@ static int create_model(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.j_pred = LIN("joint.pred_ffn", tc.join_dim, tc.pred_out);
     W.j_out = LIN("joint.ffn_out", V, tc.join_dim);
   }
-  WN_TRY(build_x6_images(c, W));
+  // (firered: the plain fp32 path, no six-product / row-block images of its encoder's weights;
+  // the decoders and the CTC head get theirs as in every other model)
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
 }
 
+extern "C" {
+
 int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
                     int32_t n_weights, int32_t device, wn_model** out) {
-  return create_model(cfg, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out) {
   WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
-  return create_model(cfg, tcfg, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -606,7 +772,7 @@ int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transduc
                                          const wn_tensor* weights, int32_t n_weights,
                                          int32_t device, wn_model** out) {
   WN_CHECK(tcfg && scfg, "wn_model_create_transducer_stateless: null argument");
-  return create_model(cfg, tcfg, scfg, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, scfg, nullptr, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -618,6 +784,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->data = src->data;      // weights, views and tables are read-only: shared
   m->cfg = src->cfg;
   m->tr.on = src->tr.on; m->tr.c = src->tr.c; m->tr.sp = src->tr.sp;
+  m->fr.on = src->fr.on; m->fr.c = src->fr.c;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;
@@ -632,6 +799,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(precision == PREC_F32 || precision == PREC_BF16 || precision == PREC_FP8,
            "wn_model_set_precision: 0 (fp32), 1 (bf16 operands, fp32 accumulate) or 2 "
            "(bf16 + MXFP8 feed-forward GEMMs)");
+  WN_CHECK(!m->fr.on || precision == PREC_F32,
+           "wn_model_set_precision: a FireRed handle stays fp32 (no bf16 / fp8 kernels for its "
+           "encoder)");
   const ModelData& W = *m->data;
   // the images belong to the model block: whichever handle asks first builds them, every
   // clone (made before or after) reads the same ones

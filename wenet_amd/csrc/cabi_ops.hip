@@ -452,7 +452,8 @@ int wn_op_dwconv(const float* x, int32_t ldx, const float* wt, const float* bias
                  int32_t M, int32_t D, int32_t K, int32_t causal, int32_t t_max, float eps,
                  void* stream) {
   WN_CHECK(x && wt && bias && cpad && ln_w && ln_b && y && off && len, "dwconv: null argument");
-  WN_CHECK(D == 64 || D == 128 || D == 256 || D == 512 || D == 768 || D == 1024 || D == 1280,
+  WN_CHECK(D == 64 || D == 128 || D == 256 || D == 512 || D == 768 || D == 1024 || D == 1280 ||
+               D == 2560,
            "dwconv: unsupported width " + std::to_string(D));
   WN_CHECK(M > 0 && B > 0 && K >= 1 && K <= 255, "dwconv: M / B / K");
   WN_CHECK(causal != 0 || K % 2 == 1, "dwconv: a symmetric kernel has an odd size");
@@ -517,6 +518,86 @@ int wn_op_conv1(const float* feats, const float* mean, const float* istd, const 
   return cmvn_conv1_relu(a, s);
 }
 
+int wn_op_attention_relshift(const float* Q, const float* K, const float* V, int32_t ldq,
+                             int32_t ldk, int32_t ldv, int32_t rows, const float* P,
+                             int32_t ldp, int32_t p_rows, int32_t p_center, const float* bias_u,
+                             const float* bias_v, float* O, int32_t ldo, const int32_t* off,
+                             const int32_t* len, int32_t n_seq, int32_t n_heads, float scale,
+                             void* stream) {
+  WN_CHECK(Q && K && V && P && bias_u && bias_v && O && off && len,
+           "attention_relshift: null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 65536 && n_heads > 0 && n_heads < 65536,
+           "attention_relshift: n_seq / n_heads");
+  const int d = n_heads * 64;
+  WN_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0,
+           "attention_relshift: strides must be multiples of 4 elements");
+  WN_CHECK(ldq >= d && ldk >= d && ldv >= d && ldo >= d && ldp >= d,
+           "attention_relshift: a stride is smaller than n_heads * 64");
+  WN_CHECK(rows > 0 && p_rows > 0, "attention_relshift: empty buffers");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           "attention_relshift: rows outside the buffer, unordered or overlapping");
+  int max_len = 0;
+  std::vector<int> h((size_t)2 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  WN_CHECK(max_len > 0, "attention_relshift: empty");
+  WN_CHECK(p_center >= max_len - 1 && (int64_t)p_center + max_len - 1 < p_rows,
+           "attention_relshift: a sequence is longer than the position table covers");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  RelShiftAttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = P; a.ldp = ldp; a.p_center = p_center; a.p_rows = p_rows;
+  a.bias_u = bias_u; a.bias_v = bias_v; a.O = O; a.ldo = ldo;
+  a.off = desc.as<int>(); a.len = a.off + n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_len = max_len; a.scale = scale;
+  return attention_relshift(a, s);
+}
+
+int wn_op_firered_frontend(const float* feats, const float* mean, const float* istd,
+                           const float* w1, const float* b1, const float* w2, const float* b2,
+                           float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,
+                           const int32_t* out_off, int32_t* out_len, int32_t B, int32_t T,
+                           int32_t F, int32_t C, void* stream) {
+  WN_CHECK(feats && w1 && b1 && w2 && b2 && out && lens && out_off && out_len,
+           "firered_frontend: null argument");
+  WN_CHECK((mean == nullptr) == (istd == nullptr), "firered_frontend: mean and istd come together");
+  WN_CHECK(F >= 7 && F <= 128 && B > 0 && B < 65536 && T > 0 && C > 0 && C <= 256 && out_rows > 0,
+           "firered_frontend: B / T / F / C");
+  const int F1 = (F - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
+  WN_CHECK(ldo >= C * F2, "firered_frontend: output stride");
+  std::vector<int> h((size_t)5 * B);
+  int max_t2 = 0, at1 = 0;
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(lens[b] >= 0 && lens[b] <= T, "firered_frontend: a length outside [0, T]");
+    // alone semantics: six zero frames behind the utterance's OWN last frame
+    const int t2 = lens[b] > 0 ? ((lens[b] + 6 - 3) / 2 + 1 - 3) / 2 + 1 : 0;
+    const int t1 = t2 > 0 ? 2 * t2 + 1 : 0;
+    out_len[b] = t2;
+    h[b] = lens[b]; h[B + b] = at1; h[2 * B + b] = t1; h[3 * B + b] = out_off[b];
+    h[4 * B + b] = t2;
+    at1 += t1;
+    max_t2 = std::max(max_t2, t2);
+  }
+  WN_CHECK(packed_ok(out_off, out_len, B, out_rows),
+           "firered_frontend: frames outside the buffer, unordered or overlapping");
+  WN_CHECK(max_t2 > 0, "firered_frontend: empty");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc, h1;
+  WN_TRY(upload_ints(desc, h, s));
+  WN_TRY(h1.ensure((size_t)at1 * F1 * C * sizeof(float)));
+  FireRedFrontArgs a;
+  a.feats = feats; a.mean = mean; a.istd = istd; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
+  a.h1 = h1.as<float>(); a.out = out; a.ldo = ldo;
+  a.len = desc.as<int>(); a.t1_off = a.len + B; a.t1_len = a.len + 2 * B;
+  a.t2_off = a.len + 3 * B; a.t2_len = a.len + 4 * B;
+  a.B = B; a.T = T; a.F = F; a.F1 = F1; a.F2 = F2; a.C = C; a.max_t2 = max_t2;
+  return firered_frontend(a, s);
+}
+
 int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
                   int32_t T, float* c1, float* c2, float* x, int32_t* enc_lens_host,
                   int32_t* route_out, void* stream) {
@@ -526,7 +607,7 @@ int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_
   struct GateDrop { wn_model* m; ~GateDrop() { m->enc_gate = nullptr; } } gate_drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0,
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on,
            "wn_op_conv2d4: needs a Conformer encoder");
   WN_CHECK(B > 0, "wn_encode: empty batch");
   WN_CHECK(B < 65536, "wn_op_conv2d4: more than 65535 utterances");

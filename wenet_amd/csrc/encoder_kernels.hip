@@ -268,7 +268,8 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DwConvArgs a) {
   // taps in groups of 8: ALL loads of a group (taps + the 8 neighbour rows) are issued before
   // the first fma -- one memory round trip per group instead of one per tap (13.9 -> 13.1 us at
   // M = 7932, K = 8, r03t; the order of the fmas is unchanged)
-  constexpr int TG = E <= 8 ? 8 : 4;
+  // (E = 40, the FireRed conv module's 2560 channels: groups of 2 keep the row in registers)
+  constexpr int TG = E <= 8 ? 8 : (E <= 20 ? 4 : 2);
   for (int k0 = 0; k0 < a.K; k0 += TG) {
     RowRegs<E> wk[TG], xv[TG];
     int kind[TG];          // 0: outside (nothing), 1: row of the utterance, 2: the pad frame
@@ -938,7 +939,7 @@ int dwconv_ln_silu(const DwConvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(dwconv_kernel<E>, g, t, 0, s, a);      \
     break;
   switch (a.D) {
-    WN_DW(1) WN_DW(2) WN_DW(4) WN_DW(8) WN_DW(12) WN_DW(16) WN_DW(20)
+    WN_DW(1) WN_DW(2) WN_DW(4) WN_DW(8) WN_DW(12) WN_DW(16) WN_DW(20) WN_DW(40)
     default:
       set_error("dwconv: unsupported width " + std::to_string(a.D));
       return -1;

@@ -139,6 +139,44 @@ int relpos_fold(float* K, int ldk, const float* P, int ldp, const float* bias_u,
 // when the calling thread's precision is PREC_BF16 (and tune().attn_bf16 != 0).
 int attention_bf16(const AttnArgs& a, hipStream_t s);
 
+// Self attention with the relative shift (firered.hip; FireRedASR's Transformer-XL form):
+// score(i, j) = ((q_i + u) . k_j + (q_i + v) . p_{i-j}) * scale over all keys of the sequence
+// (full context only), d_k = 64, fp32.  P holds the projected position row of DISTANCE r = i - j
+// in row p_center - r; every |r| < max_len must lie inside [0, p_rows).
+struct RelShiftAttnArgs {
+  const float* Q; const float* K; const float* V;
+  int ldq, ldk, ldv;
+  const float* P; int ldp;      // [p_rows][h*64]
+  int p_center, p_rows;
+  const float* bias_u; const float* bias_v;   // [h][64]
+  float* O; int ldo;
+  const int* off; const int* len;   // [n_seq] first row / rows of every sequence
+  int n_seq, n_heads, max_len;
+  float scale = 0.125f;
+};
+int attention_relshift(const RelShiftAttnArgs& a, hipStream_t s);
+
+// FireRedASR front end (firered.hip): GlobalCMVN, six zero frames behind every utterance's own
+// last frame, Conv2d(1->C,3,2) + ReLU, Conv2d(C->C,3,2) + ReLU.  Utterance b has
+// t2_len[b] = ((len + 6 - 3) / 2 + 1 - 3) / 2 + 1 output frames and t1_len[b] = 2 t2_len[b] + 1
+// rows of h1 (the conv1 frames conv2 reads).
+struct FireRedFrontArgs {
+  const float* feats;    // (B, T, F) padded
+  const float* mean;     // [F] or null (no CMVN)
+  const float* istd;     // [F]
+  const float* w1;       // [9][C]       tap-major, from (C,1,3,3)
+  const float* b1;       // [C]
+  const float* w2;       // [9][C1][C2]  tap-major, from (C2,C1,3,3)
+  const float* b2;       // [C]
+  float* h1;             // scratch [sum t1_len][F1][C]
+  float* out; int ldo;   // [sum t2_len][C * F2], column c * F2 + f2
+  const int* len;        // [B] frames of the utterance
+  const int* t1_off; const int* t1_len;
+  const int* t2_off; const int* t2_len;
+  int B, T, F, F1, F2, C, max_t2;
+};
+int firered_frontend(const FireRedFrontArgs& a, hipStream_t s);
+
 // Fused feed-forward module, fp32 (ffn_fused.hip): P[s] (S, M, D) = partial
 // act(X W1^T + b1) W2^T over hidden slice s; ffn_reduce_ln then forms
 // x += alpha (sum_s P[s] + b2) and the following LayerNorm(s).

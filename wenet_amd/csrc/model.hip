@@ -141,9 +141,11 @@ int after_norm_out(wn_model* m, hipStream_t s) {
 }
 
 // Plane images (gemm_x6.hip) of the encoder's feed-forward weights, once per model.
-int build_x6_images(const wn_config& cfg, ModelData& W) {
+int build_x6_images(const wn_config& cfg, ModelData& W, bool skip_encoder) {
   std::vector<const Linear*> ws;
-  for (const auto& L : W.layers) { ws.push_back(&L.ffm1); ws.push_back(&L.ffm2);
+  static const std::vector<EncLayer> no_layers;
+  const std::vector<EncLayer>& enc_layers = skip_encoder ? no_layers : W.layers;
+  for (const auto& L : enc_layers) { ws.push_back(&L.ffm1); ws.push_back(&L.ffm2);
                                     ws.push_back(&L.ff1); ws.push_back(&L.ff2);
                                     ws.push_back(&L.qkv); ws.push_back(&L.out);
                                     ws.push_back(&L.pw2); ws.push_back(&L.pw1); }
@@ -157,8 +159,8 @@ int build_x6_images(const wn_config& cfg, ModelData& W) {
   // linear() -> split pass + six-product GEMM like every other large fp32 GEMM
   for (const auto& L : W.tf_layers) { ws.push_back(&L.qkv); ws.push_back(&L.out);
                                        ws.push_back(&L.ff1); ws.push_back(&L.ff2); }
-  if (W.conv2.w) ws.push_back(&W.conv2);   // [d][(ky*3+kx)*d + c]: 16-channel k blocks per tap
-  if (W.sub_out.w) ws.push_back(&W.sub_out);   // K slices straight from conv2's fp32 output
+  if (W.conv2.w && !skip_encoder) ws.push_back(&W.conv2);   // [d][(ky*3+kx)*d + c]: 16-channel k blocks per tap
+  if (W.sub_out.w && !skip_encoder) ws.push_back(&W.sub_out);   // K slices straight from conv2's fp32 output
   std::vector<const Linear*> vocab;          // V rows; the image pads them to a multiple of 32
   if (W.ctc.w) vocab.push_back(&W.ctc);
   for (const Decoder* D : {&W.left, &W.right})
@@ -181,7 +183,7 @@ int build_x6_images(const wn_config& cfg, ModelData& W) {
   // with the k slots of a 16-unit block in the order a lane holds its hidden values
   if (cfg.d_model == 256) {
     std::vector<const Linear*> w2s;
-    for (const auto& L : W.layers) { w2s.push_back(&L.ffm2); w2s.push_back(&L.ff2); }
+    for (const auto& L : enc_layers) { w2s.push_back(&L.ffm2); w2s.push_back(&L.ff2); }
     size_t pbytes = 0;
     for (const Linear* l : w2s)
       if (l->w && l->in % 64 == 0 && l->out == 256) pbytes += x6_bytes(l->out, l->in);
@@ -201,7 +203,7 @@ int build_x6_images(const wn_config& cfg, ModelData& W) {
   // part 256 + h 64 + j.  One fp32 staging copy, then the ordinary split
   if (cfg.d_model == 256 && cfg.n_heads == 4) {
     size_t n_q = 0;
-    for (const auto& L : W.layers)
+    for (const auto& L : enc_layers)
       if (L.qkv.w && L.qkv.b && L.qkv.out == 768 && L.qkv.in == 256 && L.pos_tab) ++n_q;
     if (n_q > 0) {
       const size_t img = x6_bytes(768, 256), per = img + 768 * sizeof(float);
@@ -209,7 +211,7 @@ int build_x6_images(const wn_config& cfg, ModelData& W) {
       WN_TRY(stage.ensure((size_t)768 * 256 * sizeof(float)));
       WN_TRY(W.weights_x6q.ensure(n_q * per));
       char* q = W.weights_x6q.as<char>();
-      for (const auto& L : W.layers) {
+      for (const auto& L : enc_layers) {
         if (!(L.qkv.w && L.qkv.b && L.qkv.out == 768 && L.qkv.in == 256 && L.pos_tab) ||
             W.x6q_at.count(L.qkv.w))
           continue;

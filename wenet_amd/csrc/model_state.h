@@ -265,6 +265,13 @@ struct wn_model {
     wn_transducer_config c = {};
     wn_stateless_predictor_config sp = {};
   } tr;
+  // wn_model_create_firered: the FireRedASR-AED encoder (cabi_firered.hip); data->layers then
+  // hold its shapes (pw1 4d x d, depthwise / conv_norm over 2d, pw2 d x 2d, norm_mha = the
+  // plain normalisation in front of the folded QKV, pos_tab = 2 max_frames - 1 rows)
+  struct {
+    bool on = false;
+    wn_firered_config c = {};
+  } fr;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
@@ -482,7 +489,8 @@ int linear(const Linear& l, const float* A, int lda, float* C, int ldc, int M, h
 int ln(const Norm& n, const float* x, float* y, int M, int D, float eps, hipStream_t s,
        bool y_bf16 = false);
 int after_norm_out(wn_model* m, hipStream_t s);
-int build_x6_images(const wn_config& cfg, ModelData& W);
+// skip_encoder: no images of the encoder layers / subsampling weights (FireRed handles)
+int build_x6_images(const wn_config& cfg, ModelData& W, bool skip_encoder = false);
 int vocab_linear(wn_model* m, const Linear& l, const float* A, int lda, float* C, int ldc, int M,
                  hipStream_t s);
 int scatter_padded(const float* src, int lds, const int* off, const int* len, int B, int Tp, int D,
@@ -514,6 +522,13 @@ int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const 
 int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s);
 int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
                          std::vector<ChunkSess>& sess, float* out, hipStream_t s);
+// (cabi_firered.hip)
+int encode_firered(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
+                   float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
+// (cabi_model.hip: what every wn_model_create* entry point runs)
+int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
+                      const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,
+                      const wn_tensor* weights, int32_t n_weights, int32_t device, wn_model** out);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

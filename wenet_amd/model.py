@@ -1166,6 +1166,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     if configs.get('model') == 'transducer':   # init_model.py:137-154
         from wenet_amd.transducer import Transducer
         model = Transducer(configs, sd, device)
+    elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
+        from wenet_amd.firered import FireRed
+        model = FireRed(configs, sd, device)
     else:
         model = ASRModel(configs, sd, device)
     # cli/model.py:35-46: the config's tokenizer with its files looked up in the

@@ -60,6 +60,11 @@ class DecodePipeline:
 
     def __init__(self, model: ASRModel, n_streams: int = 2):
         assert n_streams >= 1
+        from wenet_amd.firered import FireRed
+        if isinstance(model, FireRed):
+            raise NotImplementedError(
+                'DecodePipeline: a FireRed model is outside the accelerated path of the pipeline '
+                '(its `attention` search re-seats the current batch per utterance length)')
         self.device = model.device
         self._owner = model
         self.models: List[ASRModel] = [model.clone() for _ in range(n_streams)]

@@ -411,6 +411,47 @@ CONFIGS['aishell_u2pp_rnnt_embed'] = _rnnt_stateless('aishell_u2pp_rnnt', 'embed
 RNNT_BLANK_BIAS = 6.0    # make_state_dict's default bias of the joint's blank logit
 
 
+# FireRedASR-AED (wenet/models/firered/convert_FireRed_AED_L_to_wenet_config_and_ckpt.py:32-105)
+# at the given widths
+def _firered(d: int, heads: int, ffn: int, enc_blocks: int, dec_blocks: int, vocab: int) -> dict:
+    return {
+        'input_dim': 80, 'output_dim': vocab,
+        'encoder': 'firered_conformer',
+        'encoder_conf': dict(gradient_checkpointing=True, input_layer='firered_conv2d4',
+                             final_norm=False, output_size=d, attention_heads=heads,
+                             linear_units=ffn, num_blocks=enc_blocks, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, attention_dropout_rate=0.0,
+                             normalize_before=True, use_dynamic_chunk=False,
+                             use_dynamic_left_chunk=False, pos_enc_layer_type='rel_pos_firered',
+                             static_chunk_size=-1, key_bias=False, value_bias=False,
+                             query_bias=False, activation_type='swish', conv_bias=False,
+                             conv_inner_factor=4, cnn_module_kernel=33,
+                             cnn_module_norm='layer_norm',
+                             selfattention_layer_type='firered_rel_selfattn'),
+        'decoder': 'transformer',
+        'decoder_conf': dict(tie_word_embedding=True, gradient_checkpointing=True,
+                             attention_heads=heads, linear_units=ffn, num_blocks=dec_blocks,
+                             dropout_rate=0.1, positional_dropout_rate=0.1,
+                             self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0,
+                             use_output_layer=True, normalize_before=True, src_attention=True,
+                             activation_type='gelu', src_key_bias=False, key_bias=False),
+        'tokenizer': 'bpe',
+        'tokenizer_conf': dict(split_with_space=True, bpe_path='train_bpe1000.model',
+                               symbol_table_path='units.txt', non_lang_syms_path=None,
+                               special_tokens=dict(sos=3, eos=4)),
+        'model': 'firered',
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False),
+    }
+
+
+FIRERED_EOS_BIAS = 0.75   # _make_firered_state_dict's logit bias of <eos>
+CONFIGS['tiny_firered'] = _firered(128, 2, 256, 2, 2, 41)
+# FireRedASR-AED-L: d 1280, 20 heads, ffn 5120, 16 + 16 blocks, vocabulary 7832
+CONFIGS['firered_aed_l'] = _firered(1280, 20, 5120, 16, 16, 7832)
+# its widths with one block each and a small vocabulary (the tests: 90 M weights, not 1.1 G)
+CONFIGS['firered_aed_l_1blk'] = _firered(1280, 20, 5120, 1, 1, 41)
+
+
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
     c = copy.deepcopy(CONFIGS[name])
@@ -527,6 +568,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
     K = ec.get('cnn_module_kernel', 15)
     if configs.get('encoder', 'conformer') == 'transformer':
         return _make_transformer_state_dict(configs, seed, sharpen_ctc)
+    if configs.get('encoder') == 'firered_conformer':
+        return _make_firered_state_dict(configs, seed, sharpen_ctc)
     idim, V = configs['input_dim'], configs['output_dim']
     sd: Dict[str, np.ndarray] = OrderedDict()
 
@@ -645,6 +688,115 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         _add_transducer(sd, configs, seed, rnnt_blank_bias)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
+
+
+def firered_rel_positional_table(d_model: int, max_len: int = 5000) -> torch.Tensor:
+    """The `pe` buffer of FireRedRelPositionalEncoding (wenet/models/firered/attention.py:27-44):
+    (1, 2 max_len - 1, d), row c = the sinusoid of the relative position max_len - 1 - c."""
+    rel = torch.arange(max_len - 1, -max_len, -1, dtype=torch.float32).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float32) *
+                         -(math.log(10000.0) / d_model))
+    pe = torch.zeros(2 * max_len - 1, d_model)
+    pe[:, 0::2] = torch.sin(rel * div_term)
+    pe[:, 1::2] = torch.cos(rel * div_term)
+    return pe.unsqueeze(0)
+
+
+def _make_firered_state_dict(configs, seed, sharpen_ctc):
+    """FireRedModel (wenet/models/firered/): names and shapes as init_model gives them.  No
+    biases on linear_q / k / v / out of the encoder's attention and on its convolutions, three
+    LayerNorms inside the attention, a conv module over 2 d channels, no norm_mha / after_norm;
+    a left-to-right decoder without linear_k biases whose output layer is tied to the
+    embedding."""
+    ec, dc = configs['encoder_conf'], configs['decoder_conf']
+    d, h, ffn = ec['output_size'], ec['attention_heads'], ec['linear_units']
+    K, inner = ec['cnn_module_kernel'], ec['conv_inner_factor']
+    idim, V = configs['input_dim'], configs['output_dim']
+    C = 32                                    # FireRedConv2dSubsampling4's odim default
+    sd: Dict[str, np.ndarray] = OrderedDict()
+
+    def lin(name, out_f, in_f, bias=True):
+        b = 1.0 / math.sqrt(in_f)
+        sd[name + '.weight'] = _uniform(seed, name + '.weight', (out_f, in_f), b)
+        if bias:
+            sd[name + '.bias'] = _uniform(seed, name + '.bias', (out_f, ), b)
+
+    def norm(name, n):
+        sd[name + '.weight'] = _normal(seed, name + '.weight', (n, ), 0.1, 1.0)
+        sd[name + '.bias'] = _normal(seed, name + '.bias', (n, ), 0.1)
+
+    if configs.get('cmvn') == 'global_cmvn':
+        sd['encoder.global_cmvn.mean'] = _normal(seed, 'cmvn.mean', (idim, ), 1.5, 11.0)
+        sd['encoder.global_cmvn.istd'] = (
+            1.0 / (2.5 + np.abs(_normal(seed, 'cmvn.std', (idim, ), 0.5)))).astype(np.float32)
+    sd['encoder.embed.conv.0.weight'] = _uniform(seed, 'conv0.w', (C, 1, 3, 3), 1.0 / 3.0)
+    sd['encoder.embed.conv.0.bias'] = _uniform(seed, 'conv0.b', (C, ), 1.0 / 3.0)
+    b = 1.0 / math.sqrt(9 * C)
+    sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (C, C, 3, 3), b)
+    sd['encoder.embed.conv.2.bias'] = _uniform(seed, 'conv2.b', (C, ), b)
+    lin('encoder.embed.out.0', d, C * (((idim - 1) // 2 - 1) // 2))
+    for i in range(ec['num_blocks']):
+        p = f'encoder.encoders.{i}'
+        a = p + '.self_attn'
+        b = math.sqrt(6.0 / (h + d // h))
+        sd[a + '.pos_bias_u'] = _uniform(seed, a + '.pos_bias_u', (h, d // h), b)
+        sd[a + '.pos_bias_v'] = _uniform(seed, a + '.pos_bias_v', (h, d // h), b)
+        for n in ('linear_q', 'linear_k', 'linear_v', 'linear_out', 'linear_pos'):
+            lin(f'{a}.{n}', d, d, bias=False)
+        for n in ('layer_norm_q', 'layer_norm_k', 'layer_norm_v'):
+            norm(f'{a}.{n}', d)
+        for ff in ('feed_forward', 'feed_forward_macaron'):
+            lin(f'{p}.{ff}.w_1', ffn, d)
+            lin(f'{p}.{ff}.w_2', d, ffn)
+        di = d * inner // 2                   # channels behind the GLU
+        sd[p + '.conv_module.pointwise_conv1.weight'] = _uniform(
+            seed, p + '.pw1.w', (2 * di, d, 1), 1.0 / math.sqrt(d))
+        sd[p + '.conv_module.depthwise_conv.weight'] = _uniform(
+            seed, p + '.dw.w', (di, 1, K), 1.0 / math.sqrt(K))
+        norm(p + '.conv_module.norm', di)
+        sd[p + '.conv_module.pointwise_conv2.weight'] = _uniform(
+            seed, p + '.pw2.w', (d, di, 1), 1.0 / math.sqrt(di))
+        for n in ('norm_ff', 'norm_ff_macaron', 'norm_conv', 'norm_final'):
+            norm(f'{p}.{n}', d)
+    sd['encoder.embed.pos_enc.pe'] = firered_rel_positional_table(d).numpy()
+    sd['decoder.embed.0.weight'] = _normal(seed, 'decoder.embed', (V, d), 1.0)
+    sd['decoder.embed.1.pe'] = positional_table(d).numpy()
+    norm('decoder.after_norm', d)
+    for j in range(dc['num_blocks']):
+        p = f'decoder.decoders.{j}'
+        for a in ('self_attn', 'src_attn'):
+            for n in ('linear_q', 'linear_k', 'linear_v', 'linear_out'):
+                lin(f'{p}.{a}.{n}', d, d, bias=n != 'linear_k')
+        lin(p + '.feed_forward.w_1', dc['linear_units'], d)
+        lin(p + '.feed_forward.w_2', d, dc['linear_units'])
+        for n in ('norm1', 'norm2', 'norm3'):
+            norm(f'{p}.{n}', d)
+    # tie_word_embedding: the output layer IS the embedding; its bias is a parameter of its
+    # own.  A tied random decoder repeats one token when the token's own embedding (logit =
+    # E . LN(E[last] + ...): the last token wins) or the nearly constant layer outputs dominate
+    # the residual stream: at this scale the positional rows (amplitude 1) weigh as much as the
+    # scaled embedding (sqrt(d) E, std 0.7), so the arg-max moves with the step
+    sd['decoder.embed.0.weight'] = sd['decoder.embed.0.weight'] * np.float32(0.7 / math.sqrt(d))
+    sd['decoder.output_layer.weight'] = sd['decoder.embed.0.weight']
+    sd['decoder.output_layer.bias'] = _uniform(seed, 'decoder.output_layer.bias', (V, ), 0.1)
+    # layer matrices x 3 (as for the Whisper decoder below: with smaller ones the next token
+    # barely depends on the input or the position), <eos> a logit bias so that some hypotheses
+    # end before the cap
+    for k in list(sd):
+        if k.startswith('decoder.decoders.') and k.endswith('.weight') and sd[k].ndim == 2:
+            sd[k] = sd[k] * np.float32(3.0)
+    eos = configs['tokenizer_conf']['special_tokens']['eos']
+    sd['decoder.output_layer.bias'][eos] += np.float32(FIRERED_EOS_BIAS)
+    lin('ctc.ctc_lo', V, d)
+    if sharpen_ctc:      # as make_state_dict: roughly 2/3 .. 4/5 of the frames come out blank
+        sd['ctc.ctc_lo.weight'] = sd['ctc.ctc_lo.weight'] * np.float32(12.0)
+        sd['ctc.ctc_lo.bias'] = sd['ctc.ctc_lo.bias'] * np.float32(12.0)
+        n = max(V - 1, 2)
+        a = math.sqrt(2.0 * math.log(n))
+        emax = a - (math.log(math.log(n)) + math.log(4 * math.pi)) / (2 * a) + 0.5772 / a
+        sd['ctc.ctc_lo.weight'][0, :] = 0.0
+        sd['ctc.ctc_lo.bias'][0] = np.float32(12.0 / math.sqrt(3.0) * emax * 1.10)
+    return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
 
 
 def whisper_positional_table(d_model: int, max_len: int = 1500) -> torch.Tensor:
