@@ -23,6 +23,16 @@ def cached_model(config_name, wseed):
     return _MODEL_CACHE[key]
 
 
+def refusal_text(exc):
+    """The library's message of a refused call, whole: the RuntimeError of wenet_amd._lib.check
+    without its '<entry point> failed (<status>): ' head and without the '<source file>:<line>: '
+    that most refusals carry in front of the message (it moves with every edit of the file)."""
+    import re
+    m = re.fullmatch(r'\w+ failed \(-?\d+\): (?:[^\n]*?\.(?:hip|h):\d+: )?(.*)', str(exc), re.S)
+    assert m, str(exc)
+    return m.group(1)
+
+
 def compare_nbest(got, ref_nbest, ref_scores, ref_times, score_atol=2e-3,
                   what=''):
     """n-best lists produced from slightly different log-probs: every reference

@@ -248,6 +248,36 @@ def test_lookahead_takes_fewer_steps(gold, model):
             steps[F]
 
 
+# The host loop issues steps in groups of 8 up to the bound longest x (n_steps + 1) + 1 and looks
+# at n_active one group late.  The recorded utterances (29 / 16 / 15 frames) have bounds of 59
+# and more; here are the two edges they leave out, on their first frames (the decisions are a
+# prefix of the recorded searches', so the fp64 formulation is a reference as it is there):
+# a bound of 7, below one group, and a search whose last step is the 6th of its second group.
+@pytest.mark.parametrize('lens,n_steps,bound,steps1', [([1, 3], 1, 7, 3), ([4, 6], 3, 25, 14)])
+def test_poll_loop_edges(gold, model, lens, n_steps, bound, steps1):
+    from wenet_amd import synthetic as S
+    from wenet_amd.transducer import basic_greedy_search
+    meta, enc, _ = gold
+    assert max(lens) * (n_steps + 1) + 1 == bound
+    enc = enc[:len(lens), :max(lens)].contiguous()
+    configs = S.make_configs(meta['config'])
+    sd = S.make_state_dict(configs, meta['wseed'], rnnt_blank_bias=meta['blank_bias'])
+    W = TF.weights64({k: v.numpy() for k, v in sd.items()}, 2)
+    form = {F: TF.lookahead_greedy_search(enc.cpu().numpy(), lens, W, meta['blank'], n_steps, F)
+            for F in (1, 16)}
+    assert form[1][1] == steps1 and form[1][0] == form[16][0] and any(form[1][0])
+    try:
+        for F in (1, 16):
+            model.tune('rnnt_lookahead', F)
+            assert basic_greedy_search(model, enc, lens, n_steps=n_steps) == form[F][0]
+            assert model.last_rnnt_steps == form[F][1]
+            for b, n in enumerate(lens):
+                assert basic_greedy_search(model, enc[b:b + 1, :n].contiguous(), [n],
+                                           n_steps) == [form[F][0][b]]
+    finally:
+        model.tune('rnnt_lookahead', 'inherit')
+
+
 # A vocabulary of 65 x 128 + 9: the joint kernel leaves 66 column-block partials per row, so the
 # advance kernel's own reduction runs (lane-strided merge with a second round for lane 0 and 1,
 # butterfly, the m * ncb pitch), which the 67-token golden model (one column block) never

@@ -429,7 +429,7 @@ def test_recognizer_refuses_a_model_without_transducer_weights():
 
 # ---- 6. refusals -------------------------------------------------------------------------------
 def test_refusals_change_no_state(gold, model):
-    from gpu_util import cached_model
+    from gpu_util import cached_model, refusal_text
     from wenet_amd.streaming import RnntBeamStreamSearch
     meta, enc, enc_dev, lens = gold
     _, _, asr = cached_model('tiny_causal', 0)
@@ -453,21 +453,30 @@ def test_refusals_change_no_state(gold, model):
         rs.advance_encoded([0, 1], x[:2], [8, 6])
         before = [_bits(rs.state(s)) for s in range(3)]
         mirror = list(rs.frames)
+        who = 'wn_rnnt_beam_stream_advance_encoded'
         for slots, xs, nt, kw, what in (
-                ([0, 1, 2, 0], torch.cat([x, x[:1]]), [1, 1, 1, 1], {}, 'n must be'),
-                ([0, 3], x[:2], [1, 1], {}, 'slot id out of range'),
-                ([0, -1], x[:2], [1, 1], {}, 'slot id out of range'),
-                ([1, 1], x[:2], [1, 1], {}, 'named twice'),
-                ([0, 1], x[:2], [1, 9], {}, 'n_t'),
-                ([0, 1], x[:2], [-1, 1], {}, 'n_t'),
-                ([2, 0], x[:2], [1, 5], {}, 'max_frames'),
-                ([2, 1], x[:2], [4, 1], dict(max_len=6), 'max_len')):
-            with pytest.raises(RuntimeError, match=what):
+                ([0, 1, 2, 0], torch.cat([x, x[:1]]), [1, 1, 1, 1], {},
+                 ': n must be in [1, n_slots]'),
+                ([0, 3], x[:2], [1, 1], {}, ': slot_ids: slot id out of range'),
+                ([0, -1], x[:2], [1, 1], {}, ': slot_ids: slot id out of range'),
+                ([1, 1], x[:2], [1, 1], {}, ': slot_ids: a slot is named twice in one call (two '
+                                            'rows would write one state)'),
+                ([0, 1], x[:2], [1, 9], {}, ': n_t: need 0 <= n_t <= chunk'),
+                ([0, 1], x[:2], [-1, 1], {}, ': n_t: need 0 <= n_t <= chunk'),
+                ([2, 0], x[:2], [1, 5], {},
+                 ': the session in slot 0 has 8 frames and would pass max_frames = 12 with 5 '
+                 'more; no session was advanced'),
+                ([2, 1], x[:2], [4, 1], dict(max_len=6),
+                 ': max_len is smaller than a hypothesis may become (7 tokens); no session was '
+                 'advanced')):
+            with pytest.raises(RuntimeError) as e:
                 rs.advance_encoded(slots, xs, nt, **kw)
+            assert refusal_text(e.value) == who + what
             assert [_bits(rs.state(s)) for s in range(3)] == before, what
             assert rs.frames == mirror
-        with pytest.raises(RuntimeError, match='slot id out of range'):
+        with pytest.raises(RuntimeError) as e:
             rs.reset([3])
+        assert refusal_text(e.value) == 'wn_rnnt_beam_stream_reset: slot_ids: slot id out of range'
         assert [_bits(rs.state(s)) for s in range(3)] == before
         # the sessions go on as if nothing had happened
         r = rs.advance_encoded([1, 0], enc_dev[[1, 0], 6:10].contiguous(), [2, 4])

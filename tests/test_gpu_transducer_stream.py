@@ -354,7 +354,7 @@ def test_recognizer_modes(sgold, smodel):
 
 # ---- refusals ----------------------------------------------------------------------------------
 def test_refusals_change_no_state(gold, model):
-    from gpu_util import cached_model
+    from gpu_util import cached_model, refusal_text
     from wenet_amd.streaming import RnntStreamSearch
     meta, enc, enc_dev, lens = gold
     _, _, asr = cached_model('tiny_causal', 0)
@@ -369,21 +369,32 @@ def test_refusals_change_no_state(gold, model):
         rs.advance_encoded([0, 1], x[:2], [8, 6])
         before = [_bits(rs.state(s)) for s in range(3)]
         mirrors = (list(rs.frames), list(rs.n_tok))
+        who = 'wn_rnnt_stream_advance_encoded'
+        # the last case: what slots 2 / 1 may hold after 4 / 1 more frames of 3 tokens each
+        need = max(min(mirrors[1][2] + 4 * 3, 40), min(mirrors[1][1] + 1 * 3, 40))
         for slots, xs, nt, kw, what in (
-                ([0, 1, 2, 0], torch.cat([x, x[:1]]), [1, 1, 1, 1], {}, 'n must be'),
-                ([0, 3], x[:2], [1, 1], {}, 'slot id out of range'),
-                ([0, -1], x[:2], [1, 1], {}, 'slot id out of range'),
-                ([1, 1], x[:2], [1, 1], {}, 'named twice'),
-                ([0, 1], x[:2], [1, 9], {}, 'n_t'),
-                ([0, 1], x[:2], [-1, 1], {}, 'n_t'),
-                ([2, 0], x[:2], [1, 5], {}, 'max_frames'),
-                ([2, 1], x[:2], [4, 1], dict(max_len=5), 'max_len')):
-            with pytest.raises(RuntimeError, match=what):
+                ([0, 1, 2, 0], torch.cat([x, x[:1]]), [1, 1, 1, 1], {},
+                 ': n must be in [1, n_slots]'),
+                ([0, 3], x[:2], [1, 1], {}, ': slot_ids: slot id out of range'),
+                ([0, -1], x[:2], [1, 1], {}, ': slot_ids: slot id out of range'),
+                ([1, 1], x[:2], [1, 1], {}, ': slot_ids: a slot is named twice in one call (two '
+                                            'rows would write one state)'),
+                ([0, 1], x[:2], [1, 9], {}, ': n_t: need 0 <= n_t <= chunk'),
+                ([0, 1], x[:2], [-1, 1], {}, ': n_t: need 0 <= n_t <= chunk'),
+                ([2, 0], x[:2], [1, 5], {},
+                 ': the session in slot 0 has 8 frames and would pass max_frames = 12 with 5 '
+                 'more; no session was advanced'),
+                ([2, 1], x[:2], [4, 1], dict(max_len=5),
+                 ": max_len is smaller than a session's token count may become (%d tokens); no "
+                 'session was advanced' % need)):
+            with pytest.raises(RuntimeError) as e:
                 rs.advance_encoded(slots, xs, nt, **kw)
+            assert refusal_text(e.value) == who + what
             assert [_bits(rs.state(s)) for s in range(3)] == before, what
             rs.frames, rs.n_tok = list(mirrors[0]), list(mirrors[1])
-        with pytest.raises(RuntimeError, match='slot id out of range'):
+        with pytest.raises(RuntimeError) as e:
             rs.reset([3])
+        assert refusal_text(e.value) == 'wn_rnnt_stream_reset: slot_ids: slot id out of range'
         assert [_bits(rs.state(s)) for s in range(3)] == before
         # the sessions go on as if nothing had happened
         r = rs.advance_encoded([1, 0], enc_dev[[1, 0], 6:10].contiguous(), [2, 4])

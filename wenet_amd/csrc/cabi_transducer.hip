@@ -5,7 +5,7 @@
 #include <algorithm>
 
 #include "model_state.h"
-#include "rnnt_predictor.h"
+#include "rnnt_host.h"
 
 extern "C" {
 
@@ -24,12 +24,9 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
   const ModelData& W = *m->data;
-  const wn_config& c = m->cfg;
-  const int B = m->B, rows = m->rows, d = c.d_model;
+  const int B = m->B, rows = m->rows;
   const wn_transducer_config& tc = m->tr.c;
-  const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
-  const int J = tc.join_dim, V = c.vocab, blank = tc.blank;
-  const bool stateless = m->tr.sp.kind != 0;
+  const int J = tc.join_dim, V = m->cfg.vocab, blank = tc.blank;
   const int F = std::min(std::max(tune().rnnt_lookahead, 1), 16);
   int longest = 0;
   for (int b = 0; b < B; ++b) longest = std::max(longest, m->len[b]);
@@ -42,81 +39,41 @@ int wn_transducer_greedy_search(wn_model* m, int32_t n_steps, int32_t* tokens_ho
 
   // ---- workspace ----------------------------------------------------------------------------
   WN_TRY(m->tr_enc.ensure((size_t)std::max(rows, 1) * J * sizeof(float)));
-  const size_t n_state = up64((size_t)L * B * H);
-  const size_t o_h = 0, o_c = n_state, o_gates = o_c + n_state,
-               o_pout = o_gates + up64((size_t)B * 4 * H), o_pproj = o_pout + up64((size_t)B * P),
-               o_pmax = o_pproj + up64((size_t)B * J), n_f32 = o_pmax + up64((size_t)M * ncb);
-  WN_TRY(m->tr_f32.ensure(n_f32 * sizeof(float)));
-  const size_t ub = up64(B), um = up64(M);
-  const size_t n_i32 = 6 * ub + 2 * um + up64((size_t)M * ncb) + 64;
-  WN_TRY(m->tr_i32.ensure(n_i32 * sizeof(int)));
+  RnntGreedyLayout w;
+  WN_TRY(w.carve(tc, B, M, ncb, 2, m->tr_f32, m->tr_i32));
   WN_TRY(m->tr_tok.ensure((size_t)B * max_tok * sizeof(int)));
   WN_TRY(m->tr_host.ensure(256 + (size_t)B * sizeof(int)));
   for (hipEvent_t& e : m->tr_ev)
     if (!e) WN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  float* f = m->tr_f32.as<float>();
   float* enc_proj = m->tr_enc.as<float>();
-  float *h = f + o_h, *cst = f + o_c, *gates = f + o_gates, *pout = f + o_pout,
-        *pproj = f + o_pproj, *pmax = f + o_pmax;
-  int* ip = m->tr_i32.as<int>();
   RnntState st;
-  st.t = ip; st.cnt = ip + ub; st.last_tok = ip + 2 * ub; st.advance = ip + 3 * ub;
-  st.done = ip + 4 * ub; st.n_tok = ip + 5 * ub;
-  st.row_enc = ip + 6 * ub; st.row_pred = st.row_enc + um;
-  int* pidx = st.row_pred + um;
-  st.n_active = pidx + up64((size_t)M * ncb); st.steps = st.n_active + 1;
+  st.t = w.t; st.cnt = w.cnt; st.last_tok = w.last_tok; st.advance = w.advance;
+  st.done = w.done; st.n_tok = w.n_tok;
+  st.row_enc = w.row_enc; st.row_pred = w.row_pred;
+  st.n_active = w.stat; st.steps = w.stat + 1;
   st.tokens = m->tr_tok.as<int>(); st.max_tok = max_tok;
   st.off = m->d_off.as<int>(); st.len = m->d_len.as<int>();
 
   // ---- once per batch: enc_proj = joint.enc_ffn(encoder_out), zero LSTM state -----------------
-  {
-    // always the fp32 GEMMs, whatever the handle's operand precision
-    const int saved = t_gemm_prec;
-    t_gemm_prec = PREC_F32;
-    const int r = rows > 0 ? linear(W.j_enc, m->enc.as<float>(), d, enc_proj, J, rows, s) : 0;
-    t_gemm_prec = saved;
-    WN_TRY(r);
-  }
-  if (n_state > 0) WN_HIP(hipMemsetAsync(h, 0, 2 * n_state * sizeof(float), s));
+  if (rows > 0) WN_TRY(rnnt_prepare(m, m->enc.as<float>(), rows, enc_proj, s));
+  if (w.n_state > 0) WN_HIP(hipMemsetAsync(w.h, 0, 2 * w.n_state * sizeof(float), s));
   WN_TRY(rnnt_init(st, B, F, blank, s));
 
-  // ---- the lock-step loop: groups of steps, n_active looked at one group late -----------------
+  // ---- the lock-step loop ---------------------------------------------------------------------
+  StatelessWindow sw;     // the tail of the utterance's token row up to n_tok
+  sw.tokens = st.tokens; sw.ld_tok = max_tok; sw.tok_len = st.n_tok;
+  RnntJointArgs ja;
+  ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = w.pproj; ja.ldp = J;
+  ja.row_enc = st.row_enc; ja.row_pred = st.row_pred;
+  ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
+  ja.part_max = w.pmax; ja.part_idx = w.pidx; ja.n_active = st.n_active;
   const int64_t bound = (int64_t)longest * ((int64_t)n_steps + 1) + 1;
-  volatile int* pin = reinterpret_cast<volatile int*>(m->tr_host.p);   // slots 0 / 1 (64 B apart)
-  int64_t issued = 0;
-  for (int g = 0; issued < bound; ++g) {
-    const int n = (int)std::min<int64_t>(RNNT_GROUP, bound - issued);
-    for (int i = 0; i < n; ++i) {
-      if (stateless) {    // the window: the tail of the utterance's token row up to n_tok
-        StatelessWindow sw;
-        sw.tokens = st.tokens; sw.ld_tok = max_tok; sw.tok_len = st.n_tok;
-        WN_TRY(stateless_step(m, sw, pproj, st.advance, st.n_active, B, s));
-      } else {
-        WN_TRY(predictor_step(W.pred_embed, E, st.last_tok, E, W.pred_rnn.data(), L, W.pred_proj,
-                              h, cst, gates, pout, st.advance, st.n_active, B, H, s));
-        RnntLinearArgs q;   // joint.pred_ffn
-        q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-        q.y = pproj; q.ldy = J; q.N = J; q.B = B;
-        q.advance = st.advance; q.n_active = st.n_active;
-        WN_TRY(rnnt_linear(q, s));
-      }
-      RnntJointArgs ja;
-      ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pproj; ja.ldp = J;
-      ja.row_enc = st.row_enc; ja.row_pred = st.row_pred;
-      ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
-      ja.part_max = pmax; ja.part_idx = pidx; ja.n_active = st.n_active;
-      WN_TRY(rnnt_joint_argmax(ja, s));
-      WN_TRY(rnnt_advance(pmax, pidx, ncb, V, st, B, F, blank, n_steps, s));
-    }
-    issued += n;
-    WN_HIP(hipMemcpyAsync(m->tr_host.p + 64 * (g & 1), st.n_active, sizeof(int),
-                          hipMemcpyDeviceToHost, s));
-    WN_HIP(hipEventRecord(m->tr_ev[g & 1], s));
-    if (g >= 1) {
-      WN_HIP(hipEventSynchronize(m->tr_ev[(g - 1) & 1]));
-      if (pin[16 * ((g - 1) & 1)] == 0) break;
-    }
-  }
+  WN_TRY(rnnt_poll_loop(bound, st.n_active, m->tr_host.p, m->tr_ev, s, [&]() -> int {
+    WN_TRY(pred_proj_step(m, sw, st.last_tok, w.h, w.c, w.gates, w.pout, w.pproj, st.advance,
+                          st.n_active, B, s));
+    WN_TRY(rnnt_joint_argmax(ja, s));
+    return rnnt_advance(w.pmax, w.pidx, ncb, V, st, B, F, blank, n_steps, s);
+  }));
 
   // ---- results: lengths and the step count first, then the token rows that were filled ---------
   int* lens_pin = reinterpret_cast<int*>(m->tr_host.p + 256);
@@ -157,8 +114,7 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
            "wn_transducer_beam_search: no current batch (call wn_encode / wn_set_encoder_out)");
   WN_CHECK(n_hyps_host && hyp_lens_host && hyp_tokens_host && hyp_scores_host && max_len >= 0,
            "wn_transducer_beam_search: null output");
-  const wn_config& c = m->cfg;
-  const int V = c.vocab;
+  const int V = m->cfg.vocab;
   WN_CHECK(beam >= 1 && beam <= 16, "wn_transducer_beam_search: beam must be in [1, 16]");
   WN_CHECK(beam <= V, "wn_transducer_beam_search: beam is larger than the vocabulary");
   WN_CHECK(ctc_weight >= 0.f && transducer_weight >= 0.f,
@@ -167,120 +123,42 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
            "wn_transducer_beam_search: ctc_weight and transducer_weight are both 0");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
-  const ModelData& W = *m->data;
-  WN_CHECK(ctc_weight == 0.f || W.ctc.w, "wn_transducer_beam_search: ctc_weight > 0 on a handle "
-                                         "without a CTC head");
-  const int B = m->B, rows = m->rows, d = c.d_model;
+  WN_CHECK(ctc_weight == 0.f || m->data->ctc.w, "wn_transducer_beam_search: ctc_weight > 0 on a "
+                                                "handle without a CTC head");
+  const int B = m->B, rows = m->rows;
   const wn_transducer_config& tc = m->tr.c;
-  const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
-  const int J = tc.join_dim, blank = tc.blank;
-  const bool stateless = m->tr.sp.kind != 0;
   int longest = 0;
   for (int b = 0; b < B; ++b) longest = std::max(longest, m->len[b]);
   const int max_tok = std::max(longest, 1);     // one symbol per frame at most
   const int64_t M64 = (int64_t)B * beam;
-  const int ldl = (V + 31) / 32 * 32;
-  WN_CHECK(M64 * std::max(max_tok, ldl) <= ((int64_t)1 << 28),
+  WN_CHECK(M64 * std::max(max_tok, ctc_pitch(V)) <= ((int64_t)1 << 28),
            "wn_transducer_beam_search: B x beam rows do not fit the workspace");
   const int M = (int)M64;
 
   // ---- workspace, sized by B x beam -----------------------------------------------------------
-  WN_TRY(m->tr_enc.ensure((size_t)std::max(rows, 1) * J * sizeof(float)));
-  const size_t n_state = up64((size_t)L * M * H), n_pp = up64((size_t)M * J), um = up64(M),
-               ub = up64(B);
-  const size_t o_h = 0, o_c = 2 * n_state, o_gates = 4 * n_state,
-               o_pout = o_gates + up64((size_t)M * 4 * H), o_pp = o_pout + up64((size_t)M * P),
-               o_logits = o_pp + 2 * n_pp, o_topv = o_logits + up64((size_t)M * ldl),
-               o_score = o_topv + up64((size_t)M * beam), n_f32 = o_score + 4 * um;
-  WN_TRY(m->tr_f32.ensure(n_f32 * sizeof(float)));
-  const size_t o_topi = 2 * ub + 7 * um, o_stat = o_topi + up64((size_t)M * beam),
-               n_i32 = o_stat + 64;
-  WN_TRY(m->tr_i32.ensure(n_i32 * sizeof(int)));
-  WN_TRY(m->tr_tok.ensure((size_t)2 * M * max_tok * sizeof(int)));
-  float* f = m->tr_f32.as<float>();
-  int* ip = m->tr_i32.as<int>();
+  WN_TRY(m->tr_enc.ensure((size_t)std::max(rows, 1) * tc.join_dim * sizeof(float)));
+  RnntBeamLayout w;
+  WN_TRY(w.carve(tc, B, beam, V, max_tok, false, m->tr_f32, m->tr_i32, m->tr_tok));
   float* enc_proj = m->tr_enc.as<float>();
-  float *gates = f + o_gates, *pout = f + o_pout, *logits = f + o_logits, *topv = f + o_topv;
-  RnntBeamSlots slots[2];
-  for (int i = 0; i < 2; ++i) {
-    slots[i].n_live = ip + i * ub;
-    slots[i].tok_len = ip + 2 * ub + i * um;
-    slots[i].score = reinterpret_cast<double*>(f + o_score) + i * um;
-    slots[i].tokens = m->tr_tok.as<int>() + (size_t)i * M * max_tok;
-  }
-  int* src = ip + 2 * ub + 2 * um;
-  int *last_tok = src + um, *advance = src + 2 * um, *row_enc = src + 3 * um,
-      *row_pred = src + 4 * um, *topi = ip + o_topi;
   const int* off = m->d_off.as<int>();
   const int* len = m->d_len.as<int>();
 
   // ---- once per batch: enc_proj, the CTC log-prob rows (cw > 0 only), zero LSTM state ----------
   const float* ctc = nullptr;
-  {
-    const int saved = t_gemm_prec;      // always the fp32 GEMMs, whatever the handle's precision
-    t_gemm_prec = PREC_F32;
-    int r = rows > 0 ? linear(W.j_enc, m->enc.as<float>(), d, enc_proj, J, rows, s) : 0;
-    if (r == 0 && ctc_weight != 0.f && rows > 0) {
-      r = m->tr_ctc.ensure(((size_t)rows * ldl + 2 * (size_t)rows) * sizeof(float));
-      if (r == 0) r = linear(W.ctc, m->enc.as<float>(), d, m->tr_ctc.as<float>(), ldl, rows, s);
-    }
-    t_gemm_prec = saved;
-    WN_TRY(r);
-  }
-  if (ctc_weight != 0.f && rows > 0) {
-    CtcRowArgs r;       // normalised in place; its top-1 is not used
-    r.logits = m->tr_ctc.as<float>(); r.ld = ldl; r.M = rows; r.V = V; r.k = 1;
-    r.blank = blank; r.blank_penalty = 0.f;
-    r.topk_val = m->tr_ctc.as<float>() + (size_t)rows * ldl;
-    r.topk_idx = reinterpret_cast<int*>(r.topk_val + rows);
-    r.logp = m->tr_ctc.as<float>(); r.ld_out = ldl;
-    WN_TRY(ctc_logsoftmax_topk(r, s));
-    ctc = m->tr_ctc.as<float>();
-  }
-  if (n_state > 0) WN_HIP(hipMemsetAsync(f + o_h, 0, 4 * n_state * sizeof(float), s));
-  WN_HIP(hipMemsetAsync(ip + o_stat, 0, sizeof(int), s));
-  WN_TRY(rnnt_beam_init(slots[0], last_tok, advance, row_enc, row_pred, off, len, B, beam, blank, s));
+  if (rows > 0)
+    WN_TRY(rnnt_prepare(m, m->enc.as<float>(), rows, enc_proj, s, ctc_weight, &m->tr_ctc, &ctc));
+  if (w.n_state > 0) WN_HIP(hipMemsetAsync(w.h, 0, 4 * w.n_state * sizeof(float), s));
+  WN_HIP(hipMemsetAsync(w.n_advance, 0, sizeof(int), s));
+  WN_TRY(rnnt_beam_init(w.slots[0], w.last_tok, w.advance, w.row_enc, w.row_pred, off, len, B,
+                        beam, tc.blank, s));
 
   // ---- exactly `longest` steps, stream-ordered, no look at the device in between ---------------
-  for (int i = 0; i < longest; ++i) {
-    const int cur = i & 1, nxt = cur ^ 1;
-    float *h = f + o_h + cur * n_state, *cst = f + o_c + cur * n_state, *pp = f + o_pp + cur * n_pp;
-    if (stateless) {    // the window: the tail of the slot's token row in the parity just written
-      StatelessWindow sw;
-      sw.tokens = slots[cur].tokens; sw.ld_tok = max_tok; sw.tok_len = slots[cur].tok_len;
-      WN_TRY(stateless_step(m, sw, pp, advance, nullptr, M, s));
-    } else {
-      WN_TRY(predictor_step(W.pred_embed, E, last_tok, E, W.pred_rnn.data(), L, W.pred_proj, h, cst,
-                            gates, pout, advance, nullptr, M, H, s));
-      RnntLinearArgs q;   // joint.pred_ffn
-      q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-      q.y = pp; q.ldy = J; q.N = J; q.B = M; q.advance = advance;
-      WN_TRY(rnnt_linear(q, s));
-    }
-    RnntJointArgs ja;
-    ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = pp; ja.ldp = J;
-    ja.row_enc = row_enc; ja.row_pred = row_pred;
-    ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
-    ja.logits = logits; ja.ldl = ldl;
-    WN_TRY(rnnt_joint_rows(ja, s));
-    RnntFuseArgs fa;
-    fa.logits = logits; fa.ldl = ldl; fa.row_enc = row_enc; fa.ctc = ctc; fa.ldc = ldl;
-    fa.cw = ctc_weight; fa.tw = transducer_weight; fa.M = M; fa.V = V; fa.k = beam;
-    fa.val = topv; fa.idx = topi;
-    WN_TRY(rnnt_fuse_topk(fa, s));
-    RnntBeamStepArgs ba;
-    ba.in = slots[cur]; ba.out = slots[nxt]; ba.max_tok = max_tok;
-    ba.top_val = topv; ba.top_idx = topi; ba.off = off; ba.len = len;
-    ba.frame = i; ba.B = B; ba.beam = beam; ba.blank = blank; ba.V = V;
-    ba.src = src; ba.last_tok = last_tok; ba.advance = advance; ba.row_enc = row_enc;
-    ba.n_advance = ip + o_stat;
-    WN_TRY(rnnt_beam_step(ba, s));
-    WN_TRY(rnnt_beam_gather(src, h, cst, pp, f + o_h + nxt * n_state, f + o_c + nxt * n_state,
-                            f + o_pp + nxt * n_pp, M, L, H, J, s));
-  }
+  WN_TRY(rnnt_beam_steps(m, w, enc_proj, ctc, ctc_weight, transducer_weight, off, len, B, beam,
+                         max_tok, longest, s));
 
   // ---- results: counts | lengths | scores | token rows into pinned memory, one wait ------------
-  const RnntBeamSlots& fin = slots[longest & 1];
+  const RnntBeamSlots& fin = w.slots[longest & 1];
+  const size_t um = up64(M);
   const size_t p_len = up64(B) * sizeof(int), p_sc = p_len + um * sizeof(int),
                p_tok = p_sc + um * sizeof(double),
                p_stat = p_tok + up64((size_t)M * max_tok) * sizeof(int);
@@ -291,7 +169,7 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
   WN_HIP(hipMemcpyAsync(hp + p_sc, fin.score, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, s));
   WN_HIP(hipMemcpyAsync(hp + p_tok, fin.tokens, (size_t)M * max_tok * sizeof(int),
                         hipMemcpyDeviceToHost, s));
-  WN_HIP(hipMemcpyAsync(hp + p_stat, ip + o_stat, sizeof(int), hipMemcpyDeviceToHost, s));
+  WN_HIP(hipMemcpyAsync(hp + p_stat, w.n_advance, sizeof(int), hipMemcpyDeviceToHost, s));
   WN_HIP(stream_wait(s));
   m->tr_beam_steps = longest;
   m->tr_beam_advance = *reinterpret_cast<const int*>(hp + p_stat);
@@ -303,18 +181,10 @@ int wn_transducer_beam_search(wn_model* m, int32_t beam, float ctc_weight,
   for (int b = 0; b < B; ++b) {
     WN_CHECK(nl[b] >= 1 && nl[b] <= beam, "wn_transducer_beam_search: an utterance ended without "
                                           "a hypothesis");
-    n_hyps_host[b] = nl[b];
-    for (int k = 0; k < beam; ++k) {
-      const int g = b * beam + k;
-      const int n = k < nl[b] ? tl[g] : 0;
-      WN_CHECK(n >= 0 && n <= max_tok, "wn_transducer_beam_search: token row overflow");
-      WN_CHECK(n <= max_len, "wn_transducer_beam_search: max_len is smaller than the longest "
-                             "result (" + std::to_string(n) + " tokens)");
-      hyp_lens_host[g] = n;
-      hyp_scores_host[g] = k < nl[b] ? sc[g] : -INFINITY;
-      std::copy(tk + (size_t)g * max_tok, tk + (size_t)g * max_tok + n,
-                hyp_tokens_host + (size_t)g * max_len);
-    }
+    const size_t g = (size_t)b * beam;
+    WN_TRY(rnnt_unpack_nbest("wn_transducer_beam_search", nl[b], beam, tl + g, sc + g,
+                             tk + g * max_tok, max_tok, n_hyps_host + b, hyp_lens_host + g,
+                             hyp_scores_host + g, hyp_tokens_host + g * max_len, max_len));
   }
   return 0;
 }
@@ -345,7 +215,8 @@ int wn_op_lstm_step(const float* x_dev, const float* const* w_host, int32_t n_la
   Linear proj;
   proj.w = proj_w_dev; proj.b = proj_b_dev; proj.out = P; proj.in = H;
   return predictor_step(x_dev, E, nullptr, E, layers.data(), n_layers, proj, h_dev, c_dev,
-                        gates.as<float>(), out_dev, advance_dev, nullptr, B, H, s);
+                        (int64_t)B * H, gates.as<float>(), out_dev, advance_dev, nullptr, B, H,
+                        s);
 }
 
 int wn_op_stateless_step(const wn_stateless_predictor_config* scfg, const int32_t* ctx_host,

@@ -4,7 +4,7 @@
 #include <algorithm>
 
 #include "model_state.h"
-#include "rnnt_predictor.h"
+#include "rnnt_host.h"
 #include "rnnt_trie.h"
 
 namespace wn {
@@ -13,14 +13,12 @@ namespace {
 constexpr int TS_MAX_BEAM = 16;
 constexpr int TS_MAX_LEN = 4095;      // rnnt_lattice: two alpha columns of U + 1 doubles in LDS
 
-size_t ts_up64(size_t n) { return (n + 63) / 64 * 64; }
-
 // sections of one int32 upload, each starting at a multiple of 64 entries
 struct IntPack {
   std::vector<int> host;
   size_t add(size_t n) {
     const size_t o = host.size();
-    host.resize(o + ts_up64(std::max<size_t>(n, 1)), 0);
+    host.resize(o + up64(std::max<size_t>(n, 1)), 0);
     return o;
   }
 };
@@ -62,7 +60,7 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
   const wn_config& c = m->cfg;
   const ModelData& W = *m->data;
   const wn_transducer_config& tc = m->tr.c;
-  const int B = m->B, rows = m->rows, d = c.d_model, V = c.vocab;
+  const int B = m->B, rows = m->rows, V = c.vocab;
   const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
   const int J = tc.join_dim, blank = tc.blank;
   for (int b = 0; b < B; ++b)
@@ -188,11 +186,11 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
   int n_lvl_max = 0;
   for (int dd = 0; dd <= depth_max; ++dd) n_lvl_max = std::max(n_lvl_max, lvl_off[dd + 1] - lvl_off[dd]);
   WN_TRY(m->tr_enc.ensure((size_t)std::max(rows, 1) * J * sizeof(float)));
-  const size_t n_state = ts_up64((size_t)L * n_tot * H);
-  const size_t o_score = 0, o_h = ts_up64(2 * (size_t)NH), o_c = o_h + n_state,
-               o_gates = o_c + n_state, o_pout = o_gates + ts_up64((size_t)n_lvl_max * 4 * H),
-               o_pproj = o_pout + ts_up64((size_t)n_tot * P),
-               n_f32 = o_pproj + ts_up64((size_t)n_tot * J);
+  const size_t n_state = up64((size_t)L * n_tot * H);
+  const size_t o_score = 0, o_h = up64(2 * (size_t)NH), o_c = o_h + n_state,
+               o_gates = o_c + n_state, o_pout = o_gates + up64((size_t)n_lvl_max * 4 * H),
+               o_pproj = o_pout + up64((size_t)n_tot * P),
+               n_f32 = o_pproj + up64((size_t)n_tot * J);
   WN_TRY(m->tr_sc_f32.ensure(n_f32 * sizeof(float)));
   WN_TRY(m->tr_sc_i32.ensure(hi.size() * sizeof(int)));
   WN_TRY(m->tr_sc_logp.ensure((size_t)n_ent * sizeof(float)));
@@ -213,13 +211,7 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
   WN_HIP(mark(0));
 
   // ---- enc_proj = joint.enc_ffn(encoder_out), always the fp32 GEMM -------------------------------
-  {
-    const int saved = t_gemm_prec;
-    t_gemm_prec = PREC_F32;
-    const int r = linear(W.j_enc, m->enc.as<float>(), d, enc_proj, J, rows, s);
-    t_gemm_prec = saved;
-    WN_TRY(r);
-  }
+  WN_TRY(rnnt_prepare(m, m->enc.as<float>(), rows, enc_proj, s));
 
   WN_HIP(mark(1));
 
@@ -235,17 +227,10 @@ int wn_transducer_score(wn_model* m, int32_t beam, const int32_t* n_hyps_host,
     const int r0 = lvl_off[dd], n = lvl_off[dd + 1] - r0;
     if (n <= 0) continue;
     if (dd > 0) WN_TRY(rnnt_trie_gather(di + o_par, h, cst, r0, n, L, lstride, H, s));
-    for (int l = 0; l < L; ++l) {
-      float* hl = h + l * lstride + (size_t)r0 * H;
-      RnntLinearArgs g;
-      if (l == 0) { g.x1 = W.pred_embed; g.ldx1 = E; g.x1_rows = di + o_tok + r0; g.K1 = E; }
-      else { g.x1 = h + (l - 1) * lstride + (size_t)r0 * H; g.ldx1 = H; g.K1 = H; }
-      g.W1 = W.pred_rnn[l].w_ih; g.b1 = W.pred_rnn[l].b_ih;
-      g.x2 = hl; g.ldx2 = H; g.W2 = W.pred_rnn[l].w_hh; g.K2 = H; g.b2 = W.pred_rnn[l].b_hh;
-      g.y = gates; g.ldy = 4 * H; g.N = 4 * H; g.B = n;
-      WN_TRY(rnnt_linear(g, s));
-      WN_TRY(rnnt_cell(gates, hl, cst + l * lstride + (size_t)r0 * H, nullptr, n, H, nullptr, s));
-    }
+    // the LSTM layers on the depth's rows of the [L][n_tot][H] state, no projection yet
+    WN_TRY(predictor_step(W.pred_embed, E, di + o_tok + r0, E, W.pred_rnn.data(), L, Linear(),
+                          h + (size_t)r0 * H, cst + (size_t)r0 * H, lstride, gates, nullptr,
+                          nullptr, nullptr, n, H, s));
   }
   const float* top = h + (L - 1) * lstride;
   int ld_top = H, k_top = H;
@@ -360,7 +345,7 @@ int wn_op_joint_logp_gather(const float* enc_proj_dev, int32_t enc_rows,
   for (int i = 0; i < M; ++i)
     for (int e = col_off_host[i]; e < col_off_host[i + 1]; ++e) ent_row[e] = i;
   static thread_local wn::DevBuf ibuf, obuf;
-  const size_t um = wn::ts_up64((size_t)M + 1), ue = wn::ts_up64(n_ent);
+  const size_t um = wn::up64((size_t)M + 1), ue = wn::up64(n_ent);
   WN_TRY(ibuf.ensure((3 * um + 2 * ue) * sizeof(int)));
   WN_TRY(obuf.ensure((size_t)n_ent * sizeof(float)));
   int* ip = ibuf.as<int>();
@@ -424,7 +409,7 @@ int wn_op_rnnt_lattice(int32_t N, const int32_t* T_host, const int32_t* U_host,
   memcpy(&ip.host[o_bb], bb.data(), (size_t)N * sizeof(int64_t));
   memcpy(&ip.host[o_lb], lb.data(), (size_t)N * sizeof(int64_t));
   static thread_local wn::DevBuf ibuf, fbuf;
-  const size_t ub = wn::ts_up64(std::max<int64_t>(nb, 1)), ul = wn::ts_up64(std::max<int64_t>(nl, 1));
+  const size_t ub = wn::up64(std::max<int64_t>(nb, 1)), ul = wn::up64(std::max<int64_t>(nl, 1));
   WN_TRY(ibuf.ensure(ip.host.size() * sizeof(int)));
   WN_TRY(fbuf.ensure((ub + ul) * sizeof(float) + (size_t)N * sizeof(double)));
   int* di = ibuf.as<int>();

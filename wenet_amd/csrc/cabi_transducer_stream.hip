@@ -3,7 +3,7 @@
 #include <algorithm>
 
 #include "model_state.h"
-#include "rnnt_predictor.h"
+#include "rnnt_host.h"
 
 // Everything a set owns is allocated in wn_rnnt_stream_create or grows on the first call that
 // needs it (the per-call workspace, whose size depends on n and the chunk): a steady stream of
@@ -24,46 +24,6 @@ struct wn_rnnt_stream_set {
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
   }
 };
-
-namespace wn {
-namespace {
-
-// argument checks of an advance call: nothing here touches the device or a session
-int rnnt_stream_check(const wn_rnnt_stream_set* S, int n, const int32_t* slot_ids,
-                      const int32_t* n_t, int chunk, const wn_rnnt_stream_result* out) {
-  WN_CHECK(n >= 1 && n <= S->n_slots, "wn_rnnt_stream_advance_encoded: n must be in [1, n_slots]");
-  WN_CHECK(out->tok_lens && out->tokens && out->times && out->frames_decoded &&
-               out->trailing_blank && out->max_len >= 0,
-           "wn_rnnt_stream_advance_encoded: null output");
-  std::vector<char> seen(S->n_slots, 0);
-  int64_t need = 0;
-  for (int i = 0; i < n; ++i) {
-    const int sl = slot_ids[i];
-    WN_CHECK(sl >= 0 && sl < S->n_slots,
-             "wn_rnnt_stream_advance_encoded: slot_ids: slot id out of range");
-    WN_CHECK(!seen[sl], "wn_rnnt_stream_advance_encoded: slot_ids: a slot is named twice in one "
-                        "call (two rows would write one state)");
-    seen[sl] = 1;
-    WN_CHECK(n_t[i] >= 0 && n_t[i] <= chunk,
-             "wn_rnnt_stream_advance_encoded: n_t: need 0 <= n_t <= chunk");
-    if (S->frames[sl] + n_t[i] > S->max_frames) {
-      set_error("wn_rnnt_stream_advance_encoded: the session in slot " + std::to_string(sl) +
-                " has " + std::to_string(S->frames[sl]) + " frames and would pass max_frames = " +
-                std::to_string(S->max_frames) + " with " + std::to_string(n_t[i]) +
-                " more; no session was advanced");
-      return -1;
-    }
-    need = std::max(need, std::min<int64_t>((int64_t)S->n_tok[sl] + (int64_t)n_t[i] * S->n_steps,
-                                            S->max_tokens));
-  }
-  WN_CHECK(out->max_len >= need,
-           "wn_rnnt_stream_advance_encoded: max_len is smaller than a session's token count may "
-           "become (" + std::to_string(need) + " tokens); no session was advanced");
-  return 0;
-}
-
-}  // namespace
-}  // namespace wn
 
 extern "C" {
 
@@ -103,11 +63,7 @@ int wn_rnnt_stream_create(wn_model* m, int32_t n_slots, int32_t max_frames, int3
   sl.trailing_blank = ip + 4 * us; sl.last_time = ip + 5 * us;
   sl.tokens = S->slot_tok.as<int>(); sl.times = sl.tokens + (size_t)n_slots * max_tokens;
   sl.max_tok = max_tokens; sl.L = L; sl.H = H; sl.J = J;
-  std::vector<int> all(n_slots);
-  for (int i = 0; i < n_slots; ++i) all[i] = i;
-  WN_TRY(S->stage.begin(all.size() * sizeof(int) + 64));
-  WN_TRY(S->stage.put_at(S->desc.p, all.data(), all.size() * sizeof(int), s));
-  WN_TRY(S->stage.end(s));
+  WN_TRY(rnnt_stage_call(S->stage, S->desc, n_slots, n_slots, nullptr, nullptr, s));
   WN_TRY(rnnt_stream_reset(sl, S->desc.as<int>(), n_slots, tc.blank, s));
   WN_HIP(hipStreamSynchronize(s));
   *out = S.release();
@@ -121,17 +77,12 @@ int wn_rnnt_stream_destroy(wn_rnnt_stream_set* set) {
 
 int wn_rnnt_stream_reset(wn_rnnt_stream_set* set, int32_t n, const int32_t* slot_ids,
                          void* stream) {
-  WN_CHECK(set && slot_ids, "wn_rnnt_stream_reset: null argument");
-  WN_CHECK(n >= 1 && n <= set->n_slots, "wn_rnnt_stream_reset: n must be in [1, n_slots]");
-  for (int i = 0; i < n; ++i)
-    WN_CHECK(slot_ids[i] >= 0 && slot_ids[i] < set->n_slots,
-             "wn_rnnt_stream_reset: slot_ids: slot id out of range");
+  WN_TRY(rnnt_reset_check("wn_rnnt_stream_reset", set && slot_ids, set ? set->n_slots : 0, n,
+                          slot_ids));
   WN_ENTER(set->m);
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(set->m->device));
-  WN_TRY(set->stage.begin((size_t)n * sizeof(int) + 64));
-  WN_TRY(set->stage.put_at(set->desc.p, slot_ids, (size_t)n * sizeof(int), s));
-  WN_TRY(set->stage.end(s));
+  WN_TRY(rnnt_stage_call(set->stage, set->desc, set->n_slots, n, slot_ids, nullptr, s));
   WN_TRY(rnnt_stream_reset(set->sl, set->desc.as<int>(), n, set->m->tr.c.blank, s));
   for (int i = 0; i < n; ++i) set->frames[slot_ids[i]] = set->n_tok[slot_ids[i]] = 0;
   return 0;
@@ -144,108 +95,72 @@ int wn_rnnt_stream_advance_encoded(wn_rnnt_stream_set* set, int32_t n, const int
   WN_CHECK(set && slot_ids && enc_out_dev && n_t_host && out,
            "wn_rnnt_stream_advance_encoded: null argument");
   WN_CHECK(chunk >= 1 && chunk <= (1 << 20), "wn_rnnt_stream_advance_encoded: chunk must be >= 1");
-  WN_TRY(rnnt_stream_check(set, n, slot_ids, n_t_host, chunk, out));
   wn_rnnt_stream_set* S = set;
+  int64_t need = 0;
+  WN_TRY(rnnt_session_check(
+      "wn_rnnt_stream_advance_encoded", S->n_slots, S->max_frames, S->frames, n, slot_ids,
+      n_t_host, chunk,
+      out->tok_lens && out->tokens && out->times && out->frames_decoded && out->trailing_blank &&
+          out->max_len >= 0,
+      [&](int sl, int n_t) {
+        need = std::max(need, std::min<int64_t>((int64_t)S->n_tok[sl] + (int64_t)n_t * S->n_steps,
+                                                S->max_tokens));
+      }));
+  WN_CHECK(out->max_len >= need,
+           "wn_rnnt_stream_advance_encoded: max_len is smaller than a session's token count may "
+           "become (" + std::to_string(need) + " tokens); no session was advanced");
   wn_model* m = S->m;
   WN_ENTER(m);
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
   const ModelData& W = *m->data;
-  const wn_config& c = m->cfg;
   const wn_transducer_config& tc = m->tr.c;
-  const int E = tc.pred_embed, H = tc.pred_hidden, L = tc.pred_layers, P = tc.pred_out;
-  const int J = tc.join_dim, V = c.vocab, blank = tc.blank, d = c.d_model;
+  const int J = tc.join_dim, V = m->cfg.vocab, blank = tc.blank;
   const int F = std::min(std::max(tune().rnnt_lookahead, 1), 16);
   const int n_steps = S->n_steps;
-  const bool stateless = m->tr.sp.kind != 0;
   const int M = n * F, ncb = rnnt_joint_col_blocks(V), rows = n * chunk;
   int longest = 0;
   for (int i = 0; i < n; ++i) longest = std::max(longest, (int)n_t_host[i]);
 
   // ---- workspace ----------------------------------------------------------------------------
-  WN_TRY(S->enc_proj.ensure((size_t)rows * J * sizeof(float)));
-  const size_t n_state = up64((size_t)L * n * H);
-  const size_t o_h = 0, o_c = n_state, o_gates = o_c + n_state,
-               o_pout = o_gates + up64((size_t)n * 4 * H), o_pproj = o_pout + up64((size_t)n * P),
-               o_pmax = o_pproj + up64((size_t)n * J), n_f32 = o_pmax + up64((size_t)M * ncb);
-  WN_TRY(S->f32.ensure(n_f32 * sizeof(float)));
-  const size_t ub = up64(n), um = up64(M);
   const size_t n_stat = 2 + 3 * (size_t)n;       // n_active | steps | n_tok | frames | trailing
-  const size_t n_i32 = 5 * ub + 2 * um + up64((size_t)M * ncb) + up64(n_stat);
-  WN_TRY(S->i32.ensure(n_i32 * sizeof(int)));
+  WN_TRY(S->enc_proj.ensure((size_t)rows * J * sizeof(float)));
+  RnntGreedyLayout w;
+  WN_TRY(w.carve(tc, n, M, ncb, n_stat, S->f32, S->i32));
   const int ld = out->max_len;
   WN_TRY(S->out_tok.ensure(std::max<size_t>(2 * (size_t)n * ld, 1) * sizeof(int)));
   const size_t p_stat = 256, p_tok = p_stat + up64(n_stat) * sizeof(int);
   WN_TRY(S->host.ensure(p_tok + 2 * (size_t)n * ld * sizeof(int)));
-  float* f = S->f32.as<float>();
   float* enc_proj = S->enc_proj.as<float>();
-  float *gates = f + o_gates, *pout = f + o_pout, *pmax = f + o_pmax;
-  int* ip = S->i32.as<int>();
   RnntStreamCall cl;
   cl.slot = S->desc.as<int>(); cl.n_t = cl.slot + up64(S->n_slots);
-  cl.h = f + o_h; cl.c = f + o_c; cl.pred_proj = f + o_pproj;
-  cl.last_tok = ip; cl.advance = ip + ub; cl.done = ip + 2 * ub; cl.t = ip + 3 * ub;
-  cl.cnt = ip + 4 * ub;
-  cl.row_enc = ip + 5 * ub; cl.row_pred = cl.row_enc + um;
-  int* pidx = cl.row_pred + um;
-  cl.n_active = pidx + up64((size_t)M * ncb); cl.steps = cl.n_active + 1;
-  cl.out_stat = cl.n_active + 2;
+  cl.h = w.h; cl.c = w.c; cl.pred_proj = w.pproj;
+  cl.last_tok = w.last_tok; cl.advance = w.advance; cl.done = w.done; cl.t = w.t; cl.cnt = w.cnt;
+  cl.row_enc = w.row_enc; cl.row_pred = w.row_pred;
+  cl.n_active = w.stat; cl.steps = w.stat + 1; cl.out_stat = w.stat + 2;
   cl.out_tok = S->out_tok.as<int>(); cl.ld_out = ld;
-
-  WN_TRY(S->stage.begin(2 * ((size_t)n * sizeof(int) + 64)));
-  WN_TRY(S->stage.put_at(S->desc.p, slot_ids, (size_t)n * sizeof(int), s));
-  WN_TRY(S->stage.put_at(S->desc.as<int>() + up64(S->n_slots), n_t_host, (size_t)n * sizeof(int), s));
-  WN_TRY(S->stage.end(s));
+  WN_TRY(rnnt_stage_call(S->stage, S->desc, S->n_slots, n, slot_ids, n_t_host, s));
 
   // ---- once per call: enc_proj = joint.enc_ffn(chunk), the sessions' state into the batch -------
-  if (longest > 0) {
-    // always the fp32 GEMMs, whatever the handle's operand precision
-    const int saved = t_gemm_prec;
-    t_gemm_prec = PREC_F32;
-    const int r = linear(W.j_enc, enc_out_dev, d, enc_proj, J, rows, s);
-    t_gemm_prec = saved;
-    WN_TRY(r);
-  }
+  if (longest > 0) WN_TRY(rnnt_prepare(m, enc_out_dev, rows, enc_proj, s));
   WN_TRY(rnnt_stream_begin(S->sl, cl, n, chunk, F, s));
 
-  // ---- the lock-step loop: groups of steps, n_active looked at one group late -----------------
+  // ---- the lock-step loop ---------------------------------------------------------------------
+  StatelessWindow sw;     // the tail of the session's own token row up to n_tok
+  sw.tokens = S->sl.tokens; sw.ld_tok = S->sl.max_tok; sw.tok_len = S->sl.n_tok;
+  sw.tok_row = cl.slot;
+  RnntJointArgs ja;
+  ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = cl.pred_proj; ja.ldp = J;
+  ja.row_enc = cl.row_enc; ja.row_pred = cl.row_pred;
+  ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
+  ja.part_max = w.pmax; ja.part_idx = w.pidx; ja.n_active = cl.n_active;
   const int64_t bound = longest > 0 ? (int64_t)longest * ((int64_t)n_steps + 1) + 1 : 0;
-  volatile int* pin = reinterpret_cast<volatile int*>(S->host.p);   // slots 0 / 1 (64 B apart)
-  int64_t issued = 0;
-  for (int g = 0; issued < bound; ++g) {
-    const int k = (int)std::min<int64_t>(RNNT_GROUP, bound - issued);
-    for (int i = 0; i < k; ++i) {
-      if (stateless) {    // the window: the tail of the session's own token row up to n_tok
-        StatelessWindow sw;
-        sw.tokens = S->sl.tokens; sw.ld_tok = S->sl.max_tok; sw.tok_len = S->sl.n_tok;
-        sw.tok_row = cl.slot;
-        WN_TRY(stateless_step(m, sw, cl.pred_proj, cl.advance, cl.n_active, n, s));
-      } else {
-        WN_TRY(predictor_step(W.pred_embed, E, cl.last_tok, E, W.pred_rnn.data(), L, W.pred_proj,
-                              cl.h, cl.c, gates, pout, cl.advance, cl.n_active, n, H, s));
-        RnntLinearArgs q;   // joint.pred_ffn
-        q.x1 = pout; q.ldx1 = P; q.K1 = P; q.W1 = W.j_pred.w; q.b1 = W.j_pred.b;
-        q.y = cl.pred_proj; q.ldy = J; q.N = J; q.B = n;
-        q.advance = cl.advance; q.n_active = cl.n_active;
-        WN_TRY(rnnt_linear(q, s));
-      }
-      RnntJointArgs ja;
-      ja.enc_proj = enc_proj; ja.lde = J; ja.pred_proj = cl.pred_proj; ja.ldp = J;
-      ja.row_enc = cl.row_enc; ja.row_pred = cl.row_pred;
-      ja.W = W.j_out.w; ja.bias = W.j_out.b; ja.M = M; ja.J = J; ja.V = V;
-      ja.part_max = pmax; ja.part_idx = pidx; ja.n_active = cl.n_active;
-      WN_TRY(rnnt_joint_argmax(ja, s));
-      WN_TRY(rnnt_stream_advance(pmax, pidx, ncb, V, S->sl, cl, n, chunk, F, blank, n_steps, s));
-    }
-    issued += k;
-    WN_HIP(hipMemcpyAsync(S->host.p + 64 * (g & 1), cl.n_active, sizeof(int),
-                          hipMemcpyDeviceToHost, s));
-    WN_HIP(hipEventRecord(S->ev[g & 1], s));
-    if (g >= 1) {
-      WN_HIP(hipEventSynchronize(S->ev[(g - 1) & 1]));
-      if (pin[16 * ((g - 1) & 1)] == 0) break;
-    }
-  }
+  WN_TRY(rnnt_poll_loop(bound, cl.n_active, S->host.p, S->ev, s, [&]() -> int {
+    WN_TRY(pred_proj_step(m, sw, cl.last_tok, cl.h, cl.c, w.gates, w.pout, cl.pred_proj,
+                          cl.advance, cl.n_active, n, s));
+    WN_TRY(rnnt_joint_argmax(ja, s));
+    return rnnt_stream_advance(w.pmax, w.pidx, ncb, V, S->sl, cl, n, chunk, F, blank, n_steps, s);
+  }));
   WN_TRY(rnnt_stream_end(S->sl, cl, n, s));
 
   // ---- results: the counters first, then the token / time rows that were filled ----------------
