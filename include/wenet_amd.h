@@ -697,6 +697,26 @@ int wn_op_firered_frontend(const float* feats, const float* mean, const float* i
                            float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,
                            const int32_t* out_off, int32_t* out_len, int32_t B, int32_t T,
                            int32_t F, int32_t C, void* stream);
+/* The middle of a Branchformer cgMLP (ConvolutionalSpatialGatingUnit, csrc/branchformer.hip),
+ * fp32, on packed rows: h [rows][ldh] holds r in columns [0, C) and the gate half in [C, 2 C);
+ *   y = (depthwise_conv_K(LayerNorm_C(gate half)) + bias) * r       (gate == 0: without "* r")
+ * with ln_w / ln_b [C] (eps 1e-5), wt [K][C] tap-major, bias [C], y [rows][ldy].  Utterance i is
+ * rows off[i] .. off[i] + len[i] - 1 (host [n_seq], ascending, disjoint); frames outside it are
+ * the conv's padding, never a neighbour's rows: K - 1 frames in front when causal, each entering
+ * the conv as ln_b (the reference pads in front of the norm), else (K - 1) / 2 zero frames on
+ * both sides.  C a multiple of 64 up to 1024; K in [1, 63], odd unless causal. */
+int wn_op_csgu_gate(const float* h, int32_t ldh, int32_t rows, int32_t C, const float* ln_w,
+                    const float* ln_b, const float* wt, const float* bias, int32_t K,
+                    int32_t causal, int32_t gate, float* y, int32_t ldy, const int32_t* off,
+                    const int32_t* len, int32_t n_seq, void* stream);
+/* The E-Branchformer merge in front of merge_proj: y = c + depthwise_conv_K(c) + bias over the C
+ * (= 2 d_model) channels of c [rows][ldc], zero padding (K - 1 in front when causal, else
+ * symmetric), the same packed layout; y must not alias c. */
+int wn_op_merge_dwconv(const float* c, int32_t ldc, int32_t rows, int32_t C, const float* wt,
+                       const float* bias, int32_t K, int32_t causal, float* y, int32_t ldy,
+                       const int32_t* off, const int32_t* len, int32_t n_seq, void* stream);
+/* Output frames one workgroup of those two kernels owns (lengths around it are the edge cases). */
+int32_t wn_csgu_time_tile(void);
 /* The Conformer front end alone -- GlobalCMVN + Conv2dSubsampling4 + the sqrt(d) scale, what
  * wn_encode runs in front of layer 0 (at position 0), under the handle's precision and tuning
  * set -- and copies of what it left, each optional (NULL), DEVICE arrays, complete on return:
@@ -933,6 +953,34 @@ typedef struct {
 int wn_model_create_firered(const wn_config* cfg, const wn_firered_config* fcfg,
                             const wn_tensor* weights, int32_t n_weights, int32_t device,
                             wn_model** out);
+
+/* Branchformer / E-Branchformer encoders (`encoder: branchformer` / `e_branchformer`,
+ * wenet/models/branchformer/, wenet/models/e_branchformer/) under the asr_model head: the
+ * Conformer front end and rel-pos attention, a convolutional gating MLP branch beside the
+ * attention branch, the two merged by merge_proj over their concatenation (E-Branchformer: a
+ * depthwise conv over the 2 d_model channels in front of it, and the macaron feed-forward
+ * pair).  A struct and an entry point of their own: wn_config and wn_model_create are unchanged.
+ * In wn_config, ffn_dim is the feed-forward width (kind 2; any multiple of 32 for kind 1) and
+ * cnn_kernel is not read (1). */
+typedef struct {
+  int32_t kind;               /* 1 branchformer (merge_method concat), 2 e_branchformer */
+  int32_t cgmlp_units;        /* cgmlp_linear_units U: U / 2 a multiple of 64 up to 1024 */
+  int32_t cgmlp_kernel;       /* cgmlp_conv_kernel: 1..63, odd unless cfg.causal */
+  int32_t merge_kernel;       /* merge_conv_kernel (kind 2): 1..63, odd unless cfg.causal */
+  int32_t linear_after_conv;  /* use_linear_after_conv */
+  int32_t head_dim;           /* d_model / n_heads: 64, or 32 (heads zero-padded to 64 columns) */
+} wn_branchformer_config;
+
+/* wn_model_create for such a state dict (the names init_model gives it; pooling_proj1/2 and
+ * weight_proj1/2 of a Branchformer layer are not read).  On the handle, wn_encode runs the layer
+ * stack in fp32 -- chunk / left set the attention mask only, as in the reference -- with every
+ * utterance encoded as the reference encodes it ALONE: the cgMLP and merge convs see an
+ * utterance's own frames, not the batch's padding or a neighbour.  The CTC, search, rescoring
+ * and alignment entry points and wn_model_clone then work unchanged; wn_encode_chunk*,
+ * wn_stream_create and a bf16 / fp8 precision are refused on such a handle. */
+int wn_model_create_branchformer(const wn_config* cfg, const wn_branchformer_config* bcfg,
+                                 const wn_tensor* weights, int32_t n_weights, int32_t device,
+                                 wn_model** out);
 
 /* Operator hook: one advance of a stateless predictor + joint.pred_ffn for M rows
  * (rnnt_stateless_step).  ctx_host (M, context) holds the window ids of every row, oldest first,

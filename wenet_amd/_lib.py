@@ -43,6 +43,13 @@ class WnFireRedConfig(Structure):
         ('attn_norm_eps', c_float)]
 
 
+class WnBranchformerConfig(Structure):
+    """wn_branchformer_config: what a Branchformer / E-Branchformer encoder has on top of
+    wn_config."""
+    _fields_ = [(n, c_int32) for n in ('kind', 'cgmlp_units', 'cgmlp_kernel', 'merge_kernel',
+                                       'linear_after_conv', 'head_dim')]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -123,6 +130,7 @@ EXPORTS = [
     'wn_op_gemm_rowln',
     'wn_model_create_transducer_stateless', 'wn_op_stateless_step',
     'wn_op_attention_relshift', 'wn_op_firered_frontend', 'wn_model_create_firered',
+    'wn_model_create_branchformer', 'wn_op_csgu_gate', 'wn_op_merge_dwconv', 'wn_csgu_time_tile',
 ]
 
 _lib = None
@@ -299,6 +307,13 @@ def lib():
                                            vp, vp, i32, pi32, pi32, i32, i32, f32, vp]
     L.wn_op_firered_frontend.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32,
                                          pi32, i32, i32, i32, i32, vp]
+    L.wn_model_create_branchformer.argtypes = [POINTER(WnConfig), POINTER(WnBranchformerConfig),
+                                               POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_csgu_gate.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, pi32,
+                                  pi32, i32, vp]
+    L.wn_op_merge_dwconv.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, pi32, pi32,
+                                     i32, vp]
+    L.wn_csgu_time_tile.argtypes = []
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

@@ -131,12 +131,14 @@ const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 // wn_model_create / wn_model_create_transducer (tcfg == nullptr: no predictor / joint) /
 // wn_model_create_transducer_stateless (scfg != nullptr: a stateless predictor, no LSTM) /
 // wn_model_create_firered (fcfg != nullptr, cabi_firered.hip: the FireRedASR-AED encoder)
+// wn_model_create_branchformer (bcfg != nullptr, cabi_branchformer.hip)
 }  // extern "C"
 
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                          const wn_stateless_predictor_config* scfg,
-                         const wn_firered_config* fcfg, const wn_tensor* weights,
-                         int32_t n_weights, int32_t device, wn_model** out) {
+                         const wn_firered_config* fcfg, const wn_branchformer_config* bcfg,
+                         const wn_tensor* weights, int32_t n_weights, int32_t device,
+                         wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   const bool fr = fcfg != nullptr;
@@ -156,7 +158,32 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
              "firered: the depthwise conv over 2 d_model channels has kernels for d_model 64, "
              "128, 256, 512 and 1280");
   }
-  WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && c.d_model / c.n_heads == 64,
+  const bool bf = bcfg != nullptr;
+  if (bf) {
+    const wn_branchformer_config& b = *bcfg;
+    WN_CHECK(!tcfg && !fr, "branchformer: an asr_model head only (no transducer on these encoders)");
+    WN_CHECK(b.kind == 1 || b.kind == 2, "branchformer: kind must be 1 (branchformer) or 2 "
+                                         "(e_branchformer)");
+    WN_CHECK(c.encoder_type == 0 && c.input_layer == 0,
+             "branchformer: the Conv2dSubsampling4 front end (encoder_type 0, input_layer 0)");
+    WN_CHECK(b.head_dim == 32 || b.head_dim == 64,
+             "branchformer: d_model / attention_heads must be 32 or 64 (other head widths have "
+             "no attention kernel)");
+    WN_CHECK(c.n_heads > 0 && c.n_heads < 256 && c.d_model == c.n_heads * b.head_dim,
+             "branchformer: d_model must be n_heads * head_dim");
+    WN_CHECK(b.cgmlp_units >= 128 && b.cgmlp_units % 128 == 0 &&
+                 b.cgmlp_units / 2 <= CSGU_MAX_C,
+             "branchformer: cgmlp_linear_units / 2 must be a multiple of 64 up to 1024 (csgu_gate)");
+    WN_CHECK(b.cgmlp_kernel >= 1 && b.cgmlp_kernel <= CSGU_MAX_K &&
+                 (c.causal || b.cgmlp_kernel % 2 == 1),
+             "branchformer: cgmlp_conv_kernel must be in [1, 63], odd unless causal");
+    WN_CHECK(b.kind == 1 || (b.merge_kernel >= 1 && b.merge_kernel <= CSGU_MAX_K &&
+                             (c.causal || b.merge_kernel % 2 == 1)),
+             "branchformer: merge_conv_kernel must be in [1, 63], odd unless causal");
+    WN_CHECK(b.linear_after_conv == 0 || b.linear_after_conv == 1,
+             "branchformer: linear_after_conv is 0 or 1");
+  }
+  WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
            "decoder head dim must be 64");
@@ -178,6 +205,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (tcfg) { m->tr.on = true; m->tr.c = *tcfg; }
   if (tcfg && scfg) m->tr.sp = *scfg;
   if (fr) { m->fr.on = true; m->fr.c = *fcfg; }
+  if (bf) { m->bf.on = true; m->bf.c = *bcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -423,7 +451,89 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
     WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d2, false));
   }
-  for (int i = 0; !tf && !fr && i < c.n_layers; ++i) {
+  for (int i = 0; bf && i < c.n_layers; ++i) {
+    // BranchformerEncoderLayer / EBranchformerEncoderLayer.  (pooling_proj1/2 and weight_proj1/2
+    // of a Branchformer layer serve merge_method learned_ave only: not read.)
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    const wn_branchformer_config& b = *bcfg;
+    const int H = c.n_heads, hd = b.head_dim, dq = H * 64, U = b.cgmlp_units, C = U / 2;
+    for (const char* n : {"norm_mha", "norm_mlp", "norm_final"})
+      WN_TRY(stage_norm(src, hs, p + "." + n, d));
+    if (b.kind == 2) {
+      WN_TRY(stage_norm(src, hs, p + ".norm_ff_macaron", d));
+      WN_TRY(stage_norm(src, hs, p + ".norm_ff", d));
+      for (const char* ff : {"feed_forward_macaron", "feed_forward"}) {
+        WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_1", F, d));
+        WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_2", d, F));
+      }
+    }
+    {  // Q | K | V, linear_pos and pos_bias_u / v as H heads of 64 columns: head h's hd rows,
+       // then 64 - hd zero rows (head_dim 32: every added product of the attention is an
+       // exact zero; head_dim 64: the reference's own layout)
+      std::vector<float> w((size_t)3 * dq * d, 0.f), bq((size_t)3 * dq, 0.f);
+      const char* parts[3] = {"linear_q", "linear_k", "linear_v"};
+      for (int j = 0; j < 3; ++j) {
+        WN_GET(pw, p + ".attn." + parts[j] + ".weight", (int64_t)d * d);
+        WN_GET(pb, p + ".attn." + parts[j] + ".bias", d);
+        for (int h = 0; h < H; ++h)
+          for (int r = 0; r < hd; ++r) {
+            memcpy(&w[((size_t)j * dq + h * 64 + r) * d], &pw[(size_t)(h * hd + r) * d],
+                   sizeof(float) * d);
+            bq[(size_t)j * dq + h * 64 + r] = pb[h * hd + r];
+          }
+      }
+      hs.add(p + ".qkv.weight", w.data(), w.size());
+      hs.add(p + ".qkv.bias", bq.data(), bq.size());
+      WN_GET(pp, p + ".attn.linear_pos.weight", (int64_t)d * d);
+      WN_GET(bu, p + ".attn.pos_bias_u", d);
+      WN_GET(bv, p + ".attn.pos_bias_v", d);
+      std::vector<float> wp((size_t)dq * d, 0.f), u(dq, 0.f), v(dq, 0.f);
+      for (int h = 0; h < H; ++h)
+        for (int r = 0; r < hd; ++r) {
+          memcpy(&wp[((size_t)h * 64 + r) * d], &pp[(size_t)(h * hd + r) * d], sizeof(float) * d);
+          u[h * 64 + r] = bu[h * hd + r];
+          v[h * 64 + r] = bv[h * hd + r];
+        }
+      hs.add(p + ".self_attn.linear_pos.weight", wp.data(), wp.size());
+      hs.add(p + ".pos_bias_u", u.data(), u.size());
+      hs.add(p + ".pos_bias_v", v.data(), v.size());
+      // linear_out [d][d] -> [d][dq]: zero columns under the padded context columns
+      WN_GET(po, p + ".attn.linear_out.weight", (int64_t)d * d);
+      WN_GET(pob, p + ".attn.linear_out.bias", d);
+      std::vector<float> wo((size_t)d * dq, 0.f);
+      for (int n = 0; n < d; ++n)
+        for (int h = 0; h < H; ++h)
+          memcpy(&wo[(size_t)n * dq + h * 64], &po[(size_t)n * d + h * hd], sizeof(float) * hd);
+      hs.add(p + ".self_attn.linear_out.weight", wo.data(), wo.size());
+      hs.add(p + ".self_attn.linear_out.bias", pob, d);
+    }
+    WN_TRY(stage_linear(src, hs, p + ".cgmlp.channel_proj1.0", U, d));
+    WN_TRY(stage_norm(src, hs, p + ".cgmlp.csgu.norm", C));
+    {  // depthwise (C,1,K) -> [K][C]
+      const int Kc = b.cgmlp_kernel;
+      WN_GET(wd, p + ".cgmlp.csgu.conv.weight", (int64_t)C * Kc);
+      WN_GET(bd, p + ".cgmlp.csgu.conv.bias", C);
+      std::vector<float> w((size_t)Kc * C);
+      for (int ch = 0; ch < C; ++ch)
+        for (int k = 0; k < Kc; ++k) w[(size_t)k * C + ch] = wd[(size_t)ch * Kc + k];
+      hs.add(p + ".csgu.dw.weight", w.data(), w.size());
+      hs.add(p + ".csgu.dw.bias", bd, C);
+    }
+    if (b.linear_after_conv) WN_TRY(stage_linear(src, hs, p + ".cgmlp.csgu.linear", C, C));
+    WN_TRY(stage_linear(src, hs, p + ".cgmlp.channel_proj2", d, C));
+    if (b.kind == 2) {  // depthwise_conv_fusion (2d,1,Km) -> [Km][2d]
+      const int Km = b.merge_kernel, d2 = 2 * d;
+      WN_GET(wd, p + ".depthwise_conv_fusion.weight", (int64_t)d2 * Km);
+      WN_GET(bd, p + ".depthwise_conv_fusion.bias", d2);
+      std::vector<float> w((size_t)Km * d2);
+      for (int ch = 0; ch < d2; ++ch)
+        for (int k = 0; k < Km; ++k) w[(size_t)k * d2 + ch] = wd[(size_t)ch * Km + k];
+      hs.add(p + ".merge.dw.weight", w.data(), w.size());
+      hs.add(p + ".merge.dw.bias", bd, d2);
+    }
+    WN_TRY(stage_linear(src, hs, p + ".merge_proj", d, 2 * d));
+  }
+  for (int i = 0; !tf && !fr && !bf && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -658,11 +768,51 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
       Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = d; lp.in = d;
       WN_TRY(linear(lp, P("fr.rel_pe"), d, L.pos_tab, d, rows, 0));
     }
+  } else if (bf) {
+    const wn_branchformer_config& b = *bcfg;
+    const int dq = c.n_heads * 64, U = b.cgmlp_units, C = U / 2;
+    W.layers.resize(c.n_layers);
+    WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * dq * sizeof(float)));
+    for (int i = 0; i < c.n_layers; ++i) {
+      const std::string p = "encoder.encoders." + std::to_string(i);
+      EncLayer& L = W.layers[i];
+      L.norm_mha = NORM(p + ".norm_mha");
+      L.norm_mlp = NORM(p + ".norm_mlp");
+      L.norm_final = NORM(p + ".norm_final");
+      if (b.kind == 2) {
+        L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
+        L.norm_ff = NORM(p + ".norm_ff");
+        L.ffm1 = LIN(p + ".feed_forward_macaron.w_1", F, d);
+        L.ffm2 = LIN(p + ".feed_forward_macaron.w_2", d, F);
+        L.ff1 = LIN(p + ".feed_forward.w_1", F, d);
+        L.ff2 = LIN(p + ".feed_forward.w_2", d, F);
+      }
+      L.qkv = LIN(p + ".qkv", 3 * dq, d);
+      L.out = LIN(p + ".self_attn.linear_out", d, dq);
+      L.bias_u = P(p + ".pos_bias_u");
+      L.bias_v = P(p + ".pos_bias_v");
+      L.pos_w = P(p + ".self_attn.linear_pos.weight");
+      L.proj1 = LIN(p + ".cgmlp.channel_proj1.0", U, d);
+      L.csgu_norm = NORM(p + ".cgmlp.csgu.norm");
+      L.csgu_wt = P(p + ".csgu.dw.weight");
+      L.csgu_b = P(p + ".csgu.dw.bias");
+      if (b.linear_after_conv) L.csgu_lin = LIN(p + ".cgmlp.csgu.linear", C, C);
+      L.proj2 = LIN(p + ".cgmlp.channel_proj2", d, C);
+      if (b.kind == 2) {
+        L.merge_wt = P(p + ".merge.dw.weight");
+        L.merge_b = P(p + ".merge.dw.bias");
+      }
+      L.merge_proj = LIN(p + ".merge_proj", d, 2 * d);
+      // p = linear_pos(pos_emb) depends on weights only: [max_pos][H x 64] per layer
+      L.pos_tab = W.pos_tabs.as<float>() + (size_t)i * c.max_pos * dq;
+      Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = dq; lp.in = d;
+      WN_TRY(linear(lp, W.pe, d, L.pos_tab, dq, c.max_pos, 0));
+    }
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && !fr && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && !bf && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -745,9 +895,9 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.j_pred = LIN("joint.pred_ffn", tc.join_dim, tc.pred_out);
     W.j_out = LIN("joint.ffn_out", V, tc.join_dim);
   }
-  // (firered: the plain fp32 path, no six-product / row-block images of its encoder's weights;
-  // the decoders and the CTC head get theirs as in every other model)
-  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr));
+  // (firered, branchformer: the plain fp32 path, no six-product / row-block images of the
+  // encoder's weights; the decoders and the CTC head get theirs as in every other model)
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -757,14 +907,14 @@ extern "C" {
 
 int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
                     int32_t n_weights, int32_t device, wn_model** out) {
-  return create_model_impl(cfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out) {
   WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
-  return create_model_impl(cfg, tcfg, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -772,7 +922,7 @@ int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transduc
                                          const wn_tensor* weights, int32_t n_weights,
                                          int32_t device, wn_model** out) {
   WN_CHECK(tcfg && scfg, "wn_model_create_transducer_stateless: null argument");
-  return create_model_impl(cfg, tcfg, scfg, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, scfg, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -785,6 +935,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->cfg = src->cfg;
   m->tr.on = src->tr.on; m->tr.c = src->tr.c; m->tr.sp = src->tr.sp;
   m->fr.on = src->fr.on; m->fr.c = src->fr.c;
+  m->bf.on = src->bf.on; m->bf.c = src->bf.c;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;
@@ -802,6 +953,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(!m->fr.on || precision == PREC_F32,
            "wn_model_set_precision: a FireRed handle stays fp32 (no bf16 / fp8 kernels for its "
            "encoder)");
+  WN_CHECK(!m->bf.on || precision == PREC_F32,
+           "wn_model_set_precision: a Branchformer handle stays fp32 (no bf16 / fp8 kernels for "
+           "its encoder)");
   const ModelData& W = *m->data;
   // the images belong to the model block: whichever handle asks first builds them, every
   // clone (made before or after) reads the same ones

@@ -598,6 +598,57 @@ int wn_op_firered_frontend(const float* feats, const float* mean, const float* i
   return firered_frontend(a, s);
 }
 
+// the descriptors both Branchformer hooks share: off | len on the device, the longest length
+static int dwt_hook_layout(const int32_t* off, const int32_t* len, int n_seq, int rows,
+                           DevBuf& desc, DwTileArgs* a, hipStream_t s, const char* who) {
+  const std::string w(who);
+  WN_CHECK(off && len && n_seq > 0 && n_seq < 65536 && rows > 0, w + ": n_seq / rows");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           w + ": rows outside the buffer, unordered or overlapping");
+  std::vector<int> h((size_t)2 * n_seq);
+  int max_len = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  WN_CHECK(max_len > 0, w + ": empty");
+  WN_TRY(upload_ints(desc, h, s));
+  a->off = desc.as<int>(); a->len = a->off + n_seq; a->B = n_seq; a->max_len = max_len;
+  return 0;
+}
+
+int wn_op_csgu_gate(const float* h, int32_t ldh, int32_t rows, int32_t C, const float* ln_w,
+                    const float* ln_b, const float* wt, const float* bias, int32_t K,
+                    int32_t causal, int32_t gate, float* y, int32_t ldy, const int32_t* off,
+                    const int32_t* len, int32_t n_seq, void* stream) {
+  WN_CHECK(h && ln_w && ln_b && wt && bias && y, "csgu_gate: null argument");
+  WN_CHECK(C > 0 && C <= CSGU_MAX_C && ldh >= 2 * C && ldy >= C, "csgu_gate: C / strides");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc, stats;
+  DwTileArgs a;
+  WN_TRY(dwt_hook_layout(off, len, n_seq, rows, desc, &a, s, "csgu_gate"));
+  WN_TRY(stats.ensure((size_t)rows * sizeof(float2)));
+  a.x = h + C; a.ldx = ldh; a.wt = wt; a.bias = bias; a.y = y; a.ldy = ldy;
+  a.C = C; a.K = K; a.causal = causal != 0;
+  a.ln_w = ln_w; a.ln_b = ln_b; a.stats = stats.as<float2>(); a.M = rows; a.eps = 1e-5f;
+  if (gate) { a.r = h; a.ldr = ldh; }
+  return csgu_gate(a, s);
+}
+
+int wn_op_merge_dwconv(const float* c, int32_t ldc, int32_t rows, int32_t C, const float* wt,
+                       const float* bias, int32_t K, int32_t causal, float* y, int32_t ldy,
+                       const int32_t* off, const int32_t* len, int32_t n_seq, void* stream) {
+  WN_CHECK(c && wt && bias && y, "merge_dwconv: null argument");
+  WN_CHECK(C > 0 && ldc >= C && ldy >= C, "merge_dwconv: C / strides");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  DwTileArgs a;
+  WN_TRY(dwt_hook_layout(off, len, n_seq, rows, desc, &a, s, "merge_dwconv"));
+  a.x = c; a.ldx = ldc; a.wt = wt; a.bias = bias; a.y = y; a.ldy = ldy;
+  a.C = C; a.K = K; a.causal = causal != 0;
+  return merge_dwconv(a, s);
+}
+
 int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
                   int32_t T, float* c1, float* c2, float* x, int32_t* enc_lens_host,
                   int32_t* route_out, void* stream) {

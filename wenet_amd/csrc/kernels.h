@@ -177,6 +177,36 @@ struct FireRedFrontArgs {
 };
 int firered_frontend(const FireRedFrontArgs& a, hipStream_t s);
 
+// Branchformer / E-Branchformer (branchformer.hip): a depthwise conv over time, tiled so that a
+// workgroup stages CSGU_TILE + K - 1 frames x 64 channels of ONE utterance once, fp32.  Frames
+// outside the utterance's own [0, len) are the conv's padding (K - 1 in front when causal,
+// (K - 1) / 2 on both sides otherwise); no row of a neighbour in the packed buffer is read.
+constexpr int CSGU_TILE = 32;      // output frames per workgroup
+constexpr int CSGU_MAX_K = 63;
+constexpr int CSGU_MAX_C = 1024;   // gate channels the LayerNorm pre-pass holds in registers
+struct DwTileArgs {
+  const float* x; int ldx;        // [rows][ldx]: the C conv channels start at x
+  const float* wt;                // [K][C] tap-major
+  const float* bias;              // [C]
+  float* y; int ldy;              // [rows][ldy]
+  const int* off; const int* len; // [B] first row / frames of every utterance
+  int B, C, K, causal, max_len;   // max_len: frames of the longest utterance
+  // csgu_gate only: LayerNorm over the C channels in front of the conv (stats: scratch, one
+  // (mean, rstd) per row, M rows); a padded frame is ln_b when causal (the reference pads in
+  // front of the norm) and 0 otherwise; r (or null: the conv alone) multiplies the result
+  const float* ln_w = nullptr; const float* ln_b = nullptr;
+  float2* stats = nullptr; int M = 0; float eps = 1e-5f;
+  const float* r = nullptr; int ldr = 0;
+};
+// y = (conv(LayerNorm(x)) + bias) [* r]: the ConvolutionalSpatialGatingUnit between the two
+// projections of a cgMLP; C a multiple of 64 up to CSGU_MAX_C.
+int csgu_gate(const DwTileArgs& a, hipStream_t s);
+// y = x + conv(x) + bias with zero padding: the E-Branchformer merge in front of merge_proj.
+int merge_dwconv(const DwTileArgs& a, hipStream_t s);
+// y = r * g over [M][C] (use_linear_after_conv: the gate behind the extra Linear)
+int csgu_mul(const float* r, int ldr, const float* g, int ldg, float* y, int ldy, int M, int C,
+             hipStream_t s);
+
 // Fused feed-forward module, fp32 (ffn_fused.hip): P[s] (S, M, D) = partial
 // act(X W1^T + b1) W2^T over hidden slice s; ffn_reduce_ln then forms
 // x += alpha (sum_s P[s] + b2) and the following LayerNorm(s).

@@ -157,6 +157,15 @@ struct EncLayer {
   const float* dw_wt = nullptr;   // [K][d]
   const float* dw_b = nullptr;
   const float* cpad = nullptr;    // [d]
+  // Branchformer / E-Branchformer layers (wn_model::bf.on, cabi_branchformer.hip): the cgMLP
+  // branch and the merge; qkv / out / pos_tab / bias_u / bias_v then have the head layout of
+  // bf.c.head_dim (32: heads zero-padded to 64 columns)
+  Norm norm_mlp, csgu_norm;
+  Linear proj1, proj2, csgu_lin, merge_proj;
+  const float* csgu_wt = nullptr;   // [K][U/2]
+  const float* csgu_b = nullptr;
+  const float* merge_wt = nullptr;  // [merge_kernel][2d]
+  const float* merge_b = nullptr;
 };
 
 struct TfLayer {  // TransformerEncoderLayer (encoder_layer.py:28-127)
@@ -272,6 +281,12 @@ struct wn_model {
     bool on = false;
     wn_firered_config c = {};
   } fr;
+  // wn_model_create_branchformer: a Branchformer (kind 1) / E-Branchformer (kind 2) encoder
+  // (cabi_branchformer.hip) behind the Conformer front end
+  struct {
+    bool on = false;
+    wn_branchformer_config c = {};
+  } bf;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
@@ -286,6 +301,7 @@ struct wn_model {
   std::vector<int> off, len;            // per utterance (rows layout)
   DevBuf d_off, d_len, d_row_utt, d_off1, d_len1, d_a_row_off;
   DevBuf c1, c2, x, t1, t2, hbuf, qkv, enc;
+  DevBuf bf_cat, bf_mrg, bf_gate, bf_stats;   // Branchformer: [x1 | x2], its merge, the gated half
   DevBuf ffn_part;                      // hidden-slice partials of the fused FFN
   DevBuf attn_kbias;                    // per-key score term of the folded rel-pos attention
   DevBuf xpad, pos_rows, d_row_t, d_zero_rows;
@@ -525,10 +541,15 @@ int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
 // (cabi_firered.hip)
 int encode_firered(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
                    float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
+// (cabi_branchformer.hip)
+int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                        int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
+                        hipStream_t s);
 // (cabi_model.hip: what every wn_model_create* entry point runs)
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,
-                      const wn_tensor* weights, int32_t n_weights, int32_t device, wn_model** out);
+                      const wn_branchformer_config* bcfg, const wn_tensor* weights,
+                      int32_t n_weights, int32_t device, wn_model** out);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

@@ -43,6 +43,10 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         raise NotImplementedError(
             f'model {model_type!r} is outside the accelerated path (asr_model family)')
     enc_type = configs.get('encoder', 'conformer')
+    if enc_type in ('branchformer', 'e_branchformer'):
+        # (wenet_amd/branchformer.py: the encoder's own keys go into a wn_branchformer_config)
+        from wenet_amd.branchformer import branchformer_config_from_yaml
+        return branchformer_config_from_yaml(configs)[0]
     if enc_type == 'conformer':
         checks = dict(input_layer='conv2d', pos_enc_layer_type='rel_pos',
                       selfattention_layer_type='rel_selfattn',
@@ -301,6 +305,10 @@ class ASRModel:
 
     def _config(self, configs: dict) -> _lib.WnConfig:
         """The wn_config of this model class (subclasses: wenet_amd/transducer.py)."""
+        if configs.get('encoder') in ('branchformer', 'e_branchformer'):
+            raise NotImplementedError(
+                f"encoder {configs['encoder']!r} is outside the accelerated path of this class: "
+                'wenet_amd.Branchformer (load_model picks it)')
         return config_from_yaml(configs)
 
     def _create(self, L, tensors, n: int, h) -> int:
@@ -1166,6 +1174,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     if configs.get('model') == 'transducer':   # init_model.py:137-154
         from wenet_amd.transducer import Transducer
         model = Transducer(configs, sd, device)
+    elif configs.get('encoder') in ('branchformer', 'e_branchformer'):
+        from wenet_amd.branchformer import Branchformer
+        model = Branchformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

@@ -452,6 +452,64 @@ CONFIGS['firered_aed_l'] = _firered(1280, 20, 5120, 16, 16, 7832)
 CONFIGS['firered_aed_l_1blk'] = _firered(1280, 20, 5120, 1, 1, 41)
 
 
+# Branchformer / E-Branchformer under the asr_model head
+# (examples/aishell/s0/conf/train_ebranchformer.yaml, train_u2++_branchformer.yaml)
+def _ebranchformer(d, heads, ffn, units, k, merge_k, blocks, dec_heads, dec_ffn, dec_blocks,
+                   vocab) -> dict:
+    return {
+        'input_dim': 80, 'output_dim': vocab,
+        'encoder': 'e_branchformer',
+        'encoder_conf': dict(output_size=d, attention_heads=heads, linear_units=ffn,
+                             num_blocks=blocks, cgmlp_linear_units=units, cgmlp_conv_kernel=k,
+                             use_linear_after_conv=False, gate_activation='identity',
+                             merge_conv_kernel=merge_k, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, attention_dropout_rate=0.1,
+                             input_layer='conv2d', activation_type='swish', causal=False,
+                             pos_enc_layer_type='rel_pos',
+                             selfattention_layer_type='rel_selfattn'),
+        'decoder': 'transformer',
+        'decoder_conf': dict(attention_heads=dec_heads, linear_units=dec_ffn,
+                             num_blocks=dec_blocks, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, self_attention_dropout_rate=0.1,
+                             src_attention_dropout_rate=0.1),
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False),
+    }
+
+
+def _branchformer(d, heads, units, k, blocks, dec_heads, dec_ffn, dec_blocks, vocab) -> dict:
+    return {
+        'input_dim': 80, 'output_dim': vocab,
+        'encoder': 'branchformer',
+        'encoder_conf': dict(output_size=d, use_attn=True, attention_heads=heads,
+                             selfattention_layer_type='rel_selfattn',
+                             pos_enc_layer_type='rel_pos', use_cgmlp=True,
+                             cgmlp_linear_units=units, cgmlp_conv_kernel=k,
+                             use_linear_after_conv=False, gate_activation='identity',
+                             merge_method='concat', cgmlp_weight=0.5,
+                             attn_branch_drop_rate=0.0, num_blocks=blocks, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, attention_dropout_rate=0.1,
+                             input_layer='conv2d', stochastic_depth_rate=0.0, causal=True,
+                             use_dynamic_chunk=True, use_dynamic_left_chunk=False),
+        'decoder': 'bitransformer',
+        'decoder_conf': dict(attention_heads=dec_heads, linear_units=dec_ffn,
+                             num_blocks=dec_blocks, r_num_blocks=dec_blocks, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, self_attention_dropout_rate=0.1,
+                             src_attention_dropout_rate=0.1),
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False,
+                           reverse_weight=0.3),
+    }
+
+
+# d 64 with 2 heads: d_k = 32, the zero-padded head layout; non-causal, both convs 31 taps
+CONFIGS['tiny_ebranchformer'] = _ebranchformer(64, 2, 128, 256, 31, 31, 2, 1, 96, 1, 41)
+# d_k = 64, causal cgMLP (the pad frame is csgu.norm.bias), chunk masks
+CONFIGS['tiny_branchformer'] = _branchformer(128, 2, 256, 15, 2, 2, 96, 1, 41)
+# the shipped recipes' widths: tools/bench_branchformer.py only
+CONFIGS['aishell_ebranchformer'] = _ebranchformer(256, 8, 1024, 1024, 31, 31, 17, 4, 2048, 6,
+                                                  4233)
+CONFIGS['aishell_u2pp_branchformer'] = _branchformer(256, 4, 2048, 63, 24, 4, 2048, 3, 4233)
+
+
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
     c = copy.deepcopy(CONFIGS[name])
@@ -556,6 +614,46 @@ def _add_transducer(sd, configs: dict, seed: int, blank_bias: float):
     sd['joint.ffn_out.bias'][blank] += np.float32(blank_bias)
 
 
+def _add_branch_layer(sd, p, configs, seed, lin, norm):
+    """What a BranchformerEncoderLayer / EBranchformerEncoderLayer holds beside its attention
+    (wenet/models/branchformer/encoder_layer.py:66-110, e_branchformer/encoder_layer.py:58-91).
+    Not the ESPnet initialisation of the reference (conv weight 1e-6, bias 1), under which a
+    dropped tap or a wrong pad value is invisible: conv taps of order 1 / sqrt(K), the gate
+    norm's bias of order 0.3."""
+    ec = configs['encoder_conf']
+    d, U = ec['output_size'], ec['cgmlp_linear_units']
+    C, K = U // 2, ec['cgmlp_conv_kernel']
+    ebf = configs['encoder'] == 'e_branchformer'
+    lin(p + '.cgmlp.channel_proj1.0', U, d)
+    sd[p + '.cgmlp.csgu.norm.weight'] = _normal(seed, p + '.csgu.norm.w', (C, ), 0.1, 1.0)
+    sd[p + '.cgmlp.csgu.norm.bias'] = _normal(seed, p + '.csgu.norm.b', (C, ), 0.3)
+    b = 1.0 / math.sqrt(K)
+    sd[p + '.cgmlp.csgu.conv.weight'] = _uniform(seed, p + '.csgu.conv.w', (C, 1, K), b)
+    sd[p + '.cgmlp.csgu.conv.bias'] = _uniform(seed, p + '.csgu.conv.b', (C, ), b)
+    if ec.get('use_linear_after_conv', False):
+        lin(p + '.cgmlp.csgu.linear', C, C)
+    lin(p + '.cgmlp.channel_proj2', d, C)
+    for n in ('norm_mha', 'norm_mlp', 'norm_final'):
+        norm(f'{p}.{n}', d)
+    lin(p + '.merge_proj', d, 2 * d)
+    if ebf:
+        Km = ec.get('merge_conv_kernel', 3)
+        b = 1.0 / math.sqrt(Km)
+        sd[p + '.depthwise_conv_fusion.weight'] = _uniform(seed, p + '.fusion.w',
+                                                           (2 * d, 1, Km), b)
+        sd[p + '.depthwise_conv_fusion.bias'] = _uniform(seed, p + '.fusion.b', (2 * d, ), b)
+        ffn = ec['linear_units']
+        for ff in ('feed_forward', 'feed_forward_macaron'):
+            lin(f'{p}.{ff}.w_1', ffn, d)
+            lin(f'{p}.{ff}.w_2', d, ffn)
+        norm(p + '.norm_ff', d)
+        norm(p + '.norm_ff_macaron', d)
+    else:
+        # (read by merge_method learned_ave only)
+        for n in ('pooling_proj1', 'pooling_proj2', 'weight_proj1', 'weight_proj2'):
+            lin(f'{p}.{n}', 1, d)
+
+
 def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
                     rnnt_blank_bias: float = RNNT_BLANK_BIAS
                     ) -> "OrderedDict[str, torch.Tensor]":
@@ -564,8 +662,9 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
     ec, dc = configs['encoder_conf'], configs['decoder_conf']
     d = ec['output_size']
     h = ec['attention_heads']
-    ffn = ec['linear_units']
+    ffn = ec.get('linear_units', 2048)
     K = ec.get('cnn_module_kernel', 15)
+    branch = configs.get('encoder') in ('branchformer', 'e_branchformer')
     if configs.get('encoder', 'conformer') == 'transformer':
         return _make_transformer_state_dict(configs, seed, sharpen_ctc)
     if configs.get('encoder') == 'firered_conformer':
@@ -613,6 +712,10 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
     norm('encoder.after_norm', d)
     for i in range(ec['num_blocks']):
         p = f'encoder.encoders.{i}'
+        if branch:   # (the layer classes call their attention `attn`)
+            attn(p + '.attn', d, rel=True)
+            _add_branch_layer(sd, p, configs, seed, lin, norm)
+            continue
         attn(p + '.self_attn', d, rel=True)
         for ff in ('feed_forward', 'feed_forward_macaron'):
             lin(f'{p}.{ff}.w_1', ffn, d)

@@ -70,7 +70,7 @@ def transducer_config_from_yaml(configs: dict):
     as_asr = copy.copy(configs)
     as_asr['model'] = 'asr_model'
     c = config_from_yaml(as_asr)
-    if c.encoder_type != 0:
+    if c.encoder_type != 0 or configs.get('encoder', 'conformer') != 'conformer':
         _refuse('encoder', configs.get('encoder'), 'conformer')
     if jc.get('enc_output_size', c.d_model) != c.d_model:
         _refuse('joint_conf.enc_output_size', jc.get('enc_output_size'), c.d_model)
@@ -139,7 +139,7 @@ def stateless_transducer_config_from_yaml(configs: dict):
     as_asr = copy.copy(configs)
     as_asr['model'] = 'asr_model'
     c = config_from_yaml(as_asr)
-    if c.encoder_type != 0:
+    if c.encoder_type != 0 or configs.get('encoder', 'conformer') != 'conformer':
         _refuse('encoder', configs.get('encoder'), 'conformer')
     if jc.get('enc_output_size', c.d_model) != c.d_model:
         _refuse('joint_conf.enc_output_size', jc.get('enc_output_size'), c.d_model)
