@@ -717,6 +717,53 @@ int wn_op_merge_dwconv(const float* c, int32_t ldc, int32_t rows, int32_t C, con
                        const int32_t* off, const int32_t* len, int32_t n_seq, void* stream);
 /* Output frames one workgroup of those two kernels owns (lengths around it are the edge cases). */
 int32_t wn_csgu_time_tile(void);
+
+/* ---- Paraformer kernels (wenet/models/paraformer/; csrc/attention_d128.hip, paraformer.hip),
+ * fp32, test hooks.  Offsets and lengths are HOST arrays (ascending, disjoint), everything else a
+ * device pointer unless it is named *_host; every argument is checked before the first launch. */
+/* Attention for heads of d_k = 128 (n_heads * 128 columns per row), full context, no position
+ * term: O = softmax((Q K^T) * scale) V per (sequence, head).  Q / O and K / V have separate
+ * layouts: self attention passes the same offsets twice, the decoder's cross attention passes
+ * tokens and frames.  d_k = 64 stays with wn_op_attention. */
+int wn_op_attention_d128(const float* Q, const float* K, const float* V, int32_t ldq,
+                         int32_t ldk, int32_t ldv, int32_t q_rows, int32_t kv_rows, float* O,
+                         int32_t ldo, const int32_t* q_off, const int32_t* q_len,
+                         const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
+                         int32_t n_heads, float scale, void* stream);
+/* The LFR front end of every utterance ALONE (paraformer/layers.py:24-92): utterance b of
+ * lens[b] frames gives out_len[b] = ceil(lens[b] / n) rows from row out_off[b]; row t stacks the
+ * m frames n t - (m - 1) / 2 + f (each index clamped to [0, lens[b] - 1]), then GlobalCMVN over
+ * the m F columns (mean NULL: none), x * xscale + pe[t + 1] (pe [pe_rows][m F]) and
+ * LayerNorm(m F; ln_w, ln_b, eps).  Rows are ldo wide, m F <= ldo <= 576, zeros behind m F. */
+int wn_op_lfr_front(const float* feats, const float* mean, const float* istd, const float* pe,
+                    int32_t pe_rows, const float* ln_w, const float* ln_b, float* out,
+                    int32_t ldo, int32_t out_rows, const int32_t* lens, const int32_t* out_off,
+                    int32_t* out_len, int32_t B, int32_t T, int32_t F, int32_t m, int32_t n,
+                    float xscale, float eps, void* stream);
+/* LayerNorm over D <= 2048 columns (a multiple of 4; the statistics divide by D) of x [M][ldx];
+ * columns D .. Dpad - 1 of y [M][ldy] are written as zeros. */
+int wn_op_layernorm_wide(const float* x, int32_t ldx, const float* w, const float* b, float* y,
+                         int32_t ldy, int32_t M, int32_t D, int32_t Dpad, float eps,
+                         void* stream);
+/* The CIF weights (paraformer/cif.py:64-78, cnn_groups 1, residual false) on packed rows h
+ * [rows][ldh]: alpha[r] = relu(sigmoid(out_w . relu(conv1d_3(h)_r + conv_b) + out_b) * smooth -
+ * noise) for every owned row, the conv's zero padding at each utterance's OWN ends.  conv_w is
+ * [d][3 d] with column tap * d + c_in (tap 0 = the frame before); d a multiple of 32. */
+int wn_op_cif_alpha(const float* h, int32_t ldh, int32_t rows, int32_t d, const float* conv_w,
+                    const float* conv_b, const float* out_w, const float* out_b, float smooth,
+                    float noise, float* alpha, const int32_t* off, const int32_t* len,
+                    int32_t n_seq, void* stream);
+/* The integrate-and-fire scan (paraformer/cif.py:110-142, 250-293) over len[i] + 1 frames of
+ * utterance i: its alphas (device, [rows], each in [0, 1]: checked), then the tail frame (alpha =
+ * tail, a zero hidden row).  threshold must be 1.0.  Embedding k of utterance i goes to emb row
+ * emb_off[i] + k (k < emb_cap[i]) and its frame to fire_t_host[emb_off[i] + k]; n_fire_host[i]
+ * counts the fires, token_num_host[i] = floor(sum of the alphas); rows n_fire .. token_num - 1 are
+ * zeros with frame -1.  Entries of fire_t_host no embedding owns are -1. */
+int wn_op_cif_fire(const float* h, int32_t ldh, int32_t rows, int32_t d, const float* alpha,
+                   const int32_t* off, const int32_t* len, int32_t n_seq, float threshold,
+                   float tail, float* emb, int32_t lde, int32_t emb_rows, const int32_t* emb_off,
+                   const int32_t* emb_cap, int32_t* fire_t_host, int32_t* n_fire_host,
+                   int32_t* token_num_host, void* stream);
 /* The Conformer front end alone -- GlobalCMVN + Conv2dSubsampling4 + the sqrt(d) scale, what
  * wn_encode runs in front of layer 0 (at position 0), under the handle's precision and tuning
  * set -- and copies of what it left, each optional (NULL), DEVICE arrays, complete on return:
@@ -981,6 +1028,39 @@ typedef struct {
 int wn_model_create_branchformer(const wn_config* cfg, const wn_branchformer_config* bcfg,
                                  const wn_tensor* weights, int32_t n_weights, int32_t device,
                                  wn_model** out);
+
+/* ---- Paraformer (`model: paraformer`, wenet/models/paraformer/): SANM encoder behind the LFR
+ * front end, CIF predictor, SANM decoder; fp32.  Of wn_config it reads feat_dim (80), d_model,
+ * n_heads (d_model / n_heads in {64, 128}), ffn_dim, n_layers (encoder blocks, encoders0
+ * included), vocab, has_cmvn (over lfr_m * feat_dim columns), dec_heads, dec_ffn_dim, norm_eps. */
+typedef struct {
+  int32_t lfr_m, lfr_n;        /* 7, 6 */
+  int32_t kernel_size;         /* FSMN taps of encoder and decoder, odd (11) */
+  int32_t dec_blocks;          /* decoder_conf.num_blocks == att_layer_num */
+  int32_t max_frames;          /* encoder frames (LFR rows) a handle's position table covers */
+  float threshold;             /* predictor_conf.threshold: must be 1.0 */
+  float tail_threshold;        /* 0.45; in (0, 1) */
+  float smooth_factor;         /* 1.0; in (0, 1] */
+  float noise_threshold;       /* 0.0; >= 0 */
+} wn_paraformer_config;
+/* State dict names as init_model gives them; encoder.embed.pos_enc.pe is rebuilt here and the
+ * timestamp branch (predictor.tp_*), `embed.weight` and the loss modules are accepted and not
+ * read.  A CTC head (ctc.ctc_lo.*) is optional.  wn_encode on the handle runs the front end and
+ * the encoder with every utterance encoded as the reference encodes it ALONE (T' = ceil(n / 6)
+ * frames); wn_ctc_* and wn_ctc_force_align then work as on any handle.  No chunks, no streams,
+ * no bf16 / fp8. */
+int wn_model_create_paraformer(const wn_config* cfg, const wn_paraformer_config* pcfg,
+                               const wn_tensor* weights, int32_t n_weights, int32_t device,
+                               wn_model** out);
+/* Predictor + decoder on the handle's CURRENT batch (the last wn_encode): HOST arrays tokens /
+ * logp (B, max_tok), tok_lens (B).  tok_lens[b] = token_num = floor(sum alpha) of utterance b
+ * (0: no token, nothing else written for it); tokens[b][i] = the arg-max of decoder row i, logp
+ * its log-probability.  Optional (NULL): fire_frames (B, max_tok) the encoder frame every
+ * embedding fired on (the tail frame is frame T'), n_fire (B).  max_tok (>= 1) is the row pitch
+ * of these arrays and must hold the largest tok_lens: T' + 1 of the longest utterance always
+ * suffices. */
+int wn_paraformer_decode(wn_model* m, int32_t* tokens, int32_t* tok_lens, float* logp,
+                         int32_t* fire_frames, int32_t* n_fire, int32_t max_tok, void* stream);
 
 /* Operator hook: one advance of a stateless predictor + joint.pred_ffn for M rows
  * (rnnt_stateless_step).  ctx_host (M, context) holds the window ids of every row, oldest first,

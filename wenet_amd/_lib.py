@@ -50,6 +50,14 @@ class WnBranchformerConfig(Structure):
                                        'linear_after_conv', 'head_dim')]
 
 
+class WnParaformerConfig(Structure):
+    """wn_paraformer_config: what a Paraformer has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('lfr_m', 'lfr_n', 'kernel_size', 'dec_blocks',
+                                       'max_frames')] + [
+        (n, c_float) for n in ('threshold', 'tail_threshold', 'smooth_factor',
+                               'noise_threshold')]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -131,6 +139,8 @@ EXPORTS = [
     'wn_model_create_transducer_stateless', 'wn_op_stateless_step',
     'wn_op_attention_relshift', 'wn_op_firered_frontend', 'wn_model_create_firered',
     'wn_model_create_branchformer', 'wn_op_csgu_gate', 'wn_op_merge_dwconv', 'wn_csgu_time_tile',
+    'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
+    'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
 ]
 
 _lib = None
@@ -314,6 +324,18 @@ def lib():
     L.wn_op_merge_dwconv.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, pi32, pi32,
                                      i32, vp]
     L.wn_csgu_time_tile.argtypes = []
+    L.wn_model_create_paraformer.argtypes = [POINTER(WnConfig), POINTER(WnParaformerConfig),
+                                             POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_paraformer_decode.argtypes = [vp, pi32, pi32, POINTER(f32), pi32, pi32, i32, vp]
+    L.wn_op_attention_d128.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, pi32, pi32,
+                                       pi32, pi32, i32, i32, f32, vp]
+    L.wn_op_lfr_front.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, pi32, pi32, pi32,
+                                  i32, i32, i32, i32, i32, f32, f32, vp]
+    L.wn_op_layernorm_wide.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp]
+    L.wn_op_cif_alpha.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, f32, f32, vp, pi32, pi32,
+                                  i32, vp]
+    L.wn_op_cif_fire.argtypes = [vp, i32, i32, i32, vp, pi32, pi32, i32, f32, f32, vp, i32, i32,
+                                 pi32, pi32, pi32, pi32, pi32, vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

@@ -120,6 +120,9 @@ __global__ __launch_bounds__(DWT_THREADS) void dwconv_tile_kernel(DwTileArgs a) 
       if (a.r) y *= a.r[row * a.ldr + c];
     } else {
       y += s_in[(o0 + o + left) * DWT_CH + lane];
+      // optional residual behind the merge (the Paraformer's FSMN blocks); null for the
+      // E-Branchformer callers, whose sum stays as it was
+      if (a.r) y += a.r[row * a.ldr + c];
     }
     a.y[row * a.ldy + c] = y;
   }
@@ -179,6 +182,7 @@ int csgu_gate(const DwTileArgs& a, hipStream_t s) {
 int merge_dwconv(const DwTileArgs& a, hipStream_t s) {
   WN_TRY(dwt_check(a, "merge_dwconv"));
   WN_CHECK(a.y != a.x, "merge_dwconv: not in place (a tile reads its neighbours' frames)");
+  WN_CHECK(!a.r || a.ldr >= a.C, "merge_dwconv: row stride of r");
   return dwt_launch<1>(a, s);
 }
 

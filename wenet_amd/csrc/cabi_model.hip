@@ -2,65 +2,13 @@
 // (ModelData, model_state.h), create / clone / destroy, operand precision, the encode gate,
 // profiling, debug and tuning switches.
 #include "model_state.h"
+#include "weight_stage.h"
 
 namespace wn {
 namespace {
 
 // ---------------------------------------------------------------------------
 // weight ingestion
-struct HostStage {
-  std::vector<float> data;
-  std::map<std::string, std::pair<size_t, size_t>> at;  // name -> (offset, n)
-  void add(const std::string& name, const float* p, size_t n) {
-    size_t o = (data.size() + 63) / 64 * 64;
-    data.resize(o + n);
-    memcpy(data.data() + o, p, n * sizeof(float));
-    at[name] = {o, n};
-  }
-  float* alloc(const std::string& name, size_t n) {
-    size_t o = (data.size() + 63) / 64 * 64;
-    data.resize(o + n, 0.f);
-    at[name] = {o, n};
-    return data.data() + o;  // valid until the next add/alloc
-  }
-};
-
-struct Src {
-  std::map<std::string, std::pair<const float*, int64_t>> t;
-  const float* get(const std::string& n, int64_t numel) const {
-    auto it = t.find(n);
-    if (it == t.end()) { set_error("missing weight: " + n); return nullptr; }
-    if (numel >= 0 && it->second.second != numel) {
-      set_error("weight " + n + " has " + std::to_string(it->second.second) +
-                " elements, expected " + std::to_string(numel));
-      return nullptr;
-    }
-    return it->second.first;
-  }
-  bool has(const std::string& n) const { return t.count(n) != 0; }
-};
-
-#define WN_GET(var, name, numel)                 \
-  const float* var = src.get((name), (numel));   \
-  if (!var) return -3;
-
-int stage_linear(const Src& src, HostStage& hs, const std::string& pfx, int out,
-                 int in, bool bias = true) {
-  WN_GET(w, pfx + ".weight", (int64_t)out * in);
-  hs.add(pfx + ".weight", w, (size_t)out * in);
-  if (bias) {
-    WN_GET(b, pfx + ".bias", out);
-    hs.add(pfx + ".bias", b, out);
-  }
-  return 0;
-}
-int stage_norm(const Src& src, HostStage& hs, const std::string& pfx, int n) {
-  WN_GET(w, pfx + ".weight", n);
-  WN_GET(b, pfx + ".bias", n);
-  hs.add(pfx + ".weight", w, n);
-  hs.add(pfx + ".bias", b, n);
-  return 0;
-}
 // fuse several Linear layers along the output dimension; part `no_bias_part` (if >= 0) has no
 // bias in the state dict (key_bias: false): zeros in its place
 int stage_fused(const Src& src, HostStage& hs, const std::string& name,
@@ -308,42 +256,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
   }
   // ---- fbank tables (runtime/core/frontend/fbank.h:91-163) -----------------
-  std::vector<int> mel_start(c.feat_dim), mel_len(c.feat_dim), mel_off(c.feat_dim);
-  {
-    float* win = hs.alloc("fbank.window", 400);
-    const double a = 2.0 * M_PI / 399.0;
-    for (int i = 0; i < 400; ++i) win[i] = (float)pow(0.5 - 0.5 * cos(a * i), 0.85);
-    float* tw = hs.alloc("fbank.twiddle", 512);
-    for (int k = 0; k < 256; ++k) {
-      tw[2 * k] = (float)cos(2.0 * M_PI * k / 512.0);
-      tw[2 * k + 1] = (float)-sin(2.0 * M_PI * k / 512.0);
-    }
-    auto mel = [](float f) { return 1127.0f * logf(1.0f + f / 700.0f); };
-    const int nbins = c.feat_dim, nfft_bins = 256;
-    const float bin_w = 16000.0f / 512.0f;
-    const float mlo = mel(20.0f), mhi = mel(8000.0f);
-    const float delta = (mhi - mlo) / (float)(nbins + 1);
-    std::vector<float> wts;
-    for (int b = 0; b < nbins; ++b) {
-      const float left = mlo + b * delta, center = mlo + (b + 1) * delta,
-                  right = mlo + (b + 2) * delta;
-      int first = -1, last = -1;
-      std::vector<float> row(nfft_bins, 0.f);
-      for (int i = 0; i < nfft_bins; ++i) {
-        const float mf = mel(bin_w * i);
-        if (mf > left && mf < right) {
-          row[i] = mf <= center ? (mf - left) / (center - left)
-                                : (right - mf) / (right - center);
-          if (first < 0) first = i;
-          last = i;
-        }
-      }
-      if (first < 0) { W.fbank_ok = false; first = last = 0; }  // e.g. 128 bins
-      mel_start[b] = first; mel_len[b] = last + 1 - first; mel_off[b] = (int)wts.size();
-      for (int i = first; i <= last; ++i) wts.push_back(row[i]);
-    }
-    hs.add("fbank.mel_w", wts.data(), wts.size());
-  }
+  const FbankTables fbt = make_fbank_tables(c.feat_dim);   // (fbank_tables.h)
+  stage_fbank_tables(fbt, hs, W);
   if (!fr) WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));   // (firered: final_norm false)
   const bool has_ctc = src.has("ctc.ctc_lo.weight");
   if (has_ctc) WN_TRY(stage_linear(src, hs, "ctc.ctc_lo", V, d));
@@ -710,17 +624,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.sub_out.out = d; W.sub_out.in = d * F2;
   }
   W.pe = P("pe");
-  W.fb_window = P("fbank.window"); W.fb_twiddle = P("fbank.twiddle");
-  W.fb_mel_w = P("fbank.mel_w");
-  {
-    std::vector<int> tab;
-    tab.insert(tab.end(), mel_start.begin(), mel_start.end());
-    tab.insert(tab.end(), mel_len.begin(), mel_len.end());
-    tab.insert(tab.end(), mel_off.begin(), mel_off.end());
-    WN_TRY(W.fb_tab_i.ensure(tab.size() * sizeof(int)));
-    WN_HIP(hipMemcpy(W.fb_tab_i.p, tab.data(), tab.size() * sizeof(int),
-                     hipMemcpyHostToDevice));
-  }
+  WN_TRY(bind_fbank_tables(fbt, W));
   if (!fr) W.after_norm = NORM("encoder.after_norm");
   if (has_ctc) W.ctc = LIN("ctc.ctc_lo", V, d);
   if (tf) {
@@ -936,6 +840,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->tr.on = src->tr.on; m->tr.c = src->tr.c; m->tr.sp = src->tr.sp;
   m->fr.on = src->fr.on; m->fr.c = src->fr.c;
   m->bf.on = src->bf.on; m->bf.c = src->bf.c;
+  m->pf.on = src->pf.on; m->pf.c = src->pf.c;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;
@@ -956,6 +861,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(!m->bf.on || precision == PREC_F32,
            "wn_model_set_precision: a Branchformer handle stays fp32 (no bf16 / fp8 kernels for "
            "its encoder)");
+  WN_CHECK(!m->pf.on || precision == PREC_F32,
+           "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "
+           "encoder and decoder)");
   const ModelData& W = *m->data;
   // the images belong to the model block: whichever handle asks first builds them, every
   // clone (made before or after) reads the same ones

@@ -202,6 +202,8 @@ struct DwTileArgs {
 // projections of a cgMLP; C a multiple of 64 up to CSGU_MAX_C.
 int csgu_gate(const DwTileArgs& a, hipStream_t s);
 // y = x + conv(x) + bias with zero padding: the E-Branchformer merge in front of merge_proj.
+// With a.r set, y = ((conv(x) + bias) + x) + r (the Paraformer's FSMN block with the residual
+// around it; r may be y's own previous content only if it is another buffer than x).
 int merge_dwconv(const DwTileArgs& a, hipStream_t s);
 // y = r * g over [M][C] (use_linear_after_conv: the gate behind the extra Linear)
 int csgu_mul(const float* r, int ldr, const float* g, int ldg, float* y, int ldy, int M, int C,
@@ -816,5 +818,61 @@ struct RnntLatticeArgs {
   int N = 0, max_U = 0;
 };
 int rnnt_lattice(const RnntLatticeArgs& a, hipStream_t s);
+
+// ---- Paraformer (attention_d128.hip, paraformer.hip), fp32 ---------------------------------
+// attention() for heads of d_k = 128 (n_heads * 128 columns): mask_mode 0, no position term,
+// separate Q and K / V layouts (self and cross attention).  attention() itself stays d_k = 64.
+int attention_d128(const AttnArgs& a, hipStream_t s);
+
+// LFR front end (paraformer/layers.py:24-92 on ONE utterance, paraformer.py:329-350): output row
+// t of utterance b stacks the m frames n t - (m - 1) / 2 + f, f < m, each index clamped to
+// [0, len[b] - 1]; then GlobalCMVN over the m F columns, x * xscale + pe[t + 1], and the
+// LayerNorm (ln_w, ln_b; statistics over m F columns) of the first encoder layer.  Rows are
+// written ldo wide with zeros in columns m F .. ldo - 1.  One wave per row.
+constexpr int LFR_MAX_D = 576;     // m F at most (9 columns per lane)
+struct LfrFrontArgs {
+  const float* feats;     // (B, T, F) padded
+  const float* mean;      // [m F] or null (no CMVN)
+  const float* istd;      // [m F]
+  const float* pe;        // [pe_rows][m F]: row p = the encoding of position p
+  const float* ln_w; const float* ln_b;   // [m F]
+  float* out; int ldo;    // [sum rows][ldo]
+  const int* len;         // [B] frames of the utterance (> 0)
+  const int* off;         // [B] first output row; utterance b owns ceil(len[b] / n) rows
+  int B, T, F, m, n, max_rows;   // max_rows: output rows of the longest utterance
+  float xscale, eps;
+};
+int lfr_front(const LfrFrontArgs& a, hipStream_t s);
+
+// LayerNorm for rows the one-wave-per-row kernels of layernorm() do not cover: D up to 2048, any
+// multiple of 4 (the statistics divide by D); columns D .. Dpad - 1 of y are written as zeros.
+int layernorm_wide(const float* x, int ldx, const float* w, const float* b, float* y, int ldy,
+                   int M, int D, int Dpad, float eps, hipStream_t s);
+
+// CIF predictor (paraformer/cif.py:55-142, 250-293; cnn_groups 1, residual false).
+// cif_stage3: img[r] = [h[t - 1] | h[t] | h[t + 1]] (3 d columns) of every owned row, zeros past
+// the utterance's own ends: the A operand of the 3-tap dense conv as ONE GEMM with K = 3 d.
+int cif_stage3(const float* h, int ldh, float* img, const int* row_utt, const int* off,
+               const int* len, int M, int d, hipStream_t s);
+// alpha[r] = relu(sigmoid(y[r] . w + b[0]) * smooth - noise) of every owned row (row_utt[r] >= 0),
+// one wave per row
+int cif_alpha_rows(const float* y, int ldy, const float* w, const float* b, float smooth,
+                   float noise, float* alpha, const int* row_utt, int M, int d, hipStream_t s);
+// The integrate-and-fire scan, one workgroup per utterance, len[b] + 1 steps (the last one is the
+// tail: alpha = tail, a zero hidden row), threshold 1.0; the scalar chain is the reference's fp32
+// operations in its order.  Embedding k of utterance b goes to emb row emb_off[b] + k and the
+// frame it fired on to fire_t[emb_off[b] + k], k < emb_cap[b]; n_fire[b] counts every fire;
+// token_num[b] = floor(sum alpha) (fp64, index order); rows n_fire .. token_num - 1 are zeros.
+struct CifFireArgs {
+  const float* h; int ldh;          // [rows][ldh] encoder output
+  const float* alpha;               // [rows]
+  const int* off; const int* len;   // [B] first row / frames
+  const int* emb_off; const int* emb_cap;   // [B]
+  float* emb; int lde;              // [sum emb_cap][lde]
+  int* fire_t; int* n_fire; int* token_num;
+  int B, d; float tail;
+};
+constexpr int CIF_MAX_D = 1024;
+int cif_fire(const CifFireArgs& a, hipStream_t s);
 
 }  // namespace wn

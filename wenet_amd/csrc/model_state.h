@@ -178,6 +178,28 @@ struct DecLayer {
   Linear self_qkv, self_out, src_q, src_kv, src_out, ff1, ff2;
 };
 
+// Paraformer (cabi_paraformer.hip): AliParaformerEncoderLayer, SanmDecoderLayer, Cif
+struct PfEncLayer {
+  Norm n1, n2;
+  Linear qkv, out, ff1, ff2;       // layer 0: qkv is [3 d][576], the 560 input columns zero-padded
+  const float* fsmn_wt = nullptr;  // [K][d] tap-major
+};
+struct PfDecLayer {
+  Norm n1, n2, n3, ffn_norm;
+  Linear ff1, ff2, src_q, src_kv, src_out;   // ff2 has no bias
+  const float* fsmn_wt = nullptr;
+};
+struct PfData {
+  std::vector<PfEncLayer> enc;
+  std::vector<PfDecLayer> dec;
+  const float* pe = nullptr;         // [max_frames + 1][560] sinusoids (positions start at 1)
+  const float* zero_bias = nullptr;  // [d]: the FSMN convs have no bias
+  Linear cif_conv;                   // [d][3 d], column tap * d + c_in
+  const float* cif_out_w = nullptr; const float* cif_out_b = nullptr;
+  Norm dec3_n1, dec3_ffn_norm, dec_after;
+  Linear dec3_ff1, dec3_ff2, dec_out;
+};
+
 struct Decoder {
   const float* embed = nullptr;  // [V][d]
   const float* pe = nullptr;     // [max_pos][d] sinusoids, or the learned [dec_max_pos][d] table
@@ -239,6 +261,7 @@ struct ModelData {
   const float* pred_conv_w = nullptr; const float* pred_conv_b = nullptr;
   Linear pred_ffn;
   Norm pred_norm;
+  PfData pf;                             // wn_model::pf.on
   // fbank tables
   const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
   const float* fb_mel_w = nullptr;
@@ -287,6 +310,14 @@ struct wn_model {
     bool on = false;
     wn_branchformer_config c = {};
   } bf;
+  // wn_model_create_paraformer: SANM encoder, CIF predictor, SANM decoder (cabi_paraformer.hip);
+  // data->layers / tf_layers stay empty, data->pf holds the weights
+  struct {
+    bool on = false;
+    wn_paraformer_config c = {};
+  } pf;
+  DevBuf pf_alpha, pf_img, pf_emb, pf_int, pf_x, pf_y, pf_t, pf_o, pf_q, pf_kv, pf_h, pf_out;
+  PinnedBuf pf_host;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
@@ -545,6 +576,9 @@ int encode_firered(wn_model* m, const float* feats_dev, const int32_t* feat_lens
 int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
                         hipStream_t s);
+// (cabi_paraformer.hip)
+int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                      int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 // (cabi_model.hip: what every wn_model_create* entry point runs)
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,

@@ -1177,6 +1177,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     elif configs.get('encoder') in ('branchformer', 'e_branchformer'):
         from wenet_amd.branchformer import Branchformer
         model = Branchformer(configs, sd, device)
+    elif configs.get('model') == 'paraformer':   # init_model.py:155: Paraformer
+        from wenet_amd.paraformer import Paraformer
+        model = Paraformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

@@ -510,6 +510,45 @@ CONFIGS['aishell_ebranchformer'] = _ebranchformer(256, 8, 1024, 1024, 31, 31, 17
 CONFIGS['aishell_u2pp_branchformer'] = _branchformer(256, 4, 2048, 63, 24, 4, 2048, 3, 4233)
 
 
+# Paraformer (examples/aishell/paraformer/conf/train_paraformer.yaml) at the given widths
+def _paraformer(d, heads, ffn, enc_blocks, dec_blocks, vocab) -> dict:
+    return {
+        'input_dim': 560, 'output_dim': vocab,
+        'encoder': 'sanm_encoder',
+        'encoder_conf': dict(attention_dropout_rate=0.0, attention_heads=heads, dropout_rate=0.0,
+                             input_layer='paraformer_dummy', kernel_size=11, linear_units=ffn,
+                             normalize_before=True, num_blocks=enc_blocks, output_size=d,
+                             pos_enc_layer_type='abs_pos_paraformer',
+                             positional_dropout_rate=0.0, sanm_shfit=0,
+                             gradient_checkpointing=True),
+        'decoder': 'sanm_decoder',
+        'decoder_conf': dict(att_layer_num=dec_blocks, attention_heads=heads, dropout_rate=0.0,
+                             kernel_size=11, linear_units=ffn, num_blocks=dec_blocks,
+                             positional_dropout_rate=0.0, sanm_shfit=0,
+                             self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0,
+                             gradient_checkpointing=True),
+        'tokenizer': 'paraformer',
+        'tokenizer_conf': {'seg_dict_path': 'seg_dict', 'symbol_table_path': 'units.txt',
+                           'special_tokens': {'<blank>': 0, '<eos>': 2, '<sos>': 1,
+                                              '<unk>': vocab - 1}},
+        'model': 'paraformer',
+        'model_conf': dict(ctc_weight=0.3, length_normalized_loss=False, lsm_weight=0.1,
+                           sampling_ratio=0.75),
+        'predictor': 'paraformer_predictor',
+        'predictor_conf': dict(cnn_groups=1, idim=d, l_order=1, noise_threshold2=0.01, r_order=1,
+                               residual=False, smooth_factor2=0.25, tail_threshold=0.45,
+                               threshold=1.0, upsample_times=3),
+    }
+
+
+# d 256 with 2 heads: d_k = 128, the released model's head width; 1 + 2 encoder blocks
+CONFIGS['tiny_paraformer'] = _paraformer(256, 2, 256, 3, 2, 50)
+# the aishell recipe: 50 encoder blocks at d 512 with 4 heads, 16 decoder blocks
+CONFIGS['paraformer_large'] = _paraformer(512, 4, 2048, 50, 16, 8404)
+# its widths with one encoder block behind encoders0 and one decoder block (the tests)
+CONFIGS['paraformer_large_1blk'] = _paraformer(512, 4, 2048, 2, 1, 50)
+
+
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
     c = copy.deepcopy(CONFIGS[name])
@@ -669,6 +708,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         return _make_transformer_state_dict(configs, seed, sharpen_ctc)
     if configs.get('encoder') == 'firered_conformer':
         return _make_firered_state_dict(configs, seed, sharpen_ctc)
+    if configs.get('encoder') == 'sanm_encoder':
+        return _make_paraformer_state_dict(configs, seed, sharpen_ctc)
     idim, V = configs['input_dim'], configs['output_dim']
     sd: Dict[str, np.ndarray] = OrderedDict()
 
@@ -890,6 +931,99 @@ def _make_firered_state_dict(configs, seed, sharpen_ctc):
             sd[k] = sd[k] * np.float32(3.0)
     eos = configs['tokenizer_conf']['special_tokens']['eos']
     sd['decoder.output_layer.bias'][eos] += np.float32(FIRERED_EOS_BIAS)
+    lin('ctc.ctc_lo', V, d)
+    if sharpen_ctc:      # as make_state_dict: roughly 2/3 .. 4/5 of the frames come out blank
+        sd['ctc.ctc_lo.weight'] = sd['ctc.ctc_lo.weight'] * np.float32(12.0)
+        sd['ctc.ctc_lo.bias'] = sd['ctc.ctc_lo.bias'] * np.float32(12.0)
+        n = max(V - 1, 2)
+        a = math.sqrt(2.0 * math.log(n))
+        emax = a - (math.log(math.log(n)) + math.log(4 * math.pi)) / (2 * a) + 0.5772 / a
+        sd['ctc.ctc_lo.weight'][0, :] = 0.0
+        sd['ctc.ctc_lo.bias'][0] = np.float32(12.0 / math.sqrt(3.0) * emax * 1.10)
+    return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+
+
+def _make_paraformer_state_dict(configs, seed, sharpen_ctc):
+    """Paraformer (wenet/models/paraformer/): names and shapes as init_model gives them --
+    encoders0 over the 560 LFR columns + num_blocks - 1 encoders, FSMN convs without bias, the CIF
+    predictor with its timestamp branch (tp_*: carried, not read by the library), SANM decoder
+    layers without embedding, decoders3, the sampler's embedding, a CTC head."""
+    ec, dc, pc = configs['encoder_conf'], configs['decoder_conf'], configs['predictor_conf']
+    d, ffn, K = ec['output_size'], ec['linear_units'], ec['kernel_size']
+    idim, V = configs['input_dim'], configs['output_dim']
+    sd: Dict[str, np.ndarray] = OrderedDict()
+
+    def lin(name, out_f, in_f, bias=True):
+        b = 1.0 / math.sqrt(in_f)
+        sd[name + '.weight'] = _uniform(seed, name + '.weight', (out_f, in_f), b)
+        if bias:
+            sd[name + '.bias'] = _uniform(seed, name + '.bias', (out_f, ), b)
+
+    def norm(name, n):
+        sd[name + '.weight'] = _normal(seed, name + '.weight', (n, ), 0.1, 1.0)
+        sd[name + '.bias'] = _normal(seed, name + '.bias', (n, ), 0.1)
+
+    def fsmn(name, k):
+        sd[name + '.fsmn_block.weight'] = _uniform(seed, name + '.fsmn', (d, 1, k),
+                                                   1.0 / math.sqrt(k))
+
+    if configs.get('cmvn') == 'global_cmvn':
+        sd['encoder.global_cmvn.mean'] = _normal(seed, 'cmvn.mean', (idim, ), 1.5, 11.0)
+        sd['encoder.global_cmvn.istd'] = (
+            1.0 / (2.5 + np.abs(_normal(seed, 'cmvn.std', (idim, ), 0.5)))).astype(np.float32)
+    sd['encoder.embed.pos_enc.pe'] = whisper_positional_table(idim, 5000).numpy()
+    for i in range(ec['num_blocks']):
+        p = 'encoder.encoders0.0' if i == 0 else f'encoder.encoders.{i - 1}'
+        a = p + '.self_attn'
+        lin(a + '.linear_out', d, d)
+        lin(a + '.linear_q_k_v', 3 * d, idim if i == 0 else d)
+        fsmn(a, K)
+        lin(p + '.feed_forward.w_1', ffn, d)
+        lin(p + '.feed_forward.w_2', d, ffn)
+        norm(p + '.norm1', idim if i == 0 else d)
+        norm(p + '.norm2', d)
+    norm('encoder.after_norm', d)
+    # Cif: Conv1d(d, d, l_order + r_order + 1) dense, Linear(d, 1).  The output weight x 4: the
+    # alphas then spread over (0, 1) instead of sitting at 0.5, so the fires fall irregularly
+    taps = pc['l_order'] + pc['r_order'] + 1
+    b = 1.0 / math.sqrt(d * taps)
+    sd['predictor.predictor.cif_conv1d.weight'] = _uniform(seed, 'cif.conv.w', (d, d, taps), b)
+    sd['predictor.predictor.cif_conv1d.bias'] = _uniform(seed, 'cif.conv.b', (d, ), b)
+    lin('predictor.predictor.cif_output', 1, d)
+    sd['predictor.predictor.cif_output.weight'] = \
+        sd['predictor.predictor.cif_output.weight'] * np.float32(4.0)
+    up = pc['upsample_times']
+    sd['predictor.tp_upsample_cnn.weight'] = _uniform(seed, 'tp.up.w', (d, d, up),
+                                                      1.0 / math.sqrt(d * up))
+    sd['predictor.tp_upsample_cnn.bias'] = _uniform(seed, 'tp.up.b', (d, ), 1.0 / math.sqrt(d * up))
+    for sfx in ('', '_reverse'):
+        b = 1.0 / math.sqrt(d)
+        sd['predictor.tp_blstm.weight_ih_l0' + sfx] = _uniform(seed, 'tp.ih' + sfx, (4 * d, d), b)
+        sd['predictor.tp_blstm.weight_hh_l0' + sfx] = _uniform(seed, 'tp.hh' + sfx, (4 * d, d), b)
+        sd['predictor.tp_blstm.bias_ih_l0' + sfx] = _uniform(seed, 'tp.bih' + sfx, (4 * d, ), b)
+        sd['predictor.tp_blstm.bias_hh_l0' + sfx] = _uniform(seed, 'tp.bhh' + sfx, (4 * d, ), b)
+    lin('predictor.tp_output', 1, 2 * d)
+    dffn = dc['linear_units']
+    for j in range(dc['num_blocks'] + 1):
+        last = j == dc['num_blocks']
+        p = 'decoder.decoders3.0' if last else f'decoder.decoders.{j}'
+        lin(p + '.feed_forward.w_1', dffn, d)
+        lin(p + '.feed_forward.w_2', d, dffn, bias=False)
+        norm(p + '.feed_forward.norm', dffn)
+        norm(p + '.norm1', d)
+        if last:
+            break
+        norm(p + '.norm2', d)
+        norm(p + '.norm3', d)
+        fsmn(p + '.self_attn', dc['kernel_size'])
+        lin(p + '.src_attn.linear_q', d, d)
+        lin(p + '.src_attn.linear_k_v', 2 * d, d)
+        lin(p + '.src_attn.linear_out', d, d)
+    norm('decoder.after_norm', d)
+    lin('decoder.output_layer', V, d)
+    # x 6: the arg-max of a row then leads its runner-up by a margin a rounding does not close
+    sd['decoder.output_layer.weight'] = sd['decoder.output_layer.weight'] * np.float32(6.0)
+    sd['embed.weight'] = _normal(seed, 'embed', (V, d), 1.0)
     lin('ctc.ctc_lo', V, d)
     if sharpen_ctc:      # as make_state_dict: roughly 2/3 .. 4/5 of the frames come out blank
         sd['ctc.ctc_lo.weight'] = sd['ctc.ctc_lo.weight'] * np.float32(12.0)

@@ -25,13 +25,88 @@ def read_symbol_table(path: str) -> Dict[str, int]:
     return table
 
 
+_PF_DROPPED = ('<sos>', '<eos>', '<blank>')
+_PF_MARKS = (' ', '</s>', '<s>', '<unk>', '<OOV>')
+
+
+def _pf_strip(token: str) -> str:
+    for mark in _PF_MARKS:
+        token = token.replace(mark, '')
+    return token
+
+
+def _pf_is_han(piece: str) -> bool:
+    """One piece counts as Chinese when, as a string, it lies inside the CJK block, inside the
+    digits, or is '@' (paraformer/search.py:11-14: a range comparison of the whole string)."""
+    return '一' <= piece <= '鿿' or '0' <= piece <= '9' or piece == '@'
+
+
+def _pf_all_han(pieces) -> bool:
+    """paraformer/search.py:17-33 over the pieces of `pieces` (the tokens of a list, or the
+    characters of one token)."""
+    cleaned = [_pf_strip(p) for p in pieces]
+    return len(cleaned) > 0 and all(_pf_is_han(p) for p in cleaned)
+
+
+def _pf_all_alpha(pieces) -> bool:
+    """paraformer/search.py:36-55: letters (not Chinese ones) and apostrophes only."""
+    cleaned = [_pf_strip(p) for p in pieces]
+    if not cleaned:
+        return False
+    for p in cleaned:
+        if p.isalpha():
+            if _pf_is_han(p):
+                return False
+        elif p != "'":
+            return False
+    return True
+
+
+def paraformer_tokens2text(tokens: List[str]) -> str:
+    """The rule of paraformer_beautify_result (paraformer/search.py:58-111) restated: special
+    tokens dropped; an all-Chinese list is joined as it is; an all-alphabetic list joins '@@'
+    pieces to the piece behind them and puts a space behind every finished word; a mixed list
+    does both, and a Chinese token takes back the space behind the word in front of it."""
+    kept = [t for t in tokens if t not in _PF_DROPPED]
+    out: List[str] = []
+    word = ''
+    if _pf_all_han(kept):
+        out = [t.replace(' ', '') for t in kept]
+    elif _pf_all_alpha(kept):
+        for t in kept:
+            if '@@' in t:
+                word += t.replace('@@', '')
+            else:
+                out += [word + t, ' ']
+                word = ''
+    else:
+        space_pending = False
+        for t in kept:
+            if _pf_all_han(t):
+                if space_pending:
+                    out.pop()
+                out.append(t)
+                space_pending = False
+            elif '@@' in t:
+                word += t.replace('@@', '')
+                space_pending = False
+            elif _pf_all_alpha(t):
+                out += [word + t, ' ']
+                word = ''
+                space_pending = True
+            else:
+                out.append(t)
+                space_pending = False
+    return ''.join(out).strip()
+
+
 class Tokenizer:
 
     def __init__(self, symbol_table, kind: str = 'char', connect_symbol: str = '',
                  bpe_path: str = None):
         if not isinstance(symbol_table, dict):
             symbol_table = read_symbol_table(symbol_table)
-        assert kind in ('char', 'bpe')
+        assert kind in ('char', 'bpe', 'paraformer')
         self.kind = kind
         self.connect_symbol = connect_symbol if kind == 'char' else ''
         self.bpe_path = bpe_path
@@ -49,6 +124,8 @@ class Tokenizer:
         return [self.char_dict[int(w)] for w in ids]  # KeyError like the reference
 
     def tokens2text(self, tokens: List[str]) -> str:
+        if self.kind == 'paraformer':   # paraformer_tokenizer.py:52-53 (detokenising only)
+            return paraformer_tokens2text(tokens)
         text = self.connect_symbol.join(tokens)
         if self.kind == 'bpe':
             text = text.replace('▁', ' ').strip()
@@ -64,8 +141,8 @@ def init_tokenizer(configs: dict, model_dir: str = None) -> Tokenizer:
     tokenizer_conf are first looked up next to the model like
     wenet/cli/model.py:41-45."""
     kind = configs.get('tokenizer', 'char')
-    if kind not in ('char', 'bpe'):
-        raise NotImplementedError(f'tokenizer {kind!r} (char and bpe are supported)')
+    if kind not in ('char', 'bpe', 'paraformer'):
+        raise NotImplementedError(f'tokenizer {kind!r} (char, bpe and paraformer are supported)')
     conf = dict(configs['tokenizer_conf'])
     if model_dir is not None:
         for key, value in conf.items():
