@@ -717,6 +717,37 @@ int wn_op_merge_dwconv(const float* c, int32_t ldc, int32_t rows, int32_t C, con
                        const int32_t* off, const int32_t* len, int32_t n_seq, void* stream);
 /* Output frames one workgroup of those two kernels owns (lengths around it are the edge cases). */
 int32_t wn_csgu_time_tile(void);
+/* Self attention with the Squeezeformer's wrapped shift (csrc/squeezeformer.hip; the reference's
+ * rel_shift on a T x T score matrix, squeezeformer/attention.py:75-99), full context, d_k = 64,
+ * fp32, one launch for all sequences.  Sequence i is rows off[i] .. off[i] + len[i] - 1 of Q / K /
+ * V / O (host [n_seq], ascending, disjoint, inside `rows`); with T = len[i]
+ *   score(a, b) = ((q_a + u) . k_b + S(a, b)) * scale
+ *   S(a, b) = (q_a + v) . p[T - 1 - (a - b)]   for b <= a
+ *           = 0                                for b == a + 1
+ *           = (q_{a+1} + v) . p[b - a - 2]     for b >= a + 2
+ * P [p_rows][ldp]: linear_pos of the first p_rows position rows, p_rows >= the longest len (rows
+ * >= T of a shorter sequence are not read).  Strides in floats, multiples of 4, >= n_heads * 64. */
+int wn_op_attention_sqshift(const float* Q, const float* K, const float* V, int32_t ldq,
+                            int32_t ldk, int32_t ldv, int32_t rows, const float* P, int32_t ldp,
+                            int32_t p_rows, const float* bias_u, const float* bias_v, float* O,
+                            int32_t ldo, const int32_t* off, const int32_t* len, int32_t n_seq,
+                            int32_t n_heads, float scale, void* stream);
+/* The depthwise conv of a Squeezeformer time reduction: x [rows][ldx] packed full-rate rows
+ * (utterance i: off[i], len[i]) -> y [out_rows][ldy] packed half-rate rows (utterance i:
+ * out_off[i], (len[i] + 1) / 2 rows, inside out_rows, disjoint),
+ *   y[t][c] = bias[c] + sum_k wt[k][c] * x[2 t - pad + k][c],   wt [K][C] tap-major,
+ * frames outside the utterance's own [0, len) being zeros.  K = 5 with pad = 3, or K = 1 with
+ * pad = 0.  C a multiple of 64; y must not overlap x. */
+int wn_op_time_reduce(const float* x, int32_t ldx, int32_t rows, int32_t C, const float* wt,
+                      const float* bias, int32_t K, int32_t pad, float* y, int32_t ldy,
+                      int32_t out_rows, const int32_t* off, const int32_t* len,
+                      const int32_t* out_off, int32_t n_seq, void* stream);
+/* Time recovery: y[off[i] + t] = skip[off[i] + t] + z[z_off[i] + t / 2] for t < len[i]; skip / y
+ * [rows][lds / ldy] full-rate, z [z_rows][ldz] half-rate ((len[i] + 1) / 2 rows from z_off[i]).
+ * y may be skip; z must not overlap y. */
+int wn_op_time_recover(const float* skip, int32_t lds, const float* z, int32_t ldz, int32_t z_rows,
+                       float* y, int32_t ldy, int32_t rows, int32_t C, const int32_t* off,
+                       const int32_t* len, const int32_t* z_off, int32_t n_seq, void* stream);
 
 /* ---- Paraformer kernels (wenet/models/paraformer/; csrc/attention_d128.hip, paraformer.hip),
  * fp32, test hooks.  Offsets and lengths are HOST arrays (ascending, disjoint), everything else a
@@ -1061,6 +1092,32 @@ int wn_model_create_paraformer(const wn_config* cfg, const wn_paraformer_config*
  * suffices. */
 int wn_paraformer_decode(wn_model* m, int32_t* tokens, int32_t* tok_lens, float* logp,
                          int32_t* fire_frames, int32_t* n_fire, int32_t max_tok, void* stream);
+
+/* Squeezeformer encoders (`encoder: squeezeformer`, wenet/models/squeezeformer/) under the
+ * asr_model head: the Conv2dSubsampling4-shaped front end (pw_conv / dw_conv / input_proj, the
+ * sqrt(d) scale in FRONT of the projection), preln, post-LN blocks of attention / FFN / conv
+ * module / FFN with an adaptive scale in front of every module, one time reduction in front of
+ * block reduce_idx and its recovery in front of block recover_idx.  In wn_config, ffn_dim is
+ * encoder_dim * feed_forward_expansion_factor, cnn_norm / cnn_kernel / causal describe the conv
+ * module. */
+typedef struct {
+  int32_t reduce_idx;      /* block in front of which the time reduction sits, or -1: none */
+  int32_t recover_idx;     /* block in front of which the recovery sits (> reduce_idx), or -1 */
+  int32_t reduce_kernel;   /* 5: conv1d (padding 3), 1: stream (no padding) */
+  int32_t do_rel_shift;    /* the wrapped rel_shift of squeezeformer/attention.py */
+} wn_squeezeformer_config;
+
+/* wn_model_create for such a state dict (the names init_model gives it), loaded strictly.  On
+ * the handle, wn_encode runs the layer stack in fp32 with every utterance encoded as the
+ * reference encodes it ALONE: T' = (len - 7) / 4 + 1 frames (the reference's batched mask counts
+ * one frame more for every utterance shorter than the batch's longest), the shift wraps at the
+ * utterance's own length, the convs and the time reduction see its own frames only.  chunk /
+ * left set the attention mask only; a chunk mask is refused with do_rel_shift (the shift kernel
+ * is full context), and an odd chunk size is refused on a model with a time reduction.
+ * wn_encode_chunk*, wn_stream_create and a bf16 / fp8 precision are refused on such a handle. */
+int wn_model_create_squeezeformer(const wn_config* cfg, const wn_squeezeformer_config* qcfg,
+                                  const wn_tensor* weights, int32_t n_weights, int32_t device,
+                                  wn_model** out);
 
 /* Operator hook: one advance of a stateless predictor + joint.pred_ffn for M rows
  * (rnnt_stateless_step).  ctx_host (M, context) holds the window ids of every row, oldest first,

@@ -58,6 +58,12 @@ class WnParaformerConfig(Structure):
                                'noise_threshold')]
 
 
+class WnSqueezeformerConfig(Structure):
+    """wn_squeezeformer_config: what a Squeezeformer encoder has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('reduce_idx', 'recover_idx', 'reduce_kernel',
+                                       'do_rel_shift')]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -139,6 +145,8 @@ EXPORTS = [
     'wn_model_create_transducer_stateless', 'wn_op_stateless_step',
     'wn_op_attention_relshift', 'wn_op_firered_frontend', 'wn_model_create_firered',
     'wn_model_create_branchformer', 'wn_op_csgu_gate', 'wn_op_merge_dwconv', 'wn_csgu_time_tile',
+    'wn_model_create_squeezeformer', 'wn_op_attention_sqshift', 'wn_op_time_reduce',
+    'wn_op_time_recover',
     'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
     'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
 ]
@@ -324,6 +332,14 @@ def lib():
     L.wn_op_merge_dwconv.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, pi32, pi32,
                                      i32, vp]
     L.wn_csgu_time_tile.argtypes = []
+    L.wn_model_create_squeezeformer.argtypes = [POINTER(WnConfig), POINTER(WnSqueezeformerConfig),
+                                                POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_attention_sqshift.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp,
+                                          vp, i32, pi32, pi32, i32, i32, f32, vp]
+    L.wn_op_time_reduce.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, pi32, pi32,
+                                    pi32, i32, vp]
+    L.wn_op_time_recover.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, pi32, pi32, pi32,
+                                     i32, vp]
     L.wn_model_create_paraformer.argtypes = [POINTER(WnConfig), POINTER(WnParaformerConfig),
                                              POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_paraformer_decode.argtypes = [vp, pi32, pi32, POINTER(f32), pi32, pi32, i32, vp]

@@ -80,13 +80,14 @@ const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 // wn_model_create_transducer_stateless (scfg != nullptr: a stateless predictor, no LSTM) /
 // wn_model_create_firered (fcfg != nullptr, cabi_firered.hip: the FireRedASR-AED encoder)
 // wn_model_create_branchformer (bcfg != nullptr, cabi_branchformer.hip)
+// wn_model_create_squeezeformer (qcfg != nullptr, cabi_squeezeformer.hip)
 }  // extern "C"
 
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                          const wn_stateless_predictor_config* scfg,
                          const wn_firered_config* fcfg, const wn_branchformer_config* bcfg,
-                         const wn_tensor* weights, int32_t n_weights, int32_t device,
-                         wn_model** out) {
+                         const wn_squeezeformer_config* qcfg, const wn_tensor* weights,
+                         int32_t n_weights, int32_t device, wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   const bool fr = fcfg != nullptr;
@@ -131,6 +132,28 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_CHECK(b.linear_after_conv == 0 || b.linear_after_conv == 1,
              "branchformer: linear_after_conv is 0 or 1");
   }
+  const bool sq = qcfg != nullptr;
+  if (sq) {
+    const wn_squeezeformer_config& q = *qcfg;
+    WN_CHECK(!tcfg && !fr && !bf, "squeezeformer: an asr_model head only");
+    WN_CHECK(c.encoder_type == 0 && c.input_layer == 0 && c.activation == 0,
+             "squeezeformer: the conv2d front end (encoder_type 0, input_layer 0), swish");
+    WN_CHECK(c.d_model == 64 || c.d_model == 128 || c.d_model == 256 || c.d_model == 512,
+             "squeezeformer: encoder_dim must be 64, 128, 256 or 512");
+    WN_CHECK((q.reduce_idx == -1 && q.recover_idx == -1) ||
+                 (q.reduce_idx >= 0 && q.reduce_idx < q.recover_idx && q.recover_idx < c.n_layers),
+             "squeezeformer: reduce_idx / recover_idx must both be -1 or satisfy 0 <= reduce_idx "
+             "< recover_idx < n_layers");
+    WN_CHECK(q.reduce_kernel == 5 || q.reduce_kernel == 1,
+             "squeezeformer: reduce_kernel must be 5 (conv1d) or 1 (stream)");
+    WN_CHECK(q.do_rel_shift == 0 || q.do_rel_shift == 1, "squeezeformer: do_rel_shift is 0 or 1");
+    WN_CHECK(!(q.do_rel_shift && c.static_chunk_size > 0),
+             "squeezeformer: do_rel_shift with static_chunk_size > 0 (the shift kernel is full "
+             "context only)");
+    WN_CHECK(!(q.reduce_idx >= 0 && c.static_chunk_size > 0 && c.static_chunk_size % 2 != 0),
+             "squeezeformer: an odd static_chunk_size with a time reduction is no chunk window at "
+             "the half rate");
+  }
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
@@ -154,6 +177,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (tcfg && scfg) m->tr.sp = *scfg;
   if (fr) { m->fr.on = true; m->fr.c = *fcfg; }
   if (bf) { m->bf.on = true; m->bf.c = *bcfg; }
+  if (sq) { m->sq.on = true; m->sq.c = *qcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -212,15 +236,20 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     // out Linear(C * F2 -> d): the kernels write the reference's own column order c * F2 + f
     WN_TRY(stage_linear(src, hs, "encoder.embed.out.0", d, C * F2));
   } else {  // conv1 (d,1,3,3) -> [tap][c]
-    WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)d * 9);
-    WN_GET(b0, "encoder.embed.conv.0.bias", d);
+    // (squeezeformer: DepthwiseConv2dSubsampling4 without dw_stride is the same pair of convs
+    // under other names, squeezeformer/subsampling.py:52-67)
+    const std::string n_c1 = sq ? "encoder.embed.pw_conv" : "encoder.embed.conv.0";
+    const std::string n_c2 = sq ? "encoder.embed.dw_conv" : "encoder.embed.conv.2";
+    const std::string n_out = sq ? "encoder.embed.input_proj.0" : "encoder.embed.out.0";
+    WN_GET(w0, n_c1 + ".weight", (int64_t)d * 9);
+    WN_GET(b0, n_c1 + ".bias", d);
     float* t = hs.alloc("conv1.w", (size_t)9 * d);
     for (int ch = 0; ch < d; ++ch)
       for (int k = 0; k < 9; ++k) t[k * d + ch] = w0[ch * 9 + k];
     hs.add("conv1.b", b0, d);
     // conv2 (n, c, ky, kx) -> [n][(ky*3+kx)*d + c]
-    WN_GET(w2, "encoder.embed.conv.2.weight", (int64_t)d * d * 9);
-    WN_GET(b2, "encoder.embed.conv.2.bias", d);
+    WN_GET(w2, n_c2 + ".weight", (int64_t)d * d * 9);
+    WN_GET(b2, n_c2 + ".bias", d);
     t = hs.alloc("conv2.w", (size_t)d * 9 * d);
     for (int n = 0; n < d; ++n)
       for (int ch = 0; ch < d; ++ch)
@@ -229,15 +258,22 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
               w2[((size_t)n * d + ch) * 9 + k];
     hs.add("conv2.b", b2, d);
     // out Linear(d*F2 -> d): input index c*F2+f  ->  f*d+c
-    WN_GET(wo, "encoder.embed.out.0.weight", (int64_t)d * d * F2);
-    WN_GET(bo, "encoder.embed.out.0.bias", d);
+    WN_GET(wo, n_out + ".weight", (int64_t)d * d * F2);
+    WN_GET(bo, n_out + ".bias", d);
     t = hs.alloc("sub_out.w", (size_t)d * d * F2);
     for (int n = 0; n < d; ++n)
       for (int ch = 0; ch < d; ++ch)
         for (int f = 0; f < F2; ++f)
           t[(size_t)n * d * F2 + (size_t)f * d + ch] =
               wo[(size_t)n * d * F2 + (size_t)ch * F2 + f];
-    hs.add("sub_out.b", bo, d);
+    if (sq) {
+      // the sqrt(d) of RelPositionalEncoding sits in FRONT of input_proj here:
+      // W (x sqrt d) + b = sqrt(d) (W x + b / sqrt d), the form the front end computes
+      float* tb = hs.alloc("sub_out.b", d);
+      for (int n = 0; n < d; ++n) tb[n] = (float)((double)bo[n] / sqrt((double)d));
+    } else {
+      hs.add("sub_out.b", bo, d);
+    }
   }
   {  // positional table: the `pe` buffer (embedding.py:47-56)
     float* t = hs.alloc("pe", (size_t)c.max_pos * d);
@@ -258,7 +294,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   // ---- fbank tables (runtime/core/frontend/fbank.h:91-163) -----------------
   const FbankTables fbt = make_fbank_tables(c.feat_dim);   // (fbank_tables.h)
   stage_fbank_tables(fbt, hs, W);
-  if (!fr) WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));   // (firered: final_norm false)
+  // (firered: final_norm false; squeezeformer: post-LN blocks, no after_norm)
+  if (!fr && !sq) WN_TRY(stage_norm(src, hs, "encoder.after_norm", d));
   const bool has_ctc = src.has("ctc.ctc_lo.weight");
   if (has_ctc) WN_TRY(stage_linear(src, hs, "ctc.ctc_lo", V, d));
   for (int i = 0; tf && i < c.n_layers; ++i) {
@@ -447,7 +484,115 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
     WN_TRY(stage_linear(src, hs, p + ".merge_proj", d, 2 * d));
   }
-  for (int i = 0; !tf && !fr && !bf && i < c.n_layers; ++i) {
+  if (sq) {
+    WN_TRY(stage_norm(src, hs, "encoder.preln", d));
+    if (qcfg->reduce_idx >= 0) {
+      const int Kr = qcfg->reduce_kernel;
+      WN_GET(wd, "encoder.time_reduction_layer.dw_conv.weight", (int64_t)d * Kr);
+      WN_GET(bd, "encoder.time_reduction_layer.dw_conv.bias", d);
+      std::vector<float> w((size_t)Kr * d);
+      for (int ch = 0; ch < d; ++ch)
+        for (int k = 0; k < Kr; ++k) w[(size_t)k * d + ch] = wd[(size_t)ch * Kr + k];
+      hs.add("sq.red.dw.weight", w.data(), w.size());
+      hs.add("sq.red.dw.bias", bd, d);
+      WN_TRY(stage_linear(src, hs, "encoder.time_reduction_layer.pw_conv", d, d));
+      WN_TRY(stage_linear(src, hs, "encoder.time_recover_layer", d, d));
+    }
+  }
+  for (int i = 0; sq && i < c.n_layers; ++i) {
+    // SqueezeformerEncoderLayer.  `ada_scale * x + ada_bias` in front of a module folds into the
+    // module's first Linear, in fp64: W' = W diag(s), b' = W a + b.
+    const std::string p = "encoder.encoders." + std::to_string(i);
+    // dst rows [row0, row0 + out) of a [.][d] matrix
+    auto fold = [&](const std::string& lin, const std::string& ada, int out, float* w, float* b,
+                    const int* perm) -> int {
+      WN_GET(pw, lin + ".weight", (int64_t)out * d);
+      WN_GET(pb, lin + ".bias", out);
+      WN_GET(sc, ada + ".ada_scale", d);
+      WN_GET(ab, ada + ".ada_bias", d);
+      for (int o = 0; o < out; ++o) {
+        const int r = perm ? perm[o] : o;
+        double acc = (double)pb[o];
+        for (int k = 0; k < d; ++k) {
+          w[(size_t)r * d + k] = (float)((double)pw[(size_t)o * d + k] * (double)sc[k]);
+          acc += (double)pw[(size_t)o * d + k] * (double)ab[k];
+        }
+        b[r] = (float)acc;
+      }
+      return 0;
+    };
+    for (const char* n : {"layer_norm1", "layer_norm2", "layer_norm3", "layer_norm4"})
+      WN_TRY(stage_norm(src, hs, p + "." + n, d));
+    {
+      std::vector<float> w((size_t)3 * d * d), b((size_t)3 * d);
+      const char* parts[3] = {"linear_q", "linear_k", "linear_v"};
+      for (int j = 0; j < 3; ++j)
+        WN_TRY(fold(p + ".self_attn." + parts[j], p + ".self_attn", d, &w[(size_t)j * d * d],
+                    &b[(size_t)j * d], nullptr));
+      hs.add(p + ".qkv.weight", w.data(), w.size());
+      hs.add(p + ".qkv.bias", b.data(), b.size());
+    }
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_out", d, d));
+    WN_TRY(stage_linear(src, hs, p + ".self_attn.linear_pos", d, d, false));
+    WN_GET(bu, p + ".self_attn.pos_bias_u", d);
+    WN_GET(bv, p + ".self_attn.pos_bias_v", d);
+    hs.add(p + ".pos_bias_u", bu, d);
+    hs.add(p + ".pos_bias_v", bv, d);
+    for (const char* ff : {"ffn1", "ffn2"}) {
+      std::vector<float> w((size_t)F * d), b(F);
+      WN_TRY(fold(p + "." + ff + ".w_1", p + "." + ff, F, w.data(), b.data(), nullptr));
+      hs.add(p + "." + ff + ".w_1.weight", w.data(), w.size());
+      hs.add(p + "." + ff + ".w_1.bias", b.data(), b.size());
+      WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_2", d, F));
+    }
+    {  // pointwise_conv1 (2d, d, 1): rows permuted per 64 as [32 a | 32 gate].  The reference
+       // pads the causal conv's K - 1 ZERO frames behind the adaptive scale and in front of
+       // pointwise_conv1, so a padded frame is the GLU of the UNFOLDED bias
+      std::vector<int> perm(2 * d);
+      for (int g = 0; g < d / 32; ++g)
+        for (int j = 0; j < 32; ++j) {
+          perm[g * 32 + j] = g * 64 + j;
+          perm[d + g * 32 + j] = g * 64 + 32 + j;
+        }
+      std::vector<float> w((size_t)2 * d * d), b(2 * d), cp(d);
+      WN_TRY(fold(p + ".conv_module.pointwise_conv1", p + ".conv_module", 2 * d, w.data(),
+                  b.data(), perm.data()));
+      WN_GET(b1, p + ".conv_module.pointwise_conv1.bias", 2 * d);
+      for (int ch = 0; ch < d; ++ch)
+        cp[ch] = (float)((double)b1[ch] / (1.0 + exp(-(double)b1[d + ch])));
+      hs.add(p + ".pw1.weight", w.data(), w.size());
+      hs.add(p + ".pw1.bias", b.data(), b.size());
+      hs.add(p + ".cpad", cp.data(), cp.size());
+    }
+    {  // depthwise (d,1,K) -> [K][d]
+      WN_GET(wd, p + ".conv_module.depthwise_conv.weight", (int64_t)d * K);
+      WN_GET(bd, p + ".conv_module.depthwise_conv.bias", d);
+      std::vector<float> w((size_t)K * d);
+      for (int ch = 0; ch < d; ++ch)
+        for (int k = 0; k < K; ++k) w[(size_t)k * d + ch] = wd[(size_t)ch * K + k];
+      hs.add(p + ".dw.weight", w.data(), w.size());
+      hs.add(p + ".dw.bias", bd, d);
+    }
+    if (c.cnn_norm == 0) {
+      WN_TRY(stage_norm(src, hs, p + ".conv_module.norm", d));
+    } else {  // eval-mode BatchNorm1d (eps 1e-5) as a per-channel affine, in fp64
+      const std::string q = p + ".conv_module.norm";
+      WN_GET(bw, q + ".weight", d);
+      WN_GET(bb, q + ".bias", d);
+      WN_GET(bm, q + ".running_mean", d);
+      WN_GET(bvar, q + ".running_var", d);
+      std::vector<float> sc(d), sh(d);
+      for (int ch = 0; ch < d; ++ch) {
+        const double g = (double)bw[ch] / sqrt((double)bvar[ch] + 1e-5);
+        sc[ch] = (float)g;
+        sh[ch] = (float)((double)bb[ch] - (double)bm[ch] * g);
+      }
+      hs.add(q + ".weight", sc.data(), sc.size());
+      hs.add(q + ".bias", sh.data(), sh.size());
+    }
+    WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d));
+  }
+  for (int i = 0; !tf && !fr && !bf && !sq && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -625,7 +770,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   W.pe = P("pe");
   WN_TRY(bind_fbank_tables(fbt, W));
-  if (!fr) W.after_norm = NORM("encoder.after_norm");
+  if (!fr && !sq) W.after_norm = NORM("encoder.after_norm");
   if (has_ctc) W.ctc = LIN("ctc.ctc_lo", V, d);
   if (tf) {
     W.tf_layers.resize(c.n_layers);
@@ -712,11 +857,52 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
       Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = dq; lp.in = d;
       WN_TRY(linear(lp, W.pe, d, L.pos_tab, dq, c.max_pos, 0));
     }
+  } else if (sq) {
+    const wn_squeezeformer_config& q = *qcfg;
+    W.sq_preln = NORM("encoder.preln");
+    if (q.reduce_idx >= 0) {
+      W.sq_red_wt = P("sq.red.dw.weight");
+      W.sq_red_b = P("sq.red.dw.bias");
+      W.sq_red_pw = LIN("encoder.time_reduction_layer.pw_conv", d, d);
+      W.sq_recover = LIN("encoder.time_recover_layer", d, d);
+    }
+    W.layers.resize(c.n_layers);
+    WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
+    for (int i = 0; i < c.n_layers; ++i) {
+      const std::string p = "encoder.encoders." + std::to_string(i);
+      EncLayer& L = W.layers[i];
+      L.norm_mha = NORM(p + ".layer_norm1");
+      L.norm_ff_mac = NORM(p + ".layer_norm2");
+      L.norm_conv = NORM(p + ".layer_norm3");
+      L.norm_final = NORM(p + ".layer_norm4");
+      L.conv_norm = NORM(p + ".conv_module.norm");
+      L.ffm1 = LIN(p + ".ffn1.w_1", F, d);
+      L.ffm2 = LIN(p + ".ffn1.w_2", d, F);
+      L.ff1 = LIN(p + ".ffn2.w_1", F, d);
+      L.ff2 = LIN(p + ".ffn2.w_2", d, F);
+      L.qkv = LIN(p + ".qkv", 3 * d, d);
+      L.out = LIN(p + ".self_attn.linear_out", d, d);
+      L.pw1 = LIN(p + ".pw1", 2 * d, d);
+      L.pw2 = LIN(p + ".conv_module.pointwise_conv2", d, d);
+      L.bias_u = P(p + ".pos_bias_u");
+      L.bias_v = P(p + ".pos_bias_v");
+      L.pos_w = P(p + ".self_attn.linear_pos.weight");
+      L.dw_wt = P(p + ".dw.weight");
+      L.dw_b = P(p + ".dw.bias");
+      L.cpad = P(p + ".cpad");
+      // p = linear_pos(pos_emb): the blocks between the reduction and the recovery run at the
+      // half rate on pos_emb[:, ::2] -- (max_pos + 1) / 2 rows of pe with a row stride of 2 d
+      const bool half = q.reduce_idx >= 0 && i >= q.reduce_idx && i < q.recover_idx;
+      L.pos_tab = W.pos_tabs.as<float>() + (size_t)i * c.max_pos * d;
+      Linear lp; lp.w = L.pos_w; lp.b = nullptr; lp.out = d; lp.in = d;
+      if (half) WN_TRY(linear(lp, W.pe, 2 * d, L.pos_tab, d, (c.max_pos + 1) / 2, 0));
+      else WN_TRY(linear(lp, W.pe, d, L.pos_tab, d, c.max_pos, 0));
+    }
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && !fr && !bf && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && !bf && !sq && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -799,9 +985,9 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.j_pred = LIN("joint.pred_ffn", tc.join_dim, tc.pred_out);
     W.j_out = LIN("joint.ffn_out", V, tc.join_dim);
   }
-  // (firered, branchformer: the plain fp32 path, no six-product / row-block images of the
+  // (firered, branchformer, squeezeformer: the plain fp32 path, no six-product / row-block images of the
   // encoder's weights; the decoders and the CTC head get theirs as in every other model)
-  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf));
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -811,14 +997,14 @@ extern "C" {
 
 int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
                     int32_t n_weights, int32_t device, wn_model** out) {
-  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out) {
   WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
-  return create_model_impl(cfg, tcfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -826,7 +1012,7 @@ int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transduc
                                          const wn_tensor* weights, int32_t n_weights,
                                          int32_t device, wn_model** out) {
   WN_CHECK(tcfg && scfg, "wn_model_create_transducer_stateless: null argument");
-  return create_model_impl(cfg, tcfg, scfg, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, scfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -840,6 +1026,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->tr.on = src->tr.on; m->tr.c = src->tr.c; m->tr.sp = src->tr.sp;
   m->fr.on = src->fr.on; m->fr.c = src->fr.c;
   m->bf.on = src->bf.on; m->bf.c = src->bf.c;
+  m->sq.on = src->sq.on; m->sq.c = src->sq.c;
   m->pf.on = src->pf.on; m->pf.c = src->pf.c;
   m->device = src->device;
   m->prec = src->prec;
@@ -860,6 +1047,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
            "encoder)");
   WN_CHECK(!m->bf.on || precision == PREC_F32,
            "wn_model_set_precision: a Branchformer handle stays fp32 (no bf16 / fp8 kernels for "
+           "its encoder)");
+  WN_CHECK(!m->sq.on || precision == PREC_F32,
+           "wn_model_set_precision: a Squeezeformer handle stays fp32 (no bf16 / fp8 kernels for "
            "its encoder)");
   WN_CHECK(!m->pf.on || precision == PREC_F32,
            "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "

@@ -557,6 +557,115 @@ int wn_op_attention_relshift(const float* Q, const float* K, const float* V, int
   return attention_relshift(a, s);
 }
 
+int wn_op_attention_sqshift(const float* Q, const float* K, const float* V, int32_t ldq,
+                            int32_t ldk, int32_t ldv, int32_t rows, const float* P, int32_t ldp,
+                            int32_t p_rows, const float* bias_u, const float* bias_v, float* O,
+                            int32_t ldo, const int32_t* off, const int32_t* len, int32_t n_seq,
+                            int32_t n_heads, float scale, void* stream) {
+  WN_CHECK(Q && K && V && P && bias_u && bias_v && O && off && len,
+           "attention_sqshift: null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 65536 && n_heads > 0 && n_heads < 65536,
+           "attention_sqshift: n_seq / n_heads");
+  const int d = n_heads * 64;
+  WN_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0,
+           "attention_sqshift: strides must be multiples of 4 elements");
+  WN_CHECK(ldq >= d && ldk >= d && ldv >= d && ldo >= d && ldp >= d,
+           "attention_sqshift: a stride is smaller than n_heads * 64");
+  WN_CHECK(rows > 0 && p_rows > 0, "attention_sqshift: empty buffers");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           "attention_sqshift: rows outside the buffer, unordered or overlapping");
+  int max_len = 0;
+  std::vector<int> h((size_t)2 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  WN_CHECK(max_len > 0, "attention_sqshift: empty");
+  WN_CHECK(p_rows >= max_len,
+           "attention_sqshift: a sequence is longer than the position table covers");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  SqShiftAttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = P; a.ldp = ldp; a.p_rows = p_rows;
+  a.bias_u = bias_u; a.bias_v = bias_v; a.O = O; a.ldo = ldo;
+  a.off = desc.as<int>(); a.len = a.off + n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_len = max_len; a.scale = scale;
+  return attention_sqshift(a, s);
+}
+
+// the layouts both time hooks share: off | len | half-rate off on the device; the half-rate rows
+// (len + 1) / 2 from off2 must lie inside rows2, ascending and disjoint
+static int time_hook_layout(const int32_t* off, const int32_t* len, const int32_t* off2, int n_seq,
+                            int rows, int rows2, DevBuf& desc, int* max_len, hipStream_t s,
+                            const char* who) {
+  const std::string w(who);
+  WN_CHECK(off && len && off2, w + ": null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 65536 && rows > 0 && rows2 > 0, w + ": n_seq / rows");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           w + ": rows outside the buffer, unordered or overlapping");
+  std::vector<int> h((size_t)3 * n_seq), len2(n_seq);
+  *max_len = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i]; h[2 * n_seq + i] = off2[i];
+    len2[i] = (len[i] + 1) / 2;
+    *max_len = std::max(*max_len, len[i]);
+  }
+  WN_CHECK(packed_ok(off2, len2.data(), n_seq, rows2),
+           w + ": half-rate rows outside the buffer, unordered or overlapping");
+  WN_CHECK(*max_len > 0, w + ": empty");
+  return upload_ints(desc, h, s);
+}
+
+int wn_op_time_reduce(const float* x, int32_t ldx, int32_t rows, int32_t C, const float* wt,
+                      const float* bias, int32_t K, int32_t pad, float* y, int32_t ldy,
+                      int32_t out_rows, const int32_t* off, const int32_t* len,
+                      const int32_t* out_off, int32_t n_seq, void* stream) {
+  WN_CHECK(x && wt && bias && y, "time_reduce: null argument");
+  WN_CHECK(C > 0 && C % 64 == 0 && ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0,
+           "time_reduce: C must be a multiple of 64, strides multiples of 4 elements, >= C");
+  WN_CHECK((K == 5 && pad == 3) || (K == 1 && pad == 0),
+           "time_reduce: 5 taps with padding 3 (conv1d) or 1 tap without padding (stream)");
+  WN_CHECK(rows > 0 && out_rows > 0, "time_reduce: empty buffers");
+  WN_CHECK(y + (int64_t)out_rows * ldy <= x || x + (int64_t)rows * ldx <= y,
+           "time_reduce: y overlaps x");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  int max_len = 0;
+  WN_TRY(time_hook_layout(off, len, out_off, n_seq, rows, out_rows, desc, &max_len, s,
+                          "time_reduce"));
+  TimeReduceArgs a;
+  a.x = x; a.ldx = ldx; a.wt = wt; a.bias = bias; a.y = y; a.ldy = ldy;
+  a.off = desc.as<int>(); a.len = a.off + n_seq; a.off2 = a.off + 2 * n_seq;
+  a.B = n_seq; a.C = C; a.K = K; a.pad = pad; a.max_len = max_len;
+  return time_reduce_dwconv(a, s);
+}
+
+int wn_op_time_recover(const float* skip, int32_t lds, const float* z, int32_t ldz, int32_t z_rows,
+                       float* y, int32_t ldy, int32_t rows, int32_t C, const int32_t* off,
+                       const int32_t* len, const int32_t* z_off, int32_t n_seq, void* stream) {
+  WN_CHECK(skip && z && y, "time_recover: null argument");
+  WN_CHECK(C > 0 && C % 64 == 0 && lds >= C && ldz >= C && ldy >= C && lds % 4 == 0 &&
+               ldz % 4 == 0 && ldy % 4 == 0,
+           "time_recover: C must be a multiple of 64, strides multiples of 4 elements, >= C");
+  WN_CHECK(rows > 0 && z_rows > 0, "time_recover: empty buffers");
+  WN_CHECK(y + (int64_t)rows * ldy <= z || z + (int64_t)z_rows * ldz <= y,
+           "time_recover: z overlaps y");
+  WN_CHECK(y == skip || y + (int64_t)rows * ldy <= skip || skip + (int64_t)rows * lds <= y,
+           "time_recover: y overlaps skip without being it");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  int max_len = 0;
+  WN_TRY(time_hook_layout(off, len, z_off, n_seq, rows, z_rows, desc, &max_len, s,
+                          "time_recover"));
+  TimeRecoverArgs a;
+  a.skip = skip; a.lds = lds; a.z = z; a.ldz = ldz; a.y = y; a.ldy = ldy;
+  a.off = desc.as<int>(); a.len = a.off + n_seq; a.off2 = a.off + 2 * n_seq;
+  a.B = n_seq; a.C = C; a.max_len = max_len;
+  return time_recover_add(a, s);
+}
+
 int wn_op_firered_frontend(const float* feats, const float* mean, const float* istd,
                            const float* w1, const float* b1, const float* w2, const float* b2,
                            float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,

@@ -156,6 +156,55 @@ struct RelShiftAttnArgs {
 };
 int attention_relshift(const RelShiftAttnArgs& a, hipStream_t s);
 
+// Self attention with the Squeezeformer's WRAPPED shift (squeezeformer.hip; the reference's
+// rel_shift on a T x T matrix), full context only, d_k = 64, fp32:
+//   score(i, j) = ((q_i + u) . k_j + S(i, j)) * scale,   len = the sequence's OWN length,
+//   S(i, j) = (q_i + v) . p[len - 1 - (i - j)]   for j <= i
+//           = 0                                  for j == i + 1
+//           = (q_{i+1} + v) . p[j - i - 2]       for j >= i + 2
+// P [p_rows][h*64] is linear_pos of the first p_rows position rows; p_rows >= max_len.
+struct SqShiftAttnArgs {
+  const float* Q; const float* K; const float* V;
+  int ldq, ldk, ldv;
+  const float* P; int ldp;
+  int p_rows;
+  const float* bias_u; const float* bias_v;   // [h][64]
+  float* O; int ldo;
+  const int* off; const int* len;   // [n_seq] first row / rows of every sequence
+  int n_seq, n_heads, max_len;
+  float scale = 0.125f;
+};
+int attention_sqshift(const SqShiftAttnArgs& a, hipStream_t s);
+
+// Squeezeformer time reduction (squeezeformer.hip): packed full-rate rows [sum len][C] ->
+// packed half-rate rows [sum ceil(len / 2)][C],
+//   y[off2[b] + t][c] = bias[c] + sum_k wt[k][c] * x[off[b] + 2 t - pad + k][c],
+// frames outside the utterance's own [0, len) being zeros.  K = 5 with pad = 3 (conv1d) or
+// K = 1 with pad = 0 (stream).  The frame the reference's conv yields behind ceil(len / 2) and
+// cuts is not produced.
+constexpr int TR_TILE = 32;        // half-rate frames per workgroup
+struct TimeReduceArgs {
+  const float* x; int ldx;
+  const float* wt;                 // [K][C] tap-major
+  const float* bias;               // [C]
+  float* y; int ldy;
+  const int* off; const int* len;  // [B] full-rate first row / frames
+  const int* off2;                 // [B] half-rate first row
+  int B, C, K, pad, max_len;       // max_len: full-rate frames of the longest utterance
+};
+int time_reduce_dwconv(const TimeReduceArgs& a, hipStream_t s);
+// Time recovery: y[off[b] + t] = skip[off[b] + t] + z[off2[b] + t / 2], t < len[b] (y may be
+// skip).  z is time_recover_layer of the half-rate rows: a Linear is row-wise, so this equals
+// the reference's repeat-then-project.
+struct TimeRecoverArgs {
+  const float* skip; int lds;
+  const float* z; int ldz;
+  float* y; int ldy;
+  const int* off; const int* len; const int* off2;
+  int B, C, max_len;
+};
+int time_recover_add(const TimeRecoverArgs& a, hipStream_t s);
+
 // FireRedASR front end (firered.hip): GlobalCMVN, six zero frames behind every utterance's own
 // last frame, Conv2d(1->C,3,2) + ReLU, Conv2d(C->C,3,2) + ReLU.  Utterance b has
 // t2_len[b] = ((len + 6 - 3) / 2 + 1 - 3) / 2 + 1 output frames and t1_len[b] = 2 t2_len[b] + 1

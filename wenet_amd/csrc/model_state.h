@@ -166,6 +166,10 @@ struct EncLayer {
   const float* csgu_b = nullptr;
   const float* merge_wt = nullptr;  // [merge_kernel][2d]
   const float* merge_b = nullptr;
+  // Squeezeformer layers (wn_model::sq.on, cabi_squeezeformer.hip) are post-LN and reuse the
+  // Conformer's slots: norm_mha / norm_ff_mac / norm_conv / norm_final = layer_norm1 .. 4,
+  // ffm1 / ffm2 = ffn1, ff1 / ff2 = ffn2; qkv, ffm1, ff1 and pw1 hold the adaptive scale folded
+  // in; pos_tab is linear_pos of pe[0::2] for a block that runs at the half rate
 };
 
 struct TfLayer {  // TransformerEncoderLayer (encoder_layer.py:28-127)
@@ -262,6 +266,11 @@ struct ModelData {
   Linear pred_ffn;
   Norm pred_norm;
   PfData pf;                             // wn_model::pf.on
+  // Squeezeformer (wn_model::sq.on): preln, the time reduction's depthwise taps [K][d] + bias
+  // and pointwise conv, time_recover_layer
+  Norm sq_preln;
+  const float* sq_red_wt = nullptr; const float* sq_red_b = nullptr;
+  Linear sq_red_pw, sq_recover;
   // fbank tables
   const float* fb_window = nullptr; const float* fb_twiddle = nullptr;
   const float* fb_mel_w = nullptr;
@@ -316,6 +325,14 @@ struct wn_model {
     bool on = false;
     wn_paraformer_config c = {};
   } pf;
+  // wn_model_create_squeezeformer: a Squeezeformer encoder (cabi_squeezeformer.hip)
+  struct {
+    bool on = false;
+    wn_squeezeformer_config c = {};
+  } sq;
+  // ... its half-rate rows, their layout (off | len | row_utt in one block) and its own stager
+  DevBuf sq_xh, sq_desc;
+  Stager sq_stage;
   DevBuf pf_alpha, pf_img, pf_emb, pf_int, pf_x, pf_y, pf_t, pf_o, pf_q, pf_kv, pf_h, pf_out;
   PinnedBuf pf_host;
   int device = 0;
@@ -576,14 +593,19 @@ int encode_firered(wn_model* m, const float* feats_dev, const int32_t* feat_lens
 int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
                         hipStream_t s);
+// (cabi_squeezeformer.hip)
+int encode_squeezeformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
+                         hipStream_t s);
 // (cabi_paraformer.hip)
 int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 // (cabi_model.hip: what every wn_model_create* entry point runs)
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,
-                      const wn_branchformer_config* bcfg, const wn_tensor* weights,
-                      int32_t n_weights, int32_t device, wn_model** out);
+                      const wn_branchformer_config* bcfg, const wn_squeezeformer_config* qcfg,
+                      const wn_tensor* weights, int32_t n_weights, int32_t device,
+                      wn_model** out);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

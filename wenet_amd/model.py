@@ -47,6 +47,10 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         # (wenet_amd/branchformer.py: the encoder's own keys go into a wn_branchformer_config)
         from wenet_amd.branchformer import branchformer_config_from_yaml
         return branchformer_config_from_yaml(configs)[0]
+    if enc_type == 'squeezeformer':
+        # (wenet_amd/squeezeformer.py: the encoder's own keys go into a wn_squeezeformer_config)
+        from wenet_amd.squeezeformer import squeezeformer_config_from_yaml
+        return squeezeformer_config_from_yaml(configs)[0]
     if enc_type == 'conformer':
         checks = dict(input_layer='conv2d', pos_enc_layer_type='rel_pos',
                       selfattention_layer_type='rel_selfattn',
@@ -309,6 +313,10 @@ class ASRModel:
             raise NotImplementedError(
                 f"encoder {configs['encoder']!r} is outside the accelerated path of this class: "
                 'wenet_amd.Branchformer (load_model picks it)')
+        if configs.get('encoder') == 'squeezeformer':
+            raise NotImplementedError(
+                "encoder 'squeezeformer' is outside the accelerated path of this class: "
+                'wenet_amd.Squeezeformer (load_model picks it)')
         return config_from_yaml(configs)
 
     def _create(self, L, tensors, n: int, h) -> int:
@@ -1180,6 +1188,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     elif configs.get('model') == 'paraformer':   # init_model.py:155: Paraformer
         from wenet_amd.paraformer import Paraformer
         model = Paraformer(configs, sd, device)
+    elif configs.get('encoder') == 'squeezeformer':
+        from wenet_amd.squeezeformer import Squeezeformer
+        model = Squeezeformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

@@ -549,6 +549,43 @@ CONFIGS['paraformer_large'] = _paraformer(512, 4, 2048, 50, 16, 8404)
 CONFIGS['paraformer_large_1blk'] = _paraformer(512, 4, 2048, 2, 1, 50)
 
 
+# Squeezeformer under the asr_model head (examples/librispeech/s0/conf/train_squeezeformer.yaml,
+# train_u2++_squeezeformer.yaml, train_squeezeformer_bidecoder_large.yaml)
+def _squeezeformer(d, heads, factor, blocks, reduce_idx, recover_idx, k, reduction, shift, cnn_norm,
+                   causal, dynamic_chunk, decoder, dec_heads, dec_ffn, dec_blocks, vocab) -> dict:
+    ec = dict(encoder_dim=d, output_size=d, attention_heads=heads, num_blocks=blocks,
+              reduce_idx=reduce_idx, recover_idx=recover_idx, pos_enc_layer_type='rel_pos',
+              time_reduction_layer_type=reduction, feed_forward_expansion_factor=factor,
+              input_dropout_rate=0.1, feed_forward_dropout_rate=0.1, attention_dropout_rate=0.1,
+              cnn_module_kernel=k, do_rel_shift=shift, cnn_norm_type=cnn_norm,
+              adaptive_scale=True, normalize_before=False, causal=causal)
+    if dynamic_chunk:
+        ec.update(use_dynamic_chunk=True, use_dynamic_left_chunk=False)
+    dc = dict(attention_heads=dec_heads, linear_units=dec_ffn, num_blocks=dec_blocks,
+              dropout_rate=0.1, positional_dropout_rate=0.1, self_attention_dropout_rate=0.1,
+              src_attention_dropout_rate=0.1)
+    mc = dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False)
+    if decoder == 'bitransformer':
+        dc['r_num_blocks'] = dec_blocks
+        mc['reverse_weight'] = 0.3
+    return {'input_dim': 80, 'output_dim': vocab, 'encoder': 'squeezeformer', 'encoder_conf': ec,
+            'decoder': decoder, 'decoder_conf': dc, 'model_conf': mc}
+
+
+# conv1d reduction, the wrapped shift, an eval-mode BatchNorm, non-causal K 31, FFN x 4
+CONFIGS['tiny_squeezeformer'] = _squeezeformer(128, 2, 4, 4, 1, 3, 31, 'conv1d', True,
+                                               'batch_norm', False, False, 'transformer', 2, 96,
+                                               1, 41)
+# stream reduction, no shift, LayerNorm, causal K 15, chunk masks, FFN x 8, two decoders
+CONFIGS['tiny_squeezeformer_u2pp'] = _squeezeformer(128, 2, 8, 4, 1, 3, 15, 'stream', False,
+                                                    'layer_norm', True, True, 'bitransformer', 2,
+                                                    96, 1, 41)
+# train_squeezeformer.yaml at its real widths: tools/bench_squeezeformer.py only
+CONFIGS['librispeech_squeezeformer'] = _squeezeformer(256, 4, 4, 12, 5, 11, 31, 'conv1d', True,
+                                                      'layer_norm', False, False, 'transformer',
+                                                      4, 2048, 6, 5002)
+
+
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
     c = copy.deepcopy(CONFIGS[name])
@@ -693,6 +730,51 @@ def _add_branch_layer(sd, p, configs, seed, lin, norm):
             lin(f'{p}.{n}', 1, d)
 
 
+def _to_squeezeformer(sd, configs, seed):
+    """The Conformer-shaped dict of make_state_dict under a SqueezeformerEncoder's names
+    (wenet/models/squeezeformer/encoder.py:149-185): the front end's convs and projection, preln
+    instead of after_norm, post-LN blocks with an adaptive scale and bias in front of every module
+    (not the ones and zeros of the reference's initialisation, under which a dropped fold is
+    invisible), the time reduction and time_recover_layer."""
+    ec = configs['encoder_conf']
+    d = ec['encoder_dim']
+    rename = {'encoder.embed.conv.0.': 'encoder.embed.pw_conv.',
+              'encoder.embed.conv.2.': 'encoder.embed.dw_conv.',
+              'encoder.embed.out.0.': 'encoder.embed.input_proj.0.',
+              'encoder.after_norm.': 'encoder.preln.'}
+    layer = {'.feed_forward_macaron.': '.ffn1.', '.feed_forward.': '.ffn2.',
+             '.norm_mha.': '.layer_norm1.', '.norm_ff_macaron.': '.layer_norm2.',
+             '.norm_conv.': '.layer_norm3.', '.norm_ff.': '.layer_norm4.'}
+    out = OrderedDict()
+    for k, v in sd.items():
+        if k.startswith('encoder.encoders.'):
+            if '.norm_final.' in k:
+                continue
+            for a, b in layer.items():
+                k = k.replace(a, b)
+        else:
+            for a, b in rename.items():
+                if k.startswith(a):
+                    k = b + k[len(a):]
+        out[k] = v
+    for i in range(ec['num_blocks']):
+        for mod in ('self_attn', 'ffn1', 'ffn2', 'conv_module'):
+            p = f'encoder.encoders.{i}.{mod}'
+            out[p + '.ada_scale'] = _normal(seed, p + '.ada_scale', (1, 1, d), 0.2, 1.0)
+            out[p + '.ada_bias'] = _normal(seed, p + '.ada_bias', (1, 1, d), 0.3)
+    Kr = 5 if ec.get('time_reduction_layer_type', 'conv1d') == 'conv1d' else 1
+    p = 'encoder.time_reduction_layer'
+    b = 1.0 / math.sqrt(Kr)
+    out[p + '.dw_conv.weight'] = _uniform(seed, p + '.dw.w', (d, 1, Kr), b)
+    out[p + '.dw_conv.bias'] = _uniform(seed, p + '.dw.b', (d, ), b)
+    b = 1.0 / math.sqrt(d)
+    out[p + '.pw_conv.weight'] = _uniform(seed, p + '.pw.w', (d, d, 1), b)
+    out[p + '.pw_conv.bias'] = _uniform(seed, p + '.pw.b', (d, ), b)
+    out['encoder.time_recover_layer.weight'] = _uniform(seed, 'recover.w', (d, d), b)
+    out['encoder.time_recover_layer.bias'] = _uniform(seed, 'recover.b', (d, ), b)
+    return out
+
+
 def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
                     rnnt_blank_bias: float = RNNT_BLANK_BIAS
                     ) -> "OrderedDict[str, torch.Tensor]":
@@ -704,6 +786,9 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
     ffn = ec.get('linear_units', 2048)
     K = ec.get('cnn_module_kernel', 15)
     branch = configs.get('encoder') in ('branchformer', 'e_branchformer')
+    squeeze = configs.get('encoder') == 'squeezeformer'
+    if squeeze:
+        ffn = d * ec.get('feed_forward_expansion_factor', 4)
     if configs.get('encoder', 'conformer') == 'transformer':
         return _make_transformer_state_dict(configs, seed, sharpen_ctc)
     if configs.get('encoder') == 'firered_conformer':
@@ -772,7 +857,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         sd[p + '.conv_module.depthwise_conv.bias'] = _uniform(
             seed, p + '.dw.b', (d, ), b)
         norm(p + '.conv_module.norm', d)
-        if ec.get('cnn_module_norm', 'batch_norm') == 'batch_norm':
+        if ec.get('cnn_norm_type' if squeeze else 'cnn_module_norm',
+                  'batch_norm') == 'batch_norm':
             # BatchNorm1d buffers (eval mode uses the running statistics)
             sd[p + '.conv_module.norm.running_mean'] = _normal(
                 seed, p + '.bn.mean', (d, ), 0.3)
@@ -830,6 +916,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
             sd[k] = sd[k] * np.float32(4.0)
     if configs.get('model') == 'transducer':
         _add_transducer(sd, configs, seed, rnnt_blank_bias)
+    if squeeze:
+        sd = _to_squeezeformer(sd, configs, seed)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
 
