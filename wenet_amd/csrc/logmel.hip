@@ -65,7 +65,9 @@ __global__ __launch_bounds__(256) void logmel_log_kernel(float* mel, int n_mels,
   const int64_t n = (int64_t)n_frames[b] * n_mels;
   float mx = -INFINITY;
   for (int64_t i = threadIdx.x; i < n; i += 256) {
-    const float v = log10f(fmaxf(p[i], 1e-10f));
+    // log10 of the clamp is -10 exactly (torch gives it; the device log10f returns -10.000001,
+    // and digital silence -- all of pad_or_trim's padding -- must come out as -1.5)
+    const float v = p[i] > 1e-10f ? log10f(p[i]) : -10.0f;
     p[i] = v;
     mx = fmaxf(mx, v);
   }
