@@ -749,6 +749,53 @@ int wn_op_time_recover(const float* skip, int32_t lds, const float* z, int32_t l
                        float* y, int32_t ldy, int32_t rows, int32_t C, const int32_t* off,
                        const int32_t* len, const int32_t* z_off, int32_t n_seq, void* stream);
 
+/* ---- Efficient Conformer kernels (wenet/models/efficient_conformer/; csrc/efficonformer.hip),
+ * fp32, test hooks.  Offsets and lengths are HOST arrays (ascending, disjoint). */
+/* Grouped self attention (GroupedRelPositionMultiHeadedAttention.pad4group / forward,
+ * efficient_conformer/attention.py:83-126, 180-258), one launch for all sequences, head width
+ * W = group * d_k of 96 or 192 (other widths are refused).  Q / K / V / O [rows][ld*] and P
+ * [p_rows][ldp] are packed (frames, D) matrices, D = n_heads * width / group; sequence i is frames
+ * off[i] .. off[i] + len[i] - 1 (of P: p_off[i] .. , p_off may be null: 0).  Head h of group row
+ * r is flat elements [h W, (h + 1) W) of frames group r .. group r + group - 1: element e is
+ * frame group r + e / D, column e % D.  Frames >= len[i] read as zeros in all four operands and
+ * are not written.  bias_u / bias_v [n_heads][W].
+ *   score(r, s) = ((q_r + u) . k_s + (q_r + v) . p_s) * scale  over all ceil(len / group) key rows
+ * chunk_size > 0 (0: full context): with m = mask_step, query row r sees key row s iff
+ *   m s < ((m r) / chunk_size + 1) * chunk_size, and for left_chunks >= 0 also
+ *   m s >= ((m r) / chunk_size - left_chunks) * chunk_size   (mask[:, ::m, ::m] of
+ * subsequent_chunk_mask, utils/mask.py).  Strides in floats, multiples of 4, >= D. */
+int wn_op_attention_grouped(const float* Q, const float* K, const float* V, int32_t ldq,
+                            int32_t ldk, int32_t ldv, int32_t rows, const float* P, int32_t ldp,
+                            int32_t p_rows, const int32_t* p_off, const float* bias_u,
+                            const float* bias_v, float* O, int32_t ldo, const int32_t* off,
+                            const int32_t* len, int32_t n_seq, int32_t n_heads, int32_t group,
+                            int32_t width, int32_t mask_step, int32_t chunk_size,
+                            int32_t left_chunks, float scale, void* stream);
+/* The depthwise conv of a StrideConv module with its norm and swish (ConvolutionModule.forward,
+ * efficient_conformer/convolution.py:64-72, 141-146): x [rows][ldx] packed rows at the incoming
+ * rate (utterance i: off[i], len[i]) -> y [out_rows][ldy] packed rows at ceil(len[i] / stride)
+ * from out_off[i],
+ *   c[t][ch] = bias[ch] + sum_k wt[k][ch] * x[stride t - pad + k][ch],  wt [K][D] tap-major,
+ *   pad = (K - 1) / 2, or K - 1 with causal; y = SiLU(norm(c)), norm_mode 0: LayerNorm over the
+ * channels (ln_w, ln_b, eps), 1: c * ln_w + ln_b.  Frames >= len[i] are zeros; frames < 0 are
+ * zeros, or the vector cpad [D] when causal and cpad is not null (the module pads in front of
+ * pointwise_conv1, convolution.py:117-119).  stride 2 only, K <= 63, D a multiple of 64 <= 512. */
+int wn_op_stride_dwconv_ln_silu(const float* x, int32_t ldx, int32_t rows, int32_t D,
+                                const float* wt, const float* bias, const float* cpad,
+                                const float* ln_w, const float* ln_b, int32_t norm_mode,
+                                float eps, int32_t K, int32_t causal, int32_t stride, float* y,
+                                int32_t ldy, int32_t out_rows, const int32_t* off,
+                                const int32_t* len, const int32_t* out_off, int32_t n_seq,
+                                void* stream);
+/* The stride layer's residual (StrideConformerEncoderLayer.forward, efficient_conformer/
+ * encoder_layer.py:138-148: AvgPool1d(stride, stride, ceil_mode=True, count_include_pad=False)):
+ *   y[out_off[i] + t] = z[out_off[i] + t] + mean(x[off[i] + 2 t .. min(2 t + 2, len[i]) - 1]),
+ * t < ceil(len[i] / 2); z / y [out_rows][ldz / ldy], y may be z.  stride 2 only. */
+int wn_op_avgpool_residual_add(const float* x, int32_t ldx, int32_t rows, const float* z,
+                               int32_t ldz, float* y, int32_t ldy, int32_t out_rows, int32_t C,
+                               int32_t stride, const int32_t* off, const int32_t* len,
+                               const int32_t* out_off, int32_t n_seq, void* stream);
+
 /* ---- Paraformer kernels (wenet/models/paraformer/; csrc/attention_d128.hip, paraformer.hip),
  * fp32, test hooks.  Offsets and lengths are HOST arrays (ascending, disjoint), everything else a
  * device pointer unless it is named *_host; every argument is checked before the first launch. */
@@ -1116,6 +1163,34 @@ typedef struct {
  * is full context), and an odd chunk size is refused on a model with a time reduction.
  * wn_encode_chunk*, wn_stream_create and a bf16 / fp8 precision are refused on such a handle. */
 int wn_model_create_squeezeformer(const wn_config* cfg, const wn_squeezeformer_config* qcfg,
+                                  const wn_tensor* weights, int32_t n_weights, int32_t device,
+                                  wn_model** out);
+
+/* Efficient Conformer encoders (`encoder: efficientConformer`, EfficientConformerEncoder,
+ * wenet/models/efficient_conformer/encoder.py:38-295) under the asr_model head: the conv2d
+ * (rate 4) or conv2d2 (rate 2, efficient_conformer/subsampling.py:25-75) front end, pre-LN
+ * macaron Conformer layers of which the ones in group_mask run the grouped attention and the
+ * ones in stride_layers halve the frame rate (StrideConformerEncoderLayer), after_norm.  In
+ * wn_config, cnn_kernel is the kernel of the layers up to and including the first stride layer. */
+typedef struct {
+  int32_t group_size;        /* frames per group of a grouped layer */
+  int32_t group_mask;        /* bit i: layer i runs GroupedRelPositionMultiHeadedAttention */
+  int32_t n_stride;          /* stride layers, <= 4 (each of stride 2) */
+  int32_t stride_layers[4];  /* ascending layer indices */
+  int32_t stride_kernel;     /* 1: the conv kernel is halved (K / 2) behind every stride layer */
+  int32_t front_rate;        /* 4: conv2d, 2: conv2d2 */
+  int32_t head_dim;          /* d_model / n_heads: 32 or 64 */
+} wn_efficonformer_config;
+
+/* wn_model_create for such a state dict (the names init_model gives it; the stride layers'
+ * concat_linear.* is never used by the reference and is not read).  On the handle, wn_encode runs
+ * the layer stack in fp32 with every utterance encoded as the reference encodes it ALONE: the
+ * zero frames of pad4group, the position rows and the average pool's last window end at the
+ * utterance's own length.  chunk / left set the attention mask; a chunk mask whose size is not
+ * divisible by the product of the strides is refused.  enc_lens_host and the padded output are
+ * at the FINAL rate: ceil(.. ceil(T' / 2) .. / 2) frames.  wn_encode_chunk*, wn_stream_create
+ * and a bf16 / fp8 precision are refused on such a handle. */
+int wn_model_create_efficonformer(const wn_config* cfg, const wn_efficonformer_config* ecfg,
                                   const wn_tensor* weights, int32_t n_weights, int32_t device,
                                   wn_model** out);
 

@@ -7,7 +7,7 @@ The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
-__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "Paraformer", "DecodeResult", "StreamingRecognizer",
+__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "EfficientConformer", "Paraformer", "DecodeResult", "StreamingRecognizer",
            "RnntBeamStreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
            "force_align_batch"]
 
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name == "Squeezeformer":
         from wenet_amd.squeezeformer import Squeezeformer
         return Squeezeformer
+    if name == "EfficientConformer":
+        from wenet_amd.efficonformer import EfficientConformer
+        return EfficientConformer
     if name == "DecodeResult":
         from wenet_amd.search import DecodeResult
         return DecodeResult

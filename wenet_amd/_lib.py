@@ -64,6 +64,13 @@ class WnSqueezeformerConfig(Structure):
                                        'do_rel_shift')]
 
 
+class WnEfficonformerConfig(Structure):
+    """wn_efficonformer_config: what an Efficient Conformer encoder has on top of wn_config."""
+    _fields_ = [('group_size', c_int32), ('group_mask', c_int32), ('n_stride', c_int32),
+                ('stride_layers', c_int32 * 4), ('stride_kernel', c_int32),
+                ('front_rate', c_int32), ('head_dim', c_int32)]
+
+
 class WnTensor(Structure):
     _fields_ = [('name', c_char_p), ('data', POINTER(c_float)),
                 ('numel', c_int64)]
@@ -147,6 +154,8 @@ EXPORTS = [
     'wn_model_create_branchformer', 'wn_op_csgu_gate', 'wn_op_merge_dwconv', 'wn_csgu_time_tile',
     'wn_model_create_squeezeformer', 'wn_op_attention_sqshift', 'wn_op_time_reduce',
     'wn_op_time_recover',
+    'wn_model_create_efficonformer', 'wn_op_attention_grouped', 'wn_op_stride_dwconv_ln_silu',
+    'wn_op_avgpool_residual_add',
     'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
     'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
 ]
@@ -340,6 +349,16 @@ def lib():
                                     pi32, i32, vp]
     L.wn_op_time_recover.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, pi32, pi32, pi32,
                                      i32, vp]
+    L.wn_model_create_efficonformer.argtypes = [POINTER(WnConfig), POINTER(WnEfficonformerConfig),
+                                                POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_attention_grouped.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, pi32, vp,
+                                          vp, vp, i32, pi32, pi32, i32, i32, i32, i32, i32, i32,
+                                          i32, f32, vp]
+    L.wn_op_stride_dwconv_ln_silu.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, f32,
+                                              i32, i32, i32, vp, i32, i32, pi32, pi32, pi32, i32,
+                                              vp]
+    L.wn_op_avgpool_residual_add.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, pi32,
+                                             pi32, pi32, i32, vp]
     L.wn_model_create_paraformer.argtypes = [POINTER(WnConfig), POINTER(WnParaformerConfig),
                                              POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_paraformer_decode.argtypes = [vp, pi32, pi32, POINTER(f32), pi32, pi32, i32, vp]

@@ -26,6 +26,7 @@ SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_bf16s.hip', 'gemm_bf16p.hip', 'gem
            'transducer_beam_stream.hip', 'cabi_transducer_beam_stream.hip',
            'firered.hip', 'cabi_firered.hip', 'branchformer.hip', 'cabi_branchformer.hip',
            'squeezeformer.hip', 'cabi_squeezeformer.hip',
+           'efficonformer.hip', 'cabi_efficonformer.hip',
            'attention_d128.hip', 'paraformer.hip', 'cabi_paraformer.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
          '-fno-gpu-rdc', '-Wno-unused-result']

@@ -153,7 +153,7 @@ int wn_model_create_branchformer(const wn_config* cfg, const wn_branchformer_con
                                  const wn_tensor* weights, int32_t n_weights, int32_t device,
                                  wn_model** out) {
   WN_CHECK(bcfg, "wn_model_create_branchformer: null argument");
-  return create_model_impl(cfg, nullptr, nullptr, nullptr, bcfg, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, bcfg, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int32_t wn_csgu_time_tile(void) { return CSGU_TILE; }

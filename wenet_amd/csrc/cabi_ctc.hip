@@ -534,6 +534,7 @@ int wn_stream_create(wn_model* m, int32_t n_slots, int32_t beam, int32_t max_fra
   WN_CHECK(!m->fr.on, "wn_stream_create: the FireRed encoder does not stream");
   WN_CHECK(!m->bf.on, "wn_stream_create: a Branchformer encoder does not stream");
   WN_CHECK(!m->sq.on, "wn_stream_create: a Squeezeformer encoder does not stream");
+  WN_CHECK(!m->ef.on, "wn_stream_create: an Efficient Conformer encoder does not stream");
   WN_CHECK(n_slots >= 1 && max_frames >= 1 && blank_id >= 0, "wn_stream_create: bad argument");
   WN_CHECK(beam >= 1, "wn_stream_create: beam_size must be positive");
   WN_CHECK(beam <= 16, "wn_stream_create: streaming sessions support beam sizes 1..16; larger "

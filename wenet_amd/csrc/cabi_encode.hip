@@ -105,6 +105,14 @@ int wn_encode(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host
     return encode_squeezeformer(m, feats_dev, feat_lens_host, B, T, chunk, left, enc_out_dev,
                                 enc_lens_host, (hipStream_t)stream);
   }
+  if (m->ef.on) {
+    WN_CHECK(m->prec == PREC_F32, "wn_encode: an Efficient Conformer handle stays fp32");
+    WN_CHECK(T >= (m->ef.c.front_rate == 4 ? 7 : 3),
+             "wn_encode: at least 7 (conv2d) / 3 (conv2d2) frames are needed by the front end");
+    WN_HIP(hipSetDevice(m->device));
+    return encode_efficonformer(m, feats_dev, feat_lens_host, B, T, chunk, left, enc_out_dev,
+                                enc_lens_host, (hipStream_t)stream);
+  }
   if (m->cfg.encoder_type == 1) {
     WN_CHECK(chunk < 0 && m->cfg.static_chunk_size <= 0,
              "chunk decoding is not implemented for the transformer encoder");
@@ -154,6 +162,8 @@ int wn_encode_chunk_batch(wn_model* m, int32_t n_sess, const float* feats_dev, i
                       "cgMLP conv cache)");
   WN_CHECK(!m->sq.on, "wn_encode_chunk: no chunk-by-chunk path for a Squeezeformer encoder (the "
                       "time reduction's caches)");
+  WN_CHECK(!m->ef.on, "wn_encode_chunk: no chunk-by-chunk path for an Efficient Conformer encoder "
+                      "(the rate-mixed attention cache)");
   WN_CHECK(time >= 7, "wn_encode_chunk: at least 7 frames are needed by Conv2dSubsampling4");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));

@@ -144,7 +144,7 @@ int wn_model_create_firered(const wn_config* cfg, const wn_firered_config* fcfg,
                             const wn_tensor* weights, int32_t n_weights, int32_t device,
                             wn_model** out) {
   WN_CHECK(fcfg, "wn_model_create_firered: null argument");
-  return create_model_impl(cfg, nullptr, nullptr, fcfg, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, fcfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 }  // extern "C"

@@ -86,7 +86,8 @@ const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                          const wn_stateless_predictor_config* scfg,
                          const wn_firered_config* fcfg, const wn_branchformer_config* bcfg,
-                         const wn_squeezeformer_config* qcfg, const wn_tensor* weights,
+                         const wn_squeezeformer_config* qcfg,
+                         const wn_efficonformer_config* ecfg, const wn_tensor* weights,
                          int32_t n_weights, int32_t device, wn_model** out) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
@@ -154,7 +155,9 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
              "squeezeformer: an odd static_chunk_size with a time reduction is no chunk window at "
              "the half rate");
   }
-  WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || c.d_model / c.n_heads == 64),
+  const bool ef = ecfg != nullptr;
+  if (ef) WN_TRY(efficonformer_config_check(c, *ecfg, tcfg || fr || bf || sq));
+  WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || ef || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
            "decoder head dim must be 64");
@@ -178,6 +181,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (fr) { m->fr.on = true; m->fr.c = *fcfg; }
   if (bf) { m->bf.on = true; m->bf.c = *bcfg; }
   if (sq) { m->sq.on = true; m->sq.c = *qcfg; }
+  if (ef) { m->ef.on = true; m->ef.c = *ecfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -235,6 +239,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     hs.add("fr.conv2.b", b2, C);
     // out Linear(C * F2 -> d): the kernels write the reference's own column order c * F2 + f
     WN_TRY(stage_linear(src, hs, "encoder.embed.out.0", d, C * F2));
+  } else if (ef && ecfg->front_rate == 2) {
+    WN_TRY(efficonformer_stage_front2(src, hs, c, m->F1()));   // (cabi_efficonformer.hip)
   } else {  // conv1 (d,1,3,3) -> [tap][c]
     // (squeezeformer: DepthwiseConv2dSubsampling4 without dw_stride is the same pair of convs
     // under other names, squeezeformer/subsampling.py:52-67)
@@ -592,7 +598,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
     WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d));
   }
-  for (int i = 0; !tf && !fr && !bf && !sq && i < c.n_layers; ++i) {
+  if (ef) WN_TRY(efficonformer_stage_layers(src, hs, c, *ecfg));   // (cabi_efficonformer.hip)
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -761,6 +768,10 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.conv2.w = P("fr.conv2.w"); W.conv2.b = P("fr.conv2.b");
     W.conv2.out = C; W.conv2.in = 9 * C;
     W.sub_out = LIN("encoder.embed.out.0", d, C * F2);
+  } else if (ef && ecfg->front_rate == 2) {   // conv2d2: one conv, then the projection
+    W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
+    W.sub_out.w = P("sub_out.w"); W.sub_out.b = P("sub_out.b");
+    W.sub_out.out = d; W.sub_out.in = d * m->F1();
   } else {
     W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
     W.conv2.w = P("conv2.w"); W.conv2.b = P("conv2.b");
@@ -898,11 +909,13 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
       if (half) WN_TRY(linear(lp, W.pe, 2 * d, L.pos_tab, d, (c.max_pos + 1) / 2, 0));
       else WN_TRY(linear(lp, W.pe, d, L.pos_tab, d, c.max_pos, 0));
     }
+  } else if (ef) {
+    WN_TRY(efficonformer_bind(W, c, *ecfg));   // (cabi_efficonformer.hip)
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && !fr && !bf && !sq && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -987,7 +1000,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   // (firered, branchformer, squeezeformer: the plain fp32 path, no six-product / row-block images of the
   // encoder's weights; the decoders and the CTC head get theirs as in every other model)
-  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq));
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq || ef));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -997,14 +1010,14 @@ extern "C" {
 
 int wn_model_create(const wn_config* cfg, const wn_tensor* weights,
                     int32_t n_weights, int32_t device, wn_model** out) {
-  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer(const wn_config* cfg, const wn_transducer_config* tcfg,
                                const wn_tensor* weights, int32_t n_weights, int32_t device,
                                wn_model** out) {
   WN_CHECK(tcfg, "wn_model_create_transducer: null argument");
-  return create_model_impl(cfg, tcfg, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, nullptr, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -1012,7 +1025,7 @@ int wn_model_create_transducer_stateless(const wn_config* cfg, const wn_transduc
                                          const wn_tensor* weights, int32_t n_weights,
                                          int32_t device, wn_model** out) {
   WN_CHECK(tcfg && scfg, "wn_model_create_transducer_stateless: null argument");
-  return create_model_impl(cfg, tcfg, scfg, nullptr, nullptr, nullptr, weights, n_weights, device, out);
+  return create_model_impl(cfg, tcfg, scfg, nullptr, nullptr, nullptr, nullptr, weights, n_weights, device, out);
 }
 
 void wn_model_destroy(wn_model* m) { delete m; }
@@ -1027,6 +1040,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->fr.on = src->fr.on; m->fr.c = src->fr.c;
   m->bf.on = src->bf.on; m->bf.c = src->bf.c;
   m->sq.on = src->sq.on; m->sq.c = src->sq.c;
+  m->ef.on = src->ef.on; m->ef.c = src->ef.c;
   m->pf.on = src->pf.on; m->pf.c = src->pf.c;
   m->device = src->device;
   m->prec = src->prec;
@@ -1051,6 +1065,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(!m->sq.on || precision == PREC_F32,
            "wn_model_set_precision: a Squeezeformer handle stays fp32 (no bf16 / fp8 kernels for "
            "its encoder)");
+  WN_CHECK(!m->ef.on || precision == PREC_F32,
+           "wn_model_set_precision: an Efficient Conformer handle stays fp32 (no bf16 / fp8 "
+           "kernels for its encoder)");
   WN_CHECK(!m->pf.on || precision == PREC_F32,
            "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "
            "encoder and decoder)");

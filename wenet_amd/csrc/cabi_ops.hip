@@ -666,6 +666,135 @@ int wn_op_time_recover(const float* skip, int32_t lds, const float* z, int32_t l
   return time_recover_add(a, s);
 }
 
+int wn_op_attention_grouped(const float* Q, const float* K, const float* V, int32_t ldq,
+                            int32_t ldk, int32_t ldv, int32_t rows, const float* P, int32_t ldp,
+                            int32_t p_rows, const int32_t* p_off, const float* bias_u,
+                            const float* bias_v, float* O, int32_t ldo, const int32_t* off,
+                            const int32_t* len, int32_t n_seq, int32_t n_heads, int32_t group,
+                            int32_t width, int32_t mask_step, int32_t chunk_size,
+                            int32_t left_chunks, float scale, void* stream) {
+  WN_CHECK(Q && K && V && P && bias_u && bias_v && O && off && len,
+           "attention_grouped: null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 65536 && n_heads > 0 && n_heads < 65536,
+           "attention_grouped: n_seq / n_heads");
+  WN_CHECK(width == 96 || width == 192,
+           "attention_grouped: width = " + std::to_string(width) +
+               " (group * d_k) has no kernel: 96 and 192 have");
+  WN_CHECK(group >= 1 && group <= 16 && (n_heads * width) % group == 0,
+           "attention_grouped: group must be in [1, 16] and divide n_heads * width");
+  const int D = n_heads * width / group;
+  WN_CHECK(D % 4 == 0, "attention_grouped: n_heads * width / group must be a multiple of 4");
+  WN_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0,
+           "attention_grouped: strides must be multiples of 4 elements");
+  WN_CHECK(ldq >= D && ldk >= D && ldv >= D && ldo >= D && ldp >= D,
+           "attention_grouped: a stride is smaller than n_heads * width / group");
+  WN_CHECK(rows > 0 && p_rows > 0, "attention_grouped: empty buffers");
+  WN_CHECK(mask_step >= 1 && mask_step <= 4096, "attention_grouped: mask_step must be in [1, 4096]");
+  WN_CHECK(chunk_size >= 0 && chunk_size <= (1 << 20),
+           "attention_grouped: chunk_size must be in [0, 2^20] (0: full context)");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           "attention_grouped: rows outside the buffer, unordered or overlapping");
+  int max_len = 0;
+  std::vector<int> h((size_t)3 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i]; h[2 * n_seq + i] = p_off ? p_off[i] : 0;
+    WN_CHECK(h[2 * n_seq + i] >= 0 && (int64_t)h[2 * n_seq + i] + len[i] <= p_rows,
+             "attention_grouped: a sequence's position rows lie outside the table (p_off, p_rows)");
+    max_len = std::max(max_len, len[i]);
+  }
+  WN_CHECK(max_len > 0 && max_len <= (1 << 18), "attention_grouped: empty, or a sequence too long");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  GroupedAttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = P; a.ldp = ldp; a.bias_u = bias_u; a.bias_v = bias_v; a.O = O; a.ldo = ldo;
+  a.off = desc.as<int>(); a.len = a.off + n_seq; a.p_off = a.off + 2 * n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.group = group; a.width = width; a.D = D;
+  a.max_len = max_len; a.mask_step = mask_step; a.chunk_size = chunk_size;
+  a.left_chunks = left_chunks; a.scale = scale;
+  return attention_grouped(a, s);
+}
+
+// the layouts both stride hooks share: off | len | outgoing-rate off on the device; the outgoing
+// rows (len + 1) / 2 from off2 must lie inside rows2, ascending and disjoint
+static int stride_hook_layout(const int32_t* off, const int32_t* len, const int32_t* off2,
+                              int n_seq, int rows, int rows2, int stride, DevBuf& desc,
+                              int* max_len, hipStream_t s, const char* who) {
+  const std::string w(who);
+  WN_CHECK(off && len && off2, w + ": null argument");
+  WN_CHECK(stride == 2, w + ": stride = " + std::to_string(stride) + " has no kernel: 2 has");
+  WN_CHECK(n_seq > 0 && n_seq < 65536 && rows > 0 && rows2 > 0, w + ": n_seq / rows");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           w + ": rows outside the buffer, unordered or overlapping");
+  std::vector<int> h((size_t)3 * n_seq), len2(n_seq);
+  *max_len = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i]; h[2 * n_seq + i] = off2[i];
+    len2[i] = (len[i] + 1) / 2;
+    *max_len = std::max(*max_len, len[i]);
+  }
+  WN_CHECK(packed_ok(off2, len2.data(), n_seq, rows2),
+           w + ": outgoing rows outside the buffer, unordered or overlapping");
+  WN_CHECK(*max_len > 0, w + ": empty");
+  return upload_ints(desc, h, s);
+}
+
+int wn_op_stride_dwconv_ln_silu(const float* x, int32_t ldx, int32_t rows, int32_t D,
+                                const float* wt, const float* bias, const float* cpad,
+                                const float* ln_w, const float* ln_b, int32_t norm_mode,
+                                float eps, int32_t K, int32_t causal, int32_t stride, float* y,
+                                int32_t ldy, int32_t out_rows, const int32_t* off,
+                                const int32_t* len, const int32_t* out_off, int32_t n_seq,
+                                void* stream) {
+  WN_CHECK(x && wt && bias && ln_w && ln_b && y, "stride_dwconv_ln_silu: null argument");
+  WN_CHECK(D >= 64 && D % 64 == 0 && D <= 512 && ldx >= D && ldy >= D,
+           "stride_dwconv_ln_silu: D must be a multiple of 64 up to 512, strides >= D");
+  WN_CHECK(K >= 1 && K <= 63 && (causal || K % 2 == 1),
+           "stride_dwconv_ln_silu: K must be in [1, 63], odd unless causal");
+  WN_CHECK(norm_mode == 0 || norm_mode == 1, "stride_dwconv_ln_silu: norm_mode is 0 or 1");
+  WN_CHECK(rows > 0 && out_rows > 0, "stride_dwconv_ln_silu: empty buffers");
+  WN_CHECK(y + (int64_t)out_rows * ldy <= x || x + (int64_t)rows * ldx <= y,
+           "stride_dwconv_ln_silu: y overlaps x");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  int max_len = 0;
+  WN_TRY(stride_hook_layout(off, len, out_off, n_seq, rows, out_rows, stride, desc, &max_len, s,
+                            "stride_dwconv_ln_silu"));
+  StrideDwConvArgs a;
+  a.x = x; a.ldx = ldx; a.wt = wt; a.bias = bias; a.cpad = cpad; a.ln_w = ln_w; a.ln_b = ln_b;
+  a.norm_mode = norm_mode; a.y = y; a.ldy = ldy;
+  a.off = desc.as<int>(); a.len = a.off + n_seq; a.off2 = a.off + 2 * n_seq;
+  a.B = n_seq; a.D = D; a.K = K; a.causal = causal; a.stride = stride; a.max_len = max_len;
+  a.eps = eps;
+  return stride_dwconv_ln_silu(a, s);
+}
+
+int wn_op_avgpool_residual_add(const float* x, int32_t ldx, int32_t rows, const float* z,
+                               int32_t ldz, float* y, int32_t ldy, int32_t out_rows, int32_t C,
+                               int32_t stride, const int32_t* off, const int32_t* len,
+                               const int32_t* out_off, int32_t n_seq, void* stream) {
+  WN_CHECK(x && z && y, "avgpool_residual_add: null argument");
+  WN_CHECK(C >= 4 && C % 4 == 0 && ldx >= C && ldz >= C && ldy >= C && ldx % 4 == 0 &&
+               ldz % 4 == 0 && ldy % 4 == 0,
+           "avgpool_residual_add: C must be a multiple of 4, strides multiples of 4 elements, >= C");
+  WN_CHECK(rows > 0 && out_rows > 0, "avgpool_residual_add: empty buffers");
+  WN_CHECK(y + (int64_t)out_rows * ldy <= x || x + (int64_t)rows * ldx <= y,
+           "avgpool_residual_add: y overlaps x");
+  WN_CHECK(y == z || y + (int64_t)out_rows * ldy <= z || z + (int64_t)out_rows * ldz <= y,
+           "avgpool_residual_add: y overlaps z without being it");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  int max_len = 0;
+  WN_TRY(stride_hook_layout(off, len, out_off, n_seq, rows, out_rows, stride, desc, &max_len, s,
+                            "avgpool_residual_add"));
+  AvgPoolResidArgs a;
+  a.x = x; a.ldx = ldx; a.z = z; a.ldz = ldz; a.y = y; a.ldy = ldy;
+  a.off = desc.as<int>(); a.len = a.off + n_seq; a.off2 = a.off + 2 * n_seq;
+  a.B = n_seq; a.C = C; a.stride = stride; a.max_len = max_len;
+  return avgpool_residual_add(a, s);
+}
+
 int wn_op_firered_frontend(const float* feats, const float* mean, const float* istd,
                            const float* w1, const float* b1, const float* w2, const float* b2,
                            float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,

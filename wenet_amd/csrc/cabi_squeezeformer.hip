@@ -218,8 +218,8 @@ int wn_model_create_squeezeformer(const wn_config* cfg, const wn_squeezeformer_c
                                   const wn_tensor* weights, int32_t n_weights, int32_t device,
                                   wn_model** out) {
   WN_CHECK(qcfg, "wn_model_create_squeezeformer: null argument");
-  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, qcfg, weights, n_weights,
-                           device, out);
+  return create_model_impl(cfg, nullptr, nullptr, nullptr, nullptr, qcfg, nullptr, weights,
+                           n_weights, device, out);
 }
 
 }  // extern "C"

@@ -205,6 +205,63 @@ struct TimeRecoverArgs {
 };
 int time_recover_add(const TimeRecoverArgs& a, hipStream_t s);
 
+// Grouped self attention of the Efficient Conformer (efficonformer.hip;
+// GroupedRelPositionMultiHeadedAttention, efficient_conformer/attention.py:83-126, 180-258), fp32.
+// Q / K / V / P / O are packed (frames, D) matrices with their own row strides; sequence i is
+// frames off[i] .. off[i] + len[i] - 1 (P: from p_off[i], or 0).  Group row r, head hh, element
+// c < width: flat element e = hh * width + c of frames group * r .., i.e. frame group * r + e / D,
+// column e % D; frames >= len[i] read as zeros in all four operands and are not written.
+//   score(r, s) = ((q_r + u) . k_s + (q_r + v) . p_s) * scale   over ALL ceil(len / group) key rows
+// chunk_size > 0: query row r sees key row s iff, with m = mask_step,
+//   m s < ((m r) / chunk_size + 1) * chunk_size  and, for left_chunks >= 0,
+//   m s >= ((m r) / chunk_size - left_chunks) * chunk_size        (mask[:, ::m, ::m], mask.py)
+struct GroupedAttnArgs {
+  const float* Q; const float* K; const float* V;
+  int ldq, ldk, ldv;
+  const float* P; int ldp;
+  const int* p_off = nullptr;                   // [n_seq] or null
+  const float* bias_u; const float* bias_v;     // [n_heads][width]
+  float* O; int ldo;
+  const int* off; const int* len;               // [n_seq] first frame / frames
+  int n_seq, n_heads, group, width, D;          // D = n_heads * width / group
+  int max_len;                                  // frames of the longest sequence
+  int mask_step = 1, chunk_size = 0, left_chunks = -1;
+  float scale;
+};
+int attention_grouped(const GroupedAttnArgs& a, hipStream_t s);
+
+// Depthwise conv over time with stride 2 + LayerNorm over the channels (norm_mode 0) or the
+// per-channel affine (1) + SiLU (efficonformer.hip; efficient_conformer/convolution.py:64-72,
+// 141-146): packed rows at the incoming rate -> packed rows at ceil(len / stride),
+//   c[t][ch] = bias[ch] + sum_k wt[k][ch] * x[stride t - pad + k][ch],  pad = (K - 1) / 2 or K - 1
+// frames >= len being zeros, frames < 0 zeros or -- causal with cpad set -- the vector cpad.
+struct StrideDwConvArgs {
+  const float* x; int ldx;
+  const float* wt;                 // [K][D] tap-major
+  const float* bias;               // [D]
+  const float* cpad = nullptr;     // [D] or null: a causal module's left-pad frame
+  const float* ln_w; const float* ln_b;
+  int norm_mode = 0;
+  float* y; int ldy;
+  const int* off; const int* len;  // [B] incoming-rate first row / frames
+  const int* off2;                 // [B] outgoing-rate first row
+  int B, D, K, causal, stride, max_len;
+  float eps = 1e-5f;
+};
+int stride_dwconv_ln_silu(const StrideDwConvArgs& a, hipStream_t s);
+
+// The stride layer's residual (efficonformer.hip; AvgPool1d(2, 2, ceil_mode=True,
+// count_include_pad=False), efficient_conformer/encoder_layer.py:138-148):
+//   y[off2[b] + t] = z[off2[b] + t] + mean(x[off[b] + 2 t .. min(2 t + 2, len) - 1]);  y may be z
+struct AvgPoolResidArgs {
+  const float* x; int ldx;
+  const float* z; int ldz;
+  float* y; int ldy;
+  const int* off; const int* len; const int* off2;
+  int B, C, stride, max_len;
+};
+int avgpool_residual_add(const AvgPoolResidArgs& a, hipStream_t s);
+
 // FireRedASR front end (firered.hip): GlobalCMVN, six zero frames behind every utterance's own
 // last frame, Conv2d(1->C,3,2) + ReLU, Conv2d(C->C,3,2) + ReLU.  Utterance b has
 // t2_len[b] = ((len + 6 - 3) / 2 + 1 - 3) / 2 + 1 output frames and t1_len[b] = 2 t2_len[b] + 1

@@ -170,6 +170,13 @@ struct EncLayer {
   // Conformer's slots: norm_mha / norm_ff_mac / norm_conv / norm_final = layer_norm1 .. 4,
   // ffm1 / ffm2 = ffn1, ff1 / ff2 = ffn2; qkv, ffm1, ff1 and pw1 hold the adaptive scale folded
   // in; pos_tab is linear_pos of pe[0::2] for a block that runs at the half rate
+  // Efficient Conformer layers (wn_model::ef.on, cabi_efficonformer.hip): the Conformer's slots;
+  // ef_rate = product of the strides in front of the layer (pos_tab is linear_pos of
+  // pe[0::ef_rate]), ef_kernel its own cnn_module_kernel.  A grouped layer keeps Q | K | V, the
+  // table and linear_out d wide and bias_u / bias_v (h, group * d_k); a plain one lays heads of 32
+  // out as 64 columns like a Branchformer's
+  int ef_rate = 1, ef_kernel = 0;
+  bool ef_grouped = false, ef_stride = false;
 };
 
 struct TfLayer {  // TransformerEncoderLayer (encoder_layer.py:28-127)
@@ -333,6 +340,15 @@ struct wn_model {
   // ... its half-rate rows, their layout (off | len | row_utt in one block) and its own stager
   DevBuf sq_xh, sq_desc;
   Stager sq_stage;
+  // wn_model_create_efficonformer: an Efficient Conformer encoder (cabi_efficonformer.hip)
+  struct {
+    bool on = false;
+    wn_efficonformer_config c = {};
+  } ef;
+  // ... the rows behind a stride layer before they become x, the layouts of every rate (off |
+  // len | row_utt per rate in one block) and their own stager
+  DevBuf ef_x2, ef_desc;
+  Stager ef_stage;
   DevBuf pf_alpha, pf_img, pf_emb, pf_int, pf_x, pf_y, pf_t, pf_o, pf_q, pf_kv, pf_h, pf_out;
   PinnedBuf pf_host;
   int device = 0;
@@ -597,6 +613,17 @@ int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat
 int encode_squeezeformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                          int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
                          hipStream_t s);
+// (cabi_efficonformer.hip)
+namespace wn { struct Src; struct HostStage; }
+int efficonformer_config_check(const wn_config& c, const wn_efficonformer_config& e,
+                               bool other_family);
+int efficonformer_stage_front2(const wn::Src& src, wn::HostStage& hs, const wn_config& c, int F1);
+int efficonformer_stage_layers(const wn::Src& src, wn::HostStage& hs, const wn_config& c,
+                               const wn_efficonformer_config& e);
+int efficonformer_bind(ModelData& W, const wn_config& c, const wn_efficonformer_config& e);
+int encode_efficonformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
+                         hipStream_t s);
 // (cabi_paraformer.hip)
 int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
@@ -604,8 +631,8 @@ int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_l
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,
                       const wn_branchformer_config* bcfg, const wn_squeezeformer_config* qcfg,
-                      const wn_tensor* weights, int32_t n_weights, int32_t device,
-                      wn_model** out);
+                      const wn_efficonformer_config* ecfg, const wn_tensor* weights,
+                      int32_t n_weights, int32_t device, wn_model** out);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

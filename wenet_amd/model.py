@@ -51,6 +51,10 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         # (wenet_amd/squeezeformer.py: the encoder's own keys go into a wn_squeezeformer_config)
         from wenet_amd.squeezeformer import squeezeformer_config_from_yaml
         return squeezeformer_config_from_yaml(configs)[0]
+    if enc_type == 'efficientConformer':
+        # (wenet_amd/efficonformer.py: the encoder's own keys go into a wn_efficonformer_config)
+        from wenet_amd.efficonformer import efficonformer_config_from_yaml
+        return efficonformer_config_from_yaml(configs)[0]
     if enc_type == 'conformer':
         checks = dict(input_layer='conv2d', pos_enc_layer_type='rel_pos',
                       selfattention_layer_type='rel_selfattn',
@@ -317,6 +321,10 @@ class ASRModel:
             raise NotImplementedError(
                 "encoder 'squeezeformer' is outside the accelerated path of this class: "
                 'wenet_amd.Squeezeformer (load_model picks it)')
+        if configs.get('encoder') == 'efficientConformer':
+            raise NotImplementedError(
+                "encoder 'efficientConformer' is outside the accelerated path of this class: "
+                'wenet_amd.EfficientConformer (load_model picks it)')
         return config_from_yaml(configs)
 
     def _create(self, L, tensors, n: int, h) -> int:
@@ -1191,6 +1199,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     elif configs.get('encoder') == 'squeezeformer':
         from wenet_amd.squeezeformer import Squeezeformer
         model = Squeezeformer(configs, sd, device)
+    elif configs.get('encoder') == 'efficientConformer':
+        from wenet_amd.efficonformer import EfficientConformer
+        model = EfficientConformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

@@ -586,6 +586,84 @@ CONFIGS['librispeech_squeezeformer'] = _squeezeformer(256, 4, 4, 12, 5, 11, 31, 
                                                       4, 2048, 6, 5002)
 
 
+# Efficient Conformer under the asr_model head (examples/aishell/s0/conf/
+# train_u2++_efficonformer_v1.yaml, ..._v1_stream.yaml, ..._v2.yaml and the two librispeech ones)
+def _efficonformer(d, heads, ffn, blocks, input_layer, stride_idx, group_idx, stride_kernel, k,
+                   cnn_norm, causal, decoder, dec_heads, dec_ffn, dec_blocks, vocab) -> dict:
+    ec = dict(output_size=d, attention_heads=heads, linear_units=ffn, num_blocks=blocks,
+              dropout_rate=0.1, positional_dropout_rate=0.1, attention_dropout_rate=0.1,
+              input_layer=input_layer, pos_enc_layer_type='rel_pos', normalize_before=True,
+              activation_type='swish', use_cnn_module=True, cnn_module_kernel=k,
+              cnn_module_norm=cnn_norm, causal=causal, use_dynamic_chunk=True,
+              use_dynamic_left_chunk=False,
+              efficient_conf=dict(stride_layer_idx=list(stride_idx), stride=[2] * len(stride_idx),
+                                  group_layer_idx=list(group_idx), group_size=3,
+                                  stride_kernel=stride_kernel))
+    dc = dict(attention_heads=dec_heads, linear_units=dec_ffn, num_blocks=dec_blocks,
+              dropout_rate=0.1, positional_dropout_rate=0.1, self_attention_dropout_rate=0.1,
+              src_attention_dropout_rate=0.1)
+    mc = dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False)
+    if decoder == 'bitransformer':
+        dc['r_num_blocks'] = dec_blocks
+        mc['reverse_weight'] = 0.3
+    return {'input_dim': 80, 'output_dim': vocab, 'encoder': 'efficientConformer',
+            'encoder_conf': ec, 'decoder': decoder, 'decoder_conf': dc, 'model_conf': mc}
+
+
+# conv2d, heads of 32 (W = 96), grouped layers 0 and 1 of which 1 strides, the kernel halved
+# behind it (15 -> 7), non-causal, LayerNorm, two decoders
+CONFIGS['tiny_efficonformer_v1'] = _efficonformer(128, 4, 256, 4, 'conv2d', [1], [0, 1], True, 15,
+                                                  'layer_norm', False, 'bitransformer', 2, 96, 1,
+                                                  41)
+# conv2d2, heads of 64 (W = 192), two grouped stride layers (one at the half rate), the kernel
+# kept, causal, an eval-mode BatchNorm
+CONFIGS['tiny_efficonformer_v2'] = _efficonformer(128, 2, 256, 5, 'conv2d2', [1, 3], [1, 3], False,
+                                                  15, 'batch_norm', True, 'transformer', 2, 96, 1,
+                                                  41)
+# train_u2++_efficonformer_v1.yaml (aishell) at its encoder's widths, a decoder of 4 heads (the
+# recipe's 8 heads of 32 have no decoder kernel): tools/bench_efficonformer.py only
+CONFIGS['aishell_efficonformer_v1'] = _efficonformer(256, 8, 2048, 12, 'conv2d', [3], [0, 1, 2, 3],
+                                                     True, 15, 'layer_norm', False,
+                                                     'bitransformer', 4, 2048, 3, 4233)
+
+
+def _to_efficonformer(sd, configs, seed):
+    """The Conformer-shaped dict of make_state_dict under an EfficientConformerEncoder's shapes
+    (wenet/models/efficient_conformer/encoder.py:140-215): pos_bias_u / v of a grouped layer are
+    (h, group * d_k), the depthwise kernel behind a stride layer is K // 2 with stride_kernel,
+    a stride layer carries the concat_linear its forward never uses, and conv2d2 has one conv
+    and a projection over d * ((idim - 1) // 2) pixels."""
+    ec = configs['encoder_conf']
+    ef = ec['efficient_conf']
+    d, h = ec['output_size'], ec['attention_heads']
+    g = ef['group_size']
+    out = OrderedDict(sd)
+    if ec['input_layer'] == 'conv2d2':
+        del out['encoder.embed.conv.2.weight'], out['encoder.embed.conv.2.bias']
+        n_in = d * ((configs['input_dim'] - 1) // 2)
+        b = 1.0 / math.sqrt(n_in)
+        out['encoder.embed.out.0.weight'] = _uniform(seed, 'out2.weight', (d, n_in), b)
+        out['encoder.embed.out.0.bias'] = _uniform(seed, 'out2.bias', (d, ), b)
+    K = ec['cnn_module_kernel']
+    for i in range(ec['num_blocks']):
+        p = f'encoder.encoders.{i}'
+        if i in ef['group_layer_idx']:
+            b = math.sqrt(6.0 / (h + g * d // h))
+            for n in ('pos_bias_u', 'pos_bias_v'):
+                out[f'{p}.self_attn.{n}'] = _uniform(seed, f'{p}.grouped.{n}', (h, g * d // h), b)
+        if K != ec['cnn_module_kernel']:
+            b = 1.0 / math.sqrt(K)
+            out[p + '.conv_module.depthwise_conv.weight'] = _uniform(seed, p + '.dwk.w',
+                                                                     (d, 1, K), b)
+        if i in ef['stride_layer_idx']:
+            b = 1.0 / math.sqrt(2 * d)
+            out[p + '.concat_linear.weight'] = _uniform(seed, p + '.cat.w', (d, 2 * d), b)
+            out[p + '.concat_linear.bias'] = _uniform(seed, p + '.cat.b', (d, ), b)
+            if ef['stride_kernel']:
+                K = K // 2
+    return out
+
+
 def make_configs(name: str) -> dict:
     """Parsed-``train.yaml`` equivalent for a named configuration."""
     c = copy.deepcopy(CONFIGS[name])
@@ -918,6 +996,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         _add_transducer(sd, configs, seed, rnnt_blank_bias)
     if squeeze:
         sd = _to_squeezeformer(sd, configs, seed)
+    if configs.get('encoder') == 'efficientConformer':
+        sd = _to_efficonformer(sd, configs, seed)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
 
