@@ -808,6 +808,17 @@ int wn_op_attention_d128(const float* Q, const float* K, const float* V, int32_t
                          int32_t ldo, const int32_t* q_off, const int32_t* q_len,
                          const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
                          int32_t n_heads, float scale, void* stream);
+/* Attention for heads of d_k = 32 (n_heads * 32 columns per row; csrc/attention_d32.hip): the
+ * decoders of 8 heads at d_model 256.  The arguments of wn_op_attention_d128 plus mask_mode:
+ * 0 = every key < kv_len (cross attention), 1 = causal, key j <= query i AND j < kv_len (kv_len
+ * < q_len is the padded batch of wn_decoder_forward: keys at or past kv_len are hidden from every
+ * query).  No position term, no kbias, no chunk window (mask_mode 2 is refused by name).  fp32
+ * whatever the handles' compute type. */
+int wn_op_attention_d32(const float* Q, const float* K, const float* V, int32_t ldq,
+                        int32_t ldk, int32_t ldv, int32_t q_rows, int32_t kv_rows, float* O,
+                        int32_t ldo, const int32_t* q_off, const int32_t* q_len,
+                        const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
+                        int32_t n_heads, float scale, int32_t mask_mode, void* stream);
 /* The LFR front end of every utterance ALONE (paraformer/layers.py:24-92): utterance b of
  * lens[b] frames gives out_len[b] = ceil(lens[b] / n) rows from row out_off[b]; row t stacks the
  * m frames n t - (m - 1) / 2 + f (each index clamped to [0, lens[b] - 1]), then GlobalCMVN over
@@ -872,7 +883,7 @@ int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_
  * n_done_host.  Index arrays a kernel dereferences (the path rows, last_tok of the embedding) are
  * read back and range-checked before the launch; the other arrays are only copied or clamped.
  * Layouts: qkv [n][3d] (Q | K | V), cache [steps][n][2d] (K | V), path / tok rows of max_len
- * ints, d = heads * 64.
+ * ints, d = heads * 64 (attn_self_step: or heads * 32, the decoders of 8 heads at 256).
  *   attn_self_step   stores K | V of qkv into cache[step], then row r attends over positions
  *                    0..step, position j read from cache[j][path[r][j]]; out [n][d]
  *   attn_step_embed  x[r] = emb[last_tok[r]] * scale + pe[pos]; emb [V][d], pe [max_pos][d]

@@ -16,6 +16,12 @@ Writes profiles/efficonformer_aishell.json and docs/LOG_round26.md (or both into
   stride_dwconv_us / avgpool_residual_us   likewise, with the bytes the kernels must move
 The hook's descriptor upload (one small host-to-device copy) is inside every bracket.  The path
 is untuned and every figure comes from ONE run of this tool: a record, not a pass mark.
+
+    python tools/bench_efficonformer.py --leg dec8 [--steps 10] [--warmup 3] [--out-dir DIR]
+
+The decoder leg (dec8_leg below): `aishell_efficonformer_v1_dec8`, the recipe with its own 8-head
+decoders, beside the 4-head `aishell_efficonformer_v1`; writes
+profiles/efficonformer_aishell_dec8.json and docs/LOG_round27.md.
 """
 import argparse
 import json
@@ -127,13 +133,69 @@ def hook_launches(lens0, H, d, K, steps, warmup):
                 avgpool_residual_bytes=int(4 * d * (M + 2 * M2)), rows=M, half_rows=M2)
 
 
+def wall_ms(fn, steps, warmup):
+    """Wall time per call of a decode (host work and result copies included)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def dec8_leg(args):
+    """The decoder leg: `aishell_efficonformer_v1_dec8` (the recipe as shipped: two decoders of 8
+    heads of 32 on attention_d32 and the d_k = 32 step kernel) beside the 4-head
+    `aishell_efficonformer_v1` (heads of 64 on attention_kernel), same process, same batch:
+    model.decode wall time of `attention_rescoring` and of `attention`, both at beam 10.  Two
+    different models (the same weight matrices cut into 8 or 4 heads: other functions, other
+    hypotheses): a record of one run, gating nothing.  Writes
+    profiles/efficonformer_aishell_dec8.json and docs/LOG_round27.md."""
+    from wenet_amd import EfficientConformer
+    from wenet_amd import synthetic as S
+    feats, lens = S.make_features(args.batch, (800, 1200), seed=7)
+    feats = feats.cuda()
+    res = dict(status='measured', batch=args.batch, audio_s=float(lens.sum()) * 0.01,
+               steps=args.steps, warmup=args.warmup, dtype='fp32', runs=1, tuned=False, beam=10)
+    for key, name in (('dec8', 'aishell_efficonformer_v1_dec8'),
+                      ('dec4', 'aishell_efficonformer_v1')):
+        configs = S.make_configs(name)
+        model = EfficientConformer(configs, S.make_state_dict(configs, 0), device='cuda:0')
+        res[key + '_config'] = name
+        res[key + '_heads'] = configs['decoder_conf']['attention_heads']
+        for mode in ('attention_rescoring', 'attention'):
+            kw = dict(beam_size=10, ctc_weight=0.5, reverse_weight=0.3) \
+                if mode == 'attention_rescoring' else dict(beam_size=10)
+            out = model.decode([mode], feats, lens, **kw)[mode]
+            res[f'{key}_{mode}_ms'] = wall_ms(lambda: model.decode([mode], feats, lens, **kw),
+                                              args.steps, args.warmup)
+            res[f'{key}_{mode}_tokens'] = int(sum(len(r.tokens) for r in out))
+        del model
+    pdir = args.out_dir or os.path.join(ROOT, 'profiles')
+    ldir = args.out_dir or os.path.join(ROOT, 'docs')
+    os.makedirs(pdir, exist_ok=True)
+    with open(os.path.join(pdir, 'efficonformer_aishell_dec8.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    with open(os.path.join(ldir, 'LOG_round27.md'), 'w') as f:
+        f.write(LOG_DEC8.format(**res))
+    print(json.dumps(res))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--out-dir', default=None)
+    ap.add_argument('--leg', choices=('encoder', 'dec8'), default='encoder',
+                    help='encoder: the encoder and its kernels; dec8: the 8-head decoders')
     args = ap.parse_args(argv)
+    if args.leg == 'dec8':
+        return dec8_leg(args)
     from wenet_amd import ASRModel, EfficientConformer
     from wenet_amd import synthetic as S
     t0 = time.time()
@@ -207,6 +269,25 @@ has not been measured.  Not measured either: a kernel trace of the encoder (the
 per-launch times inside the layer stack), W = 192, chunk masks, the causal and batch_norm
 variants, the conv2d2 front end, occupancy or LDS-bank counters of `attention_grouped` (the
 compiler reports 264 registers at W = 96 and 404 at W = 192, one wave per SIMD, no scratch).
+"""
+
+LOG_DEC8 = """# Round 27: decoder heads of 32
+
+`tools/bench_efficonformer.py --leg dec8`: `{dec8_config}` (the recipe as
+shipped: two decoders of {dec8_heads} heads of 32 on `attention_d32` and the d_k = 32 step kernel) beside `{dec4_config}`
+({dec4_heads} heads of 64 on `attention_kernel`), synthetic weights, same process, same batch:
+B = {batch} x 8-12 s ({audio_s:.1f} s of audio), fp32, beam {beam}, wall time of `model.decode`
+per call over {steps} calls after {warmup}.  All numbers: profiles/efficonformer_aishell_dec8.json.
+Two DIFFERENT models (the same synthetic weight matrices cut into 8 or 4 heads: other functions,
+other hypotheses), ONE run, untuned: a record, not a pass mark and not a ratio.
+
+| mode | 8 heads of 32: ms | tokens out | 4 heads of 64: ms | tokens out |
+| --- | --- | --- | --- | --- |
+| `attention_rescoring` | {dec8_attention_rescoring_ms:.2f} | {dec8_attention_rescoring_tokens} | {dec4_attention_rescoring_ms:.2f} | {dec4_attention_rescoring_tokens} |
+| `attention` | {dec8_attention_ms:.2f} | {dec8_attention_tokens} | {dec4_attention_ms:.2f} | {dec4_attention_tokens} |
+
+Not measured: a kernel trace of either decode (the share of the attention launches in these wall
+times), `attention_d32` per launch, more than one wave per block, LDS-bank counters.
 """
 
 if __name__ == '__main__':

@@ -158,6 +158,7 @@ EXPORTS = [
     'wn_op_avgpool_residual_add',
     'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
     'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
+    'wn_op_attention_d32',
 ]
 
 _lib = None
@@ -364,6 +365,8 @@ def lib():
     L.wn_paraformer_decode.argtypes = [vp, pi32, pi32, POINTER(f32), pi32, pi32, i32, vp]
     L.wn_op_attention_d128.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, pi32, pi32,
                                        pi32, pi32, i32, i32, f32, vp]
+    L.wn_op_attention_d32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, pi32, pi32,
+                                      pi32, pi32, i32, i32, f32, i32, vp]
     L.wn_op_lfr_front.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, pi32, pi32, pi32,
                                   i32, i32, i32, i32, i32, f32, f32, vp]
     L.wn_op_layernorm_wide.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp]

@@ -69,6 +69,55 @@ __global__ __launch_bounds__(64) void self_attn_step_kernel(
   out[(int64_t)r * ldo + h * 64 + lane] = acc / l_run;
 }
 
+// The same step for heads of d_k = 32 (Q at column h*32, K at h*32, V at d + h*32): one wave per
+// (hypothesis, head), lane = key for the scores, 64 cached keys per block.  With lane =
+// dimension the P.V phase would leave lanes 32..63 idle, so it takes TWO keys per pass: lanes
+// 0..31 the even key of the pair, lanes 32..63 the odd one, each half a coalesced 128-byte cache
+// row; the two partial sums meet in one exchange with lane^32 at the end.
+__global__ __launch_bounds__(64) void self_attn_step_d32_kernel(
+    const float* __restrict__ q, int ldq, const float* __restrict__ cache, int n, int d,
+    const int* __restrict__ path, int max_len, int len, float scale, float* __restrict__ out,
+    int ldo) {
+  const int r = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+  const int half = lane >> 5, dim = lane & 31;
+  const float* qp = q + (int64_t)r * ldq + h * 32;
+  f32x4 qv[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) qv[i] = *reinterpret_cast<const f32x4*>(qp + 4 * i);
+  float m_run = -INFINITY, l_run = 0.f, acc = 0.f;   // acc: output dim `dim`, keys of `half`
+  for (int j0 = 0; j0 < len; j0 += 64) {
+    const int j = j0 + lane;
+    float sc = -INFINITY;
+    int row = 0;
+    if (j < len) {
+      row = j * n + path[(int64_t)r * max_len + j];
+      const float* kp = cache + (int64_t)row * 2 * d + h * 32;
+      float dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const f32x4 kv = *reinterpret_cast<const f32x4*>(kp + 4 * i);
+        dot += qv[i][0] * kv[0] + qv[i][1] * kv[1] + qv[i][2] * kv[2] + qv[i][3] * kv[3];
+      }
+      sc = dot * scale;
+    }
+    const float m_new = fmaxf(m_run, wave_max(sc));
+    const float p = j < len ? __expf(sc - m_new) : 0.f;
+    const float corr = __expf(m_run - m_new);
+    l_run = l_run * corr + wave_sum(p);
+    acc *= corr;
+    const int nb = min(64, len - j0);
+    for (int t0 = 0; t0 < nb; t0 += 2) {
+      const int t = t0 + half;                 // <= 63
+      const float pt = __shfl(p, t, 64);
+      const int rt = __shfl(row, t, 64);
+      if (t < nb) acc += pt * cache[(int64_t)rt * 2 * d + d + h * 32 + dim];
+    }
+    m_run = m_new;
+  }
+  acc += __shfl_xor(acc, 32, 64);
+  if (half == 0) out[(int64_t)r * ldo + h * 32 + dim] = acc / l_run;
+}
+
 // K | V of this step's rows -> cache[step]
 __global__ void cache_store_kernel(const float* __restrict__ qkv, int d, int n,
                                    float* __restrict__ cache_step) {
@@ -235,10 +284,16 @@ int attn_prompt_cache_store(const float* qkv, int d, int B, int P, int N, float*
 
 int attn_self_step(const float* qkv, int d, int heads, int n, float* cache, int step,
                    const int* path, int max_len, float* out, hipStream_t s) {
+  WN_CHECK(heads > 0 && (d == heads * 64 || d == heads * 32),
+           "attn_self_step: d must be heads * 64 or heads * 32");
   hipLaunchKernelGGL(cache_store_kernel, dim3(n), dim3(128), 0, s, qkv, d, n,
                      cache + (int64_t)step * n * 2 * d);
-  hipLaunchKernelGGL(self_attn_step_kernel, dim3(n, heads), dim3(64), 0, s, qkv, 3 * d, cache, n,
-                     d, path, max_len, step + 1, 0.125f, out, d);
+  if (d == heads * 32)   // heads of 32: the two-keys-per-pass form
+    hipLaunchKernelGGL(self_attn_step_d32_kernel, dim3(n, heads), dim3(64), 0, s, qkv, 3 * d,
+                       cache, n, d, path, max_len, step + 1, 1.0f / sqrtf(32.0f), out, d);
+  else
+    hipLaunchKernelGGL(self_attn_step_kernel, dim3(n, heads), dim3(64), 0, s, qkv, 3 * d, cache,
+                       n, d, path, max_len, step + 1, 0.125f, out, d);
   WN_HIP(hipGetLastError());
   return 0;
 }

@@ -73,6 +73,18 @@ struct PrefillCache {
 // FFN activation of the decoders: ReLU, or the Whisper decoder's exact GELU
 inline int dec_act(const wn_config& c) { return c.dec_activation == 1 ? ACT_GELU : ACT_RELU; }
 
+// The decoders' self / cross attention by head width: heads of 64 on attention() as ever (the
+// scale is the literal 0.125f), heads of 32 directly on attention_d32 -- never through
+// attention_form(), so their attention stays fp32 on bf16 and fp8 handles.
+inline int dec_attention(const wn_config& c, AttnArgs& a, hipStream_t s) {
+  if (c.d_model / c.dec_heads == 32) {
+    a.scale = 1.0f / sqrtf(32.0f);
+    return attention_d32(a, s);
+  }
+  a.scale = 0.125f;
+  return attention(a, s);
+}
+
 // embed + the decoder layers over a ragged batch of R token rows (n_seq
 // sequences); the result stays in m->r_x.  With `mem_cache` the cross-attention
 // K/V projections of the encoder output are computed once per batch and layer
@@ -121,8 +133,8 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
     // & subsequent_mask, decoder.py:171-177)
     if (self_kvlen) a.kv_len = self_kvlen;
     a.n_seq = n_seq; a.n_heads = c.dec_heads; a.max_q_len = max_q;
-    a.mask_mode = 1; a.scale = 0.125f;
-    WN_TRY(attention(a, s));
+    a.mask_mode = 1;
+    WN_TRY(dec_attention(c, a, s));
     WN_TRY(linear(L.self_out, t2, d, x, d, R, s, ACT_NONE, x, d));
     // cross attention over the utterance's encoder frames   decoder_layer.py:123-138
     // (K/V projected once per utterance, not once per hypothesis)
@@ -144,8 +156,8 @@ int decoder_layers(wn_model* m, const Decoder& D, int R, int n_seq, int max_q,
       cx.q_off = cg->q_off; cx.q_len = cg->q_len; cx.kv_off = cg->kv_off; cx.kv_len = cg->kv_len;
       cx.n_seq = cg->n_seq; cx.max_q_len = cg->max_q;
     }
-    cx.mask_mode = 0; cx.scale = 0.125f;
-    WN_TRY(attention(cx, s));
+    cx.mask_mode = 0;
+    WN_TRY(dec_attention(c, cx, s));
     WN_TRY(linear(L.src_out, t1, d, x, d, R, s, ACT_NONE, x, d));
     // FFN (ReLU; GELU in the Whisper decoder)            decoder_layer.py:140-147
     WN_TRY(ln(L.n3, x, t1, R, d, eps, s));
@@ -626,8 +638,8 @@ int beam_search_run(wn_model* m, int beam, int maxlen, float length_penalty,
       cx.q_off = b_qoff.as<int>(); cx.q_len = b_qlen.as<int>();
       cx.kv_off = b_kvoff.as<int>(); cx.kv_len = b_kvlen.as<int>();
       cx.n_seq = n_cx; cx.n_heads = c.dec_heads; cx.max_q_len = cx_q;
-      cx.mask_mode = 0; cx.scale = 0.125f;
-      WN_TRY(attention(cx, s));
+      cx.mask_mode = 0;
+      WN_TRY(dec_attention(c, cx, s));
       WN_TRY(step_linear(m, skinny, L.src_out, t1, d, x, d, BN, s, ACT_NONE, x, d));
       WN_TRY(ln(L.n3, x, t1, BN, d, eps, s));
       WN_TRY(step_linear(m, skinny, L.ff1, t1, d, hb, c.dec_ffn_dim, BN, s, act));

@@ -159,8 +159,10 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (ef) WN_TRY(efficonformer_config_check(c, *ecfg, tcfg || fr || bf || sq));
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || ef || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
-  WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 || c.d_model / c.dec_heads == 64,
-           "decoder head dim must be 64");
+  WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 ||
+               (c.d_model % c.dec_heads == 0 &&
+                (c.d_model / c.dec_heads == 64 || c.d_model / c.dec_heads == 32)),
+           "decoder head dim must be 32 or 64");
   WN_CHECK(c.ffn_dim % 32 == 0 && c.feat_dim >= 7 && c.feat_dim <= 128,
            "unsupported ffn_dim / feat_dim");
   WN_CHECK(c.dec_activation == 0 || c.dec_activation == 1, "dec_activation: 0 relu, 1 gelu");

@@ -949,13 +949,63 @@ int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_
   return ctc_logsoftmax_topk(a, (hipStream_t)stream);
 }
 
+// ---- attention for decoder heads of 32 (attention_d32.hip) ------------------------------------
+
+int wn_op_attention_d32(const float* Q, const float* K, const float* V, int32_t ldq, int32_t ldk,
+                        int32_t ldv, int32_t q_rows, int32_t kv_rows, float* O, int32_t ldo,
+                        const int32_t* q_off, const int32_t* q_len, const int32_t* kv_off,
+                        const int32_t* kv_len, int32_t n_seq, int32_t n_heads, float scale,
+                        int32_t mask_mode, void* stream) {
+  WN_CHECK(Q && K && V && O && q_off && q_len && kv_off && kv_len,
+           "attention_d32: null argument");
+  WN_CHECK(mask_mode == 0 || mask_mode == 1,
+           "attention_d32: mask_mode must be 0 (keys < kv_len) or 1 (causal), not 2 (chunk window)");
+  WN_CHECK(n_seq > 0 && n_seq < 32768 && n_heads > 0 && n_heads < 256,
+           "attention_d32: n_seq / n_heads");
+  const int d = n_heads * 32;
+  WN_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0,
+           "attention_d32: strides must be multiples of 4 elements");
+  WN_CHECK(ldq >= d && ldk >= d && ldv >= d && ldo >= d,
+           "attention_d32: a stride is smaller than n_heads * 32");
+  WN_CHECK(q_rows > 0 && kv_rows > 0, "attention_d32: empty buffers");
+  WN_CHECK(((uintptr_t)Q & 15) == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)V & 15) == 0,
+           "attention_d32: Q, K and V must be 16-byte aligned");
+  WN_CHECK(packed_ok(q_off, q_len, n_seq, q_rows),
+           "attention_d32: query rows outside the buffer, unordered or overlapping");
+  int max_q = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    WN_CHECK(kv_len[i] >= 0 && kv_off[i] >= 0 && (int64_t)kv_off[i] + kv_len[i] <= kv_rows,
+             "attention_d32: key rows outside the buffer");
+    WN_CHECK(q_len[i] == 0 || kv_len[i] > 0, "attention_d32: queries without keys");
+    max_q = std::max(max_q, q_len[i]);
+  }
+  WN_CHECK(max_q > 0, "attention_d32: empty");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  std::vector<int> h((size_t)4 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = q_off[i]; h[n_seq + i] = q_len[i];
+    h[2 * n_seq + i] = kv_off[i]; h[3 * n_seq + i] = kv_len[i];
+  }
+  WN_TRY(upload_ints(desc, h, s));
+  const int* dd = desc.as<int>();
+  AttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.O = O; a.ldo = ldo;
+  a.q_off = dd; a.q_len = dd + n_seq; a.kv_off = dd + 2 * n_seq; a.kv_len = dd + 3 * n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_q_len = max_q;
+  a.mask_mode = mask_mode; a.scale = scale;
+  return attention_d32(a, s);
+}
+
 // ---- the `attention` decode mode's kernels (attn_search.hip), one launcher per hook ----------
 
 int wn_op_attn_self_step(const float* qkv, int32_t d, int32_t heads, int32_t n, float* cache,
                          int32_t step, const int32_t* path, int32_t max_len, float* out,
                          void* stream) {
   WN_CHECK(qkv && cache && path && out, "attn_self_step: null argument");
-  WN_CHECK(heads >= 1 && heads < 256 && d == heads * 64, "attn_self_step: d must be heads * 64");
+  WN_CHECK(heads >= 1 && heads < 256 && (d == heads * 64 || d == heads * 32),
+           "attn_self_step: d must be heads * 64 or heads * 32");
   WN_CHECK(n >= 1 && n <= 4096, "attn_self_step: n outside [1, 4096]");
   WN_CHECK(step >= 0 && step + 1 <= max_len && max_len <= 65536,
            "attn_self_step: step outside [0, max_len)");

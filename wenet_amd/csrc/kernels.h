@@ -930,6 +930,12 @@ int rnnt_lattice(const RnntLatticeArgs& a, hipStream_t s);
 // separate Q and K / V layouts (self and cross attention).  attention() itself stays d_k = 64.
 int attention_d128(const AttnArgs& a, hipStream_t s);
 
+// ---- decoders with heads of 32 (attention_d32.hip), fp32 -----------------------------------
+// attention() for heads of d_k = 32 (n_heads * 32 columns): mask_mode 0 (cross attention) or 1
+// (causal, kv_len < q_len allowed: the padded batches of wn_decoder_forward), no position term,
+// no kbias, no block list.  Always fp32: it does not go through attention_form().
+int attention_d32(const AttnArgs& a, hipStream_t s);
+
 // LFR front end (paraformer/layers.py:24-92 on ONE utterance, paraformer.py:329-350): output row
 // t of utterance b stacks the m frames n t - (m - 1) / 2 + f, f < m, each index clamped to
 // [0, len[b] - 1]; then GlobalCMVN over the m F columns, x * xscale + pe[t + 1], and the

@@ -620,11 +620,38 @@ CONFIGS['tiny_efficonformer_v1'] = _efficonformer(128, 4, 256, 4, 'conv2d', [1],
 CONFIGS['tiny_efficonformer_v2'] = _efficonformer(128, 2, 256, 5, 'conv2d2', [1, 3], [1, 3], False,
                                                   15, 'batch_norm', True, 'transformer', 2, 96, 1,
                                                   41)
-# train_u2++_efficonformer_v1.yaml (aishell) at its encoder's widths, a decoder of 4 heads (the
-# recipe's 8 heads of 32 have no decoder kernel): tools/bench_efficonformer.py only
+# train_u2++_efficonformer_v1.yaml (aishell) at its encoder's widths, a decoder of 4 heads (it
+# predates the d_k = 32 decoder kernels and profiles/efficonformer_aishell.json was measured on
+# it; the recipe's own 8 heads: aishell_efficonformer_v1_dec8): tools/bench_efficonformer.py only
 CONFIGS['aishell_efficonformer_v1'] = _efficonformer(256, 8, 2048, 12, 'conv2d', [3], [0, 1, 2, 3],
                                                      True, 15, 'layer_norm', False,
                                                      'bitransformer', 4, 2048, 3, 4233)
+# decoders with heads of 32 (csrc/attention_d32.hip, self_attn_step_d32_kernel): tiny_efficonformer_v1
+# with 4 decoder heads at 128
+CONFIGS['tiny_efficonformer_v1_dec32'] = _efficonformer(128, 4, 256, 4, 'conv2d', [1], [0, 1], True,
+                                                        15, 'layer_norm', False, 'bitransformer', 4,
+                                                        96, 1, 41)
+# train_u2++_efficonformer_v1.yaml (aishell) as shipped: the decoders' 8 heads of 32 ...
+CONFIGS['aishell_efficonformer_v1_dec8'] = _efficonformer(256, 8, 2048, 12, 'conv2d', [3],
+                                                          [0, 1, 2, 3], True, 15, 'layer_norm',
+                                                          False, 'bitransformer', 8, 2048, 3, 4233)
+# ... and one encoder block (grouped), one block per decoder, a small vocabulary at the same
+# widths: the width test
+CONFIGS['aishell_efficonformer_v1_dec8_1blk'] = _efficonformer(256, 8, 2048, 1, 'conv2d', [], [0],
+                                                               True, 15, 'layer_norm', False,
+                                                               'bitransformer', 8, 2048, 1, 41)
+# the tiny_bn Conformer (LayerNorm in the conv module) under two decoders of 4 heads at 128
+CONFIGS['tiny_dec32'] = {
+    'input_dim': 80, 'output_dim': 41,
+    'encoder': 'conformer',
+    'encoder_conf': dict(CONFIGS['tiny_bn']['encoder_conf'], cnn_module_norm='layer_norm'),
+    'decoder': 'bitransformer',
+    'decoder_conf': dict(attention_heads=4, linear_units=96, num_blocks=2, r_num_blocks=2,
+                         dropout_rate=0.1, positional_dropout_rate=0.1,
+                         self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0),
+    'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False,
+                       reverse_weight=0.3),
+}
 
 
 def _to_efficonformer(sd, configs, seed):
