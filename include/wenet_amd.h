@@ -1151,6 +1151,45 @@ int wn_model_create_paraformer(const wn_config* cfg, const wn_paraformer_config*
 int wn_paraformer_decode(wn_model* m, int32_t* tokens, int32_t* tok_lens, float* logp,
                          int32_t* fire_frames, int32_t* n_fire, int32_t max_tok, void* stream);
 
+/* ---- SenseVoice Small (`model: sensevoice_small`, wenet/models/sensevoice/): four query rows
+ * (language | event | emotion | text norm, rows of a 16 x 560 embedding table) in front of the LFR
+ * rows of every utterance, the SANM encoder stack, after_norm, a second stack (tp_encoders) and
+ * tp_norm, a CTC head; fp32.  Of wn_config it reads feat_dim (80), d_model, n_heads (d_model /
+ * n_heads in {64, 128}), ffn_dim, n_layers (blocks of the first stack, encoders0 included),
+ * vocab, has_cmvn (must be 1), norm_eps. */
+typedef struct {
+  int32_t lfr_m, lfr_n;        /* 7, 6 */
+  int32_t kernel_size;         /* FSMN taps of both stacks, odd (11) */
+  int32_t tp_blocks;           /* encoder_conf.tp_blocks (20) */
+  int32_t max_frames;          /* LFR rows a handle's position table covers (+ the query rows) */
+  int32_t n_query;             /* 4: any other value is refused */
+  int32_t n_embed;             /* 16: any other value is refused */
+} wn_sensevoice_config;
+/* State dict names as init_model gives them: global_cmvn.mean / .istd (the model takes the CMVN
+ * off its encoder), embed.weight (16, 560), encoder.encoders0.0.*, encoder.encoders.N.*,
+ * encoder.after_norm.*, encoder.tp_encoders.N.*, encoder.tp_norm.*, ctc.ctc_lo.*; CMVN and the
+ * CTC head are required.  encoder.embed.pos_enc.pe is rebuilt here.  wn_encode on the handle
+ * encodes every utterance as the reference encodes it ALONE: ceil(n / 6) + 4 frames (none for
+ * n == 0); wn_ctc_* then work as on any handle.  No chunks, no streams, no bf16 / fp8. */
+int wn_model_create_sensevoice(const wn_config* cfg, const wn_sensevoice_config* scfg,
+                               const wn_tensor* weights, int32_t n_weights, int32_t device,
+                               wn_model** out);
+/* The query ids (HOST, B x 4, each in [0, 16)) of the NEXT wn_encode only, which must run on B
+ * utterances; qid_host NULL (B ignored) drops stored ids.  Without stored ids every utterance
+ * gets (0, 1, 2, 15): language auto, the fixed event / emotion rows, no text normalisation. */
+int wn_sensevoice_set_queries(wn_model* m, const int32_t* qid_host, int32_t B);
+/* The SenseVoice front end alone (test hook; lens / out_off / qid are HOST arrays checked before
+ * the launch): utterance b of lens[b] frames gives out_len[b] = ceil(lens[b] / n) + 4 rows from
+ * row out_off[b] (0 rows for lens[b] == 0).  Row t < 4 is embed[qid[b][t]] (no CMVN), row t >= 4
+ * the LFR row t - 4 with GlobalCMVN (mean NULL: none); every row takes x * xscale + pe[t + 1] and
+ * LayerNorm(m F; ln_w, ln_b, eps).  Rows are ldo wide, m F <= ldo <= 576, zeros behind m F. */
+int wn_op_sv_front(const float* feats, const float* mean, const float* istd, const float* embed,
+                   const float* pe, int32_t pe_rows, const float* ln_w, const float* ln_b,
+                   float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,
+                   const int32_t* out_off, const int32_t* qid, int32_t* out_len, int32_t B,
+                   int32_t T, int32_t F, int32_t m, int32_t n, float xscale, float eps,
+                   void* stream);
+
 /* Squeezeformer encoders (`encoder: squeezeformer`, wenet/models/squeezeformer/) under the
  * asr_model head: the Conv2dSubsampling4-shaped front end (pw_conv / dw_conv / input_proj, the
  * sqrt(d) scale in FRONT of the projection), preln, post-LN blocks of attention / FFN / conv

@@ -7,7 +7,7 @@ The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
-__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "EfficientConformer", "Paraformer", "DecodeResult", "StreamingRecognizer",
+__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "EfficientConformer", "Paraformer", "SenseVoiceSmall", "DecodeResult", "StreamingRecognizer",
            "RnntBeamStreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
            "force_align_batch"]
 
@@ -28,6 +28,9 @@ def __getattr__(name):
     if name == "Paraformer":
         from wenet_amd.paraformer import Paraformer
         return Paraformer
+    if name == "SenseVoiceSmall":
+        from wenet_amd.sensevoice import SenseVoiceSmall
+        return SenseVoiceSmall
     if name == "Squeezeformer":
         from wenet_amd.squeezeformer import Squeezeformer
         return Squeezeformer

@@ -58,6 +58,12 @@ class WnParaformerConfig(Structure):
                                'noise_threshold')]
 
 
+class WnSenseVoiceConfig(Structure):
+    """wn_sensevoice_config: what a SenseVoice Small model has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('lfr_m', 'lfr_n', 'kernel_size', 'tp_blocks',
+                                       'max_frames', 'n_query', 'n_embed')]
+
+
 class WnSqueezeformerConfig(Structure):
     """wn_squeezeformer_config: what a Squeezeformer encoder has on top of wn_config."""
     _fields_ = [(n, c_int32) for n in ('reduce_idx', 'recover_idx', 'reduce_kernel',
@@ -159,6 +165,7 @@ EXPORTS = [
     'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
     'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
     'wn_op_attention_d32',
+    'wn_model_create_sensevoice', 'wn_sensevoice_set_queries', 'wn_op_sv_front',
 ]
 
 _lib = None
@@ -374,6 +381,12 @@ def lib():
                                   i32, vp]
     L.wn_op_cif_fire.argtypes = [vp, i32, i32, i32, vp, pi32, pi32, i32, f32, f32, vp, i32, i32,
                                  pi32, pi32, pi32, pi32, pi32, vp]
+    L.wn_model_create_sensevoice.argtypes = [POINTER(WnConfig), POINTER(WnSenseVoiceConfig),
+                                             POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_sensevoice_set_queries.argtypes = [vp, pi32, i32]
+    # feats mean istd embed pe | pe_rows | ln_w ln_b out | ldo out_rows | lens out_off qid out_len
+    L.wn_op_sv_front.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, pi32, pi32, pi32,
+                                 pi32, i32, i32, i32, i32, i32, f32, f32, vp]
     for n in EXPORTS:
         if n not in ('wn_last_error', 'wn_version', 'wn_model_destroy',
                      'wn_resample_length', 'wn_profile_kernel_name',

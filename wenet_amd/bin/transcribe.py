@@ -40,6 +40,11 @@ def get_args(argv=None):
                    help='Whisper models: the task token of the prompt (default transcribe)')
     p.add_argument('--lang', default=None,
                    help='Whisper models: language code of the prompt, e.g. en, zh (default en)')
+    p.add_argument('--lid', default=None,
+                   help='SenseVoice models: language of the query row (auto, zh, en, yue, ja, ko, '
+                        'nospeech; default auto)')
+    p.add_argument('--itn', default=None, choices=['withitn', 'woitn'],
+                   help='SenseVoice models: text normalisation of the query row (default woitn)')
     p.add_argument('--stream', action='store_true',
                    help='decode through a streaming session, printing partial results')
     p.add_argument('--chunk', type=int, default=16,
@@ -132,7 +137,7 @@ def main(argv=None):
             result = stream_file(model, args.audio_file, args.chunk, args.beam or 10,
                                  search=args.search)
     elif args.beam is None and args.context_path is None and args.task is None \
-            and args.lang is None:
+            and args.lang is None and args.lid is None and args.itn is None:
         result = model.transcribe(args.audio_file)      # asr_model.py:345-358
     else:
         graph = None
@@ -147,6 +152,10 @@ def main(argv=None):
             if not whisper.is_whisper(model.special_tokens):
                 raise SystemExit('--task / --lang are read by Whisper models only')
             infos = dict(tasks=[args.task or 'transcribe'], langs=[args.lang or 'en'])
+        if args.lid is not None or args.itn is not None:
+            if not isinstance(model, wenet_amd.SenseVoiceSmall):
+                raise SystemExit('--lid / --itn are read by SenseVoice models only')
+            infos = dict(lid=args.lid or 'auto', itn=args.itn or 'woitn')
         speech = model.compute_feature(args.audio_file)
         method = model.default_decode_method
         result = model.decode([method], speech.unsqueeze(0),

@@ -28,7 +28,7 @@ SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_bf16s.hip', 'gemm_bf16p.hip', 'gem
            'squeezeformer.hip', 'cabi_squeezeformer.hip',
            'efficonformer.hip', 'cabi_efficonformer.hip',
            'attention_d128.hip', 'paraformer.hip', 'cabi_paraformer.hip',
-           'attention_d32.hip']
+           'attention_d32.hip', 'sensevoice.hip', 'cabi_sensevoice.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
          '-fno-gpu-rdc', '-Wno-unused-result']
 # WN_ABLATION=1 python -m wenet_amd.build: a MEASUREMENT build that also compiles the kernel

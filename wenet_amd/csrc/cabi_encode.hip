@@ -67,10 +67,22 @@ int wn_encode(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host
   struct GateDrop { wn_model* m; ~GateDrop() { m->enc_gate = nullptr; } } gate_drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() || !m->data->tf_layers.empty() || m->pf.on,
+  WN_CHECK(!m->data->layers.empty() || !m->data->tf_layers.empty() || m->pf.on || m->sv.on,
            "wn_encode: this handle has no weights");
   WN_CHECK(B > 0, "wn_encode: empty batch");
   WN_CHECK(chunk != 0, "decoding_chunk_size must not be 0 (asr_model.py:310)");
+  if (m->sv.on) {
+    // (stored query ids serve one encode, however it ends: encode_sensevoice takes them first)
+    struct QidDrop { wn_model* m; ~QidDrop() { m->sv.qid.clear(); } } qid_drop{m};
+    WN_CHECK(chunk < 0, "chunk decoding is not implemented for the SenseVoice encoder (it "
+                        "attends over the full utterance)");
+    WN_CHECK(m->prec == PREC_F32, "wn_encode: a SenseVoice handle stays fp32");
+    WN_CHECK(T >= 1, "wn_encode: empty features");
+    WN_HIP(hipSetDevice(m->device));
+    WN_TRY(encode_gate_wait(m, (hipStream_t)stream));
+    return encode_sensevoice(m, feats_dev, feat_lens_host, B, T, enc_out_dev, enc_lens_host,
+                             (hipStream_t)stream);
+  }
   if (m->pf.on) {
     WN_CHECK(chunk < 0, "chunk decoding is not implemented for the Paraformer encoder (it "
                         "attends over the full utterance)");

@@ -1044,6 +1044,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->sq.on = src->sq.on; m->sq.c = src->sq.c;
   m->ef.on = src->ef.on; m->ef.c = src->ef.c;
   m->pf.on = src->pf.on; m->pf.c = src->pf.c;
+  m->sv.on = src->sv.on; m->sv.c = src->sv.c;
   m->device = src->device;
   m->prec = src->prec;
   m->fp8_ffn = src->fp8_ffn;
@@ -1073,6 +1074,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(!m->pf.on || precision == PREC_F32,
            "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "
            "encoder and decoder)");
+  WN_CHECK(!m->sv.on || precision == PREC_F32,
+           "wn_model_set_precision: a SenseVoice handle stays fp32 (no bf16 / fp8 kernels for its "
+           "encoder)");
   const ModelData& W = *m->data;
   // the images belong to the model block: whichever handle asks first builds them, every
   // clone (made before or after) reads the same ones

@@ -59,12 +59,12 @@ int pf_attention(const wn_model* m, AttnArgs& a, hipStream_t s) {
 }
 
 // y = x + conv_K(x) [+ r]: the FSMN memory block over the C channels at x (zero padding, no bias)
-int pf_fsmn(const wn_model* m, const float* x, int ldx, const float* wt, const float* r, int ldr,
-            float* y, const int* off, const int* len, int B, int max_len, hipStream_t s) {
+int pf_fsmn(const wn_model* m, int K, const float* x, int ldx, const float* wt, const float* r,
+            int ldr, float* y, const int* off, const int* len, int B, int max_len, hipStream_t s) {
   DwTileArgs a;
   a.x = x; a.ldx = ldx; a.wt = wt; a.bias = m->data->pf.zero_bias; a.y = y;
   a.ldy = m->cfg.d_model; a.off = off; a.len = len; a.B = B; a.C = m->cfg.d_model;
-  a.K = m->pf.c.kernel_size; a.causal = 0; a.max_len = max_len;
+  a.K = K; a.causal = 0; a.max_len = max_len;
   a.r = r; a.ldr = ldr;
   return merge_dwconv(a, s);
 }
@@ -82,6 +82,45 @@ int pf_dec_ffn(wn_model* m, const Linear& w1, const Norm& nrm, const Linear& w2,
 }  // namespace
 }  // namespace wn
 
+// The layer loop of both SANM stacks (the Paraformer's encoder, SenseVoice's two stacks): the
+// workspace rows m->x / t1 / t2 / hbuf / qkv are sized by the caller.
+int pf_encoder_layers(wn_model* m, const std::vector<PfEncLayer>& layers, int n_run,
+                      bool first_wide, int ld0, int K, int B, int M, int max_len, hipStream_t s) {
+  const wn_config& c = m->cfg;
+  const int d = c.d_model, H = c.n_heads, F = c.ffn_dim;
+  float* x = m->x.as<float>();
+  float* t1 = m->t1.as<float>();
+  float* t2 = m->t2.as<float>();
+  float* hb = m->hbuf.as<float>();
+  float* qkv = m->qkv.as<float>();
+  const int* d_off = m->d_off.as<int>();
+  const int* d_len = m->d_len.as<int>();
+  for (int li = 0; li < n_run; ++li) {
+    // AliParaformerEncoderLayer.forward (layers.py:144-180): x1 = [x +] linear_out(attention)
+    // + fsmn(v); out = x1 + w_2(relu(w_1(LN(x1)))).  A wide first layer reads the 560 (576)
+    // columns the front end normalised and has no residual around the attention.
+    const PfEncLayer& L = layers[li];
+    const bool wide = first_wide && li == 0;
+    if (!wide) WN_TRY(ln(L.n1, x, t1, M, d, c.norm_eps, s));
+    WN_TRY(linear(L.qkv, t1, wide ? ld0 : d, qkv, 3 * d, M, s));
+    AttnArgs a;
+    a.Q = qkv; a.K = qkv + d; a.V = qkv + 2 * d;
+    a.ldq = a.ldk = a.ldv = 3 * d;
+    a.O = t2; a.ldo = d;
+    a.q_off = a.kv_off = d_off; a.q_len = a.kv_len = d_len;
+    a.n_seq = B; a.n_heads = H; a.max_q_len = max_len;
+    WN_TRY(pf_attention(m, a, s));
+    // t1 = v + conv(v) [+ x], then x = t1 + linear_out(t2)
+    WN_TRY(pf_fsmn(m, K, qkv + 2 * d, 3 * d, L.fsmn_wt, wide ? nullptr : x, d, t1, d_off, d_len,
+                   B, max_len, s));
+    WN_TRY(linear(L.out, t2, d, x, d, M, s, ACT_NONE, t1, d));
+    WN_TRY(ln(L.n2, x, t1, M, d, c.norm_eps, s));
+    WN_TRY(linear(L.ff1, t1, d, hb, F, M, s, ACT_RELU));
+    WN_TRY(linear(L.ff2, hb, F, x, d, M, s, ACT_NONE, x, d));
+  }
+  return 0;
+}
+
 // wn_encode on a Paraformer handle.  Every utterance is encoded as the reference encodes it
 // ALONE: T' = ceil(len / 6) rows whose frame indices clamp to the utterance's own last frame --
 // the reference's batched LFR pads a shorter utterance from the batch's zero padding when the
@@ -91,7 +130,7 @@ int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_l
   const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const wn_paraformer_config& p = m->pf.c;
-  const int d = c.d_model, H = c.n_heads, F = c.ffn_dim, D0 = p.lfr_m * c.feat_dim;
+  const int d = c.d_model, F = c.ffn_dim, D0 = p.lfr_m * c.feat_dim;
   const int ld0 = cdiv(D0, 32) * 32;
   auto out_len = [&](int n) { return n > 0 ? (n + p.lfr_n - 1) / p.lfr_n : 0; };
   const int Tp = out_len(T);
@@ -119,13 +158,8 @@ int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_l
     WN_TRY(m->t2.ensure((size_t)M * d * sizeof(float)));
     WN_TRY(m->hbuf.ensure((size_t)M * F * sizeof(float)));
     WN_TRY(m->qkv.ensure((size_t)M * 3 * d * sizeof(float)));
-    float* x = m->x.as<float>();
     float* t1 = m->t1.as<float>();
-    float* t2 = m->t2.as<float>();
-    float* hb = m->hbuf.as<float>();
-    float* qkv = m->qkv.as<float>();
     const int* d_off = m->d_off.as<int>();
-    const int* d_len = m->d_len.as<int>();
     LfrFrontArgs fa;
     fa.feats = feats_dev; fa.mean = W.cmvn_mean; fa.istd = W.cmvn_istd; fa.pe = W.pf.pe;
     fa.ln_w = W.pf.enc[0].n1.w; fa.ln_b = W.pf.enc[0].n1.b;
@@ -134,28 +168,7 @@ int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_l
     fa.xscale = sqrtf((float)d); fa.eps = c.norm_eps;
     WN_TRY(lfr_front(fa, s));
     const int n_run = m->dbg_layers >= 0 ? std::min(m->dbg_layers, c.n_layers) : c.n_layers;
-    for (int li = 0; li < n_run; ++li) {
-      // AliParaformerEncoderLayer.forward (layers.py:144-180): x1 = [x +] linear_out(attention)
-      // + fsmn(v); out = x1 + w_2(relu(w_1(LN(x1)))).  Layer 0 reads the 560 (576) columns the
-      // front end normalised and has no residual around the attention.
-      const PfEncLayer& L = W.pf.enc[li];
-      if (li > 0) WN_TRY(ln(L.n1, x, t1, M, d, c.norm_eps, s));
-      WN_TRY(linear(L.qkv, t1, li == 0 ? ld0 : d, qkv, 3 * d, M, s));
-      AttnArgs a;
-      a.Q = qkv; a.K = qkv + d; a.V = qkv + 2 * d;
-      a.ldq = a.ldk = a.ldv = 3 * d;
-      a.O = t2; a.ldo = d;
-      a.q_off = a.kv_off = d_off; a.q_len = a.kv_len = d_len;
-      a.n_seq = B; a.n_heads = H; a.max_q_len = max_len;
-      WN_TRY(pf_attention(m, a, s));
-      // t1 = v + conv(v) [+ x], then x = t1 + linear_out(t2)
-      WN_TRY(pf_fsmn(m, qkv + 2 * d, 3 * d, L.fsmn_wt, li > 0 ? x : nullptr, d, t1, d_off, d_len,
-                     B, max_len, s));
-      WN_TRY(linear(L.out, t2, d, x, d, M, s, ACT_NONE, t1, d));
-      WN_TRY(ln(L.n2, x, t1, M, d, c.norm_eps, s));
-      WN_TRY(linear(L.ff1, t1, d, hb, F, M, s, ACT_RELU));
-      WN_TRY(linear(L.ff2, hb, F, x, d, M, s, ACT_NONE, x, d));
-    }
+    WN_TRY(pf_encoder_layers(m, W.pf.enc, n_run, true, ld0, p.kernel_size, B, M, max_len, s));
     WN_TRY(after_norm_out(m, s));
   }
   if (enc_out_dev) {
@@ -455,7 +468,7 @@ int wn_paraformer_decode(wn_model* m, int32_t* tokens, int32_t* tok_lens, float*
     WN_TRY(ln(L.n1, x, t, Mt, d, 1e-12f, s));
     WN_TRY(pf_dec_ffn(m, L.ff1, L.ffn_norm, L.ff2, t, o, Mt, s));
     WN_TRY(ln(L.n2, o, t, Mt, d, 1e-12f, s));
-    WN_TRY(pf_fsmn(m, t, d, L.fsmn_wt, x, d, y, dev_t_off, dev_t_len, B, max_t, s));
+    WN_TRY(pf_fsmn(m, p.kernel_size, t, d, L.fsmn_wt, x, d, y, dev_t_off, dev_t_len, B, max_t, s));
     WN_TRY(ln(L.n3, y, t, Mt, d, 1e-12f, s));
     WN_TRY(linear(L.src_q, t, d, q, d, Mt, s));
     WN_TRY(linear(L.src_kv, enc, d, kv, 2 * d, M, s));     // once per layer for the batch

@@ -956,6 +956,30 @@ struct LfrFrontArgs {
 };
 int lfr_front(const LfrFrontArgs& a, hipStream_t s);
 
+// SenseVoice front end (sensevoice/sensevoice_small_model.py:249-290 on ONE utterance;
+// sensevoice.hip): utterance b owns SV_QUERY + ceil(len[b] / n) rows (none with len[b] == 0).
+// Row t < SV_QUERY is embed[qid[b][t]] (no CMVN); row t >= SV_QUERY is LFR row t - SV_QUERY as in
+// lfr_front, with GlobalCMVN.  Every row then takes x * xscale + pe[t + 1] -- the positions run
+// over the concatenated sequence -- and the LayerNorm of the first encoder layer; written ldo
+// wide with zeros behind m F.  One wave per row.
+constexpr int SV_QUERY = 4;       // lid | event | emotion | text norm
+constexpr int SV_EMBED = 16;      // rows of embed.weight
+struct SvFrontArgs {
+  const float* feats;     // (B, T, F) padded
+  const float* mean;      // [m F] or null (no CMVN)
+  const float* istd;      // [m F]
+  const float* embed;     // [SV_EMBED][m F]
+  const float* pe;        // [pe_rows][m F]: row p = the encoding of position p
+  const float* ln_w; const float* ln_b;   // [m F]
+  float* out; int ldo;    // [sum rows][ldo]
+  const int* len;         // [B] frames of the utterance
+  const int* off;         // [B] first output row
+  const int* qid;         // [B][SV_QUERY], each in [0, SV_EMBED): validated on the host
+  int B, T, F, m, n, max_rows;   // max_rows: output rows of the longest utterance (queries included)
+  float xscale, eps;
+};
+int sv_front(const SvFrontArgs& a, hipStream_t s);
+
 // LayerNorm for rows the one-wave-per-row kernels of layernorm() do not cover: D up to 2048, any
 // multiple of 4 (the statistics divide by D); columns D .. Dpad - 1 of y are written as zeros.
 int layernorm_wide(const float* x, int ldx, const float* w, const float* b, float* y, int ldy,

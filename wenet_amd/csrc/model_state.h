@@ -211,6 +211,14 @@ struct PfData {
   Linear dec3_ff1, dec3_ff2, dec_out;
 };
 
+// SenseVoice Small (cabi_sensevoice.hip): the first stack is PfData::enc (with pe and zero_bias),
+// the second one and what the front end reads are here
+struct SvData {
+  std::vector<PfEncLayer> tp;        // encoder.tp_encoders
+  Norm tp_norm;
+  const float* embed = nullptr;      // [16][560] query rows
+};
+
 struct Decoder {
   const float* embed = nullptr;  // [V][d]
   const float* pe = nullptr;     // [max_pos][d] sinusoids, or the learned [dec_max_pos][d] table
@@ -272,7 +280,8 @@ struct ModelData {
   const float* pred_conv_w = nullptr; const float* pred_conv_b = nullptr;
   Linear pred_ffn;
   Norm pred_norm;
-  PfData pf;                             // wn_model::pf.on
+  PfData pf;                             // wn_model::pf.on (sv.on: enc, pe, zero_bias)
+  SvData sv;                             // wn_model::sv.on
   // Squeezeformer (wn_model::sq.on): preln, the time reduction's depthwise taps [K][d] + bias
   // and pointwise conv, time_recover_layer
   Norm sq_preln;
@@ -351,6 +360,16 @@ struct wn_model {
   Stager ef_stage;
   DevBuf pf_alpha, pf_img, pf_emb, pf_int, pf_x, pf_y, pf_t, pf_o, pf_q, pf_kv, pf_h, pf_out;
   PinnedBuf pf_host;
+  // wn_model_create_sensevoice: SenseVoice Small (cabi_sensevoice.hip); data->pf.enc and
+  // data->sv hold the weights.  qid: the query ids wn_sensevoice_set_queries stored for the next
+  // wn_encode (empty: the defaults); sv_desc = feature lengths | query ids on the device
+  struct {
+    bool on = false;
+    wn_sensevoice_config c = {};
+    std::vector<int> qid;
+  } sv;
+  DevBuf sv_desc;
+  Stager sv_stage;
   int device = 0;
   // never null: wn_workspace_create gives an empty block
   std::shared_ptr<const ModelData> data = std::make_shared<ModelData>();
@@ -626,6 +645,16 @@ int encode_efficonformer(wn_model* m, const float* feats_dev, const int32_t* fea
                          hipStream_t s);
 // (cabi_paraformer.hip)
 int encode_paraformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                      int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
+// AliParaformerEncoderLayer.forward (layers.py:144-180) over the current batch's M packed rows for
+// the first n_run layers of `layers`: x1 = [x +] linear_out(attention) + fsmn(v); out = x1 +
+// w_2(relu(w_1(LN(x1)))).  first_wide: layers[0] reads the ld0 columns the front end normalised
+// into m->t1 and has no residual around the attention; every other layer reads and writes m->x.
+// K: the FSMN taps.
+int pf_encoder_layers(wn_model* m, const std::vector<wn::PfEncLayer>& layers, int n_run,
+                      bool first_wide, int ld0, int K, int B, int M, int max_len, hipStream_t s);
+// (cabi_sensevoice.hip)
+int encode_sensevoice(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 // (cabi_model.hip: what every wn_model_create* entry point runs)
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,

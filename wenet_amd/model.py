@@ -1179,7 +1179,10 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     sd = torch.load(os.path.join(model_dir, 'final.pt'), map_location='cpu',
                     mmap=True)
     sd = dict(sd)
-    if configs.get('cmvn') == 'global_cmvn' and \
+    sensevoice = configs.get('model') == 'sensevoice_small'
+    if sensevoice and 'global_cmvn.mean' in sd:
+        pass        # (SenseVoiceSmall keeps the CMVN on the model, not on its encoder)
+    elif configs.get('cmvn') == 'global_cmvn' and \
             'encoder.global_cmvn.mean' not in sd:
         cmvn_file = os.path.join(model_dir, 'global_cmvn')
         if not os.path.exists(cmvn_file):
@@ -1193,6 +1196,9 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     elif configs.get('encoder') in ('branchformer', 'e_branchformer'):
         from wenet_amd.branchformer import Branchformer
         model = Branchformer(configs, sd, device)
+    elif sensevoice:   # init_model.py:96: SenseVoiceSmall
+        from wenet_amd.sensevoice import SenseVoiceSmall
+        model = SenseVoiceSmall(configs, sd, device)
     elif configs.get('model') == 'paraformer':   # init_model.py:155: Paraformer
         from wenet_amd.paraformer import Paraformer
         model = Paraformer(configs, sd, device)

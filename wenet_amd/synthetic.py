@@ -549,6 +549,40 @@ CONFIGS['paraformer_large'] = _paraformer(512, 4, 2048, 50, 16, 8404)
 CONFIGS['paraformer_large_1blk'] = _paraformer(512, 4, 2048, 2, 1, 50)
 
 
+# SenseVoice Small as wenet/models/sensevoice/convert_sensevoice_small_to_wenet_config_and_ckpt.py
+# writes its train.yaml (the encoder_conf of the released config.yaml without the two keys the
+# converter deletes), at the given widths
+def _sensevoice(d, heads, ffn, blocks, tp_blocks, kernel, vocab) -> dict:
+    return {
+        'input_dim': 560, 'output_dim': vocab,
+        'encoder': 'sanm_encoder_with_tp',
+        'encoder_conf': dict(output_size=d, attention_heads=heads, linear_units=ffn,
+                             num_blocks=blocks, tp_blocks=tp_blocks, dropout_rate=0.1,
+                             positional_dropout_rate=0.1, attention_dropout_rate=0.1,
+                             input_layer='paraformer_dummy', normalize_before=True,
+                             kernel_size=kernel, sanm_shfit=0,
+                             pos_enc_layer_type='abs_pos_paraformer'),
+        'lfr_conf': {'lfr_m': 7, 'lfr_n': 6},
+        'decoder': None,
+        'ctc_conf': {'ctc_blank_id': 0},
+        'tokenizer': 'sentencepiece',
+        'tokenizer_conf': {'model_path': 'chn_jpn_yue_eng_ko_spectok.bpe.model',
+                           'special_tokens': {'</s>': 2, '<s>': 1, '<blank>': 0, '<unk>': 0}},
+        'model': 'sensevoice_small',
+        'model_conf': dict(length_normalized_loss=False, ctc_weight=1.0, lsm_weight=0.1),
+    }
+
+
+# d 256 with 2 heads: d_k = 128, the released model's head width; 1 + 1 blocks and 2 tp blocks
+CONFIGS['tiny_sensevoice'] = _sensevoice(256, 2, 256, 2, 2, 11, 50)
+# d_k = 64 (the existing attention kernel), 3 taps, one tp block
+CONFIGS['tiny_sensevoice_h64'] = _sensevoice(128, 2, 64, 2, 1, 3, 50)
+# the released widths with one block behind encoders0 and one tp block (the tests)
+CONFIGS['sensevoice_small_1blk'] = _sensevoice(512, 4, 2048, 2, 1, 11, 50)
+# the released model: 50 + 20 blocks at d 512 with 4 heads (tools/bench_sensevoice.py only)
+CONFIGS['sensevoice_small'] = _sensevoice(512, 4, 2048, 50, 20, 11, 25055)
+
+
 # Squeezeformer under the asr_model head (examples/librispeech/s0/conf/train_squeezeformer.yaml,
 # train_u2++_squeezeformer.yaml, train_squeezeformer_bidecoder_large.yaml)
 def _squeezeformer(d, heads, factor, blocks, reduce_idx, recover_idx, k, reduction, shift, cnn_norm,
@@ -885,7 +919,7 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
                     ) -> "OrderedDict[str, torch.Tensor]":
     """Deterministic random weights with the reference's names and shapes.
     `rnnt_blank_bias`: `model: transducer` configurations only (_add_transducer)."""
-    ec, dc = configs['encoder_conf'], configs['decoder_conf']
+    ec, dc = configs['encoder_conf'], configs.get('decoder_conf') or {}
     d = ec['output_size']
     h = ec['attention_heads']
     ffn = ec.get('linear_units', 2048)
@@ -900,6 +934,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         return _make_firered_state_dict(configs, seed, sharpen_ctc)
     if configs.get('encoder') == 'sanm_encoder':
         return _make_paraformer_state_dict(configs, seed, sharpen_ctc)
+    if configs.get('encoder') == 'sanm_encoder_with_tp':
+        return _make_sensevoice_state_dict(configs, seed, sharpen_ctc)
     idim, V = configs['input_dim'], configs['output_dim']
     sd: Dict[str, np.ndarray] = OrderedDict()
 
@@ -1228,6 +1264,60 @@ def _make_paraformer_state_dict(configs, seed, sharpen_ctc):
         emax = a - (math.log(math.log(n)) + math.log(4 * math.pi)) / (2 * a) + 0.5772 / a
         sd['ctc.ctc_lo.weight'][0, :] = 0.0
         sd['ctc.ctc_lo.bias'][0] = np.float32(12.0 / math.sqrt(3.0) * emax * 1.10)
+    return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+
+
+def _make_sensevoice_state_dict(configs, seed, sharpen_ctc):
+    """SenseVoice Small (wenet/models/sensevoice/): names and shapes as init_model gives them --
+    the CMVN on the model (`global_cmvn.*`, not on its encoder), the 16 x 560 query table,
+    encoders0 over the 560 columns + num_blocks - 1 encoders, after_norm, tp_encoders, tp_norm,
+    a CTC head."""
+    ec = configs['encoder_conf']
+    d, ffn, K = ec['output_size'], ec['linear_units'], ec['kernel_size']
+    idim, V = configs['input_dim'], configs['output_dim']
+    sd: Dict[str, np.ndarray] = OrderedDict()
+
+    def lin(name, out_f, in_f):
+        b = 1.0 / math.sqrt(in_f)
+        sd[name + '.weight'] = _uniform(seed, name + '.weight', (out_f, in_f), b)
+        sd[name + '.bias'] = _uniform(seed, name + '.bias', (out_f, ), b)
+
+    def norm(name, n):
+        sd[name + '.weight'] = _normal(seed, name + '.weight', (n, ), 0.1, 1.0)
+        sd[name + '.bias'] = _normal(seed, name + '.bias', (n, ), 0.1)
+
+    def layer(p, in_f):
+        a = p + '.self_attn'
+        lin(a + '.linear_out', d, d)
+        lin(a + '.linear_q_k_v', 3 * d, in_f)
+        sd[a + '.fsmn_block.weight'] = _uniform(seed, a + '.fsmn', (d, 1, K), 1.0 / math.sqrt(K))
+        lin(p + '.feed_forward.w_1', ffn, d)
+        lin(p + '.feed_forward.w_2', d, ffn)
+        norm(p + '.norm1', in_f)
+        norm(p + '.norm2', d)
+
+    sd['encoder.embed.pos_enc.pe'] = whisper_positional_table(idim, 5000).numpy()
+    for i in range(ec['num_blocks']):
+        layer('encoder.encoders0.0' if i == 0 else f'encoder.encoders.{i - 1}',
+              idim if i == 0 else d)
+    norm('encoder.after_norm', d)
+    for i in range(ec['tp_blocks']):
+        layer(f'encoder.tp_encoders.{i}', d)
+    norm('encoder.tp_norm', d)
+    lin('ctc.ctc_lo', V, d)
+    if sharpen_ctc:      # as make_state_dict: roughly 2/3 .. 4/5 of the frames come out blank
+        sd['ctc.ctc_lo.weight'] = sd['ctc.ctc_lo.weight'] * np.float32(12.0)
+        sd['ctc.ctc_lo.bias'] = sd['ctc.ctc_lo.bias'] * np.float32(12.0)
+        n = max(V - 1, 2)
+        a = math.sqrt(2.0 * math.log(n))
+        emax = a - (math.log(math.log(n)) + math.log(4 * math.pi)) / (2 * a) + 0.5772 / a
+        sd['ctc.ctc_lo.weight'][0, :] = 0.0
+        sd['ctc.ctc_lo.bias'][0] = np.float32(12.0 / math.sqrt(3.0) * emax * 1.10)
+    # query rows of the size of a CMVN-normalised LFR row (~ unit variance)
+    sd['embed.weight'] = _normal(seed, 'sv.embed', (16, idim), 1.0)
+    sd['global_cmvn.mean'] = _normal(seed, 'cmvn.mean', (idim, ), 1.5, 11.0)
+    sd['global_cmvn.istd'] = (
+        1.0 / (2.5 + np.abs(_normal(seed, 'cmvn.std', (idim, ), 0.5)))).astype(np.float32)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
 
 
