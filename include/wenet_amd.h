@@ -541,6 +541,31 @@ int wn_op_gemm(const float* A_dev, const float* W_dev, const float* bias_dev,
 int wn_op_gemm_bf16(const float* A_dev, const float* W_dev, const float* bias_dev,
                     const float* resid_dev, float* C_dev, int32_t M, int32_t N,
                     int32_t K, float alpha, int32_t act, void* stream);
+/* The whole argument block of the fp32 / bf16-on-the-fly GEMM (csrc/gemm.hip, gemm_bf16.hip) as
+ * the model's launchers fill it: strides, the GLU epilogue, gathered rows and the implicit
+ * 3x3 / stride-2 operand (test infrastructure).  Everything is checked on the host BEFORE
+ * anything is launched, so that no accepted call reads outside A's a_elems floats or writes
+ * outside [0, M) x [0, N) (N / 2 with glu) of C.  a_row_off is a HOST array of M entries (or
+ * NULL: plain rows of stride lda); element (row, k) of the operand then lives at
+ * A[a_row_off[row] + (tap / 3) * conv_sy + (tap % 3) * conv_sx + k % conv_C], tap = k / conv_C,
+ * with K == 9 * conv_C (3x3 taps) or K == conv_C (gathered rows). */
+typedef struct wn_gemm_op {
+  const float* A; const float* W; const float* bias; const float* resid; float* C;
+  int32_t M, N, K;
+  int32_t lda, ldc, ldr;
+  float alpha;
+  int32_t act;         /* 0 none, 1 SiLU, 2 ReLU, 3 exact GELU */
+  int32_t glu;         /* W rows as [32 values | 32 gates] per 64; C has N / 2 columns */
+  int32_t precision;   /* WN_PREC_F32 / WN_PREC_BF16 for this call */
+  const int64_t* a_row_off;
+  int64_t a_elems;     /* floats in the A buffer */
+  int32_t conv_C;
+  int64_t conv_sy, conv_sx;
+} wn_gemm_op;
+/* Calls gemm_f32 directly (never the six-product path).  *route_out = the kernel instantiation
+ * that ran: BM/64 | BN/64 << 4 | WGM << 8 | WGN << 12 | (K tile / 32) << 16 | PF << 20 |
+ * GLU << 22 | CONV << 23 | precision << 24 | act << 25 | resid << 27. */
+int wn_op_gemm_ex(const wn_gemm_op* op, int32_t* route_out, void* stream);
 /* The skinny GEMM of the decoder step (gemm_skinny.hip), M <= 256 (more is refused, -1):
  * C[M,N] = resid + act(A[M,K] * W[N,K]^T + bias), act 0 none / 2 ReLU / 3 exact GELU; a block
  * owns all M rows of 128 columns and one of split_k K slices (0 = the shape rule), the slice

@@ -20,6 +20,10 @@ At the end: the kernels that own a complete row -- LayerNorm, the FFN slice redu
 -- as written-out formulas, a decoder of the plane image (csrc/x6.h) and the row regimes, for
 tests/test_gpu_rows.py.
 
+Last: the fp32 and bf16-on-the-fly matrix-core GEMMs with every argument of GemmArgs -- strides,
+epilogues, GLU, gathered rows, the implicit 3x3 / stride-2 operand -- as `ref_gemm`, and the list
+of cases GEMM_CASES that tests/test_gpu_gemm_ops.py runs and tests/test_kernel_refs.py checks.
+
 No GPU in here.
 """
 import math
@@ -946,3 +950,308 @@ def bound(e_plain, scale, bf16=False):
 
 def cap_ok(e_plain, scale, bf16=False):
     return e_plain <= (CAP_BF16 if bf16 else CAP_F32) * scale
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp32 and bf16-on-the-fly matrix-core GEMMs (csrc/gemm.hip, gemm_bf16.hip) through
+# wn_op_gemm_ex; GPU tests in tests/test_gpu_gemm_ops.py
+
+
+def glu_perm(d):
+    """Rows of a (2 d, K) GLU weight [values | gates] in the order the GLU epilogue reads them:
+    per 64 rows [32 values | 32 gates] (what wn_model_create gives pointwise_conv1)."""
+    return torch.cat([torch.cat([torch.arange(32) + 32 * u, torch.arange(32) + 32 * u + d])
+                      for u in range(d // 32)])
+
+
+def gemm_route_code(bm, bn, wgm, wgn, bk, pf, glu=False, conv=False, prec=0, act=0, resid=False):
+    """The instantiation code wn_op_gemm_ex reports (csrc/common.h gemm_route_code)."""
+    return (bm // 64 | (bn // 64) << 4 | wgm << 8 | wgn << 12 | (bk // 32) << 16 | pf << 20 |
+            int(glu) << 22 | int(conv) << 23 | prec << 24 | act << 25 | int(resid) << 27)
+
+
+# pre-activations / gates of the `wide` regime: exp overflow and underflow of x * rcp(1 + exp(-x))
+GEMM_WIDE = (0.0, 20.0, -20.0, 88.0, -88.0, 90.0, -90.0, 104.0, -104.0)
+GATE_ON, GATE_OFF = 40.0, -200.0      # sigmoid == 1.0f / a product that rounds to 0.0f
+
+
+def gemm_act(z, act):
+    """0 none, 1 SiLU (x * sigmoid(x)), 2 ReLU, 3 exact GELU (erf)."""
+    if act == 1:
+        return z * torch.sigmoid(z)
+    if act == 2:
+        return F.relu(z)
+    if act == 3:
+        return F.gelu(z)
+    return z
+
+
+def _coded_w(N, K):
+    """W[n][k] = (37 n + 11 k) mod 251 - 125: integers of at most 8 bits (exact in bf16) that
+    differ between neighbouring rows, columns, 32- / 64- / 128-wide tiles and K tiles."""
+    n = torch.arange(N, dtype=torch.int32).unsqueeze(1)
+    k = torch.arange(K, dtype=torch.int32).unsqueeze(0)
+    return ((37 * n + 11 * k) % 251 - 125).float()
+
+
+def _gemm_spec(kind, M, N, K, route, **kw):
+    s = dict(kind=kind, M=M, N=N, K=K, route=route, act=0, resid=0, glu=False, prec=0,
+             regime='unit', alpha=1.0, lens=None, F1=0, conv_C=0, stride=2, taps=3,
+             tile1_route=None, seed=0)
+    s.update(kw)
+    return s
+
+
+def gemm_case_id(s):
+    bm, bn, wgm, wgn, bk, pf = s['route']
+    t = ['bf16' if s['prec'] else 'f32', s['kind'], f'{bm}x{bn}w{wgm}x{wgn}k{bk}pf{pf}',
+         f"{s['M']}x{s['N']}x{s['K']}", f"act{s['act']}", ('r0', 'r1', 'rC')[s['resid']], s['regime']]
+    if s['glu']:
+        t.insert(2, 'glu')
+    return '-'.join(t)
+
+
+def rows_layout(lens, taps, stride, gap=1, lead=1):
+    """Packed utterances of `lens` frames with `gap` unowned frames between them: (first frame of
+    every output row, total frames).  Output t of an utterance reads frames stride * t .. + taps."""
+    first, at = [], lead
+    for n in lens:
+        first += [at + stride * t for t in range((n - taps) // stride + 1)]
+        at += n + gap
+    return first, at
+
+
+def conv3_layout(t1_lens, F1, gap=1, lead=1):
+    """Packed channels-last images of t1_lens[u] x F1 pixels: (first pixel of every output row of
+    the 3x3 / stride-2 conv, image offsets in frames, total frames)."""
+    first, offs, at = [], [], lead
+    F2 = (F1 - 3) // 2 + 1
+    for n in t1_lens:
+        offs.append(at)
+        for t2 in range((n - 3) // 2 + 1):
+            first += [(at + 2 * t2) * F1 + 2 * f2 for f2 in range(F2)]
+        at += n + gap
+    return first, offs, at
+
+
+def gemm_rows(s):
+    """M of a spec (gathered kinds: the output rows their layout gives)."""
+    if s['kind'] == 'rows':
+        return len(rows_layout(s['lens'], s['taps'], s['stride'])[0])
+    if s['kind'] == 'conv3':
+        return len(conv3_layout(s['lens'], s['F1'])[0])
+    return s['M']
+
+
+def make_gemm_case(s):
+    """The tensors of a spec of GEMM_CASES.  kind plain: A (M, K).  kind rows: `buf`, packed frames
+    of d = K / taps channels; output row r is `taps` consecutive frames from frame first[r] on
+    (a_row_off = first * d, conv_C = K).  kind conv3: `buf`, packed channels-last images of F1
+    pixels x conv_C channels per frame; a_row_off = first pixel * conv_C, conv_sy = F1 * conv_C,
+    conv_sx = conv_C, K = 9 conv_C.  Every float of `buf` that no (row, k) reads holds POISON.
+    `W` is what the kernel gets ((N, K); GLU: rows permuted); `W_un` / `b_un` the un-permuted GLU
+    weight [values | gates]; `w_t` the torch-layout conv weight."""
+    g = torch.Generator().manual_seed(1000 + s['seed'])
+    kind, N, K, regime, glu = s['kind'], s['N'], s['K'], s['regime'], s['glu']
+    M = gemm_rows(s)
+    assert M == s['M'], (M, s['M'])
+    coded = regime == 'coded'
+    c = dict(spec=s, M=M, N=N, K=K)
+    # ---- the A operand
+    if kind == 'plain':
+        if coded:
+            A = torch.zeros(M, K)
+            A[torch.arange(M), (13 * torch.arange(M) + 5) % K] = 1.0
+        else:
+            A = torch.randn(M, K, generator=g)
+        c['A'] = A
+    else:
+        if kind == 'rows':
+            d = K // s['taps']
+            first, frames = rows_layout(s['lens'], s['taps'], s['stride'])
+            px, reach = frames, [t * d + e for t in range(s['taps']) for e in range(d)]
+            c.update(conv_C=K, conv_sy=0, conv_sx=0)
+        else:
+            d, F1 = s['conv_C'], s['F1']
+            first, offs, frames = conv3_layout(s['lens'], F1)
+            px = frames * F1
+            reach = [(ky * F1 + kx) * d + e for ky in range(3) for kx in range(3) for e in range(d)]
+            c.update(conv_C=d, conv_sy=F1 * d, conv_sx=d, img_off=offs)
+        if coded:
+            buf = torch.zeros(px, d)
+            buf[torch.arange(px), (5 * torch.arange(px) + 1) % d] = 1.0
+        else:
+            buf = torch.randn(px, d, generator=g)
+        buf = buf.reshape(-1)
+        off = torch.tensor(first, dtype=torch.int64) * d
+        own = torch.zeros(buf.numel(), dtype=torch.bool)
+        own[(off.unsqueeze(1) + torch.tensor(reach).unsqueeze(0)).reshape(-1)] = True
+        buf[~own] = POISON
+        c.update(buf=buf, a_row_off=off, d=d, own=own)
+    # ---- W, bias
+    W = _coded_w(N, K) if coded else torch.randn(N, K, generator=g) / math.sqrt(K)
+    if coded:
+        bias = (torch.arange(N) % 7 - 3).float()
+    else:
+        bias = 0.3 * torch.randn(N, generator=g)
+    if regime == 'wide':
+        wide = torch.tensor(GEMM_WIDE)[torch.arange(N) % len(GEMM_WIDE)]
+    if glu:
+        h = N // 2
+        if coded:
+            # value rows coded, gate rows zero with a bias that opens (1.0f) or shuts the gate
+            W[h:] = 0.0
+            bias[h:] = torch.where((5 * torch.arange(h) + torch.arange(h) // 32) % 3 != 0,
+                                   GATE_ON, GATE_OFF)
+        elif regime == 'wide':
+            bias[h:] = wide[:h]
+        perm = glu_perm(h)
+        c.update(W_un=W, b_un=bias, W=W[perm].contiguous(), bias=bias[perm].contiguous())
+    else:
+        if regime == 'wide':
+            bias = wide
+        c.update(W=W, bias=bias)
+        if kind == 'rows':      # the Conv1d weight (N, d, taps) this (N, taps * d) matrix is
+            c['w_t'] = W.view(N, s['taps'], d).permute(0, 2, 1).contiguous()
+        if kind == 'conv3':     # the Conv2d weight (N, C, 3, 3)
+            c['w_t'] = W.view(N, 3, 3, d).permute(0, 3, 1, 2).contiguous()
+    if s['resid']:
+        if coded:
+            r = torch.arange(M, dtype=torch.int32).unsqueeze(1)
+            n = torch.arange(N, dtype=torch.int32).unsqueeze(0)
+            c['resid'] = ((3 * r + 5 * n) % 17 - 8).float()
+        else:
+            c['resid'] = torch.randn(M, N, generator=g)
+    return c
+
+
+def gemm_operand(c):
+    """The (M, K) operand of a gathered case by explicit indexing of the flat buffer:
+    element (r, k) = buf[a_row_off[r] + (tap / 3) * conv_sy + (tap % 3) * conv_sx + k % conv_C]."""
+    k = torch.arange(c['K'])
+    tap = k // c['conv_C']
+    koff = (tap // 3) * c['conv_sy'] + (tap % 3) * c['conv_sx'] + k % c['conv_C']
+    return c['buf'][c['a_row_off'].unsqueeze(1) + koff.unsqueeze(0)]
+
+
+def ref_gemm(c, fp32=False):
+    """resid + alpha * act(X W^T + bias) in fp64 (fp32: the same statement evaluated in fp32, the
+    yardstick).  precision 1: both operands rounded to bf16 first.  GLU: F.glu over the
+    UN-permuted weight [values | gates].  rows: X by explicit indexing of the flat buffer.
+    conv3: F.conv2d (stride 2) on every utterance's channels-last image with the Conv2d-layout
+    weight.  Returns (M, N) -- (M, N / 2) with GLU -- fp64."""
+    s = c['spec']
+    dt = torch.float32 if fp32 else torch.float64
+    rnd = _r16 if s['prec'] == 1 else (lambda t: t)
+    if s['kind'] == 'conv3':
+        d, F1 = c['d'], s['F1']
+        img = c['buf'].view(-1, F1, d)
+        w = rnd(c['w_t']).to(dt)
+        zs = []
+        for o, n in zip(c['img_off'], s['lens']):
+            x = rnd(img[o:o + n]).to(dt).permute(2, 0, 1).unsqueeze(0)        # (1, C, t1, F1)
+            y = F.conv2d(x, w, stride=2)[0]                                    # (N, t2, F2)
+            zs.append(y.permute(1, 2, 0).reshape(-1, c['N']))
+        z = torch.cat(zs)
+    else:
+        X = c['A'] if s['kind'] == 'plain' else gemm_operand(c)
+        Wm = c['W_un'] if s['glu'] else c['W']
+        z = rnd(X).to(dt) @ rnd(Wm).to(dt).t()
+    z = z + (c['b_un'] if s['glu'] else c['bias']).to(dt)
+    y = F.glu(z, dim=-1) if s['glu'] else gemm_act(z, s['act'])
+    y = y * s['alpha']
+    if s['resid']:
+        y = c['resid'].to(dt) + y
+    return y.double()
+
+
+def gemm_refs(c):
+    """(fp64 reference, e_plain, scale = max |ref|) of a case."""
+    ref = ref_gemm(c)
+    plain = ref_gemm(c, fp32=True)
+    return ref, (plain - ref).abs().max().item(), ref.abs().max().item()
+
+
+def _gemm_cases():
+    S = _gemm_spec
+    out = []
+
+    def epis(kind, M, N, K, route, combos, **kw):
+        for regime, act, resid in combos:
+            alpha = 0.5 if resid == 1 else 1.0
+            out.append(S(kind, M, N, K, route, regime=regime, act=act, resid=resid, alpha=alpha,
+                         seed=len(out), **kw))
+
+    every = [('unit', a, r) for a in range(4) for r in (0, 1)]
+    coded = [('coded', 0, 0), ('coded', 2, 1), ('coded', 0, 2)]
+    wide = [('wide', 1, 0), ('wide', 3, 0)]
+    few = [('unit', 0, 0), ('unit', 2, 1), ('coded', 0, 0)]
+    for prec in (0, 1):
+        P = dict(prec=prec)
+        ks = (32, ) if prec == 0 else (64, 96)
+        bk = lambda K: 32 if prec == 0 else (64 if K % 64 == 0 else 32)
+        # ---- plain rows, the 128x128 / 2x4 block (fp32: 384 tiles, bf16: 224)
+        Nw = 24571 if prec == 0 else 14331
+        for K in ks:
+            r = (128, 128, 2, 4, bk(K), 1)
+            epis('plain', 200, Nw, K, r, (every + [('unit', 0, 2)] + coded + wide) if K == ks[0]
+                 else every + few[2:], **P)
+        if prec == 0:
+            # tall: the XCD block order over 96 M panels
+            epis('plain', 12285, 500, 32, (128, 128, 2, 4, 32, 1), [('unit', 0, 0), ('coded', 0, 0)])
+            # t128 = 192, t64x128 = 384; ragged in M and N
+            epis('plain', 100, 24570, 32, (64, 128, 2, 4, 32, 1), every + coded[:2])
+        # ---- the 64x64 / 2x2 block
+        for K in ks:
+            r = (64, 64, 2, 2, bk(K), 1)
+            epis('plain', 333, 200, K, r, (every + coded + wide) if K == ks[0]
+                 else every + few[2:], **P)
+            epis('plain', 1, 1, K, r, few, **P)
+            epis('plain', 65, 67, K, r, few + wide + [('unit', 0, 2)], **P)
+        if prec == 0:
+            # PF = 2 (K >= 1024; act 0 and ReLU only): 32, 33 (the tail) and 34 K tiles
+            for K in (1024, 1056, 1088):
+                epis('plain', 65, 67, K, (64, 64, 2, 2, 32, 2),
+                     [('unit', 0, 0), ('unit', 0, 1), ('unit', 2, 0), ('unit', 2, 1),
+                      ('coded', 0, 0), ('coded', 2, 1)])
+            big2 = (128, 128, 2, 4, 32, 2)
+            epis('plain', 200, 24571, 1024, big2, [('unit', 2, 1)])
+            epis('plain', 200, 24571, 1056, big2, [('unit', 0, 0), ('unit', 2, 0)])
+            epis('plain', 200, 24571, 1088, big2, [('coded', 0, 1)])
+            epis('plain', 100, 24570, 1024, (64, 128, 2, 4, 32, 2), [('unit', 2, 0)])
+            epis('plain', 100, 24570, 1056, (64, 128, 2, 4, 32, 2), [('unit', 0, 1)])
+        # ---- GLU
+        glu3 = [('unit', 0, 0), ('coded', 0, 0), ('wide', 0, 0)]
+        for K in ks:
+            for N in (64, 128, 192):
+                for M in (1, 63, 130):
+                    if K == ks[0] or (N, M) == (192, 130):
+                        epis('plain', M, N, K, (64, 128, 2, 2, bk(K), 1),
+                             glu3 if M == 63 or N == 192 else glu3[:2], glu=True, **P)
+            epis('plain', 129, 14272, K, (128, 128, 4, 2, bk(K), 1),
+                 glu3 if K == ks[0] else glu3[:1], glu=True, **P)
+        # ---- gathered rows: a 3-tap stride-2 Conv1d over packed utterances
+        gath = [('unit', 0, 0), ('unit', 0, 1), ('unit', 2, 0), ('unit', 2, 1), ('unit', 3, 0),
+                ('unit', 3, 1), ('coded', 0, 0), ('coded', 2, 1)]
+        big = (128, 128, 2, 2) if prec == 0 else (128, 128, 2, 4)
+        for K in ((96, ) if prec == 0 else (96, 192)):
+            epis('rows', 66, 200, K, (64, 128, 2, 2, bk(K), 1), gath, lens=[37, 3, 95], **P)
+            epis('rows', 129, Nw, K, big + (bk(K), 1), gath, lens=[150, 111], **P)
+        # ---- the implicit 3x3 / stride-2 operand: two images, F1 = 7
+        for C in (32, 64):
+            conv = [('unit', 2, 0), ('coded', 2, 0)]
+            epis('conv3', 69, 70, 9 * C, (64, 128, 2, 2, bk(C), 1), conv, lens=[31, 17], F1=7,
+                 conv_C=C, **P)
+            epis('conv3', 138, Nw, 9 * C, big + (bk(C), 1), conv if C == 32 else conv[:1],
+                 lens=[61, 33], F1=7, conv_C=C, **P)
+    # ---- bf16 256x256 / 4x2: t256 = 2 * 513 = 1026; under gemm_tile_bf16 = 1 the 128x128 block
+    t1 = (128, 128, 2, 4, 64, 1)
+    epis('plain', 257, 131069, 64, (256, 256, 4, 2, 64, 1),
+         [('unit', 0, 0), ('coded', 2, 1), ('wide', 1, 0), ('unit', 3, 1)], prec=1, tile1_route=t1)
+    # K >= 2048 with t256 = 2 * 128 = 256
+    epis('plain', 257, 32765, 2048, (256, 256, 4, 2, 64, 1), [('unit', 0, 0)], prec=1,
+         tile1_route=t1)
+    return out
+
+
+GEMM_CASES = _gemm_cases()

@@ -72,7 +72,11 @@ def _gemm_bf16(A, W, bias=None, resid=None, alpha=1.0, act=0):
     (7936, 2048, 256), (7936, 256, 2048), (513, 4233, 256), (2000, 768, 256),
     (129, 130, 2432), (3000, 1280, 5120), (3000, 5120, 1280), (4097, 384, 160)])
 def test_gemm_bf16_plain_asymmetric(M, N, K):
-    """Both K-tile widths (K % 64 == 0 and not), every block shape, ragged M / N."""
+    """Both K-tile widths (K % 64 == 0 and not), ragged M / N.  Block shapes by the route report
+    of wn_op_gemm_ex: 64x64 / 2x2 for ten of the shapes (both K tiles), 128x128 / 2x4 (K tile 64)
+    for (7936, 2048, 256), (3000, 1280, 5120) and (3000, 5120, 1280); the largest t256 here is
+    248, so the 256x256 / 4x2 block never runs, nor do the GLU and gathered-row blocks or
+    128x128 with a K tile of 32: those are tests/test_gpu_gemm_ops.py."""
     g = torch.Generator().manual_seed(M * 131 + N * 7 + K)
     A = torch.randn(M, K, generator=g)
     W = torch.randn(N, K, generator=g)  # asymmetric operands (transpose check)

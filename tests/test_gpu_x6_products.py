@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import x6_probe as P
+from kernel_refs import glu_perm as _glu_perm
 
 pytestmark = pytest.mark.gpu
 
@@ -150,12 +151,6 @@ def test_gemm_x6r_one_term(N, epi, kind):
         worst = _check(f'x6r epi {epi} {M}x{N} {kind}', outs[0], ref, worst)
         assert torch.equal(outs[0], outs[1])
     print(f'\n[x6r epi {epi} N {N} {kind}] max |err| / |a w| = {worst / ULP:.2f} x 2^-24')
-
-
-def _glu_perm(d):
-    """Weight rows per 64 as [32 values | 32 gates] (what wn_model_create gives pointwise_conv1)."""
-    return torch.cat([torch.cat([torch.arange(32) + 32 * u, torch.arange(32) + 32 * u + d])
-                      for u in range(d // 32)])
 
 
 def test_gemm_x6r_glu_value_half_one_term():

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import kernel_refs as KR
 from oracle import wenet_oracle as O
@@ -797,3 +798,106 @@ def test_oracle_defines_the_scale_of_an_all_zero_mx_block():
     q, E = O.mx_quantize(x)
     assert (E[:, 2] == 0).all() and (q.view(torch.uint8)[:, 64:96] == 0).all()
     assert (E[:, [0, 1, 3]] > 0).all()
+
+
+# ---------------------------------------------------------------------------------------------
+# the GEMM references (tests/test_gpu_gemm_ops.py): every statement of ref_gemm against a second
+# one, and the yardstick of every GPU case
+
+
+def _gemm_spec_of(kind, prec=0, glu=False, regime='unit', **match):
+    for s in KR.GEMM_CASES:
+        if (s['kind'], s['prec'], s['glu'], s['regime']) == (kind, prec, glu, regime) and \
+                all(s[k] == v for k, v in match.items()):
+            return s
+    raise KeyError((kind, prec, glu, regime, match))
+
+
+@pytest.mark.parametrize('act', [0, 1, 2, 3])
+@pytest.mark.parametrize('prec', [0, 1])
+def test_ref_gemm_plain_is_linear(prec, act):
+    """torch.nn.Linear + the torch.nn activation module, alpha and the residual by hand."""
+    c = KR.make_gemm_case(_gemm_spec_of('plain', prec, M=333, act=act, resid=1))
+    s = c['spec']
+    lin = torch.nn.Linear(c['K'], c['N']).double()
+    rnd = KR._r16 if prec else (lambda t: t)
+    with torch.no_grad():
+        lin.weight.copy_(rnd(c['W']).double())
+        lin.bias.copy_(c['bias'].double())
+        mod = [torch.nn.Identity(), torch.nn.SiLU(), torch.nn.ReLU(), torch.nn.GELU()][act]
+        want = c['resid'].double() + s['alpha'] * mod(lin(rnd(c['A']).double()))
+    assert s['alpha'] == 0.5
+    _close(KR.ref_gemm(c), want)
+
+
+@pytest.mark.parametrize('N,M', [(64, 1), (192, 130), (14272, 129)])
+def test_ref_gemm_glu_is_the_epilogue_over_the_permuted_weight(N, M):
+    """F.glu over [values | gates] == per 64 permuted columns, value j (0..31) times the sigmoid
+    of gate 32 + j, at output column 32 * block + j -- the GLU epilogue's own column rule, on the
+    weight the kernel gets."""
+    c = KR.make_gemm_case(_gemm_spec_of('plain', glu=True, N=N, M=M))
+    z = c['A'].double() @ c['W'].double().t() + c['bias'].double()          # permuted columns
+    z = z.view(M, N // 64, 2, 32)
+    want = (z[:, :, 0] * torch.sigmoid(z[:, :, 1])).reshape(M, N // 2)
+    _close(KR.ref_gemm(c), want)
+    assert sorted(KR.glu_perm(N // 2).tolist()) == list(range(N))
+
+
+@pytest.mark.parametrize('prec', [0, 1])
+def test_ref_gemm_rows_is_conv1d(prec):
+    """The gathered-rows operand == Conv1d(d, N, 3, stride 2) over every utterance's frames."""
+    c = KR.make_gemm_case(_gemm_spec_of('rows', prec, M=66, act=0, resid=0))
+    s, d = c['spec'], c['d']
+    rnd = KR._r16 if prec else (lambda t: t)
+    frames = c['buf'].view(-1, d)
+    outs, at = [], 1
+    for n in s['lens']:
+        x = rnd(frames[at:at + n]).double().t().unsqueeze(0)                  # (1, d, n)
+        outs.append(F.conv1d(x, rnd(c['w_t']).double(), c['bias'].double(), stride=s['stride'])[0].t())
+        at += n + 1
+    _close(KR.ref_gemm(c), torch.cat(outs))
+
+
+@pytest.mark.parametrize('C', [32, 64])
+@pytest.mark.parametrize('prec', [0, 1])
+def test_ref_gemm_conv3_is_the_gathered_operand(prec, C):
+    """F.conv2d on the channels-last images == the operand indexed tap by tap out of the flat
+    buffer (GemmArgs' address rule) times the (N, (ky * 3 + kx) * C + c) weight."""
+    c = KR.make_gemm_case(_gemm_spec_of('conv3', prec, M=69, conv_C=C))
+    rnd = KR._r16 if prec else (lambda t: t)
+    X = KR.gemm_operand(c)
+    assert X.shape == (69, 9 * C) and X.abs().max() < KR.POISON
+    want = F.relu(rnd(X).double() @ rnd(c['W']).double().t() + c['bias'].double())
+    _close(KR.ref_gemm(c), want)
+
+
+def test_gemm_cases_yardstick_and_coded_values():
+    """Every case of the GPU file: its id is unique, its reference is finite (no POISON reaches
+    it), the cap on e_plain holds from the reference alone; a coded case's reference rounds to a
+    matrix of (half-)integers that the fp32 evaluation reproduces to the bit, with more than one
+    value per row and per column (a misplaced row or column is then a different number); a wide
+    case's pre-activations reach past +-88 and +-104."""
+    ids = [KR.gemm_case_id(s) for s in KR.GEMM_CASES]
+    assert len(set(ids)) == len(ids)
+    for s, name in zip(KR.GEMM_CASES, ids):
+        c = KR.make_gemm_case(s)
+        ref, e_plain, scale = KR.gemm_refs(c)
+        n_out = s['N'] // 2 if s['glu'] else s['N']
+        assert ref.shape == (s['M'], n_out), name
+        assert torch.isfinite(ref).all() and scale < 1e6, name
+        assert KR.cap_ok(e_plain, scale), (name, e_plain, scale)
+        if 'buf' in c:
+            assert (c['buf'][c['own']].abs() < KR.POISON).all() and \
+                (c['buf'][~c['own']] == KR.POISON).all() and not c['own'].all(), name
+        if s['regime'] == 'coded':
+            # (a shut GLU gate leaves 1e-85 of its value in fp64: 0.0f once rounded to fp32)
+            r32 = ref.float()
+            assert e_plain < 1e-80 and torch.equal(KR.ref_gemm(c, fp32=True).float(), r32), name
+            assert torch.equal(2 * r32, torch.round(2 * r32)) and (ref - r32).abs().max() < 1e-80, \
+                name
+            if s['M'] > 1 and n_out > 1:
+                assert (ref.max(0).values > ref.min(0).values).float().mean() > 0.9, name
+                assert (ref.max(1).values > ref.min(1).values).float().mean() > 0.9, name
+        if s['regime'] == 'wide':
+            bias = c['b_un'][s['N'] // 2:] if s['glu'] else c['bias']
+            assert bias.max() >= 104.0 and bias.min() <= -104.0 or s['N'] < 9, name

@@ -124,11 +124,21 @@ class WnAttentionOp(Structure):
                 ('flags', c_int32), ('precision', c_int32), ('x6_galign', c_int32)]
 
 
+class WnGemmOp(Structure):
+    """wn_gemm_op: the arguments of wn_op_gemm_ex."""
+    _fields_ = [('A', c_void_p), ('W', c_void_p), ('bias', c_void_p), ('resid', c_void_p),
+                ('C', c_void_p), ('M', c_int32), ('N', c_int32), ('K', c_int32),
+                ('lda', c_int32), ('ldc', c_int32), ('ldr', c_int32), ('alpha', c_float),
+                ('act', c_int32), ('glu', c_int32), ('precision', c_int32),
+                ('a_row_off', POINTER(c_int64)), ('a_elems', c_int64), ('conv_C', c_int32),
+                ('conv_sy', c_int64), ('conv_sx', c_int64)]
+
+
 # every symbol include/wenet_amd.h declares
 EXPORTS = [
     'wn_last_error', 'wn_version', 'wn_model_create', 'wn_model_destroy', 'wn_model_clone',
     'wn_model_set_precision', 'wn_model_get_precision', 'wn_batch_size', 'wn_model_set_encode_gate', 'wn_op_gemm_bf16',
-    'wn_op_gemm_bf16_stored',
+    'wn_op_gemm_bf16_stored', 'wn_op_gemm_ex',
     'wn_attention_beam_search', 'wn_attention_beam_search_prompt', 'wn_attention_truncated',
     'wn_op_gemm_skinny', 'wn_encode_chunk_batch', 'wn_op_gemm_lowp', 'wn_op_mx_quantize', 'wn_op_ffn_fused', 'wn_op_gemm_x6', 'wn_op_ffn_x6', 'wn_op_gemm_x6r', 'wn_op_gemm_x6r512', 'wn_profile_kernel_name', 'wn_profile_ffn_split', 'wn_profile_ffn_clocks', 'wn_profile_gemm_clocks', 'wn_filter_blank_embedding',
     'wn_workspace_create', 'wn_resample_length', 'wn_resample', 'wn_fbank', 'wn_log_mel', 'wn_encode', 'wn_encode_chunk', 'wn_set_encoder_out',
@@ -243,6 +253,7 @@ def lib():
     L.wn_op_gemm.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]
     L.wn_op_gemm_skinny.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.wn_op_gemm_bf16.argtypes = L.wn_op_gemm.argtypes
+    L.wn_op_gemm_ex.argtypes = [POINTER(WnGemmOp), pi32, vp]
     L.wn_op_gemm_bf16_stored.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp]
     L.wn_op_gemm_lowp.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32,
                                   i32, vp]

@@ -94,6 +94,68 @@ int wn_op_gemm_bf16(const float* A, const float* W, const float* bias,
   return r;
 }
 
+int wn_op_gemm_ex(const wn_gemm_op* op, int32_t* route_out, void* stream) {
+  WN_CHECK(op && route_out, "gemm_ex: null argument");
+  const wn_gemm_op& o = *op;
+  WN_CHECK(o.A && o.W && o.C, "gemm_ex: null operand");
+  WN_CHECK(o.M > 0 && o.N > 0 && o.K > 0, "gemm_ex: empty problem");
+  WN_CHECK(o.precision == PREC_F32 || o.precision == PREC_BF16, "gemm_ex: precision");
+  WN_CHECK(o.act >= ACT_NONE && o.act <= ACT_GELU, "gemm_ex: activation");
+  WN_CHECK(o.glu == 0 || o.glu == 1, "gemm_ex: glu is 0 or 1");
+  WN_CHECK(o.K % 32 == 0, "gemm_ex: K must be a multiple of 32");
+  WN_CHECK(reinterpret_cast<uintptr_t>(o.A) % 16 == 0 && reinterpret_cast<uintptr_t>(o.W) % 16 == 0,
+           "gemm_ex: A and W must be 16-byte aligned");
+  const bool conv = o.a_row_off != nullptr;
+  if (o.glu) {
+    WN_CHECK(o.N % 64 == 0, "gemm_ex(GLU): N must be a multiple of 64");
+    // (an activation, a residual or alpha with it: gemm_f32's own refusal)
+    WN_CHECK(!conv, "gemm_ex(GLU): no gathered A with the GLU epilogue");
+  }
+  WN_CHECK(o.ldc >= (o.glu ? o.N / 2 : o.N), "gemm_ex: ldc is smaller than the output row");
+  WN_CHECK(o.resid == nullptr || o.ldr >= o.N, "gemm_ex: ldr is smaller than N");
+  WN_CHECK(o.a_elems > 0, "gemm_ex: a_elems");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf rows;
+  if (conv) {
+    WN_CHECK(o.act != ACT_SILU, "gemm_ex: no SiLU epilogue with a gathered A");
+    WN_CHECK(o.conv_C > 0 && o.conv_C % 32 == 0 && (o.K == 9 * o.conv_C || o.K == o.conv_C),
+             "gemm_ex(conv): K must be 9*C (3x3 taps) or C (gathered rows), C % 32 == 0");
+    WN_CHECK(o.conv_sy >= 0 && o.conv_sx >= 0 && o.conv_sy % 4 == 0 && o.conv_sx % 4 == 0,
+             "gemm_ex(conv): tap strides must be non-negative multiples of 4 floats");
+    const int64_t last_tap = o.K == o.conv_C ? 0 : 2 * o.conv_sy + 2 * o.conv_sx;
+    WN_CHECK(last_tap + o.conv_C <= o.a_elems, "gemm_ex(conv): a gathered read past a_elems");
+    for (int r = 0; r < o.M; ++r) {
+      WN_CHECK(o.a_row_off[r] >= 0 && o.a_row_off[r] % 4 == 0,
+               "gemm_ex(conv): a row offset is negative or not a multiple of 4 floats");
+      WN_CHECK(o.a_row_off[r] <= o.a_elems - last_tap - o.conv_C,
+               "gemm_ex(conv): a gathered read past a_elems");
+    }
+    WN_TRY(rows.ensure((size_t)o.M * sizeof(int64_t)));
+    WN_HIP(hipMemcpyAsync(rows.p, o.a_row_off, (size_t)o.M * sizeof(int64_t),
+                          hipMemcpyHostToDevice, s));
+    WN_HIP(hipStreamSynchronize(s));
+  } else {
+    WN_CHECK(o.lda % 4 == 0, "gemm_ex: lda must be a multiple of 4 floats");
+    WN_CHECK(o.lda >= o.K, "gemm_ex: lda is smaller than K");
+    WN_CHECK((int64_t)(o.M - 1) * o.lda + o.K <= o.a_elems, "gemm_ex: a read past a_elems");
+  }
+  GemmArgs g;
+  g.A = o.A; g.W = o.W; g.bias = o.bias; g.resid = o.resid; g.C = o.C;
+  g.M = o.M; g.N = o.N; g.K = o.K; g.lda = o.lda; g.ldc = o.ldc; g.ldr = o.ldr;
+  g.alpha = o.alpha; g.act = o.act; g.glu = o.glu != 0;
+  if (conv) {
+    g.a_row_off = rows.as<int64_t>(); g.conv_C = o.conv_C;
+    g.conv_sy = o.conv_sy; g.conv_sx = o.conv_sx;
+  }
+  const int saved = t_gemm_prec;
+  t_gemm_prec = o.precision;
+  t_gemm_route = 0;
+  const int r = gemm_f32(g, s);
+  t_gemm_prec = saved;
+  *route_out = t_gemm_route;
+  return r;
+}
+
 int wn_op_gemm_bf16_stored(const float* A, const float* W, const float* bias,
                            const float* resid, void* C, int32_t M, int32_t N, int32_t K,
                            float alpha, int32_t act, int32_t c_bf16, void* stream) {

@@ -152,6 +152,16 @@ int gemm_f32(const GemmArgs& a, hipStream_t stream);
 enum GemmPrecision { PREC_F32 = 0, PREC_BF16 = 1 };
 extern thread_local int t_gemm_prec;
 int gemm_bf16(const GemmArgs& a, hipStream_t stream);  // called by gemm_f32
+// The kernel instantiation the last gemm_f32 call of this host thread launched (gemm.hip /
+// gemm_bf16.hip; the host-side launch<> stores it, no kernel reads it): wn_op_gemm_ex reports
+// it to the operator tests.  BM/64 | BN/64 << 4 | WGM << 8 | WGN << 12 | (K tile / 32) << 16 |
+// PF << 20 | GLU << 22 | CONV << 23 | precision << 24 | act << 25 | resid << 27.
+extern thread_local int t_gemm_route;
+constexpr int gemm_route_code(int bm, int bn, int wgm, int wgn, int bk, int pf, bool glu,
+                              bool conv, int prec, int act, bool resid) {
+  return bm / 64 | (bn / 64) << 4 | wgm << 8 | wgn << 12 | (bk / 32) << 16 | pf << 20 |
+         (int)glu << 22 | (int)conv << 23 | prec << 24 | act << 25 | (int)resid << 27;
+}
 // bf16 image of the calling handle's weight slab (PrecisionScope): W pointers
 // inside [t_wslab_f32, t_wslab_f32 + t_wslab_elems) map to t_wslab_bf16 + offset.
 extern thread_local const float* t_wslab_f32;

@@ -29,6 +29,7 @@
 namespace wn {
 
 thread_local int t_gemm_prec = PREC_F32;
+thread_local int t_gemm_route = 0;
 
 namespace {
 
@@ -199,6 +200,7 @@ int launch(const GemmArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WGM * WGN * 64), lds,
                      stream, a, tiles_m, tiles_n);
   WN_HIP(hipGetLastError());
+  t_gemm_route = gemm_route_code(BM, BN, WGM, WGN, BKT, PF, GLU, CONV, PREC_F32, ACT, RESID);
   return 0;
 }
 
@@ -261,7 +263,12 @@ int gemm_f32(const GemmArgs& a, hipStream_t stream) {
   } else {
     WN_CHECK(a.lda % 4 == 0, "gemm: lda must be a multiple of 4 floats");
   }
-  if (a.glu) WN_CHECK(a.N % 64 == 0, "gemm(GLU): N must be a multiple of 64");
+  if (a.glu) {
+    WN_CHECK(a.N % 64 == 0, "gemm(GLU): N must be a multiple of 64");
+    // the GLU epilogue has no activation, residual or alpha: refuse what it would drop
+    WN_CHECK(a.act == ACT_NONE && a.resid == nullptr && a.alpha == 1.0f,
+             "gemm(GLU): no activation, residual or alpha with the GLU epilogue");
+  }
   if (t_gemm_prec == PREC_BF16) return gemm_bf16(a, stream);
   WN_CHECK(!a.a_bf16 && !a.c_bf16, "gemm: bf16 operands need the bf16 mode");
   // Tile choice (measured on M = 7932 rows, profiles/): 8 waves per block hide

@@ -188,6 +188,7 @@ int launch(const GemmArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WGM * WGN * 64), lds,
                      stream, a, tiles_m, tiles_n);
   WN_HIP(hipGetLastError());
+  t_gemm_route = gemm_route_code(BM, BN, WGM, WGN, BKT, 1, GLU, CONV, PREC_BF16, ACT, RESID);
   return 0;
 }
 
