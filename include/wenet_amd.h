@@ -600,6 +600,42 @@ int wn_op_gemm_lowp(const void* A_dev, const void* W_dev, const void* a_scale_de
  * (block rule: the smallest power of two 2^e with amax <= 448 * 2^e; csrc/mxfp8.h). */
 int wn_op_mx_quantize(const float* x_dev, int32_t rows, int32_t K, void* q_dev,
                       void* scale_dev, void* stream);
+/* The whole argument block of the stored-operand GEMMs (csrc/gemm_bf16s.hip, gemm_bf16p.hip) as
+ * the model's launchers fill it (test infrastructure).  Operands arrive in their storage type,
+ * as with wn_op_gemm_lowp; nothing is converted.  dtype 1: bf16 A (M, lda) and W (N, K); dtype 2:
+ * MXFP8, e4m3 A (M, lda) and W (N, K) with scale dwords [K/128][a_scale_pitch] /
+ * [K/128][w_scale_pitch].  c_mode 0: fp32 C (M, ldc); 1: bf16 C (bf16 operands); 2: MXFP8 C
+ * (MXFP8 operands) with its scale dwords [ceil(N/128)][c_scale_pitch].  lda / ldc are in
+ * elements of A / C, ldr in floats.  glu (bf16 operands, fp32 C): W rows as [32 values |
+ * 32 gates] per 64, C has N / 2 columns.  Every argument the kernels assume is checked on the
+ * host BEFORE anything is launched, each with its own message: 16-byte aligned A, W, C, bias
+ * and residual, lda % 8 (bf16) / % 16 (MXFP8), ldc % 4 / 8 / 16 by C mode, ldr % 4, lda >= K,
+ * ldc and ldr not smaller than the output row, pitches not smaller than the rows, the byte sizes
+ * of the buffers, no residual with a bf16 or MXFP8 C, K % 32 (bf16) or K % 128, K >= 256,
+ * N % 8 (N % 32 with an MXFP8 C) for MXFP8. */
+typedef struct wn_gemm_lowp_op {
+  const void* A; const void* W; const float* bias; const float* resid; void* C;
+  const void* a_scale; const void* w_scale; void* c_scale;
+  int32_t M, N, K;
+  int32_t lda, ldc, ldr;
+  int32_t a_scale_pitch, w_scale_pitch, c_scale_pitch;
+  float alpha;
+  int32_t act;         /* 0 none, 1 SiLU, 2 ReLU, 3 GELU */
+  int32_t glu;
+  int32_t dtype;       /* 1 bf16, 2 MXFP8 */
+  int32_t c_mode;      /* 0 fp32, 1 bf16, 2 MXFP8 */
+  int64_t a_bytes, w_bytes;                               /* bytes in the A / W buffers */
+  int64_t a_scale_bytes, w_scale_bytes, c_scale_bytes;    /* and in the scale arrays */
+} wn_gemm_lowp_op;
+/* Calls gemm_bf16_stored / gemm_mxfp8 directly.  *route_out = the kernel instantiation that ran:
+ * the fields of wn_op_gemm_ex | MXFP8 elements << 19 | kernel family << 28 (1 gemm_bf16s_kernel,
+ * 2 gemm_lp_kernel) | c_mode << 30 (the K tile field is 3 bits; PF is 2 for gemm_bf16s_kernel). */
+int wn_op_gemm_lowp_ex(const wn_gemm_lowp_op* op, int32_t* route_out, void* stream);
+/* wn_op_mx_quantize with every argument of the quantiser: x (rows, ld) fp32, ld % 4 == 0,
+ * ld >= K, K % 32 == 0; q (rows, K) e4m3 bytes; scale dwords [ceil(K/128)][pitch], pitch >= rows
+ * (of the last dword of a row only the bytes of blocks < K / 32 are written). */
+int wn_op_mx_quantize_ex(const float* x_dev, int32_t ld, int32_t rows, int32_t K, void* q_dev,
+                         void* scale_dev, int32_t pitch, void* stream);
 /* The fused fp32 feed-forward module the encoder runs (csrc/ffn_fused.hip;
  * positionwise_feed_forward.py:50-58 inside encoder_layer.py:220-228): x_inout (M, D) +=
  * alpha * (act(X W1^T + b1) W2^T + b2) with X (M, D) the already normalised input, then

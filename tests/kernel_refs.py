@@ -24,6 +24,10 @@ Last: the fp32 and bf16-on-the-fly matrix-core GEMMs with every argument of Gemm
 epilogues, GLU, gathered rows, the implicit 3x3 / stride-2 operand -- as `ref_gemm`, and the list
 of cases GEMM_CASES that tests/test_gpu_gemm_ops.py runs and tests/test_kernel_refs.py checks.
 
+After them: the stored-operand GEMMs (csrc/gemm_bf16s.hip, gemm_bf16p.hip) and the MXFP8 quantiser
+-- `mx_encode` / `mx_decode` from the OCP MX rule, `ref_gemm_lowp` on the decoded operands and the
+cases GEMM_LOWP_CASES of tests/test_gpu_gemm_lowp_ops.py.
+
 No GPU in here.
 """
 import math
@@ -1255,3 +1259,351 @@ def _gemm_cases():
 
 
 GEMM_CASES = _gemm_cases()
+
+
+# ---------------------------------------------------------------------------------------------
+# the stored-operand GEMMs (csrc/gemm_bf16s.hip, gemm_bf16p.hip) through wn_op_gemm_lowp_ex and the
+# MXFP8 quantiser through wn_op_mx_quantize_ex; GPU tests in tests/test_gpu_gemm_lowp_ops.py
+
+
+def e4m3_encode(v):
+    """fp64 values -> OCP e4m3 bytes (1 sign, 4 exponent bits of bias 7, 3 mantissa bits, no
+    infinity, largest finite value 448): round to nearest even, saturating; a zero keeps its sign.
+    Normal numbers have the quantum 2^(floor(log2 |v|) - 3), everything below 2^-6 the subnormal
+    quantum 2^-9."""
+    v = v.double()
+    a = v.abs()
+    ex = torch.frexp(a)[1] - 1                                   # floor(log2 a); a = 0: anything
+    quantum = torch.exp2(torch.where(a < 2.0 ** -6, torch.full_like(ex, -9), ex - 3).double())
+    q = torch.clamp(torch.round(a / quantum) * quantum, max=448.0)        # torch.round: ties to even
+    ex = torch.frexp(q)[1] - 1                                   # the rounding may have carried
+    sub = q < 2.0 ** -6
+    field = torch.where(sub, torch.zeros_like(ex), ex + 7)
+    man = torch.where(sub, q * 2.0 ** 9, (q / torch.exp2(ex.double()) - 1.0) * 8.0)
+    byte = field.long() * 8 + man.long() + torch.signbit(v).long() * 128
+    return byte.to(torch.uint8)
+
+
+def e4m3_decode(b):
+    b = b.long()
+    field, man = (b >> 3) & 15, (b & 7).double()
+    mag = torch.where(field == 0, man * 2.0 ** -9, (1.0 + man / 8.0) * torch.exp2(field.double() - 7.0))
+    return torch.where((b & 128) != 0, -mag, mag)
+
+
+def mx_encode(x):
+    """(rows, K) fp32, K % 32 == 0 -> (e4m3 bytes (rows, K), E8M0 bytes (rows, K / 32)), the OCP
+    MX rule with the block scale csrc/mxfp8.h states: one scale 2^e per 32 consecutive k, the
+    smallest power of two with amax <= 448 * 2^e, stored as E = e + 127 clamped to [0, 253];
+    elements = e4m3(v * 2^-e), round to nearest even, saturating."""
+    rows, K = x.shape
+    xb = x.double().reshape(rows, K // 32, 32)
+    amax = xb.abs().amax(-1)
+    e = torch.frexp(amax)[1] - 1 - 8                             # amax < 2 * 256 * 2^e
+    e = e + (amax > 448.0 * torch.exp2(e.double())).to(e.dtype)
+    e = torch.where(amax == 0, torch.full_like(e, -127), e)      # every power of two will do
+    E = torch.clamp(e + 127, 0, 253)
+    q = e4m3_encode(xb * torch.exp2(127.0 - E.double()).unsqueeze(-1))
+    return q.reshape(rows, K), E.to(torch.uint8)
+
+
+def mx_decode(q, E):
+    """The fp64 values an MXFP8 image stands for: e4m3 element x 2^(E - 127) of its 32-block."""
+    rows, K = q.shape
+    v = e4m3_decode(q).reshape(rows, K // 32, 32)
+    return (v * torch.exp2(E.double() - 127.0).unsqueeze(-1)).reshape(rows, K)
+
+
+def mx_scale_dwords(E, pitch, fill=0xfe):
+    """E bytes (rows, nblk) -> the dword array [ceil(nblk / 4)][pitch] the kernels read (byte b of
+    dword [kt][row] = block 4 kt + b), as int32; every byte no (row, block) owns holds `fill`."""
+    rows, nblk = E.shape
+    nk = (nblk + 3) // 4
+    by = torch.full((nk, pitch, 4), fill, dtype=torch.uint8)
+    for kb in range(nblk):
+        by[kb // 4, :rows, kb % 4] = E[:, kb]
+    return by.view(torch.int32).reshape(nk, pitch)
+
+
+def mx_scale_bytes(dw, rows, nblk):
+    """The inverse: int32 [nk][pitch] -> E bytes (rows, nblk)."""
+    by = dw.contiguous().view(torch.uint8).reshape(dw.shape[0], dw.shape[1], 4)
+    return torch.stack([by[kb // 4, :rows, kb % 4] for kb in range(nblk)], dim=1)
+
+
+def bf16_tie_share(v, b):
+    """The share of the elements of v (fp64) that lie within b of a bf16 rounding boundary: v - b
+    and v + b round to different bf16 numbers.  (elementwise mask, share)"""
+    near = (v - b).float().to(torch.bfloat16) != (v + b).float().to(torch.bfloat16)
+    return near, near.float().mean().item()
+
+
+GELU_E5_ABS = 4.7e-6       # |gelu_e5 - gelu| (csrc/gemm_bf16p.hip; tests/test_gelu_form.py)
+FAM_STORED, FAM_PIPELINED = 1, 2
+
+
+def lowp_route_code(s):
+    """The code wn_op_gemm_lowp_ex reports for a spec (csrc/common.h gemm_route_code): the fields
+    of gemm_route_code | MXFP8 << 19 | family << 28 | C mode << 30, as an int32."""
+    bm, bn, wgm, wgn, bk = s['route']
+    pipe = s['fam'] == FAM_PIPELINED
+    code = gemm_route_code(bm, bn, wgm, wgn, bk, 1 if pipe else 2, glu=s['glu'],
+                           prec=0 if s['et'] else 1, act=s['act'], resid=bool(s['resid']))
+    code |= s['et'] << 19 | s['fam'] << 28 | s['cm'] << 30
+    return code - (1 << 32) if code >> 31 else code
+
+
+def _lowp_spec(fam, et, M, N, K, route, **kw):
+    s = dict(fam=fam, et=et, M=M, N=N, K=K, route=route, cm=0, act=0, resid=0, glu=False,
+             regime='unit', alpha=1.0, tile=8 if fam == FAM_PIPELINED and not et else 0,
+             model_pitch=True, w_pad=0, seed=0)
+    s.update(kw)
+    return s
+
+
+def gemm_lowp_case_id(s):
+    bm, bn, wgm, wgn, bk = s['route']
+    t = ['mx' if s['et'] else 'bf16', ('stored', 'pipe')[s['fam'] - 1],
+         f'{bm}x{bn}w{wgm}x{wgn}k{bk}', f"{s['M']}x{s['N']}x{s['K']}", f"act{s['act']}",
+         f"r{s['resid']}", ('c32', 'c16', 'cmx')[s['cm']], s['regime']]
+    if s['glu']:
+        t.insert(2, 'glu')
+    if s['fam'] == FAM_PIPELINED and not s['et'] and s['tile'] != 8:
+        t.insert(2, f"tile{s['tile']}")
+    return '-'.join(t)
+
+
+def _coded_hot_k(M, K):
+    return (13 * torch.arange(M) + 5) % K
+
+
+def make_gemm_lowp_case(s):
+    """The tensors of a spec of GEMM_LOWP_CASES.  `A` (M, K) / `W` (N, K) hold, as fp32, exactly
+    the values of the storage type (bf16, or e4m3 x block scale); MXFP8 cases also carry the
+    images Aq / AE and Wq / WE (element bytes, E8M0 bytes (rows, K / 32)).  `W` is what the kernel
+    gets (GLU: rows permuted), `W_un` / `b_un` the un-permuted GLU weight [values | gates].
+    Regimes: see the docstring of tests/test_gpu_gemm_lowp_ops.py."""
+    g = torch.Generator().manual_seed(7000 + s['seed'])
+    M, N, K, et, regime, glu = s['M'], s['N'], s['K'], s['et'], s['regime'], s['glu']
+    nb = K // 32
+    c = dict(spec=s, M=M, N=N, K=K)
+    mi = torch.arange(M).unsqueeze(1)
+    ni = torch.arange(N).unsqueeze(1)
+    ki = torch.arange(K).unsqueeze(0)
+    kb = torch.arange(nb).unsqueeze(0)
+    if regime in ('coded-hot', 'coded-dense'):
+        w_int = ((37 * ni + 11 * ki) % 17 - 8).double()
+        if regime == 'coded-hot':
+            # one product per output: 2^s(m) at k = h(m) against w_int 2^t(n, k / 32)
+            hot = _coded_hot_k(M, K)
+            a_int = torch.zeros(M, K, dtype=torch.float64)
+            a_int[torch.arange(M), hot] = 1.0
+            a_e = (5 * mi + 3 * kb) % 11 - 5                     # the blocks that hold only zeros
+            a_e[torch.arange(M), hot // 32] = torch.arange(M) % 9 - 4
+            w_e = (3 * ni + 5 * kb) % 9 - 4
+        else:
+            # dense small integers, one power of two per row: every k-step's products are integers
+            a_int = ((7 * mi + 3 * ki + (mi * ki) % 5) % 5 - 2).double()
+            a_e = ((mi % 7) - 3).expand(M, nb)
+            w_e = ((ni % 5) - 2).expand(N, nb)
+        if et:
+            c['Aq'], c['AE'] = e4m3_encode(a_int), (a_e + 127).to(torch.uint8)
+            c['Wq'], c['WE'] = e4m3_encode(w_int), (w_e + 127).to(torch.uint8)
+        A = a_int * torch.exp2(a_e.double()).repeat_interleave(32, dim=1)
+        W = w_int * torch.exp2(w_e.double()).repeat_interleave(32, dim=1)
+        bias = (torch.arange(N) % 7 - 3).float()
+    else:
+        if et:
+            if regime == 'unit':
+                A0 = torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g))
+                A0 = A0 * torch.exp2(torch.randint(-6, 6, (1, nb), generator=g).float()
+                                     ).repeat_interleave(32, dim=1)
+                W0 = torch.randn(N, K, generator=g) * 0.2
+            else:
+                A0 = torch.randn(M, K, generator=g)
+                W0 = torch.randn(N, K, generator=g) / math.sqrt(K)
+            c['Aq'], c['AE'] = mx_encode(A0)
+            c['Wq'], c['WE'] = mx_encode(W0)
+            A, W = mx_decode(c['Aq'], c['AE']), mx_decode(c['Wq'], c['WE'])
+        else:
+            A = _r16(torch.randn(M, K, generator=g)).double()
+            W = _r16(torch.randn(N, K, generator=g) / math.sqrt(K)).double()
+        bias = 0.3 * torch.randn(N, generator=g)
+        if s['cm'] == 1:
+            # bf16 C: keep the outputs off zero, where every absolute bound spans many bf16
+            # rounding boundaries (the tie share of the test)
+            bias = bias + 4.0
+    A, W = A.float(), W.float()
+    assert torch.isfinite(A).all() and torch.isfinite(W).all()
+    if not et:
+        assert torch.equal(_r16(A), A) and torch.equal(_r16(W), W)
+    else:
+        assert torch.equal(mx_decode(c['Aq'], c['AE']).float(), A)
+        assert torch.equal(mx_decode(c['Wq'], c['WE']).float(), W)
+    if regime == 'wide':
+        wide = torch.tensor(GEMM_WIDE)[torch.arange(N) % len(GEMM_WIDE)]
+    if glu:
+        h = N // 2
+        if regime.startswith('coded'):
+            W[h:] = 0.0
+            bias[h:] = torch.where((5 * torch.arange(h) + torch.arange(h) // 32) % 3 != 0,
+                                   GATE_ON, GATE_OFF)
+        elif regime == 'wide':
+            bias[h:] = wide[:h]
+        perm = glu_perm(h)
+        c.update(W_un=W, b_un=bias, W=W[perm].contiguous(), bias=bias[perm].contiguous())
+    else:
+        if regime == 'wide':
+            bias = wide
+        c.update(W=W, bias=bias)
+    c['A'] = A
+    if s['resid']:
+        if regime.startswith('coded'):
+            c['resid'] = ((3 * mi + 5 * torch.arange(N).unsqueeze(0)) % 17 - 8).float()
+        else:
+            c['resid'] = torch.randn(M, N, generator=g)
+    return c
+
+
+def ref_gemm_lowp(c, fp32=False):
+    """resid + alpha * act(A W^T + bias) on the DECODED operands, in fp64 (fp32: the same formula
+    in torch fp32, the yardstick).  GLU: F.glu over the un-permuted weight.  A bf16 or MXFP8 C is
+    not rounded here: the GPU test compares it with the rounding of the kernel's own fp32 C."""
+    s = c['spec']
+    dt = torch.float32 if fp32 else torch.float64
+    Wm = c['W_un'] if s['glu'] else c['W']
+    z = c['A'].to(dt) @ Wm.to(dt).t() + (c['b_un'] if s['glu'] else c['bias']).to(dt)
+    y = F.glu(z, dim=-1) if s['glu'] else gemm_act(z, s['act'])
+    y = y * s['alpha']
+    if s['resid']:
+        y = c['resid'].to(dt) + y
+    return y.double()
+
+
+def gemm_lowp_refs(c):
+    """(fp64 reference, e_plain, scale = max |ref|, S = max sum_k |a||w|) of a case."""
+    ref = ref_gemm_lowp(c)
+    plain = ref_gemm_lowp(c, fp32=True)
+    S = (c['A'].double().abs() @ c['W'].double().abs().t()).max().item()
+    return ref, (plain - ref).abs().max().item(), ref.abs().max().item(), S
+
+
+def _gemm_lowp_cases():
+    S = _lowp_spec
+    out = []
+
+    def add(fam, et, M, N, K, route, regime, act, resid, cm=0, **kw):
+        alpha = 0.5 if resid else 1.0
+        n = len(out)
+        out.append(S(fam, et, M, N, K, route, regime=regime, act=act, resid=resid, cm=cm,
+                     alpha=alpha, seed=n, model_pitch=n % 2 == 0, **kw))
+
+    # ---- the pipelined kernel: bf16 under gemm_tile_bf16 = 8, MXFP8 always; K tiles 2 3 4 5
+    for et in (0, 1):
+        P = FAM_PIPELINED
+        r = (256, 256, 2, 4, 128 if et else 64)
+        k2, k3, k4, k5 = [t * (128 if et else 64) for t in (2, 3, 4, 5)]
+        # every activation x residual form with fp32 C; every M, N, tile count
+        add(P, et, 1, 8, k2, r, 'unit', 0, 0)
+        add(P, et, 255, 256, k3, r, 'unit', 0, 1, w_pad=5)
+        add(P, et, 256, 264, k4, r, 'unit', 1, 0)
+        add(P, et, 257, 520, k5, r, 'unit', 1, 1)
+        add(P, et, 300, 8, k3, r, 'unit', 2, 0)
+        add(P, et, 1030, 264, k2, r, 'unit', 2, 1)        # 5 M panels: the last group has 1
+        add(P, et, 1281, 256, k4, r, 'unit', 3, 0)        # 6 M panels: the last group has 2
+        add(P, et, 257, 264, k5, r, 'unit', 3, 1)
+        # exact: one product per output (M >= K: every k is some row's hot k)
+        add(P, et, 257, 264, k2 if et else k4, r, 'coded-hot', 0, 0, w_pad=5)
+        add(P, et, 1030, 264, k5, r, 'coded-hot', 2, 1)
+        add(P, et, 1281, 520, k3, r, 'coded-hot', 0, 1)
+        # exact: dense integers, every K tile count
+        add(P, et, 300, 264, k5, r, 'coded-dense', 0, 0)
+        add(P, et, 1030, 264, k4, r, 'coded-dense', 2, 1, w_pad=5)
+        add(P, et, 255, 520, k2, r, 'coded-dense', 0, 0)
+        add(P, et, 257, 256, k3, r, 'coded-dense', 0, 1)
+        add(P, et, 257, 264, k2, r, 'wide', 1, 0)
+        add(P, et, 300, 520, k3, r, 'wide', 3, 0)
+        if not et:
+            # bf16 C: every activation
+            add(P, 0, 255, 520, k2, r, 'unit', 0, 0, cm=1)
+            add(P, 0, 1030, 264, k3, r, 'unit', 1, 0, cm=1)
+            add(P, 0, 257, 8, k4, r, 'unit', 2, 0, cm=1)
+            add(P, 0, 1281, 256, k5, r, 'unit', 3, 0, cm=1)
+            add(P, 0, 1, 264, k2, r, 'unit', 0, 0, cm=1)
+            add(P, 0, 300, 264, k4, r, 'coded-hot', 0, 0, cm=1)
+            add(P, 0, 256, 520, k5, r, 'coded-dense', 2, 0, cm=1)
+        else:
+            # MXFP8 C: every activation; N = 288 leaves one used byte in the last scale dword
+            add(P, 1, 255, 32, k2, r, 'unit', 0, 0, cm=2)
+            add(P, 1, 1030, 288, k3, r, 'unit', 1, 0, cm=2)
+            add(P, 1, 257, 544, k4, r, 'unit', 2, 0, cm=2, w_pad=5)
+            add(P, 1, 1281, 288, k5, r, 'unit', 3, 0, cm=2)
+            add(P, 1, 1, 288, k2, r, 'unit', 0, 0, cm=2)
+            add(P, 1, 256, 544, k3, r, 'unit', 3, 0, cm=2)
+            add(P, 1, 300, 288, k2, r, 'coded-hot', 0, 0, cm=2)
+            add(P, 1, 257, 288, k2, r, 'wide', 1, 0, cm=2)
+    # ---- the natural dispatch: t256 = 2 * 97 = 194 >= 192
+    add(FAM_PIPELINED, 0, 257, 24584, 128, (256, 256, 2, 4, 64), 'unit', 0, 0, tile=0)
+    add(FAM_PIPELINED, 0, 257, 24584, 128, (256, 256, 2, 4, 64), 'coded-hot', 2, 1, tile=0)
+
+    # ---- gemm_bf16s_kernel (t256 < 192: the dispatch of gemm_bf16_stored stays in its file)
+    T = FAM_STORED
+    every = [(a, r) for a in range(4) for r in (0, 1)]
+    bk = lambda K: 64 if K % 64 == 0 else 32
+    for K in (64, 96):
+        small, big = (64, 64, 2, 2, bk(K)), (128, 128, 2, 4, bk(K))
+        for act, resid in every:
+            add(T, 0, 333, 200, K, small, 'unit', act, resid)
+            add(T, 0, 200, 14332, K, big, 'unit', act, resid)        # t128 = 2 * 112 = 224
+        for act in range(4):
+            add(T, 0, 333, 200, K, small, 'unit', act, 0, cm=1)
+            add(T, 0, 200, 14336, K, big, 'unit', act, 0, cm=1)
+        add(T, 0, 200, 14332, K, big, 'coded-hot', 2, 1)
+        add(T, 0, 200, 14332, K, big, 'coded-dense', 0, 0)
+    # 1, 2, 3 and 5 K tiles of both widths; a single row
+    for K in (32, 64, 128, 192, 96, 160, 320):
+        small = (64, 64, 2, 2, bk(K))
+        add(T, 0, 65, 68, K, small, 'coded-dense', 2, 1)
+        add(T, 0, 333, 200, K, small, 'coded-hot', 0, 0)
+        add(T, 0, 1, 4, K, small, 'unit', 0, 0)
+    add(T, 0, 65, 68, 64, (64, 64, 2, 2, 64), 'wide', 1, 0)
+    add(T, 0, 65, 68, 96, (64, 64, 2, 2, 32), 'wide', 3, 0)
+    add(T, 0, 65, 72, 64, (64, 64, 2, 2, 64), 'coded-dense', 2, 0, cm=1)
+    add(T, 0, 333, 200, 160, (64, 64, 2, 2, 32), 'coded-hot', 0, 0, cm=1)
+    # GLU
+    for K in (64, 96):
+        for N in (64, 128, 192):
+            for M in (1, 63, 130):
+                if K == 64 or (N, M) == (192, 130):
+                    for regime in (('unit', 'coded-hot', 'wide') if M == 63 or N == 192
+                                   else ('unit', 'coded-hot')):
+                        add(T, 0, M, N, K, (64, 128, 2, 2, bk(K)), regime, 0, 0, glu=True)
+        for regime in (('unit', 'coded-hot', 'wide') if K == 64 else ('unit', )):
+            add(T, 0, 129, 14272, K, (128, 128, 4, 2, bk(K)), regime, 0, 0, glu=True)
+    # the 256x256 stored block: t256 = 2 * 128 = 256 with K >= 2048, and N % 8 != 0, which the
+    # pipelined kernel does not take
+    add(T, 0, 257, 32764, 2048, (256, 256, 4, 2, 64), 'unit', 0, 0)
+    return out
+
+
+GEMM_LOWP_CASES = _gemm_lowp_cases()
+
+
+def mx_quantize_case(rows, K, seed=5):
+    """x (rows, K): rows scaled over e^+-3, the first min(rows, 6) of them the special rows of
+    test_mx_quantize_matches_oracle_bit_for_bit (tests/test_gpu_fp8.py)."""
+    g = torch.Generator().manual_seed(seed + 1000 * rows + K)
+    x = torch.randn(rows, K, generator=g) * torch.exp(torch.randn(rows, 1, generator=g) * 3)
+    sp = [x[0].clone() for _ in range(6)]
+    sp[0][:32] = 1e-4
+    sp[0][0] = 448.0 * 2.0 ** -5                                 # amax on a block-scale boundary
+    sp[1][:32] = 1e-4
+    sp[1][0] = 449.0 * 2.0 ** 3                                  # just above it
+    sp[2][:32] = torch.linspace(-1, 1, 32) * 2.0 ** -12          # e4m3 subnormals after scaling
+    sp[2][0] = 1.0
+    sp[3][:32] = 0.0                                             # one all-zero block
+    sp[4] = torch.randn(K, generator=g) * 1e-30                  # tiny values
+    sp[5] = torch.zeros(K)                                       # all-zero blocks
+    for r in range(min(rows, 6)):
+        x[r] = sp[r]
+    return x

@@ -86,12 +86,14 @@ def tune(**kw):
             L.wn_tune_set(k.encode(), val)
 
 
-def record(name, err, e_plain, scale, bf16=False):
+def record(name, err, e_plain, scale, bf16=False, extra=0.0, check=True):
     """Prints the figures of a case, appends its ratio err / bound to the file
     WN_KERNEL_OPS_RATIOS names (profiles/r21a_kernel_ops_error_ratios.txt is one such run,
     r23a_frontend_error_ratios.txt one of tests/test_gpu_frontend.py), then
-    asserts the cap on the yardstick and the bound."""
-    b = KR.bound(e_plain, scale, bf16)
+    asserts the cap on the yardstick and the bound.  extra: a documented absolute error of the
+    kernel's own formula, added to the bound; check=False: figures only (a kernel whose
+    arithmetic e_plain is no yardstick for, asserted by its caller against another bound)."""
+    b = KR.bound(e_plain, scale, bf16) + extra
     ratio = err / b if b > 0 else (0.0 if err == 0 else float('inf'))
     line = f'{name} err={err:.3e} e_plain={e_plain:.3e} scale={scale:.3e} ratio={ratio:.3f}'
     print(line)
@@ -99,6 +101,8 @@ def record(name, err, e_plain, scale, bf16=False):
     if path:
         with open(path, 'a') as f:
             f.write(line + '\n')
+    if not check:
+        return
     assert KR.cap_ok(e_plain, scale, bf16), line
     assert err <= b, line
 

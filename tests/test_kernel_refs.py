@@ -901,3 +901,197 @@ def test_gemm_cases_yardstick_and_coded_values():
         if s['regime'] == 'wide':
             bias = c['b_un'][s['N'] // 2:] if s['glu'] else c['bias']
             assert bias.max() >= 104.0 and bias.min() <= -104.0 or s['N'] < 9, name
+
+
+# ---------------------------------------------------------------------------------------------
+# the stored-operand GEMMs and the MXFP8 quantiser (tests/test_gpu_gemm_lowp_ops.py): mx_encode /
+# mx_decode against the oracle and against torch.float8_e4m3fn, the cases of GEMM_LOWP_CASES
+
+
+def _mx_edge_rows():
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(40, 256, generator=g) * torch.exp(torch.randn(40, 1, generator=g) * 3)
+    x[0] = 0.0                                                   # zero blocks
+    x[1, :32] = 0.0
+    x[1, 40] = -0.0
+    for j, e in enumerate(range(-20, 20, 5)):                    # amax on / just above a boundary
+        x[2, 32 * j:32 * j + 32] = 1e-4 * 2.0 ** e
+        x[2, 32 * j] = 448.0 * 2.0 ** e
+        x[3, 32 * j:32 * j + 32] = 1e-4 * 2.0 ** e
+        x[3, 32 * j + 5] = -448.0 * 2.0 ** e * (1 + 2.0 ** -23)
+    x[4, 0] = 449.0 * 2.0 ** 3
+    x[5, :64] = torch.randn(64, generator=g) * 1e-30             # tiny values
+    x[5, 64:96] = torch.randn(32, generator=g) * 1e-41           # fp32 subnormals: E clamps at 0
+    x[6, :32] = torch.linspace(-1, 1, 32) * 2.0 ** -9            # e4m3 subnormals after scaling
+    x[6, 0] = 1.0
+    x[7, :32] = torch.arange(32) * 2.0 ** -10                    # ties between subnormals
+    x[7, 31] = 256.0
+    x[8, :32] = torch.finfo(torch.float32).max                   # the largest finite value
+    x[8, 32:64] = torch.finfo(torch.float32).max * torch.linspace(-1, 1, 32)
+    x[9, :32] = (16.0 + torch.arange(32)) * 2.0 ** 4             # ties between normals (17 -> 16)
+    return x
+
+
+def test_mx_encode_is_the_oracle_and_float8():
+    """mx_encode against oracle.mx_quantize (bytes and scales) and, element by element, against
+    the cast to torch.float8_e4m3fn of the scaled values; mx_decode against oracle.mx_round."""
+    x = _mx_edge_rows()
+    q, E = KR.mx_encode(x)
+    oq, oE = O.mx_quantize(x)
+    assert torch.equal(E, oE) and torch.equal(q, oq.view(torch.uint8))
+    assert torch.equal(KR.mx_decode(q, E).float(), O.mx_round(x))
+    # second statement: the scale by a search over powers of two, the elements by float8
+    xb = x.double().view(40, 8, 32)
+    amax = xb.abs().amax(-1)
+    for r in range(40):
+        for b in range(8):
+            e = -127
+            while amax[r, b] > 448.0 * 2.0 ** e and e < 126:
+                e += 1
+            assert int(E[r, b]) == e + 127, (r, b)
+            v = (xb[r, b] * 2.0 ** (127 - int(E[r, b]))).float()
+            assert v.abs().max() <= 448.0
+            assert torch.equal(v.to(torch.float8_e4m3fn).view(torch.uint8), q[r, 32 * b:32 * b + 32])
+    assert E[0].max() == 0 and q[0].max() == 0 and q[1, 40] == 0x80
+    assert (E[5, 2] == 0) and E[8, 0] == 127 + 120 and q[8, 0] == 0x78   # rounds to 2^8 * 2^120
+    # every byte but the two NaNs decodes to what float8 says and encodes back to itself
+    by = torch.arange(256, dtype=torch.uint8)
+    ok = (by & 0x7f) != 0x7f
+    assert torch.equal(KR.e4m3_decode(by)[ok].float(), by.view(torch.float8_e4m3fn).float()[ok])
+    assert torch.equal(KR.e4m3_encode(KR.e4m3_decode(by))[ok], by[ok])
+    # scale dwords: there and back, unowned bytes keep the fill
+    dw = KR.mx_scale_dwords(E[:, :5], 43)
+    assert dw.shape == (2, 43) and torch.equal(KR.mx_scale_bytes(dw, 40, 5), E[:, :5])
+    assert (dw.view(torch.uint8).view(2, 43, 4)[1, :, 1:] == 0xfe).all() and (dw[:, 40:] == -0x01010102).all()
+
+
+def test_gemm_lowp_route_codes_extend_the_old_ones():
+    assert KR.gemm_route_code(128, 128, 2, 4, 64, 1, prec=1, act=3, resid=True) == \
+        2 | 2 << 4 | 2 << 8 | 4 << 12 | 2 << 16 | 1 << 20 | 1 << 24 | 3 << 25 | 1 << 27
+    codes = [KR.lowp_route_code(s) for s in KR.GEMM_LOWP_CASES]
+    old = {KR.gemm_route_code(*s['route'], glu=s['glu'], conv=s['kind'] != 'plain', prec=s['prec'],
+                              act=s['act'], resid=s['resid'] != 0) for s in KR.GEMM_CASES}
+    assert not old & set(codes) and all(-2 ** 31 <= c < 2 ** 31 for c in codes)
+    assert len({(c, s['tile'] == 0) for c, s in zip(codes, KR.GEMM_LOWP_CASES)}) >= 60
+
+
+def _lowp_small():
+    return [s for s in KR.GEMM_LOWP_CASES if s['M'] * s['N'] * s['K'] < 2e9]
+
+
+def test_gemm_lowp_cases_cover_what_the_issue_lists():
+    cases = KR.GEMM_LOWP_CASES
+    ids = [KR.gemm_lowp_case_id(s) for s in cases]
+    assert len(set(ids)) == len(ids)
+    for et in (0, 1):
+        P = [s for s in cases if s['fam'] == KR.FAM_PIPELINED and s['et'] == et and s['N'] < 20000]
+        kt = 128 if et else 64
+        assert {s['M'] for s in P} == {1, 255, 256, 257, 300, 1030, 1281}
+        assert {s['K'] // kt for s in P} == {2, 3, 4, 5}
+        assert {(s['act'], s['resid']) for s in P if s['cm'] == 0} == \
+            {(a, r) for a in range(4) for r in (0, 1)}
+        assert {s['N'] for s in P if s['cm'] == 0} == {8, 256, 264, 520}
+        lp = [s for s in P if s['cm'] != 0]
+        assert {s['act'] for s in lp} == {0, 1, 2, 3}
+        assert {s['N'] for s in lp} == ({32, 288, 544} if et else {8, 256, 264, 520})
+        assert any((s['M'], s['N']) == (1030, 264) and s['regime'] == r for s in P
+                   for r in ('coded-hot', )) and {s['regime'] for s in P} == \
+            {'unit', 'coded-hot', 'coded-dense', 'wide'}
+        assert sum(s['w_pad'] == 5 for s in P) >= 2
+    mx = [s for s in cases if s['et']]
+    assert abs(sum(s['model_pitch'] for s in mx) - len(mx) / 2) <= 1
+    T = [s for s in cases if s['fam'] == KR.FAM_STORED]
+    for r in {(64, 64, 2, 2), (128, 128, 2, 4)}:
+        for bk in (32, 64):
+            B = [s for s in T if s['route'] == r + (bk, )]
+            assert {(s['act'], s['resid']) for s in B if s['cm'] == 0} >= \
+                {(a, q) for a in range(4) for q in (0, 1)}
+            assert {s['act'] for s in B if s['cm'] == 1} == {0, 1, 2, 3}
+    assert {(s['route'][:4], s['route'][4]) for s in T if s['glu']} == \
+        {((64, 128, 2, 2), 64), ((64, 128, 2, 2), 32), ((128, 128, 4, 2), 64), ((128, 128, 4, 2), 32)}
+    assert any(s['route'] == (256, 256, 4, 2, 64) for s in T)
+    # the dispatch rules the routes were written from
+    cd = lambda a, b: -(-a // b)
+    for s in cases:
+        t128, t256 = cd(s['M'], 128) * cd(s['N'], 128), cd(s['M'], 256) * cd(s['N'], 256)
+        if s['fam'] == KR.FAM_PIPELINED:
+            assert s['et'] or s['tile'] == 8 or (s['tile'] == 0 and t256 >= 192)
+            continue
+        pipe_ok = s['K'] % 64 == 0 and s['K'] >= 128 and s['N'] % 8 == 0 and not s['glu']
+        assert s['tile'] == 0 and (t256 < 192 or not pipe_ok)
+        bk = 64 if s['K'] % 64 == 0 else 32
+        if s['glu']:
+            want = (128, 128, 4, 2) if t128 >= 224 else (64, 128, 2, 2)
+        elif bk == 64 and t256 >= 256 and (t256 >= 1024 or s['K'] >= 2048):
+            want = (256, 256, 4, 2)
+        else:
+            want = (128, 128, 2, 4) if t128 >= 224 else (64, 64, 2, 2)
+        assert s['route'] == want + (bk, ), KR.gemm_lowp_case_id(s)
+
+
+@pytest.mark.parametrize('which', ['pipe-bf16', 'pipe-mx', 'stored', 'stored-glu'])
+def test_gemm_lowp_cases_yardstick_exactness_and_tie_share(which):
+    """Every case but the two whose reference is large (they run on the GPU machine only): the
+    reference is finite, e_plain is under the cap; a coded case is exact in fp32, every k is some
+    row's hot k when the rows allow it, and the scale bytes of neighbouring blocks and rows differ;
+    a bf16-C case has less than 2 % of its reference within the fp32 bound of a bf16 rounding
+    boundary."""
+    sel = dict([('pipe-bf16', lambda s: s['fam'] == 2 and not s['et']),
+                ('pipe-mx', lambda s: s['fam'] == 2 and s['et']),
+                ('stored', lambda s: s['fam'] == 1 and not s['glu']),
+                ('stored-glu', lambda s: s['glu'])])[which]
+    n = 0
+    for s in _lowp_small():
+        if not sel(s):
+            continue
+        n += 1
+        name = KR.gemm_lowp_case_id(s)
+        c = KR.make_gemm_lowp_case(s)
+        ref, e_plain, scale, S = KR.gemm_lowp_refs(c)
+        n_out = s['N'] // 2 if s['glu'] else s['N']
+        assert ref.shape == (s['M'], n_out) and torch.isfinite(ref).all() and scale < 1e6, name
+        assert KR.cap_ok(e_plain, scale), (name, e_plain, scale)
+        if s['regime'].startswith('coded'):
+            r32 = ref.float()
+            assert e_plain < 1e-80 and (ref - r32).abs().max() < 1e-80, name
+            assert torch.equal(KR.ref_gemm_lowp(c, fp32=True).float(), r32), name
+            assert torch.equal(r32 * 1024, torch.round(r32 * 1024)), name
+            if s['M'] > 1:
+                assert (ref.max(0).values > ref.min(0).values).float().mean() > 0.9, name
+                assert (ref.max(1).values > ref.min(1).values).float().mean() > 0.9, name
+        if s['regime'] == 'coded-hot':
+            hot = KR._coded_hot_k(s['M'], s['K'])
+            assert (c['A'] != 0).sum(1).eq(1).all() and len(set(c['A'][c['A'] != 0].tolist())) >= \
+                min(8, s['M']), name
+            if s['M'] >= s['K']:
+                assert len(set(hot.tolist())) == s['K'], name
+            if s['et']:
+                WE = c['WE'].int()
+                assert len(set(WE.flatten().tolist())) >= 8
+                assert (WE[:, 1:] != WE[:, :-1]).all() and (WE[1:] != WE[:-1]).all(), name
+        if s['regime'] == 'coded-dense':
+            assert c['A'].abs().max() <= 2 * 8 and (c['A'] != 0).float().mean() > 0.7, name
+            if s['et']:
+                assert (c['AE'] == c['AE'][:, :1]).all() and (c['WE'] == c['WE'][:, :1]).all()
+                assert KR.e4m3_decode(c['Aq']).abs().max() == 2 and \
+                    KR.e4m3_decode(c['Wq']).abs().max() == 8, name
+        if s['regime'] == 'wide':
+            bias = c['b_un'][s['N'] // 2:] if s['glu'] else c['bias']
+            assert bias.max() >= 104.0 and bias.min() <= -104.0, name
+        if s['cm'] == 1 and s['regime'] == 'unit':
+            b = KR.bound(e_plain, scale) + (KR.GELU_E5_ABS * abs(s['alpha']) if s['act'] == 3 and
+                                           s['fam'] == KR.FAM_PIPELINED else 0.0)
+            assert KR.bf16_tie_share(ref, b)[1] < 0.02, name
+    assert n >= 15
+
+
+def test_mx_quantize_cases_have_their_special_rows():
+    for rows in (1, 4, 5, 300):
+        for K in (32, 160, 256, 544):
+            x = KR.mx_quantize_case(rows, K)
+            q, E = KR.mx_encode(x)
+            assert x[0, 0] == 14.0 and E[0, 0] == 127 - 5 and q[0, 0] == 0x7e
+            if rows >= 4:
+                assert E[1, 0] == 127 + 4 and (q[2, 12:20] & 0x78).eq(0).all() and (q[2, 12:20] & 7).ne(0).all() and E[3, 0] == 0
+            if rows >= 6:
+                assert 0 < E[4].max() < 40 and (q[5] == 0).all() and (E[5] == 0).all()

@@ -134,11 +134,24 @@ class WnGemmOp(Structure):
                 ('conv_sy', c_int64), ('conv_sx', c_int64)]
 
 
+class WnGemmLowpOp(Structure):
+    """wn_gemm_lowp_op: the arguments of wn_op_gemm_lowp_ex."""
+    _fields_ = [('A', c_void_p), ('W', c_void_p), ('bias', c_void_p), ('resid', c_void_p),
+                ('C', c_void_p), ('a_scale', c_void_p), ('w_scale', c_void_p),
+                ('c_scale', c_void_p), ('M', c_int32), ('N', c_int32), ('K', c_int32),
+                ('lda', c_int32), ('ldc', c_int32), ('ldr', c_int32),
+                ('a_scale_pitch', c_int32), ('w_scale_pitch', c_int32),
+                ('c_scale_pitch', c_int32), ('alpha', c_float), ('act', c_int32),
+                ('glu', c_int32), ('dtype', c_int32), ('c_mode', c_int32),
+                ('a_bytes', c_int64), ('w_bytes', c_int64), ('a_scale_bytes', c_int64),
+                ('w_scale_bytes', c_int64), ('c_scale_bytes', c_int64)]
+
+
 # every symbol include/wenet_amd.h declares
 EXPORTS = [
     'wn_last_error', 'wn_version', 'wn_model_create', 'wn_model_destroy', 'wn_model_clone',
     'wn_model_set_precision', 'wn_model_get_precision', 'wn_batch_size', 'wn_model_set_encode_gate', 'wn_op_gemm_bf16',
-    'wn_op_gemm_bf16_stored', 'wn_op_gemm_ex',
+    'wn_op_gemm_bf16_stored', 'wn_op_gemm_ex', 'wn_op_gemm_lowp_ex', 'wn_op_mx_quantize_ex',
     'wn_attention_beam_search', 'wn_attention_beam_search_prompt', 'wn_attention_truncated',
     'wn_op_gemm_skinny', 'wn_encode_chunk_batch', 'wn_op_gemm_lowp', 'wn_op_mx_quantize', 'wn_op_ffn_fused', 'wn_op_gemm_x6', 'wn_op_ffn_x6', 'wn_op_gemm_x6r', 'wn_op_gemm_x6r512', 'wn_profile_kernel_name', 'wn_profile_ffn_split', 'wn_profile_ffn_clocks', 'wn_profile_gemm_clocks', 'wn_filter_blank_embedding',
     'wn_workspace_create', 'wn_resample_length', 'wn_resample', 'wn_fbank', 'wn_log_mel', 'wn_encode', 'wn_encode_chunk', 'wn_set_encoder_out',
@@ -258,6 +271,8 @@ def lib():
     L.wn_op_gemm_lowp.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32,
                                   i32, vp]
     L.wn_op_mx_quantize.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.wn_op_gemm_lowp_ex.argtypes = [POINTER(WnGemmLowpOp), pi32, vp]
+    L.wn_op_mx_quantize_ex.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp]
     L.wn_op_ffn_fused.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32,
                                   f32, vp]
     L.wn_op_gemm_x6.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp]

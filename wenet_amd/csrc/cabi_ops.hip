@@ -241,6 +241,111 @@ int wn_op_mx_quantize(const float* x, int32_t rows, int32_t K, void* q, void* sc
                      (hipStream_t)stream);
 }
 
+int wn_op_gemm_lowp_ex(const wn_gemm_lowp_op* op, int32_t* route_out, void* stream) {
+  WN_CHECK(op && route_out, "gemm_lowp_ex: null argument");
+  const wn_gemm_lowp_op& o = *op;
+  auto al = [](const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
+  WN_CHECK(o.A && o.W && o.C, "gemm_lowp_ex: null operand");
+  WN_CHECK(o.M > 0 && o.N > 0 && o.K > 0, "gemm_lowp_ex: empty problem");
+  WN_CHECK(o.dtype == 1 || o.dtype == 2, "gemm_lowp_ex: dtype is 1 (bf16) or 2 (MXFP8)");
+  WN_CHECK(o.c_mode >= 0 && o.c_mode <= 2, "gemm_lowp_ex: c_mode is 0, 1 or 2");
+  WN_CHECK(o.act >= ACT_NONE && o.act <= ACT_GELU, "gemm_lowp_ex: activation");
+  WN_CHECK(o.glu == 0 || o.glu == 1, "gemm_lowp_ex: glu is 0 or 1");
+  const bool fp8 = o.dtype == 2;
+  const int esz = fp8 ? 1 : 2;
+  WN_CHECK(o.c_mode != 1 || !fp8, "gemm_lowp_ex: a bf16 C needs bf16 operands");
+  WN_CHECK(o.c_mode != 2 || fp8, "gemm_lowp_ex: an MXFP8 C needs MXFP8 operands");
+  WN_CHECK(o.c_mode == 0 || o.resid == nullptr,
+           "gemm_lowp_ex: no residual with a bf16 or MXFP8 C");
+  if (o.glu) {
+    WN_CHECK(!fp8 && o.c_mode == 0, "gemm_lowp_ex(GLU): bf16 operands and an fp32 C only");
+    WN_CHECK(o.N % 64 == 0, "gemm_lowp_ex(GLU): N must be a multiple of 64");
+    WN_CHECK(o.act == ACT_NONE && o.resid == nullptr && o.alpha == 1.0f,
+             "gemm_lowp_ex(GLU): no activation, residual or alpha with the GLU epilogue");
+  }
+  WN_CHECK(al(o.A, 16) && al(o.W, 16), "gemm_lowp_ex: A and W must be 16-byte aligned");
+  WN_CHECK(al(o.C, 16), "gemm_lowp_ex: C must be 16-byte aligned");
+  WN_CHECK(al(o.bias, 16) && al(o.resid, 16),
+           "gemm_lowp_ex: bias and residual must be 16-byte aligned");
+  if (fp8) {
+    WN_CHECK(o.K % 128 == 0 && o.K >= 256,
+             "gemm_lowp_ex(MXFP8): K must be a multiple of 128, at least 256");
+    WN_CHECK(o.N % 8 == 0, "gemm_lowp_ex(MXFP8): N must be a multiple of 8");
+    WN_CHECK(o.c_mode != 2 || o.N % 32 == 0,
+             "gemm_lowp_ex(MXFP8 C): N must be a multiple of 32");
+    WN_CHECK(o.lda % 16 == 0, "gemm_lowp_ex(MXFP8): lda must be a multiple of 16 elements");
+  } else {
+    WN_CHECK(o.K % 32 == 0, "gemm_lowp_ex: K must be a multiple of 32");
+    WN_CHECK(o.lda % 8 == 0, "gemm_lowp_ex: lda must be a multiple of 8 elements");
+  }
+  WN_CHECK(o.lda >= o.K, "gemm_lowp_ex: lda is smaller than K");
+  const int n_out = o.glu ? o.N / 2 : o.N;
+  WN_CHECK(o.ldc >= n_out, "gemm_lowp_ex: ldc is smaller than the output row");
+  WN_CHECK(o.ldc % (o.c_mode == 2 ? 16 : o.c_mode == 1 ? 8 : 4) == 0,
+           "gemm_lowp_ex: ldc must be a multiple of 4 (fp32 C), 8 (bf16 C) or 16 (MXFP8 C)");
+  if (o.resid) {
+    WN_CHECK(o.ldr >= o.N, "gemm_lowp_ex: ldr is smaller than N");
+    WN_CHECK(o.ldr % 4 == 0, "gemm_lowp_ex: ldr must be a multiple of 4 floats");
+  }
+  WN_CHECK(((int64_t)(o.M - 1) * o.lda + o.K) * esz <= o.a_bytes,
+           "gemm_lowp_ex: a read past a_bytes");
+  WN_CHECK((int64_t)o.N * o.K * esz <= o.w_bytes, "gemm_lowp_ex: a read past w_bytes");
+  if (fp8) {
+    const int64_t nk = o.K / 128;
+    WN_CHECK(o.a_scale && o.w_scale, "gemm_lowp_ex(MXFP8): null block scales");
+    WN_CHECK(al(o.a_scale, 4) && al(o.w_scale, 4) && al(o.c_scale, 4),
+             "gemm_lowp_ex(MXFP8): scale arrays must be 4-byte aligned");
+    WN_CHECK(o.a_scale_pitch >= o.M, "gemm_lowp_ex(MXFP8): a_scale_pitch is smaller than M");
+    WN_CHECK(o.w_scale_pitch >= o.N, "gemm_lowp_ex(MXFP8): w_scale_pitch is smaller than N");
+    WN_CHECK(nk * o.a_scale_pitch * 4 <= o.a_scale_bytes,
+             "gemm_lowp_ex(MXFP8): a read past a_scale_bytes");
+    WN_CHECK(nk * o.w_scale_pitch * 4 <= o.w_scale_bytes,
+             "gemm_lowp_ex(MXFP8): a read past w_scale_bytes");
+    if (o.c_mode == 2) {
+      WN_CHECK(o.c_scale, "gemm_lowp_ex(MXFP8 C): null C scales");
+      WN_CHECK(o.c_scale_pitch >= o.M, "gemm_lowp_ex(MXFP8 C): c_scale_pitch is smaller than M");
+      WN_CHECK((int64_t)cdiv(o.N, 128) * o.c_scale_pitch * 4 <= o.c_scale_bytes,
+               "gemm_lowp_ex(MXFP8 C): a store past c_scale_bytes");
+    }
+  }
+  GemmArgs g;
+  g.A = reinterpret_cast<const float*>(o.A); g.W = nullptr; g.bias = o.bias; g.resid = o.resid;
+  g.C = reinterpret_cast<float*>(o.C);
+  g.M = o.M; g.N = o.N; g.K = o.K; g.lda = o.lda; g.ldc = o.ldc; g.ldr = o.ldr;
+  g.alpha = o.alpha; g.act = o.act; g.glu = o.glu != 0;
+  t_gemm_route = 0;
+  int r;
+  if (fp8) {
+    g.fp8 = true; g.c_mx = o.c_mode == 2;
+    g.a_scale = reinterpret_cast<const unsigned*>(o.a_scale); g.a_scale_pitch = o.a_scale_pitch;
+    g.w_scale = reinterpret_cast<const unsigned*>(o.w_scale); g.w_scale_pitch = o.w_scale_pitch;
+    g.c_scale = reinterpret_cast<unsigned*>(o.c_scale); g.c_scale_pitch = o.c_scale_pitch;
+    WN_CHECK(gemm_bf16p_supported(g),
+             "gemm_lowp_ex(MXFP8): a shape the pipelined kernel does not take (operand of 2 GiB?)");
+    r = gemm_mxfp8(g, o.W, (hipStream_t)stream);
+  } else {
+    g.a_bf16 = true; g.c_bf16 = o.c_mode == 1;
+    r = gemm_bf16_stored(g, o.W, (hipStream_t)stream);
+  }
+  *route_out = t_gemm_route;
+  return r;
+}
+
+int wn_op_mx_quantize_ex(const float* x, int32_t ld, int32_t rows, int32_t K, void* q,
+                         void* scale, int32_t pitch, void* stream) {
+  WN_CHECK(x && q && scale, "mx_quantize_ex: null argument");
+  WN_CHECK(rows > 0 && K > 0, "mx_quantize_ex: empty problem");
+  WN_CHECK(K % 32 == 0, "mx_quantize_ex: K must be a multiple of 32");
+  WN_CHECK(ld % 4 == 0, "mx_quantize_ex: ld must be a multiple of 4 floats");
+  WN_CHECK(ld >= K, "mx_quantize_ex: ld is smaller than K");
+  WN_CHECK(pitch >= rows, "mx_quantize_ex: pitch is smaller than rows");
+  WN_CHECK(reinterpret_cast<uintptr_t>(x) % 16 == 0, "mx_quantize_ex: x must be 16-byte aligned");
+  WN_CHECK(reinterpret_cast<uintptr_t>(q) % 4 == 0 && reinterpret_cast<uintptr_t>(scale) % 4 == 0,
+           "mx_quantize_ex: q and scale must be 4-byte aligned");
+  return mx_quantize(x, ld, rows, K, q, reinterpret_cast<unsigned*>(scale), pitch,
+                     (hipStream_t)stream);
+}
+
 int wn_op_ffn_fused(const float* X, const float* W1, const float* b1, const float* W2,
                     const float* b2, float* x, const float* ln_w, const float* ln_b,
                     float* y, int32_t M, int32_t D, int32_t F, int32_t act, float alpha,

@@ -152,15 +152,24 @@ int gemm_f32(const GemmArgs& a, hipStream_t stream);
 enum GemmPrecision { PREC_F32 = 0, PREC_BF16 = 1 };
 extern thread_local int t_gemm_prec;
 int gemm_bf16(const GemmArgs& a, hipStream_t stream);  // called by gemm_f32
-// The kernel instantiation the last gemm_f32 call of this host thread launched (gemm.hip /
-// gemm_bf16.hip; the host-side launch<> stores it, no kernel reads it): wn_op_gemm_ex reports
-// it to the operator tests.  BM/64 | BN/64 << 4 | WGM << 8 | WGN << 12 | (K tile / 32) << 16 |
-// PF << 20 | GLU << 22 | CONV << 23 | precision << 24 | act << 25 | resid << 27.
+// The kernel instantiation the last GEMM call of this host thread launched (gemm.hip,
+// gemm_bf16.hip, gemm_bf16s.hip, gemm_bf16p.hip; the host-side launch<> stores it, no kernel reads
+// it): wn_op_gemm_ex / wn_op_gemm_lowp_ex report it to the operator tests.  BM/64 | BN/64 << 4 |
+// WGM << 8 | WGN << 12 | (K tile / 32) << 16 (3 bits) | MXFP8 elements << 19 | PF << 20 |
+// GLU << 22 | CONV << 23 | precision << 24 | act << 25 | resid << 27 | kernel family << 28 |
+// C mode << 30.  Family: 0 operands converted on the fly (gemm.hip, gemm_bf16.hip), 1 stored bf16
+// operands (gemm_bf16s.hip), 2 pipelined (gemm_bf16p.hip); C mode: 0 fp32, 1 bf16, 2 MXFP8 (the
+// code of an MXFP8 C is negative as an int32).  The fields added for the stored-operand kernels
+// are zero on the on-the-fly routes, whose codes keep their values.
 extern thread_local int t_gemm_route;
+enum GemmFamily { FAM_ONTHEFLY = 0, FAM_STORED = 1, FAM_PIPELINED = 2 };
 constexpr int gemm_route_code(int bm, int bn, int wgm, int wgn, int bk, int pf, bool glu,
-                              bool conv, int prec, int act, bool resid) {
-  return bm / 64 | (bn / 64) << 4 | wgm << 8 | wgn << 12 | (bk / 32) << 16 | pf << 20 |
-         (int)glu << 22 | (int)conv << 23 | prec << 24 | act << 25 | (int)resid << 27;
+                              bool conv, int prec, int act, bool resid, int family = 0,
+                              int mx = 0, int c_mode = 0) {
+  return (int)((unsigned)(bm / 64 | (bn / 64) << 4 | wgm << 8 | wgn << 12 | (bk / 32) << 16 |
+                          mx << 19 | pf << 20 | (int)glu << 22 | (int)conv << 23 | prec << 24 |
+                          act << 25 | (int)resid << 27 | family << 28) |
+               (unsigned)c_mode << 30);
 }
 // bf16 image of the calling handle's weight slab (PrecisionScope): W pointers
 // inside [t_wslab_f32, t_wslab_f32 + t_wslab_elems) map to t_wslab_bf16 + offset.

@@ -575,6 +575,8 @@ int launch_p(const GemmArgs& a, const void* Wq, hipStream_t stream) {
   size_t lds = 2 * TILE_BYTES + (ET == 1 ? 2 * SCALE_BYTES : 0);
   if (CM != 2 && lds < (size_t)8 * EPI_WAVE) lds = (size_t)8 * EPI_WAVE;
   auto kern = gemm_lp_kernel<ET, ACT, RESID, CM, VAR>;
+  t_gemm_route = gemm_route_code(PBM, PBN, 2, 4, KROW / (ET == 1 ? 1 : 2), 1, false, false,
+                                 ET == 1 ? PREC_F32 : PREC_BF16, ACT, RESID, FAM_PIPELINED, ET, CM);
   WN_MAX_DYN_LDS(kern, lds);
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, stream, a, Wq, tiles_m,
                      tiles_n);

@@ -157,6 +157,8 @@ int launch(const GemmArgs& a, const __bf16* Wh, hipStream_t stream) {
   const int tiles_m = cdiv(a.M, BM), tiles_n = cdiv(a.N, BN);
   const size_t lds = 2 * (BM + BN) * (BKT + 8) * sizeof(__bf16);
   auto kern = gemm_bf16s_kernel<BM, BN, WGM, WGN, ACT, RESID, GLU, CH, BKT>;
+  t_gemm_route = gemm_route_code(BM, BN, WGM, WGN, BKT, 2, GLU, false, PREC_BF16, ACT, RESID,
+                                 FAM_STORED, 0, CH ? 1 : 0);
   WN_MAX_DYN_LDS(kern, lds);
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WGM * WGN * 64), lds,
                      stream, a, Wh, tiles_m, tiles_n);
