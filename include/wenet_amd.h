@@ -924,7 +924,9 @@ int wn_op_cif_fire(const float* h, int32_t ldh, int32_t rows, int32_t d, const f
  * enc_lens_host [B] (or NULL) = l2.  *route_out = what ran, 0 if M == 0, else
  *   1 << 16 | linear_x6 << 13 | projection << 12 | slices << 8 | tile << 4 | kind
  *   kind        0 conv2 as the gathered-row v_mfma_f32 GEMM, 1 six-product with the fp32 gather,
- *               2 six-product gathering from conv1's plane image
+ *               2 six-product gathering from conv1's plane image, 3 six-product computing
+ *               conv1's patch in LDS (no conv1 tensor: c1 is then computed for the caller by
+ *               the fp32 conv1 kernel, the same values; tile = 0)
  *   tile        (kinds 1, 2) 0 one launch of 128-row tiles, 1 one launch of 256-row tiles,
  *               2 256-row tiles + the remainder as 128-row tiles, 3 256-row tiles + the
  *               remainder as `slices` K slices
@@ -934,6 +936,20 @@ int wn_op_cif_fire(const float* h, int32_t ldh, int32_t rows, int32_t d, const f
 int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host,
                   int32_t B, int32_t T, float* c1, float* c2, float* x,
                   int32_t* enc_lens_host, int32_t* route_out, void* stream);
+/* wn_op_conv2d4 for batches that take kind 3, with conv2's kernel writing the CALLER's buffer
+ * c2 [M][F2][d] (device, 16-byte aligned; required) instead of the handle's workspace, so that a
+ * test can put a frame around what the kernel itself stores; the projection reads c2.  x [M][d]
+ * optional.  -1 (and c2 untouched) if the batch takes another route. */
+int wn_op_conv2_patch_into(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host,
+                           int32_t B, int32_t T, float* c2, float* x, int32_t* route_out,
+                           void* stream);
+/* Host only: the most conv1 frames one 128-row tile of kind 3 reads for a batch of l2[B] output
+ * frames per utterance (F2 positions per frame); kind 3 is taken up to 21.  -1 on bad arguments. */
+int wn_conv2_patch_max_frames(const int32_t* l2, int32_t B, int32_t F2);
+/* The k-block order of conv2's weight image for kind 3 (host only, no device needed):
+ * src_of_dst[kbc * taps]: k block kb of the (channel chunk, tap)-ordered image is k block
+ * src_of_dst[kb] of the tap-major image (kbc = 16-channel chunks per tap). */
+int wn_conv2_kperm(int32_t kbc, int32_t taps, int32_t* src_of_dst);
 /* CTC head tail: blank penalty, log-softmax, top-k (logp NULL: the top-k only). */
 int wn_op_ctc_rows(const float* logits, int32_t ld, int32_t M, int32_t V, int32_t k,
                    int32_t blank, float blank_penalty, float* topk_val, int32_t* topk_idx,

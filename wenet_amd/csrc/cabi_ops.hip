@@ -1086,6 +1086,16 @@ int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_
                          dim3(256), 0, s, m->c1.as<char>(), cdiv(M1 * F1, 32),
                          m->d_off1.as<int>(), m->d_len1.as<int>(), F1, d, c1);
       WN_HIP(hipGetLastError());
+    } else if (c1 && (m->front_route & 15) == CONV2_PATCH) {
+      // no conv1 tensor exists on this route: the fp32 conv1 kernel computes the same values
+      // (same operation order; the patch holds their exact split)
+      const ModelData& W = *m->data;
+      Conv1Args a;
+      a.feats = feats_dev; a.mean = W.cmvn_mean; a.istd = W.cmvn_istd;
+      a.w = W.conv1_w; a.bias = W.conv1_b; a.out = c1;
+      a.t1_off = m->d_off1.as<int>(); a.t1_len = m->d_len1.as<int>();
+      a.B = B; a.T = T; a.F = m->cfg.feat_dim; a.F1 = F1; a.C = d; a.max_t1 = max_t1;
+      WN_TRY(cmvn_conv1_relu(a, s));
     } else if (c1) {
       WN_HIP(hipMemcpyAsync(c1, m->c1.p, (size_t)M1 * F1 * d * sizeof(float),
                             hipMemcpyDeviceToDevice, s));
@@ -1098,6 +1108,52 @@ int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_
                             s));
   }
   WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_op_conv2_patch_into(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host,
+                           int32_t B, int32_t T, float* c2, float* x, int32_t* route_out,
+                           void* stream) {
+  WN_CHECK(m && feats_dev && feat_lens_host && c2 && route_out,
+           "wn_op_conv2_patch_into: null argument");
+  WN_ENTER(m);
+  struct Drop { wn_model* m; ~Drop() { m->enc_gate = nullptr; m->c2_ext = nullptr; } } drop{m};
+  m->pb_valid = false;
+  PrecisionScope prec_scope(m);
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on,
+           "wn_op_conv2_patch_into: needs a Conformer encoder");
+  WN_CHECK(B > 0 && B < 65536 && T >= 7, "wn_op_conv2_patch_into: B / T");
+  WN_CHECK(((uintptr_t)c2 & 15) == 0, "wn_op_conv2_patch_into: c2 must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  m->c2_ext = c2;
+  WN_TRY(subsample_conv2d4(m, feats_dev, feat_lens_host, B, T, nullptr, 0, s));
+  WN_TRY(encode_gate_wait(m, s));
+  *route_out = m->front_route;
+  // (any other route wrote the handle's workspace and left c2 alone)
+  WN_CHECK(m->rows > 0 && (m->front_route & 15) == CONV2_PATCH,
+           "wn_op_conv2_patch_into: this batch does not take the patch kernel (kind 3)");
+  if (x)
+    WN_HIP(hipMemcpyAsync(x, m->x.p, (size_t)m->rows * m->cfg.d_model * sizeof(float),
+                          hipMemcpyDeviceToDevice, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_conv2_patch_max_frames(const int32_t* l2, int32_t B, int32_t F2) {
+  WN_CHECK(l2 && B > 0 && F2 > 0, "wn_conv2_patch_max_frames: arguments");
+  std::vector<int> off2(B), len2(B);
+  int M = 0;
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(l2[b] >= 0, "wn_conv2_patch_max_frames: negative length");
+    off2[b] = M; len2[b] = l2[b]; M += l2[b];
+  }
+  return M > 0 ? conv2_patch_max_frames(off2, len2, F2) : 0;
+}
+
+int wn_conv2_kperm(int32_t kbc, int32_t taps, int32_t* src_of_dst) {
+  WN_CHECK(kbc > 0 && taps > 0 && src_of_dst, "wn_conv2_kperm: arguments");
+  for (int kb = 0; kb < kbc * taps; ++kb) src_of_dst[kb] = conv2_kperm_src(kb, kbc, taps);
   return 0;
 }
 

@@ -1,5 +1,7 @@
 // Launch wrappers of the non-GEMM kernels of libwenet_amd.
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace wn {
@@ -393,6 +395,32 @@ struct X6ConvForm {
   int slices = 0;          // K slices of the tail (X6CONV_256_KTAIL)
 };
 X6ConvForm gemm_x6_conv_form(const X6Args& a);
+// conv2 with conv1 computed inside the block (conv2_patch.hip): d_model 256, F1 <= 39, 128-row
+// tiles; no plane image of conv1's output.
+constexpr int CONV2P_D = 256, CONV2P_BM = 128;
+constexpr int CONV2P_FRAMES = 21;   // conv1 frames a tile's patch holds (LDS: two blocks per CU)
+struct Conv2PatchArgs {
+  const float* feats = nullptr;       // (B, T, F)
+  int B = 0, T = 0, F = 0;
+  const float* mean = nullptr;        // GlobalCMVN (or null)
+  const float* istd = nullptr;
+  const float* w1 = nullptr;          // conv1 [9][256]
+  const float* b1 = nullptr;
+  const void* W3p = nullptr;          // conv2's weight image, k blocks in conv2_kperm_src order
+  const float* bias = nullptr;        // conv2 [256]
+  const int* row_utt2 = nullptr;      // utterance of an output frame
+  const int* off2 = nullptr;          // first output frame / first conv1 frame of an utterance
+  const int* off1 = nullptr;
+  int rows = 0;                       // GEMM rows: output frames x F2
+  int F1 = 0, F2 = 0;
+  int max_frames = 0;                 // conv2_patch_max_frames() of the batch
+  float* C = nullptr; int ldc = 0;    // relu(conv2 + bias), fp32 [rows][ldc]
+};
+// k block `kb` of the (channel chunk, tap)-ordered image = k block (kb % taps) * kbc + kb / taps
+// of the tap-major one (kbc = channel chunks per tap)
+int conv2_kperm_src(int kb, int kbc, int taps);
+int conv2_patch_max_frames(const std::vector<int>& off2, const std::vector<int>& len2, int F2);
+int conv2_patch(const Conv2PatchArgs& a, hipStream_t s);
 // Fused six-product feed-forward module (ffn_x6f.hip): hidden tensor in registers, d_model 256.
 struct FfnX6Args {
   const float* X = nullptr;    // X = LayerNorm(x): [M][ldx] fp32 (split into planes in registers)

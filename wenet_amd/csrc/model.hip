@@ -179,6 +179,19 @@ int build_x6_images(const wn_config& cfg, ModelData& W, bool skip_encoder) {
       p += x6_bytes(l->out, l->in);
     }
   }
+  // conv2's image with the k blocks in (channel chunk, tap) order (conv2_patch.hip, d_model 256):
+  // 24-KB slabs of the tap-major image above
+  if (cfg.d_model == CONV2P_D && !skip_encoder && W.conv2.w && W.conv2.out == CONV2P_D &&
+      W.conv2.in == 9 * CONV2P_D && W.x6_at.count(W.conv2.w)) {
+    const int kbc = CONV2P_D / 16, nkb = 9 * kbc;
+    const size_t slab = x6_bytes(CONV2P_D, 16);
+    WN_TRY(W.conv2_x6p.ensure(nkb * slab));
+    const char* src = reinterpret_cast<const char*>(W.x6_at[W.conv2.w]);
+    for (int kb = 0; kb < nkb; ++kb)
+      WN_HIP(hipMemcpyAsync(W.conv2_x6p.as<char>() + kb * slab,
+                            src + conv2_kperm_src(kb, kbc, 9) * slab, slab,
+                            hipMemcpyDeviceToDevice, nullptr));
+  }
   // fused six-product feed-forward module (ffn_x6f.hip, d_model 256): the second layer's image
   // with the k slots of a 16-unit block in the order a lane holds its hidden values
   if (cfg.d_model == 256) {
@@ -426,7 +439,7 @@ int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
 // are added by ffn_reduce_ln together with the bias, the scale and layer 0's norm_ff_macaron
 // (x starts as zeros: 0 + alpha (sum + b) is alpha (sum + b) exactly).  191 us on v_mfma_f32
 // (102 TF, r05e) before.  Returns 1 if it ran, 0 if the shape stays on linear().
-int sub_out_linear(wn_model* m, int M, int F2, hipStream_t s) {
+int sub_out_linear(wn_model* m, const float* c2, int M, int F2, hipStream_t s) {
   const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const int d = c.d_model, K = F2 * d;
@@ -444,7 +457,7 @@ int sub_out_linear(wn_model* m, int M, int F2, hipStream_t s) {
   if (S < 2) return 0;
   WN_TRY(m->ffn_part.ensure((size_t)S * M * d * sizeof(float)));
   X6Args g;
-  g.A = m->c2.as<float>(); g.lda = K; g.a_bytes = (int64_t)M * K * 4;
+  g.A = c2; g.lda = K; g.a_bytes = (int64_t)M * K * 4;
   g.B3 = it->second; g.M = M; g.N = d; g.K = K; g.epi = 1; g.ksplit = S; g.bm = bm;
   g.C = m->ffn_part.as<float>();
   WN_TRY(gemm_x6(g, s));
@@ -473,8 +486,9 @@ int encode_gate_wait(wn_model* m, hipStream_t s) {
 
 // How subsample_conv2d4 runs conv2 for M output frames / M1 conv1 frames under the calling
 // thread's precision and tune() (the function switches on this, wn_op_conv2d4 reports it);
-// *w6: the plane image of conv2's weight for the two six-product kinds.
-int conv2_kind(const wn_model* m, int M, int M1, const void** w6) {
+// *w6: the plane image of conv2's weight for the six-product kinds; *patch_frames: what
+// conv2_patch_max_frames() gave for the batch where CONV2_PATCH is returned.
+int conv2_kind(const wn_model* m, int M, int M1, const void** w6, int* patch_frames) {
   const ModelData& W = *m->data;
   const int d = m->cfg.d_model, F1 = m->F1(), F2 = m->F2();
   // fp32 on the bf16 matrix cores (gemm_x6.hip): conv1 writes the plane image of its
@@ -489,6 +503,22 @@ int conv2_kind(const wn_model* m, int M, int M1, const void** w6) {
   if (*w6 && (tune().x6_af32 != 0 || tune().x6_conv_af32 != 0) &&
       (int64_t)M1 * F1 * d * 4 < ((int64_t)1 << 31))
     return CONV2_X6_AF32;
+  // conv1's patch computed inside conv2 (conv2_patch.hip): d_model 256, the one-launch 128-row
+  // form, every tile's conv1 frames inside the LDS patch.  From two rounds of tiles on: a
+  // PROVISIONAL threshold -- the kernel was measured at config 2 (150 k rows) only; smaller
+  // batches keep the route they were measured on until a second size is measured
+  // (docs/LOG_round30.md)
+  if (*w6 && W.conv2_x6p.p && d == CONV2P_D && F1 <= 39 && tune().x6_conv_bm == 128 &&
+      tune().x6_conv_patch != 0 &&
+      (tune().x6_conv_patch == 2 || (int64_t)M * F2 >= 2 * 512 * CONV2P_BM) &&
+      (int64_t)M * F2 < (1 << 24) && m->rows == M) {
+    const int frames = conv2_patch_max_frames(m->off, m->len, F2);
+    if (frames <= CONV2P_FRAMES) {
+      *w6 = W.conv2_x6p.p;
+      *patch_frames = frames;
+      return CONV2_PATCH;
+    }
+  }
   return *w6 ? CONV2_X6_PLANES : CONV2_GEMM_F32;
 }
 
@@ -526,7 +556,11 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
     // their launch gaps that otherwise stand in the encoder chain (two-stream timeline r13b) --
     // and in front of conv1
     if (tune().enc_gate_pos == 0) WN_TRY(encode_gate_wait(m, s));
-    WN_TRY(m->c1.ensure((size_t)M1 * F1 * d * sizeof(float)));
+    const void* w6 = nullptr;
+    int patch_frames = 0;
+    const int kind = conv2_kind(m, M, M1, &w6, &patch_frames);
+    // (the patch kernel has no conv1 tensor: ~1 GB per handle at config 2)
+    if (kind != CONV2_PATCH) WN_TRY(m->c1.ensure((size_t)M1 * F1 * d * sizeof(float)));
     WN_TRY(m->c2.ensure((size_t)M * F2 * d * sizeof(float)));
     WN_TRY(m->x.ensure((size_t)M * d * sizeof(float)));
     WN_TRY(m->t1.ensure((size_t)M * d * sizeof(float)));
@@ -534,8 +568,30 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
     WN_TRY(m->hbuf.ensure((size_t)M * c.ffn_dim * sizeof(float)));
     WN_TRY(m->qkv.ensure((size_t)M * 3 * d * sizeof(float)));
     WN_TRY(m->d_a_row_off.ensure((size_t)M * F2 * sizeof(int64_t)));
-    const void* w6 = nullptr;
-    const int kind = conv2_kind(m, M, M1, &w6);
+    if (kind == CONV2_PATCH) {
+      // enc_gate_pos = 1 (the gate behind conv1; at 0 it was consumed above): there is no conv1
+      // launch to run beside the previous decode's encoder here -- the front end IS conv2
+      WN_TRY(encode_gate_wait(m, s));
+      // (test hook wn_op_conv2_patch_into: the kernel writes the caller's framed buffer)
+      float* c2 = m->c2_ext ? m->c2_ext : m->c2.as<float>();
+      Conv2PatchArgs a;
+      a.feats = feats_dev; a.B = B; a.T = T; a.F = c.feat_dim;
+      a.mean = W.cmvn_mean; a.istd = W.cmvn_istd; a.w1 = W.conv1_w; a.b1 = W.conv1_b;
+      a.W3p = w6; a.bias = W.conv2.b;
+      a.row_utt2 = m->d_row_utt.as<int>(); a.off2 = m->d_off.as<int>();
+      a.off1 = m->d_off1.as<int>();
+      a.rows = M * F2; a.F1 = F1; a.F2 = F2;
+      a.max_frames = patch_frames;
+      a.C = c2; a.ldc = d;
+      WN_TRY(conv2_patch(a, s));
+      const int r = sub_out_linear(m, c2, M, F2, s);
+      if (r < 0) return r;
+      if (r == 0)
+        WN_TRY(linear(W.sub_out, c2, F2 * d, m->x.as<float>(), d, M,
+                      s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
+      m->front_route = front_route_code(kind, X6ConvForm(), r != 0, r == 0 && t_linear_took_x6);
+      return 0;
+    }
     if (kind == CONV2_X6_AF32) {
       // conv1 as always (fp32, channels last); conv2 gathers its A rows from it, 64 B per
       // pixel and k block, and splits them in registers
@@ -606,7 +662,7 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
       }
       const X6ConvForm form = gemm_x6_conv_form(g);
       WN_TRY(gemm_x6(g, s));
-      const int r = sub_out_linear(m, M, F2, s);
+      const int r = sub_out_linear(m, m->c2.as<float>(), M, F2, s);
       if (r < 0) return r;
       if (r == 0)
         WN_TRY(linear(W.sub_out, m->c2.as<float>(), F2 * d, m->x.as<float>(), d, M,

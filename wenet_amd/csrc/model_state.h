@@ -245,6 +245,7 @@ struct ModelData {
   DevBuf weights_x6;
   std::map<const float*, const void*> x6_at;
   DevBuf weights_x6p;                    // k-slot-permuted FFN w_2 images (ffn_x6f.hip)
+  DevBuf conv2_x6p;                      // conv2's image, k blocks (channel chunk, tap) (conv2_patch.hip)
   std::map<const float*, const void*> x6p_at;
   // QKV weights with the rows permuted per head ([Q_h | K_h | V_h] x 64) as X3 images + the
   // biases in the same order: the QKV projection that writes the attention's key-tile images
@@ -394,6 +395,7 @@ struct wn_model {
   int ctc_rows = 0, ctc_k = 0;
   bool ctc_valid = false;
   bool ln0_done = false;   // t1 already holds layer 0's norm_ff_macaron(x) (sub_out_linear)
+  float* c2_ext = nullptr; // wn_op_conv2_patch_into: conv2_patch writes here instead of c2
   int front_route = 0;     // front_route_code() of the last subsample_conv2d4 (0: no rows)
   DevBuf logits, topk_val, topk_idx;
   // searches
@@ -603,9 +605,10 @@ int encode_gate_wait(wn_model* m, hipStream_t s);
 enum Conv2Kind {
   CONV2_GEMM_F32 = 0,    // conv1 fp32, conv2 as the gathered-row v_mfma_f32 GEMM (gemm_f32)
   CONV2_X6_AF32 = 1,     // conv1 fp32, conv2 six-product with the fp32 gather
-  CONV2_X6_PLANES = 2    // conv1 writes its plane image, conv2 six-product gathers from it
+  CONV2_X6_PLANES = 2,   // conv1 writes its plane image, conv2 six-product gathers from it
+  CONV2_PATCH = 3        // six-product conv2 computes conv1's patch in LDS (conv2_patch.hip)
 };
-int conv2_kind(const wn_model* m, int M, int M1, const void** w6);
+int conv2_kind(const wn_model* m, int M, int M1, const void** w6, int* patch_frames);
 // bit 16: set (rows ran) | bit 13: linear() took the six-product kernel | bit 12: the projection
 // ran as sub_out_linear | bits 8-11: K slices of conv2's tail | bits 4-7: X6ConvTile |
 // bits 0-3: Conv2Kind

@@ -67,6 +67,11 @@ namespace wn {
      when decodes are in flight); 0 = 256-row tiles on eight waves + the last round as K         \
      slices (3 % faster alone; A/B) */                                                          \
   X(x6_conv_bm, 128)                                                                            \
+  /* subsampling at d_model 256 with x6_conv_bm = 128: 1 = from two rounds of 128-row tiles on   \
+     (131 072 GEMM rows; config 2 has 150 k) conv2 computes conv1's patch in LDS itself          \
+     (conv2_patch.hip: no conv1 launch, no pixel table, no plane image); 0 = conv1's plane image \
+     + gathered conv2 at every size (A/B); 2 = the patch kernel at every size (tests) */         \
+  X(x6_conv_patch, 1)                                                                           \
   /* gemm_x6: 4 = clock stamps; 8 = wn_profile_gemm_clocks returns the row-block kernel's      \
      phase stamps (gemm_x6r.hip); WN_ABLATION builds: 1 no MFMAs, 2 no DMA */                  \
   X(x6_probe, 0)                                                                                \
