@@ -136,6 +136,12 @@ int wn_model_clone(const wn_model* src, wn_model** out);
 int wn_model_set_precision(wn_model* m, int32_t precision);
 int32_t wn_model_get_precision(const wn_model* m);
 
+/* The columns one head occupies in the staged QKV of the encoder's plain (non-grouped) rel-pos
+ * layers: 32 on Branchformer / E-Branchformer and Efficient Conformer handles with heads of 32
+ * (their attention is attention_d32_relpos), 64 otherwise (attention_kernel); -1 for a null
+ * handle.  No reference counterpart: it names the route, so a test need not time anything. */
+int32_t wn_model_encoder_head_cols(const wn_model* m);
+
 /* Number of utterances of the handle's CURRENT batch (what the last wn_encode /
  * wn_set_encoder_out / wn_set_ctc_probs installed; 0 before any, -1 for a null handle): the
  * per-utterance output arrays of the searches and of wn_rescore are sized by it.  No
@@ -880,6 +886,26 @@ int wn_op_attention_d32(const float* Q, const float* K, const float* V, int32_t 
                         int32_t ldo, const int32_t* q_off, const int32_t* q_len,
                         const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
                         int32_t n_heads, float scale, int32_t mask_mode, void* stream);
+/* Rel-pos SELF attention for ENCODER heads of d_k = 32 (csrc/attention_d32_relpos.hip): the
+ * arguments of wn_op_attention_d32 (kv_off / kv_len must repeat q_off / q_len) plus the projected
+ * position table P [p_rows][ldp] (row j for key j, head h at column h * 32; p_rows >= the longest
+ * sequence), bias_u / bias_v [n_heads][32] and the chunk window of mask_mode 2:
+ *   score(i, j) = ((q_i + u) . k_j + (q_i + v) . p_j) * scale
+ * mask_mode 0 = every key < kv_len; 2 = query i sees the keys from left_chunks chunks back
+ * (left_chunks < 0: from the start) to the end of its own chunk of chunk_size (> 0) rows, the rule
+ * of wn_op_attention's mode 2.  mask_mode 1 is refused by name.  fp32 whatever the handles'
+ * compute type. */
+int wn_op_attention_d32_relpos(const float* Q, const float* K, const float* V, int32_t ldq,
+                               int32_t ldk, int32_t ldv, int32_t q_rows, int32_t kv_rows, float* O,
+                               int32_t ldo, const int32_t* q_off, const int32_t* q_len,
+                               const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
+                               int32_t n_heads, float scale, int32_t mask_mode, const float* P,
+                               int32_t ldp, int32_t p_rows, const float* bias_u,
+                               const float* bias_v, int32_t chunk_size, int32_t left_chunks,
+                               void* stream);
+/* The launcher's block choice: 2 waves (64 query rows) per block while the longest sequence is
+ * shorter than this, 4 waves (128 rows) from it on. */
+int32_t wn_attention_d32_relpos_nw4_len(void);
 /* The LFR front end of every utterance ALONE (paraformer/layers.py:24-92): utterance b of
  * lens[b] frames gives out_len[b] = ceil(lens[b] / n) rows from row out_off[b]; row t stacks the
  * m frames n t - (m - 1) / 2 + f (each index clamped to [0, lens[b] - 1]), then GlobalCMVN over

@@ -11,8 +11,9 @@ Writes profiles/efficonformer_aishell.json and docs/LOG_round26.md (or both into
   encoder_ms / conformer_encoder_ms   wn_encode of the batch, HIP events around `steps` calls
   attention_grouped_us   one launch on the batch's packed rate-4 rows (8 heads, W = 96, g = 3)
                     through the operator hook, HIP events around 4 x `steps` calls
-  attention_relpos_us    attention_kernel with the rel-pos term on the same rows as the plain
-                    layers of this model run it: 8 heads of 32 laid out as 64 columns each
+  attention_relpos_us    attention_kernel with the rel-pos term on the same rows, 8 heads of 32
+                    laid out as 64 columns each (how the plain layers of this model ran before
+                    attention_d32_relpos: --leg enc32 has the two side by side)
   stride_dwconv_us / avgpool_residual_us   likewise, with the bytes the kernels must move
 The hook's descriptor upload (one small host-to-device copy) is inside every bracket.  The path
 is untuned and every figure comes from ONE run of this tool: a record, not a pass mark.
@@ -22,6 +23,16 @@ is untuned and every figure comes from ONE run of this tool: a record, not a pas
 The decoder leg (dec8_leg below): `aishell_efficonformer_v1_dec8`, the recipe with its own 8-head
 decoders, beside the 4-head `aishell_efficonformer_v1`; writes
 profiles/efficonformer_aishell_dec8.json and docs/LOG_round27.md.
+
+    python tools/bench_efficonformer.py --leg enc32 [--steps 10] [--warmup 3] [--repeats 5]
+                                        [--parent PARENT.json] [--out-dir DIR]
+
+The encoder leg of heads of 32 (enc32_leg below): the `aishell_ebranchformer` and
+`aishell_efficonformer_v1` encoders, whose d_k = 32 layers run on attention_d32_relpos, `repeats`
+brackets each, and the kernel per launch through its hook beside attention_kernel on the padded
+layout; --parent names the JSON of `--leg enc32 --encoders-only` brackets of the parent commit's
+tree, taken alternately with this one's on the same GPU.  Writes profiles/encoder_d32_aishell.json
+and docs/LOG_round31.md.
 """
 import argparse
 import json
@@ -77,7 +88,7 @@ def hook_launches(lens0, H, d, K, steps, warmup):
                                              len(lens), H, g, W, g, 0, -1, W ** -0.5, st),
                    'attention_grouped')
 
-    # the plain layers' attention: heads of 32 as 64 columns, the upper 32 zero
+    # the d_k = 64 kernel on heads of 32 as 64 columns, the upper 32 zero
     qkv2 = torch.zeros(M, 3 * dq, device='cuda')
     qkv2.view(M, 3 * H, 64)[:, :, :32] = torch.randn(M, 3 * H, 32, device='cuda', generator=gen)
     P2 = torch.zeros(tmax, dq, device='cuda')
@@ -185,17 +196,152 @@ def dec8_leg(args):
     return 0
 
 
+def enc32_encoders(batch, steps, warmup, repeats):
+    """`repeats` brackets of `steps` wn_encode calls per d_k = 32 encoder, ms per call each."""
+    from wenet_amd import Branchformer, EfficientConformer
+    from wenet_amd import synthetic as S
+    feats, lens = S.make_features(batch, (800, 1200), seed=7)
+    feats = feats.cuda()
+    out = dict(batch=batch, audio_s=float(lens.sum()) * 0.01, steps=steps, warmup=warmup,
+               lens0=[(int(n) - 7) // 4 + 1 for n in lens])
+    for name, cls in (('aishell_ebranchformer', Branchformer),
+                      ('aishell_efficonformer_v1', EfficientConformer)):
+        configs = S.make_configs(name)
+        model = cls(configs, S.make_state_dict(configs, 0), device='cuda:0')
+        out[name + '_ms'] = [timed(lambda: model._forward_encoder(feats, lens), steps, warmup)
+                             for _ in range(repeats)]
+        del model
+    return out
+
+
+def enc32_launches(lens0, H, steps, warmup, repeats):
+    """us per launch, `repeats` brackets of 4 x steps calls: attention_d32_relpos through its hook on
+    rows of H * 32 columns, and attention_kernel with the rel-pos term on the same rows laid out as
+    H * 64 columns with zero upper halves (what these encoders ran before)."""
+    from wenet_amd import _lib
+    L = _lib.lib()
+    d, dq = H * 32, H * 64
+    lens = np.asarray(lens0, dtype=np.int32)
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    M, tmax = int(lens.sum()), int(lens.max())
+    gen = torch.Generator(device='cuda').manual_seed(0)
+    qkv = torch.randn(M, 3 * H, 32, device='cuda', generator=gen)
+    P = torch.randn(tmax, H, 32, device='cuda', generator=gen)
+    bu = torch.randn(H, 32, device='cuda', generator=gen) * 0.5
+    bv = torch.randn(H, 32, device='cuda', generator=gen) * 0.5
+    O = torch.empty(M, d, device='cuda')
+    st = torch.cuda.current_stream().cuda_stream
+    po, pl = _lib.i32p(off), _lib.i32p(lens)
+
+    def native():
+        q = qkv.data_ptr()
+        _lib.check(L.wn_op_attention_d32_relpos(
+            q, q + 4 * d, q + 8 * d, 3 * d, 3 * d, 3 * d, M, M, O.data_ptr(), d, po, pl, po, pl,
+            len(lens), H, 32 ** -0.5, 0, P.data_ptr(), d, tmax, bu.data_ptr(), bv.data_ptr(), 0,
+            -1, st), 'attention_d32_relpos')
+
+    def pad(t):
+        z = torch.zeros(*t.shape[:-1], 64, device='cuda')
+        z[..., :32] = t
+        return z
+    qkv2, P2, bu2, bv2 = pad(qkv), pad(P), pad(bu), pad(bv)
+    O2 = torch.empty(M, dq, device='cuda')
+    op = _lib.WnAttentionOp()
+    op.Q, op.K, op.V = qkv2.data_ptr(), qkv2.data_ptr() + 4 * dq, qkv2.data_ptr() + 8 * dq
+    op.ldq = op.ldk = op.ldv = 3 * dq
+    op.q_rows = op.kv_rows = M
+    op.P, op.ldp, op.p_rows = P2.data_ptr(), dq, tmax
+    op.bias_u, op.bias_v = bu2.data_ptr(), bv2.data_ptr()
+    op.O, op.ldo = O2.data_ptr(), dq
+    op.q_off = op.kv_off = po
+    op.q_len = op.kv_len = pl
+    op.n_seq, op.n_heads = len(lens), H
+    op.mask_mode, op.chunk_size, op.left_chunks, op.scale = 0, 0, -1, 32 ** -0.5
+    op.flags, op.precision, op.x6_galign = 0, 0, 0
+    form = np.zeros(1, dtype=np.int32)
+
+    def padded():
+        _lib.check(L.wn_op_attention(op, _lib.i32p(form), st), 'attention')
+
+    n = steps * 4
+    res = dict(rows=M, max_len=tmax, nw4_len=int(L.wn_attention_d32_relpos_nw4_len()),
+               attention_d32_relpos_us=[], attention_padded_us=[])
+    for _ in range(repeats):      # alternating brackets
+        res['attention_d32_relpos_us'].append(timed(native, n, warmup) * 1e3)
+        res['attention_padded_us'].append(timed(padded, n, warmup) * 1e3)
+    res['attention_padded_form'] = int(form[0])
+    res['max_abs_diff'] = (O.view(M, H, 32) - O2.view(M, H, 64)[:, :, :32]).abs().max().item()
+    return res
+
+
+def _stat(v):
+    return dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+
+
+def enc32_leg(args):
+    res = enc32_encoders(args.batch, args.steps, args.warmup, args.repeats)
+    if args.encoders_only:
+        print(json.dumps(res))
+        return 0
+    res.update(status='measured', dtype='fp32', repeats=args.repeats, tuned=False)
+    lens0 = res.pop('lens0')
+    res.update(enc32_launches(lens0, 8, args.steps, args.warmup, args.repeats))
+    # the rows of the Efficient Conformer's plain layers: behind its stride layer
+    half = enc32_launches([(n + 1) // 2 for n in lens0], 8, args.steps, args.warmup, args.repeats)
+    res.update({'half_' + k: v for k, v in half.items()})
+    parent = None
+    if args.parent:
+        with open(args.parent) as f:
+            parent = [json.loads(l) for l in f if l.startswith('{')]
+    rows = []
+    for name in ('aishell_ebranchformer', 'aishell_efficonformer_v1'):
+        new = _stat(res[name + '_ms'])
+        line = f'| `{name}` | {new["median"]:.2f} ({new["min"]:.2f} .. {new["max"]:.2f}) |'
+        if parent:
+            res['parent_' + name + '_ms'] = sum((p[name + '_ms'] for p in parent), [])
+            old = _stat(res['parent_' + name + '_ms'])
+            line += f' {old["median"]:.2f} ({old["min"]:.2f} .. {old["max"]:.2f}) |'
+        else:
+            line += ' not measured |'
+        rows.append(line)
+    krows = []
+    for pre, what in (('', 'rate-4 rows'), ('half_', 'rate-8 rows')):
+        a, b = _stat(res[pre + 'attention_d32_relpos_us']), _stat(res[pre + 'attention_padded_us'])
+        krows.append(f'| {what}: {res[pre + "rows"]} rows, longest {res[pre + "max_len"]} | '
+                     f'{a["median"]:.1f} ({a["min"]:.1f} .. {a["max"]:.1f}) | '
+                     f'{b["median"]:.1f} ({b["min"]:.1f} .. {b["max"]:.1f}) | '
+                     f'{res[pre + "attention_padded_form"]} | {res[pre + "max_abs_diff"]:.2e} |')
+    pdir = args.out_dir or os.path.join(ROOT, 'profiles')
+    ldir = args.out_dir or os.path.join(ROOT, 'docs')
+    os.makedirs(pdir, exist_ok=True)
+    with open(os.path.join(pdir, 'encoder_d32_aishell.json'), 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+    with open(os.path.join(ldir, 'LOG_round31.md'), 'w') as f:
+        f.write(LOG_ENC32.format(encoders='\n'.join(rows), kernels='\n'.join(krows), **res))
+    print(json.dumps(res))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--out-dir', default=None)
-    ap.add_argument('--leg', choices=('encoder', 'dec8'), default='encoder',
-                    help='encoder: the encoder and its kernels; dec8: the 8-head decoders')
+    ap.add_argument('--leg', choices=('encoder', 'dec8', 'enc32'), default='encoder',
+                    help='encoder: the encoder and its kernels; dec8: the 8-head decoders; '
+                         'enc32: the encoders with heads of 32 and attention_d32_relpos')
+    ap.add_argument('--repeats', type=int, default=5, help='enc32: brackets per figure')
+    ap.add_argument('--encoders-only', action='store_true',
+                    help='enc32: print the encoder brackets as one JSON line and write nothing')
+    ap.add_argument('--parent', default=None,
+                    help='enc32: file of --encoders-only lines measured on the parent commit')
     args = ap.parse_args(argv)
     if args.leg == 'dec8':
         return dec8_leg(args)
+    if args.leg == 'enc32':
+        return enc32_leg(args)
     from wenet_amd import ASRModel, EfficientConformer
     from wenet_amd import synthetic as S
     t0 = time.time()
@@ -288,6 +434,32 @@ other hypotheses), ONE run, untuned: a record, not a pass mark and not a ratio.
 
 Not measured: a kernel trace of either decode (the share of the attention launches in these wall
 times), `attention_d32` per launch, more than one wave per block, LDS-bank counters.
+"""
+
+LOG_ENC32 = """# Round 31: encoder heads of 32 on `attention_d32_relpos`
+
+`tools/bench_efficonformer.py --leg enc32`: the two encoder families with heads of 32, synthetic
+weights, B = {batch} x 8-12 s ({audio_s:.1f} s of audio), fp32, untuned.  Every figure is the median
+(smallest .. largest) of {repeats} brackets of HIP events; an encoder bracket is {steps} `wn_encode`
+calls after {warmup}.  The parent commit's tree (heads of 32 zero-padded to 64 columns on
+`attention_kernel`) was measured by the same function in processes alternating with this one's on
+the same GPU.  All numbers: profiles/encoder_d32_aishell.json.
+
+| encoder, ms per batch | this commit | parent commit |
+| --- | --- | --- |
+{encoders}
+
+One launch through the operator hooks at 8 heads, full context, on the batch's packed rows behind
+the front end and behind a stride layer, brackets of {steps} x 4 calls alternating between the two
+kernels; the hook's descriptor upload is inside every bracket.  The launcher takes blocks of 4
+waves from a longest sequence of {nw4_len} rows on, of 2 below.
+
+| rows | `attention_d32_relpos`, us | `attention_kernel` on the padded layout, us | its form code | largest difference of the two outputs |
+| --- | --- | --- | --- | --- |
+{kernels}
+
+Not measured: a kernel trace of either encoder (the share of the attention launches in the
+encoder times), chunk masks, the QKV and output projections in isolation, LDS-bank counters.
 """
 
 if __name__ == '__main__':

@@ -187,7 +187,8 @@ EXPORTS = [
     'wn_op_avgpool_residual_add',
     'wn_op_attention_d128', 'wn_op_lfr_front', 'wn_op_layernorm_wide', 'wn_op_cif_alpha',
     'wn_op_cif_fire', 'wn_model_create_paraformer', 'wn_paraformer_decode',
-    'wn_op_attention_d32',
+    'wn_op_attention_d32', 'wn_op_attention_d32_relpos', 'wn_attention_d32_relpos_nw4_len',
+    'wn_model_encoder_head_cols',
     'wn_model_create_sensevoice', 'wn_sensevoice_set_queries', 'wn_op_sv_front',
 ]
 
@@ -403,6 +404,11 @@ def lib():
                                        pi32, pi32, i32, i32, f32, vp]
     L.wn_op_attention_d32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, pi32, pi32,
                                       pi32, pi32, i32, i32, f32, i32, vp]
+    L.wn_op_attention_d32_relpos.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, pi32,
+                                             pi32, pi32, pi32, i32, i32, f32, i32, vp, i32, i32,
+                                             vp, vp, i32, i32, vp]
+    L.wn_attention_d32_relpos_nw4_len.argtypes = []
+    L.wn_model_encoder_head_cols.argtypes = [vp]
     L.wn_op_lfr_front.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, pi32, pi32, pi32,
                                   i32, i32, i32, i32, i32, f32, f32, vp]
     L.wn_op_layernorm_wide.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, vp]

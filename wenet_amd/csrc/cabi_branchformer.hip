@@ -17,7 +17,8 @@ static int encoder_layers_branchformer(wn_model* m, int chunk, int left, hipStre
   const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const wn_branchformer_config& b = m->bf.c;
-  const int d = c.d_model, d2 = 2 * d, H = c.n_heads, dq = H * 64, M = m->rows;
+  const int d = c.d_model, d2 = 2 * d, H = c.n_heads, dq = H * enc_head_cols(b.head_dim);
+  const int M = m->rows;
   const int U = b.cgmlp_units, C = U / 2;
   float* x = m->x.as<float>();
   float* t1 = m->t1.as<float>();
@@ -45,8 +46,8 @@ static int encoder_layers_branchformer(wn_model* m, int chunk, int left, hipStre
       WN_TRY(linear(L.ffm1, t1, d, hb, c.ffn_dim, M, s, ACT_SILU));
       WN_TRY(linear(L.ffm2, hb, c.ffn_dim, x, d, M, s, ACT_NONE, x, d, 0.5f));
     }
-    // branch 1: rel-pos attention without the shift; heads of bf.c.head_dim = 32 are laid out as
-    // 64 columns with the upper 32 zero, so the d_k = 64 kernel adds exact zeros
+    // branch 1: rel-pos attention without the shift; heads of bf.c.head_dim = 32 run 32 wide on
+    // attention_d32_relpos, heads of 64 on attention()
     WN_TRY(ln(L.norm_mha, x, t1, M, d, eps, s));
     WN_TRY(linear(L.qkv, t1, d, qkv, 3 * dq, M, s));
     AttnArgs a;
@@ -59,7 +60,7 @@ static int encoder_layers_branchformer(wn_model* m, int chunk, int left, hipStre
     a.n_seq = m->B; a.n_heads = H; a.max_q_len = max_len;
     a.mask_mode = mask_mode; a.chunk_size = cs; a.left_chunks = lc;
     a.scale = 1.0f / sqrtf((float)b.head_dim);
-    WN_TRY(attention(a, s));
+    WN_TRY(b.head_dim == 32 ? attention_d32_relpos(a, s) : attention(a, s));
     WN_TRY(linear(L.out, ctx, dq, cat, d2, M, s));
     // branch 2: cgMLP                                   branchformer/cgmlp.py:86-131, 161-194
     WN_TRY(ln(L.norm_mlp, x, t1, M, d, eps, s));
@@ -112,7 +113,8 @@ int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat
                         hipStream_t s) {
   const wn_config& c = m->cfg;
   const wn_branchformer_config& b = m->bf.c;
-  const int d = c.d_model, dq = c.n_heads * 64, U = b.cgmlp_units, C = U / 2;
+  const int d = c.d_model, dq = c.n_heads * enc_head_cols(b.head_dim), U = b.cgmlp_units;
+  const int C = U / 2;
   const int Tp = ((T - 1) / 2 - 1) / 2;
   // the workspace the front end sizes for a Conformer (d-wide heads, ffn_dim hidden units) is
   // sized for this encoder FIRST: its own ensure() calls then find room and move nothing

@@ -102,7 +102,8 @@ int efficonformer_stage_front2(const Src& src, HostStage& hs, const wn_config& c
 // stride layer's concat_linear.* is never used by the reference's forward and is not read
 int efficonformer_stage_layers(const Src& src, HostStage& hs, const wn_config& c,
                                const wn_efficonformer_config& e) {
-  const int d = c.d_model, F = c.ffn_dim, H = c.n_heads, hd = e.head_dim, dq = H * 64;
+  const int d = c.d_model, F = c.ffn_dim, H = c.n_heads, hd = e.head_dim;
+  const int hc = enc_head_cols(hd), dq = H * hc;
   for (int i = 0; i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     const bool grouped = (e.group_mask >> i) & 1;
@@ -150,17 +151,17 @@ int efficonformer_stage_layers(const Src& src, HostStage& hs, const wn_config& c
       hs.add(p + ".pos_bias_u", bu, (size_t)e.group_size * d);
       hs.add(p + ".pos_bias_v", bv, (size_t)e.group_size * d);
     } else {
-      // H heads of 64 columns: head h's hd rows, then 64 - hd zero rows (head_dim 32: every
-      // added product of the d_k = 64 attention is an exact zero, as for an E-Branchformer)
+      // H heads of hc = enc_head_cols(hd) columns, the reference's own layout: heads of 32 on
+      // attention_d32_relpos, of 64 on attention(), as for an E-Branchformer
       std::vector<float> w((size_t)3 * dq * d, 0.f), bq((size_t)3 * dq, 0.f);
       for (int j = 0; j < 3; ++j) {
         WN_GET(pw, p + ".self_attn." + parts[j] + ".weight", (int64_t)d * d);
         WN_GET(pb, p + ".self_attn." + parts[j] + ".bias", d);
         for (int h = 0; h < H; ++h)
           for (int r = 0; r < hd; ++r) {
-            memcpy(&w[((size_t)j * dq + h * 64 + r) * d], &pw[(size_t)(h * hd + r) * d],
+            memcpy(&w[((size_t)j * dq + h * hc + r) * d], &pw[(size_t)(h * hd + r) * d],
                    sizeof(float) * d);
-            bq[(size_t)j * dq + h * 64 + r] = pb[h * hd + r];
+            bq[(size_t)j * dq + h * hc + r] = pb[h * hd + r];
           }
       }
       hs.add(p + ".qkv.weight", w.data(), w.size());
@@ -171,9 +172,9 @@ int efficonformer_stage_layers(const Src& src, HostStage& hs, const wn_config& c
       std::vector<float> wp((size_t)dq * d, 0.f), u(dq, 0.f), v(dq, 0.f);
       for (int h = 0; h < H; ++h)
         for (int r = 0; r < hd; ++r) {
-          memcpy(&wp[((size_t)h * 64 + r) * d], &pp[(size_t)(h * hd + r) * d], sizeof(float) * d);
-          u[h * 64 + r] = bu[h * hd + r];
-          v[h * 64 + r] = bv[h * hd + r];
+          memcpy(&wp[((size_t)h * hc + r) * d], &pp[(size_t)(h * hd + r) * d], sizeof(float) * d);
+          u[h * hc + r] = bu[h * hd + r];
+          v[h * hc + r] = bv[h * hd + r];
         }
       hs.add(p + ".self_attn.linear_pos.weight", wp.data(), wp.size());
       hs.add(p + ".pos_bias_u", u.data(), u.size());
@@ -183,7 +184,7 @@ int efficonformer_stage_layers(const Src& src, HostStage& hs, const wn_config& c
       std::vector<float> wo((size_t)d * dq, 0.f);
       for (int n = 0; n < d; ++n)
         for (int h = 0; h < H; ++h)
-          memcpy(&wo[(size_t)n * dq + h * 64], &po[(size_t)n * d + h * hd], sizeof(float) * hd);
+          memcpy(&wo[(size_t)n * dq + h * hc], &po[(size_t)n * d + h * hd], sizeof(float) * hd);
       hs.add(p + ".self_attn.linear_out.weight", wo.data(), wo.size());
       hs.add(p + ".self_attn.linear_out.bias", pob, d);
     }
@@ -220,7 +221,8 @@ int efficonformer_stage_layers(const Src& src, HostStage& hs, const wn_config& c
 }
 
 int efficonformer_bind(ModelData& W, const wn_config& c, const wn_efficonformer_config& e) {
-  const int d = c.d_model, F = c.ffn_dim, dq = c.n_heads * 64, wmax = std::max(d, dq);
+  const int d = c.d_model, F = c.ffn_dim, dq = c.n_heads * enc_head_cols(e.head_dim);
+  const int wmax = std::max(d, dq);
   auto P = [&](const std::string& n) { return W.w.at(n); };
   auto LIN = [&](const std::string& p, int o, int i) {
     Linear l; l.w = P(p + ".weight"); l.b = P(p + ".bias"); l.out = o; l.in = i; return l;
@@ -288,7 +290,7 @@ int efficonformer_layer(wn_model* m, const EncLayer& L, const EfLayout& a, const
                         int cs, int lc, hipStream_t s) {
   const wn_config& c = m->cfg;
   const wn_efficonformer_config& e = m->ef.c;
-  const int d = c.d_model, H = c.n_heads, dq = H * 64, M = a.M;
+  const int d = c.d_model, H = c.n_heads, dq = H * enc_head_cols(e.head_dim), M = a.M;
   float* x = m->x.as<float>();
   float* t1 = m->t1.as<float>();
   float* t2 = m->t2.as<float>();
@@ -327,7 +329,7 @@ int efficonformer_layer(wn_model* m, const EncLayer& L, const EfLayout& a, const
     // mask of size cs / rate at this rate, with the same number of left chunks
     at.mask_mode = cs > 0 ? 2 : 0; at.chunk_size = cs / L.ef_rate; at.left_chunks = lc;
     at.scale = 1.0f / sqrtf((float)e.head_dim);
-    WN_TRY(attention(at, s));
+    WN_TRY(e.head_dim == 32 ? attention_d32_relpos(at, s) : attention(at, s));
     WN_TRY(linear(L.out, t2, dq, x, d, M, s, ACT_NONE, x, d));
   }
   // ---- conv module                             efficient_conformer/convolution.py:93-154
@@ -382,7 +384,7 @@ int encode_efficonformer(wn_model* m, const float* feats_dev, const int32_t* fea
   const ModelData& W = *m->data;
   const wn_config& c = m->cfg;
   const wn_efficonformer_config& e = m->ef.c;
-  const int d = c.d_model, dq = c.n_heads * 64, nS = e.n_stride;
+  const int d = c.d_model, dq = c.n_heads * enc_head_cols(e.head_dim), nS = e.n_stride;
   const int Tp0 = e.front_rate == 4 ? ((T - 1) / 2 - 1) / 2 : (T - 1) / 2;
   // the chunk mask of the decode-time branches of mask.py:126-198, as the Conformer path
   int cs = 0, lc = -1;

@@ -415,7 +415,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     // of a Branchformer layer serve merge_method learned_ave only: not read.)
     const std::string p = "encoder.encoders." + std::to_string(i);
     const wn_branchformer_config& b = *bcfg;
-    const int H = c.n_heads, hd = b.head_dim, dq = H * 64, U = b.cgmlp_units, C = U / 2;
+    const int H = c.n_heads, hd = b.head_dim, hc = enc_head_cols(hd), dq = H * hc, U = b.cgmlp_units, C = U / 2;
     for (const char* n : {"norm_mha", "norm_mlp", "norm_final"})
       WN_TRY(stage_norm(src, hs, p + "." + n, d));
     if (b.kind == 2) {
@@ -426,9 +426,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
         WN_TRY(stage_linear(src, hs, p + "." + ff + ".w_2", d, F));
       }
     }
-    {  // Q | K | V, linear_pos and pos_bias_u / v as H heads of 64 columns: head h's hd rows,
-       // then 64 - hd zero rows (head_dim 32: every added product of the attention is an
-       // exact zero; head_dim 64: the reference's own layout)
+    {  // Q | K | V, linear_pos and pos_bias_u / v as H heads of hc = enc_head_cols(hd) columns:
+       // the reference's own layout, heads of 32 on attention_d32_relpos, of 64 on attention()
       std::vector<float> w((size_t)3 * dq * d, 0.f), bq((size_t)3 * dq, 0.f);
       const char* parts[3] = {"linear_q", "linear_k", "linear_v"};
       for (int j = 0; j < 3; ++j) {
@@ -436,9 +435,9 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
         WN_GET(pb, p + ".attn." + parts[j] + ".bias", d);
         for (int h = 0; h < H; ++h)
           for (int r = 0; r < hd; ++r) {
-            memcpy(&w[((size_t)j * dq + h * 64 + r) * d], &pw[(size_t)(h * hd + r) * d],
+            memcpy(&w[((size_t)j * dq + h * hc + r) * d], &pw[(size_t)(h * hd + r) * d],
                    sizeof(float) * d);
-            bq[(size_t)j * dq + h * 64 + r] = pb[h * hd + r];
+            bq[(size_t)j * dq + h * hc + r] = pb[h * hd + r];
           }
       }
       hs.add(p + ".qkv.weight", w.data(), w.size());
@@ -449,20 +448,20 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
       std::vector<float> wp((size_t)dq * d, 0.f), u(dq, 0.f), v(dq, 0.f);
       for (int h = 0; h < H; ++h)
         for (int r = 0; r < hd; ++r) {
-          memcpy(&wp[((size_t)h * 64 + r) * d], &pp[(size_t)(h * hd + r) * d], sizeof(float) * d);
-          u[h * 64 + r] = bu[h * hd + r];
-          v[h * 64 + r] = bv[h * hd + r];
+          memcpy(&wp[((size_t)h * hc + r) * d], &pp[(size_t)(h * hd + r) * d], sizeof(float) * d);
+          u[h * hc + r] = bu[h * hd + r];
+          v[h * hc + r] = bv[h * hd + r];
         }
       hs.add(p + ".self_attn.linear_pos.weight", wp.data(), wp.size());
       hs.add(p + ".pos_bias_u", u.data(), u.size());
       hs.add(p + ".pos_bias_v", v.data(), v.size());
-      // linear_out [d][d] -> [d][dq]: zero columns under the padded context columns
+      // linear_out [d][d] -> [d][dq]
       WN_GET(po, p + ".attn.linear_out.weight", (int64_t)d * d);
       WN_GET(pob, p + ".attn.linear_out.bias", d);
       std::vector<float> wo((size_t)d * dq, 0.f);
       for (int n = 0; n < d; ++n)
         for (int h = 0; h < H; ++h)
-          memcpy(&wo[(size_t)n * dq + h * 64], &po[(size_t)n * d + h * hd], sizeof(float) * hd);
+          memcpy(&wo[(size_t)n * dq + h * hc], &po[(size_t)n * d + h * hd], sizeof(float) * hd);
       hs.add(p + ".self_attn.linear_out.weight", wo.data(), wo.size());
       hs.add(p + ".self_attn.linear_out.bias", pob, d);
     }
@@ -832,7 +831,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
   } else if (bf) {
     const wn_branchformer_config& b = *bcfg;
-    const int dq = c.n_heads * 64, U = b.cgmlp_units, C = U / 2;
+    const int dq = c.n_heads * enc_head_cols(b.head_dim), U = b.cgmlp_units, C = U / 2;
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * dq * sizeof(float)));
     for (int i = 0; i < c.n_layers; ++i) {
@@ -1130,6 +1129,13 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
 
 int32_t wn_model_get_precision(const wn_model* m) {
   return m ? (m->fp8_ffn ? (int32_t)PREC_FP8 : m->prec) : -1;
+}
+
+int32_t wn_model_encoder_head_cols(const wn_model* m) {
+  if (!m) return -1;
+  if (m->bf.on) return enc_head_cols(m->bf.c.head_dim);
+  if (m->ef.on) return enc_head_cols(m->ef.c.head_dim);
+  return 64;
 }
 
 int32_t wn_batch_size(const wn_model* m) { return m ? m->B : -1; }

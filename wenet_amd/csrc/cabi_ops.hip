@@ -1221,6 +1221,67 @@ int wn_op_attention_d32(const float* Q, const float* K, const float* V, int32_t 
   return attention_d32(a, s);
 }
 
+// ---- rel-pos attention for encoder heads of 32 (attention_d32_relpos.hip) ----------------------
+
+int wn_op_attention_d32_relpos(const float* Q, const float* K, const float* V, int32_t ldq,
+                               int32_t ldk, int32_t ldv, int32_t q_rows, int32_t kv_rows, float* O,
+                               int32_t ldo, const int32_t* q_off, const int32_t* q_len,
+                               const int32_t* kv_off, const int32_t* kv_len, int32_t n_seq,
+                               int32_t n_heads, float scale, int32_t mask_mode, const float* P,
+                               int32_t ldp, int32_t p_rows, const float* bias_u,
+                               const float* bias_v, int32_t chunk_size, int32_t left_chunks,
+                               void* stream) {
+  WN_CHECK(Q && K && V && O && q_off && q_len && kv_off && kv_len && P && bias_u && bias_v,
+           "attention_d32_relpos: null argument");
+  WN_CHECK(mask_mode == 0 || mask_mode == 2,
+           "attention_d32_relpos: mask_mode must be 0 (keys < kv_len) or 2 (chunk window), not 1 "
+           "(causal)");
+  WN_CHECK(mask_mode != 2 || chunk_size > 0,
+           "attention_d32_relpos: chunk_size must be positive under mask_mode 2");
+  WN_CHECK(n_seq > 0 && n_seq < 32768 && n_heads > 0 && n_heads < 256,
+           "attention_d32_relpos: n_seq / n_heads");
+  const int d = n_heads * 32;
+  WN_CHECK(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0,
+           "attention_d32_relpos: strides must be multiples of 4 elements");
+  WN_CHECK(ldq >= d && ldk >= d && ldv >= d && ldo >= d && ldp >= d,
+           "attention_d32_relpos: a stride is smaller than n_heads * 32");
+  WN_CHECK(q_rows > 0 && kv_rows > 0 && p_rows > 0, "attention_d32_relpos: empty buffers");
+  WN_CHECK(((uintptr_t)Q & 15) == 0 && ((uintptr_t)K & 15) == 0 && ((uintptr_t)V & 15) == 0 &&
+               ((uintptr_t)P & 15) == 0 && ((uintptr_t)bias_u & 15) == 0 &&
+               ((uintptr_t)bias_v & 15) == 0,
+           "attention_d32_relpos: Q, K, V, P, bias_u and bias_v must be 16-byte aligned");
+  WN_CHECK(packed_ok(q_off, q_len, n_seq, q_rows),
+           "attention_d32_relpos: query rows outside the buffer, unordered or overlapping");
+  int max_q = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    WN_CHECK(kv_len[i] == q_len[i] && kv_off[i] == q_off[i],
+             "attention_d32_relpos: self attention only, q_len != kv_len or q_off != kv_off");
+    WN_CHECK((int64_t)kv_off[i] + kv_len[i] <= kv_rows,
+             "attention_d32_relpos: key rows outside the buffer");
+    max_q = std::max(max_q, q_len[i]);
+  }
+  WN_CHECK(max_q > 0, "attention_d32_relpos: empty");
+  WN_CHECK(p_rows >= max_q,
+           "attention_d32_relpos: p_rows is smaller than the longest sequence");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  std::vector<int> h((size_t)2 * n_seq);
+  for (int i = 0; i < n_seq; ++i) { h[i] = q_off[i]; h[n_seq + i] = q_len[i]; }
+  WN_TRY(upload_ints(desc, h, s));
+  const int* dd = desc.as<int>();
+  AttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = P; a.ldp = ldp; a.bias_u = bias_u; a.bias_v = bias_v;
+  a.O = O; a.ldo = ldo;
+  a.q_off = a.kv_off = dd; a.q_len = a.kv_len = dd + n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_q_len = max_q;
+  a.mask_mode = mask_mode; a.chunk_size = chunk_size; a.left_chunks = left_chunks;
+  a.scale = scale;
+  return attention_d32_relpos(a, s);
+}
+
+int32_t wn_attention_d32_relpos_nw4_len(void) { return ATTN_D32_RELPOS_NW4_LEN; }
+
 // ---- the `attention` decode mode's kernels (attn_search.hip), one launcher per hook ----------
 
 int wn_op_attn_self_step(const float* qkv, int32_t d, int32_t heads, int32_t n, float* cache,

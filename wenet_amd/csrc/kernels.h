@@ -964,6 +964,15 @@ int attention_d128(const AttnArgs& a, hipStream_t s);
 // no kbias, no block list.  Always fp32: it does not go through attention_form().
 int attention_d32(const AttnArgs& a, hipStream_t s);
 
+// ---- encoders with heads of 32 (attention_d32_relpos.hip), fp32 ----------------------------
+// Rel-pos SELF attention for heads of d_k = 32 (n_heads * 32 columns; kv_off / kv_len are q_off /
+// q_len): score ((q + u) . k_j + (q + v) . p_j) * scale folded while the keys are staged, P row j
+// for key j (ldp, column h * 32), bias_u / bias_v [h][32]; mask_mode 0 or 2 (chunk window, the rule
+// of attention()'s mode 2).  mask_mode 1, kbias, p_off, block lists and the bf16 flags are refused.
+// Blocks of 2 waves, of 4 when max_q_len >= ATTN_D32_RELPOS_NW4_LEN.  Always fp32.
+constexpr int ATTN_D32_RELPOS_NW4_LEN = 129;
+int attention_d32_relpos(const AttnArgs& a, hipStream_t s);
+
 // LFR front end (paraformer/layers.py:24-92 on ONE utterance, paraformer.py:329-350): output row
 // t of utterance b stacks the m frames n t - (m - 1) / 2 + f, f < m, each index clamped to
 // [0, len[b] - 1]; then GlobalCMVN over the m F columns, x * xscale + pe[t + 1], and the

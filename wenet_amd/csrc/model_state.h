@@ -148,6 +148,11 @@ struct SideStream {
 struct Linear { const float* w = nullptr; const float* b = nullptr; int out = 0, in = 0; };
 struct Norm { const float* w = nullptr; const float* b = nullptr; };
 
+// Columns one head occupies in the staged Q | K | V, position table, pos_bias_u / v and linear_out
+// input of a Branchformer layer or a plain Efficient Conformer layer: heads of 32 run 32 wide on
+// attention_d32_relpos, heads of 64 on attention()
+inline int enc_head_cols(int head_dim) { return head_dim == 32 ? 32 : 64; }
+
 struct EncLayer {
   Norm norm_ff_mac, norm_mha, norm_conv, norm_ff, norm_final, conv_norm;
   Linear ffm1, ffm2, ff1, ff2, qkv, out, pw1, pw2;
@@ -159,7 +164,7 @@ struct EncLayer {
   const float* cpad = nullptr;    // [d]
   // Branchformer / E-Branchformer layers (wn_model::bf.on, cabi_branchformer.hip): the cgMLP
   // branch and the merge; qkv / out / pos_tab / bias_u / bias_v then have the head layout of
-  // bf.c.head_dim (32: heads zero-padded to 64 columns)
+  // bf.c.head_dim: enc_head_cols() columns per head (32 and 64: the reference's own layout)
   Norm norm_mlp, csgu_norm;
   Linear proj1, proj2, csgu_lin, merge_proj;
   const float* csgu_wt = nullptr;   // [K][U/2]
@@ -173,8 +178,8 @@ struct EncLayer {
   // Efficient Conformer layers (wn_model::ef.on, cabi_efficonformer.hip): the Conformer's slots;
   // ef_rate = product of the strides in front of the layer (pos_tab is linear_pos of
   // pe[0::ef_rate]), ef_kernel its own cnn_module_kernel.  A grouped layer keeps Q | K | V, the
-  // table and linear_out d wide and bias_u / bias_v (h, group * d_k); a plain one lays heads of 32
-  // out as 64 columns like a Branchformer's
+  // table and linear_out d wide and bias_u / bias_v (h, group * d_k); a plain one has the head layout
+  // of a Branchformer's (enc_head_cols() columns per head)
   int ef_rate = 1, ef_kernel = 0;
   bool ef_grouped = false, ef_stride = false;
 };

@@ -389,6 +389,12 @@ class ASRModel:
     def compute_dtype(self) -> str:
         return {1: 'bf16', 2: 'fp8'}.get(self._L.wn_model_get_precision(self._h), 'fp32')
 
+    @property
+    def encoder_head_cols(self) -> int:
+        """Columns one head occupies in the staged QKV of the encoder's plain rel-pos layers: 32
+        when they run on attention_d32_relpos, else 64.  No counterpart in the reference."""
+        return int(self._L.wn_model_encoder_head_cols(self._h))
+
     # torch.nn.Module-flavoured no-ops so reference driver code keeps working
     def eval(self):
         return self
