@@ -64,7 +64,11 @@ typedef struct {
                                 1: transformer (TransformerEncoderLayer,
                                    encoder_layer.py:28-127; Whisper encoder) */
   int32_t input_layer;       /* 0: conv2d (Conv2dSubsampling4)
-                                1: conv1d2 (Conv1dSubsampling2, subsampling.py:117-171) */
+                                1: conv1d2 (Conv1dSubsampling2, subsampling.py:117-171)
+                                2: conv2d6 (Conv2dSubsampling6, subsampling.py:231-280): rate 6,
+                                   right context 10; encoder_type 0 of an asr_model only, d_model
+                                   256 / 512, feat_dim 80; every precision runs this front end in
+                                   fp32 semantics (conv2d6_patch) */
   int32_t activation;        /* FFN activation: 0 swish/SiLU, 1 gelu (exact erf) */
   int32_t key_bias;          /* attention linear_k has a bias (Whisper: 0) */
   int32_t cnn_norm;          /* conv-module norm: 0 layer_norm, 1 batch_norm (eval:
@@ -972,6 +976,22 @@ int wn_op_conv2_patch_into(wn_model* m, const float* feats_dev, const int32_t* f
 /* Host only: the most conv1 frames one 128-row tile of kind 3 reads for a batch of l2[B] output
  * frames per utterance (F2 positions per frame); kind 3 is taken up to 21.  -1 on bad arguments. */
 int wn_conv2_patch_max_frames(const int32_t* l2, int32_t B, int32_t F2);
+/* The Conv2dSubsampling6 front end alone (handles with input_layer 2; others are refused by
+ * name): GlobalCMVN + conv1 + conv2 in ONE kernel that writes the CALLER's c2 [M][12][d] (device,
+ * 16-byte aligned, required; M = sum l2, l2 = wn_conv2d6_frames(feat_len)), so that a test can put
+ * a frame around it, then the projection * sqrt(d) -> x [M][d] (optional).  enc_lens_host [B]
+ * (or NULL) = l2.  Needs T >= 11; complete on return. */
+int wn_op_conv2d6(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
+                  int32_t T, float* c2, float* x, int32_t* enc_lens_host, void* stream);
+/* Host only: the tile list conv2d6_patch runs a batch of l2[B] output frames per utterance on, at
+ * `ft` frames per tile (0: the shipped count at d_model 512; 5, 8, 10).  Writes up to `cap` tiles of four ints
+ * (utterance, first output frame, frame count, packed first frame) and returns the number of
+ * tiles; -1 on bad arguments. */
+int wn_conv2d6_tiles(const int32_t* l2, int32_t B, int32_t ft, int32_t* tiles_out, int32_t cap);
+/* Host only: output frames of L feature frames, max(0, ((L - 1) / 2 - 2) / 3). */
+int wn_conv2d6_frames(int32_t L);
+/* Host only: the shipped frames per tile at d_model 256 (5) / 512 (8). */
+int wn_conv2d6_ft(int32_t d_model);
 /* The k-block order of conv2's weight image for kind 3 (host only, no device needed):
  * src_of_dst[kbc * taps]: k block kb of the (channel chunk, tap)-ordered image is k block
  * src_of_dst[kb] of the tap-major image (kbc = 16-channel chunks per tap). */

@@ -159,6 +159,7 @@ EXPORTS = [
     'wn_set_context_graph', 'wn_ctc_prefix_beam_search', 'wn_attention_rescoring', 'wn_rescore', 'wn_rescore_prefetch', 'wn_decoder_forward', 'wn_decoder_next_topk', 'wn_op_gemm',
     'wn_op_layernorm', 'wn_op_log_add', 'wn_op_attention', 'wn_op_dwconv', 'wn_op_conv1',
     'wn_op_conv2d4', 'wn_conv2_kperm', 'wn_op_conv2_patch_into', 'wn_conv2_patch_max_frames',
+    'wn_op_conv2d6', 'wn_conv2d6_tiles', 'wn_conv2d6_frames', 'wn_conv2d6_ft',
     'wn_op_ctc_rows', 'wn_debug_set', 'wn_profile_enable',
     'wn_profile_collect', 'wn_tune_set', 'wn_model_tune_set', 'wn_tune_get',
     'wn_stream_create', 'wn_stream_destroy', 'wn_stream_set_endpoint', 'wn_stream_reset',
@@ -299,6 +300,10 @@ def lib():
     L.wn_conv2_kperm.argtypes = [i32, i32, pi32]
     L.wn_op_conv2_patch_into.argtypes = [vp, vp, pi32, i32, i32, vp, vp, pi32, vp]
     L.wn_conv2_patch_max_frames.argtypes = [pi32, i32, i32]
+    L.wn_op_conv2d6.argtypes = [vp, vp, pi32, i32, i32, vp, vp, pi32, vp]
+    L.wn_conv2d6_tiles.argtypes = [pi32, i32, i32, pi32, i32]
+    L.wn_conv2d6_frames.argtypes = [i32]
+    L.wn_conv2d6_ft.argtypes = [i32]
     L.wn_op_ctc_rows.argtypes = [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp]
     L.wn_debug_set.argtypes = [vp, c_char_p, i32]
     L.wn_tune_set.argtypes = [c_char_p, i32]

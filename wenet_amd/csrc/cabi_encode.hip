@@ -134,13 +134,18 @@ int wn_encode(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host
     return encode_transformer(m, feats_dev, feat_lens_host, B, T, enc_out_dev,
                               enc_lens_host, (hipStream_t)stream);
   }
-  WN_CHECK(T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
+  const bool sub6 = m->cfg.input_layer == 2;
+  WN_CHECK(sub6 || T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
+  WN_CHECK(!sub6 || T >= 11, "wn_encode: at least 11 frames are needed by Conv2dSubsampling6");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
   const wn_config& c = m->cfg;
   const int d = c.d_model;
-  const int Tp = ((T - 1) / 2 - 1) / 2;
-  WN_TRY(subsample_conv2d4(m, feats_dev, feat_lens_host, B, T, enc_lens_host, 0, s));
+  const int Tp = sub6 ? conv2d6_frames(T) : ((T - 1) / 2 - 1) / 2;
+  if (sub6)
+    WN_TRY(subsample_conv2d6(m, feats_dev, feat_lens_host, B, T, enc_lens_host, 0, s));
+  else
+    WN_TRY(subsample_conv2d4(m, feats_dev, feat_lens_host, B, T, enc_lens_host, 0, s));
   WN_TRY(encode_gate_wait(m, s));     // (paths that did not consume the gate behind conv1)
   const int M = m->rows;
   if (M > 0) {
@@ -176,11 +181,15 @@ int wn_encode_chunk_batch(wn_model* m, int32_t n_sess, const float* feats_dev, i
                       "time reduction's caches)");
   WN_CHECK(!m->ef.on, "wn_encode_chunk: no chunk-by-chunk path for an Efficient Conformer encoder "
                       "(the rate-mixed attention cache)");
-  WN_CHECK(time >= 7, "wn_encode_chunk: at least 7 frames are needed by Conv2dSubsampling4");
+  const bool sub6 = m->cfg.input_layer == 2;
+  WN_CHECK(sub6 || time >= 7,
+           "wn_encode_chunk: at least 7 frames are needed by Conv2dSubsampling4");
+  WN_CHECK(!sub6 || time >= 11,
+           "wn_encode_chunk: at least 11 frames are needed by Conv2dSubsampling6");
   hipStream_t s = (hipStream_t)stream;
   WN_HIP(hipSetDevice(m->device));
   const wn_config& c = m->cfg;
-  const int R = ((time - 1) / 2 - 1) / 2;
+  const int R = sub6 ? conv2d6_frames(time) : ((time - 1) / 2 - 1) / 2;
   const int lorder = c.causal ? c.cnn_kernel - 1 : 0;
   std::vector<ChunkSess> sess(n_sess);
   std::vector<int32_t> lens(n_sess, time);
@@ -209,8 +218,12 @@ int wn_encode_chunk_batch(wn_model* m, int32_t n_sess, const float* feats_dev, i
     ss.t1 = t1c; ss.next_start = next_start; ss.nt = nt; ss.kv_off = 0;
     if (new_cache_t1_out) new_cache_t1_out[b] = nt;
   }
-  WN_TRY(subsample_conv2d4(m, feats_dev, lens.data(), n_sess, time, nullptr,
-                           offsets_host[0], s));
+  if (sub6)
+    WN_TRY(subsample_conv2d6(m, feats_dev, lens.data(), n_sess, time, nullptr, offsets_host[0],
+                             s));
+  else
+    WN_TRY(subsample_conv2d4(m, feats_dev, lens.data(), n_sess, time, nullptr,
+                             offsets_host[0], s));
   WN_CHECK(m->rows == n_sess * R, "wn_encode_chunk: internal row count");
   WN_TRY(encoder_layers_chunk(m, n_sess, R, offsets_host, sess, out_dev, s));
   m->rows = 0; m->B = 0;  // the handle holds no decodable batch after a chunk call

@@ -170,8 +170,15 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
            "learned decoder positions need dec_max_pos >= 1 and a single decoder");
   const bool tf = c.encoder_type == 1;
   WN_CHECK(c.encoder_type == 0 || c.encoder_type == 1, "unknown encoder_type");
-  WN_CHECK(tf ? c.input_layer == 1 : c.input_layer == 0,
-           "supported pairs: conformer + conv2d, transformer + conv1d2");
+  const bool sub6 = c.input_layer == 2;
+  WN_CHECK(tf ? c.input_layer == 1 : (c.input_layer == 0 || sub6),
+           "supported pairs: conformer + conv2d / conv2d6, transformer + conv1d2");
+  WN_CHECK(!sub6 || !(tf || tcfg || fr || bf || sq || ef),
+           "input_layer 2 (conv2d6): the Conformer encoder of an asr_model only (encoder_type 0, "
+           "no other encoder family, no transducer)");
+  WN_CHECK(!sub6 || c.d_model == 256 || c.d_model == 512,
+           "input_layer 2 (conv2d6): d_model must be 256 or 512 (conv2d6_patch)");
+  WN_CHECK(!sub6 || c.feat_dim == CONV2D6_F, "input_layer 2 (conv2d6): feat_dim must be 80");
   WN_CHECK(tf || (c.cnn_kernel >= 1 && (c.causal || c.cnn_kernel % 2 == 1)),
            "cnn_module_kernel must be odd for a non-causal conv module");
   WN_HIP(hipSetDevice(device));
@@ -243,6 +250,39 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_TRY(stage_linear(src, hs, "encoder.embed.out.0", d, C * F2));
   } else if (ef && ecfg->front_rate == 2) {
     WN_TRY(efficonformer_stage_front2(src, hs, c, m->F1()));   // (cabi_efficonformer.hip)
+  } else if (sub6) {
+    // Conv2dSubsampling6 (subsampling.py:231-280): conv1 (d,1,3,3) -> [tap][c] as below
+    WN_GET(w0, "encoder.embed.conv.0.weight", (int64_t)d * 9);
+    WN_GET(b0, "encoder.embed.conv.0.bias", d);
+    float* t = hs.alloc("conv1.w", (size_t)9 * d);
+    for (int ch = 0; ch < d; ++ch)
+      for (int k = 0; k < 9; ++k) t[k * d + ch] = w0[ch * 9 + k];
+    hs.add("conv1.b", b0, d);
+    // conv2 (n, c, 5, 5) -> [n][kb * 16 + c % 16], the 16-channel k blocks in conv2d6_patch's
+    // (channel chunk, tap) order: k block kb holds tap src / kbc, chunk src % kbc of the
+    // tap-major order, src = conv2_kperm_src(kb, kbc, 25)
+    WN_GET(w2, "encoder.embed.conv.2.weight", (int64_t)d * d * 25);
+    WN_GET(b2, "encoder.embed.conv.2.bias", d);
+    t = hs.alloc("conv2.w", (size_t)d * 25 * d);
+    const int kbc = d / 16;
+    for (int kb = 0; kb < 25 * kbc; ++kb) {
+      const int src_kb = conv2_kperm_src(kb, kbc, 25);
+      const int tap = src_kb / kbc, chunk = src_kb % kbc;
+      for (int n = 0; n < d; ++n)
+        for (int e = 0; e < 16; ++e)
+          t[(size_t)n * 25 * d + (size_t)kb * 16 + e] =
+              w2[((size_t)n * d + chunk * 16 + e) * 25 + tap];
+    }
+    hs.add("conv2.b", b2, d);
+    // linear (d * F2 -> d): input index c * F2 + f -> f * d + c, the order c2 is stored in
+    WN_GET(wo, "encoder.embed.linear.weight", (int64_t)d * d * F2);
+    WN_GET(bo, "encoder.embed.linear.bias", d);
+    t = hs.alloc("sub_out.w", (size_t)d * d * F2);
+    for (int n = 0; n < d; ++n)
+      for (int ch = 0; ch < d; ++ch)
+        for (int f = 0; f < F2; ++f)
+          t[(size_t)n * d * F2 + (size_t)f * d + ch] = wo[(size_t)n * d * F2 + (size_t)ch * F2 + f];
+    hs.add("sub_out.b", bo, d);
   } else {  // conv1 (d,1,3,3) -> [tap][c]
     // (squeezeformer: DepthwiseConv2dSubsampling4 without dw_stride is the same pair of convs
     // under other names, squeezeformer/subsampling.py:52-67)
@@ -776,7 +816,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   } else {
     W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
     W.conv2.w = P("conv2.w"); W.conv2.b = P("conv2.b");
-    W.conv2.out = d; W.conv2.in = 9 * d;
+    W.conv2.out = d; W.conv2.in = (sub6 ? 25 : 9) * d;
     W.sub_out.w = P("sub_out.w"); W.sub_out.b = P("sub_out.b");
     W.sub_out.out = d; W.sub_out.in = d * F2;
   }

@@ -1063,8 +1063,9 @@ int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_
   struct GateDrop { wn_model* m; ~GateDrop() { m->enc_gate = nullptr; } } gate_drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on,
-           "wn_op_conv2d4: needs a Conformer encoder");
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on &&
+               m->cfg.input_layer == 0,
+           "wn_op_conv2d4: needs a Conformer encoder with input_layer 0 (conv2d)");
   WN_CHECK(B > 0, "wn_encode: empty batch");
   WN_CHECK(B < 65536, "wn_op_conv2d4: more than 65535 utterances");
   WN_CHECK(T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
@@ -1120,8 +1121,9 @@ int wn_op_conv2_patch_into(wn_model* m, const float* feats_dev, const int32_t* f
   struct Drop { wn_model* m; ~Drop() { m->enc_gate = nullptr; m->c2_ext = nullptr; } } drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on,
-           "wn_op_conv2_patch_into: needs a Conformer encoder");
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on &&
+               m->cfg.input_layer == 0,
+           "wn_op_conv2_patch_into: needs a Conformer encoder with input_layer 0 (conv2d)");
   WN_CHECK(B > 0 && B < 65536 && T >= 7, "wn_op_conv2_patch_into: B / T");
   WN_CHECK(((uintptr_t)c2 & 15) == 0, "wn_op_conv2_patch_into: c2 must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
@@ -1150,6 +1152,48 @@ int wn_conv2_patch_max_frames(const int32_t* l2, int32_t B, int32_t F2) {
   }
   return M > 0 ? conv2_patch_max_frames(off2, len2, F2) : 0;
 }
+
+int wn_op_conv2d6(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
+                  int32_t T, float* c2, float* x, int32_t* enc_lens_host, void* stream) {
+  WN_CHECK(m && feats_dev && feat_lens_host && c2, "wn_op_conv2d6: null argument");
+  WN_ENTER(m);
+  struct Drop { wn_model* m; ~Drop() { m->enc_gate = nullptr; m->c2_ext = nullptr; } } drop{m};
+  m->pb_valid = false;
+  PrecisionScope prec_scope(m);
+  WN_CHECK(m->cfg.input_layer == 2 && m->cfg.encoder_type == 0 && !m->data->layers.empty(),
+           "wn_op_conv2d6: needs a handle with input_layer 2 (conv2d6)");
+  WN_CHECK(B > 0 && B < 65536 && T >= 11, "wn_op_conv2d6: B / T (at least 11 frames)");
+  WN_CHECK(((uintptr_t)c2 & 15) == 0, "wn_op_conv2d6: c2 must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  WN_HIP(hipSetDevice(m->device));
+  m->c2_ext = c2;
+  WN_TRY(subsample_conv2d6(m, feats_dev, feat_lens_host, B, T, enc_lens_host, 0, s));
+  WN_TRY(encode_gate_wait(m, s));
+  if (x && m->rows > 0)
+    WN_HIP(hipMemcpyAsync(x, m->x.p, (size_t)m->rows * m->cfg.d_model * sizeof(float),
+                          hipMemcpyDeviceToDevice, s));
+  WN_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+
+int wn_conv2d6_tiles(const int32_t* l2, int32_t B, int32_t ft, int32_t* tiles_out, int32_t cap) {
+  WN_CHECK(l2 && B > 0 && cap >= 0 && (tiles_out || cap == 0), "wn_conv2d6_tiles: arguments");
+  WN_CHECK(ft == 0 || conv2d6_ft(ft, 512) == ft, "wn_conv2d6_tiles: ft must be 0, 5, 8 or 10");
+  std::vector<int> off2(B), len2(B), tiles;
+  int M = 0;
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(l2[b] >= 0, "wn_conv2d6_tiles: negative length");
+    off2[b] = M; len2[b] = l2[b]; M += l2[b];
+  }
+  conv2d6_tiles(off2, len2, conv2d6_ft(ft, 512), &tiles);
+  const int n = (int)tiles.size() / 4;
+  for (int i = 0; i < std::min(n, (int)cap) * 4; ++i) tiles_out[i] = tiles[i];
+  return n;
+}
+
+int wn_conv2d6_frames(int32_t L) { return conv2d6_frames(L); }
+
+int wn_conv2d6_ft(int32_t d_model) { return conv2d6_ft(0, d_model); }
 
 int wn_conv2_kperm(int32_t kbc, int32_t taps, int32_t* src_of_dst) {
   WN_CHECK(kbc > 0 && taps > 0 && src_of_dst, "wn_conv2_kperm: arguments");

@@ -421,6 +421,35 @@ struct Conv2PatchArgs {
 int conv2_kperm_src(int kb, int kbc, int taps);
 int conv2_patch_max_frames(const std::vector<int>& off2, const std::vector<int>& len2, int F2);
 int conv2_patch(const Conv2PatchArgs& a, hipStream_t s);
+// Conv2dSubsampling6's front end in one launch (conv2d6.hip): CMVN + conv1 + ReLU + conv2 (5 x 5,
+// stride 3) + bias + ReLU -> c2 [M][12][d] fp32; F = 80, d 256 / 512; tiles of `ft` whole output
+// frames of one utterance.
+constexpr int CONV2D6_F = 80;
+constexpr int CONV2D6_FT = 8;       // shipped frames per tile at d 512 (docs/LOG_round32.md)
+constexpr int CONV2D6_FT_256 = 5;   // ... at d 256
+constexpr int CONV2D6_WIDE = 2;     // shipped column split at d 512, Conv2d6Args::wide's encoding
+struct Conv2d6Args {
+  const float* feats = nullptr;       // (B, T, F)
+  int B = 0, T = 0, F = 0;
+  const float* mean = nullptr;        // GlobalCMVN (or null)
+  const float* istd = nullptr;
+  const float* w1 = nullptr;          // conv1 [9][d]
+  const float* b1 = nullptr;
+  const void* W3 = nullptr;           // conv2's weight image (d x 25 d), k blocks (chunk, tap)
+  const float* bias = nullptr;        // conv2 [d]
+  const int4* tiles = nullptr;        // conv2d6_tiles(): (utterance, t0, frames, packed frame)
+  int n_tiles = 0;
+  int d = 0;
+  int ft = CONV2D6_FT;                // frames per tile the list was built for: 5, 8 or 10
+  int wide = 0;                       // d 512: 0 shipped, 1 two column halves, 2 eight waves
+                                      // (ft 10 has no eight-wave kernel: it takes the halves)
+  float* C = nullptr; int ldc = 0;    // relu(conv2 + bias), fp32 [M * 12][ldc]
+};
+int conv2d6_frames(int L);            // output frames of L feature frames: ((L - 1) / 2 - 2) / 3
+int conv2d6_ft(int ft, int d);        // ft if it has a kernel, else the shipped one at width d
+void conv2d6_tiles(const std::vector<int>& off2, const std::vector<int>& len2, int ft,
+                   std::vector<int>* tiles);
+int conv2d6_patch(const Conv2d6Args& a, hipStream_t s);
 // Fused six-product feed-forward module (ffn_x6f.hip): hidden tensor in registers, d_model 256.
 struct FfnX6Args {
   const float* X = nullptr;    // X = LayerNorm(x): [M][ldx] fp32 (split into planes in registers)

@@ -159,7 +159,9 @@ int build_x6_images(const wn_config& cfg, ModelData& W, bool skip_encoder) {
   // linear() -> split pass + six-product GEMM like every other large fp32 GEMM
   for (const auto& L : W.tf_layers) { ws.push_back(&L.qkv); ws.push_back(&L.out);
                                        ws.push_back(&L.ff1); ws.push_back(&L.ff2); }
-  if (W.conv2.w && !skip_encoder) ws.push_back(&W.conv2);   // [d][(ky*3+kx)*d + c]: 16-channel k blocks per tap
+  // conv2d: [d][(ky*3+kx)*d + c], 16-channel k blocks per tap; conv2d6: staged with its k blocks
+  // already in (channel chunk, tap) order, 25 taps (cabi_model.hip): this image is conv2d6_patch's
+  if (W.conv2.w && !skip_encoder) ws.push_back(&W.conv2);
   if (W.sub_out.w && !skip_encoder) ws.push_back(&W.sub_out);   // K slices straight from conv2's fp32 output
   std::vector<const Linear*> vocab;          // V rows; the image pads them to a multiple of 32
   if (W.ctc.w) vocab.push_back(&W.ctc);
@@ -384,7 +386,7 @@ int scatter_padded(const float* src, int lds, const int* off, const int* len, in
 
 // ---- set the per-utterance row layout of the current batch -----------------
 int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
-               const std::vector<int>& len, int rows, hipStream_t s) {
+               const std::vector<int>& len, int rows, hipStream_t s, int extra_desc_ints) {
   m->B = B; m->Tp = Tp; m->off = off; m->len = len; m->rows = rows;
   m->mem_cache_valid = false;
   if (m->kv_ready) {     // a prefetch nobody consumed may still be reading m->enc
@@ -423,7 +425,8 @@ int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
     std::copy(tab.begin(), tab.end(), row_utt.begin() + m->attn_blk_off);
     m->attn_n_blk = (int)tab.size();
   }
-  WN_TRY(m->stage.begin((size_t)(row_utt.size() + 4 * B + 64) * sizeof(int) + 1024));
+  WN_TRY(m->stage.begin((size_t)(row_utt.size() + 4 * B + 64 + extra_desc_ints) * sizeof(int) +
+                        1024));
   WN_TRY(upload_desc(m, m->d_off, off, s));
   WN_TRY(upload_desc(m, m->d_len, len, s));
   WN_TRY(upload_desc(m, m->d_row_utt, row_utt, s));
@@ -694,6 +697,61 @@ int subsample_conv2d4(wn_model* m, const float* feats_dev,
                   s, ACT_NONE, nullptr, 0, sqrtf((float)d)));
     m->front_route = front_route_code(kind, X6ConvForm(), false, t_linear_took_x6);
   }
+  return 0;
+}
+
+// GlobalCMVN + Conv2dSubsampling6 + the sqrt(d) scale (subsampling.py:231-280): one launch of
+// conv2d6_patch (conv2d6.hip) for every batch and precision, then the projection Linear(12 d -> d).
+// l2 = ((L - 1) / 2 - 2) / 3 is what x_mask[:, :, 2::2][:, :, 4::3] leaves and the convolutions'
+// own output length; frame t2 reads features up to 6 t2 + 10 < L, never the padding.
+int subsample_conv2d6(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                      int T, int32_t* enc_lens_host, int pos0, hipStream_t s) {
+  const ModelData& W = *m->data;
+  const wn_config& c = m->cfg;
+  const int d = c.d_model, F2 = m->F2();
+  const int Tp = conv2d6_frames(T);
+  m->ln0_done = false;
+  m->front_route = 0;
+  WN_CHECK(pos0 + Tp <= c.max_pos, "utterance longer than the positional table");
+  std::vector<int> off2(B), len2(B), tiles;
+  int M = 0;
+  for (int b = 0; b < B; ++b) {
+    const int L = feat_lens_host[b];
+    WN_CHECK(L >= 0 && L <= T, "wn_encode: feature length out of range");
+    off2[b] = M; len2[b] = conv2d6_frames(L); M += len2[b];
+    if (enc_lens_host) enc_lens_host[b] = len2[b];
+  }
+  const int ft = conv2d6_ft(tune().conv2d6_ft, d);
+  conv2d6_tiles(off2, len2, ft, &tiles);
+  WN_TRY(set_layout(m, B, Tp, off2, len2, M, s, (int)tiles.size() + 16));
+  if (M > 0) WN_TRY(upload_desc(m, m->d_tiles6, tiles, s));
+  WN_TRY(m->stage.end(s));
+  if (M == 0) return 0;
+  WN_TRY(encode_gate_wait(m, s));     // no conv1 launch to run beside a previous decode
+  auto it = W.x6_at.find(W.conv2.w);
+  WN_CHECK(it != W.x6_at.end(), "conv2d6: the handle has no plane image of conv2's weight");
+  WN_TRY(m->c2.ensure((size_t)M * F2 * d * sizeof(float)));
+  WN_TRY(m->x.ensure((size_t)M * d * sizeof(float)));
+  WN_TRY(m->t1.ensure((size_t)M * d * sizeof(float)));
+  WN_TRY(m->t2.ensure((size_t)M * d * sizeof(float)));
+  WN_TRY(m->hbuf.ensure((size_t)M * c.ffn_dim * sizeof(float)));
+  WN_TRY(m->qkv.ensure((size_t)M * 3 * d * sizeof(float)));
+  // (test hook wn_op_conv2d6: the kernel writes the caller's framed buffer)
+  float* c2 = m->c2_ext ? m->c2_ext : m->c2.as<float>();
+  Conv2d6Args a;
+  a.feats = feats_dev; a.B = B; a.T = T; a.F = c.feat_dim;
+  a.mean = W.cmvn_mean; a.istd = W.cmvn_istd; a.w1 = W.conv1_w; a.b1 = W.conv1_b;
+  a.W3 = it->second; a.bias = W.conv2.b;
+  a.tiles = reinterpret_cast<const int4*>(m->d_tiles6.p); a.n_tiles = (int)tiles.size() / 4;
+  a.d = d; a.ft = ft; a.wide = tune().conv2d6_wide;
+  a.C = c2; a.ldc = d;
+  WN_TRY(conv2d6_patch(a, s));
+  const int r = sub_out_linear(m, c2, M, F2, s);
+  if (r < 0) return r;
+  if (r == 0)
+    WN_TRY(linear(W.sub_out, c2, F2 * d, m->x.as<float>(), d, M, s, ACT_NONE, nullptr, 0,
+                  sqrtf((float)d)));
+  m->front_route = 1 << 16;
   return 0;
 }
 

@@ -389,6 +389,7 @@ struct wn_model {
   int B = 0, Tp = 0, rows = 0;          // rows of the encoder-output layout
   std::vector<int> off, len;            // per utterance (rows layout)
   DevBuf d_off, d_len, d_row_utt, d_off1, d_len1, d_a_row_off;
+  DevBuf d_tiles6;         // conv2d6_tiles() of the current batch (conv2d6.hip)
   DevBuf c1, c2, x, t1, t2, hbuf, qkv, enc;
   DevBuf bf_cat, bf_mrg, bf_gate, bf_stats;   // Branchformer: [x1 | x2], its merge, the gated half
   DevBuf ffn_part;                      // hidden-slice partials of the fused FFN
@@ -400,7 +401,7 @@ struct wn_model {
   int ctc_rows = 0, ctc_k = 0;
   bool ctc_valid = false;
   bool ln0_done = false;   // t1 already holds layer 0's norm_ff_macaron(x) (sub_out_linear)
-  float* c2_ext = nullptr; // wn_op_conv2_patch_into: conv2_patch writes here instead of c2
+  float* c2_ext = nullptr; // wn_op_conv2_patch_into / wn_op_conv2d6: the kernel writes here instead of c2
   int front_route = 0;     // front_route_code() of the last subsample_conv2d4 (0: no rows)
   DevBuf logits, topk_val, topk_idx;
   // searches
@@ -500,7 +501,8 @@ struct wn_model {
   DevBuf fb_off, fb_nfr;
 
   int F1() const { return (cfg.feat_dim - 1) / 2; }
-  int F2() const { return (F1() - 1) / 2; }
+  // conv2's output width: Conv2dSubsampling4 (3 x 3, stride 2) / Conv2dSubsampling6 (5 x 5, stride 3)
+  int F2() const { return cfg.input_layer == 2 ? (F1() - 2) / 3 : (F1() - 1) / 2; }
 };
 
 
@@ -602,8 +604,11 @@ int vocab_linear(wn_model* m, const Linear& l, const float* A, int lda, float* C
 int scatter_padded(const float* src, int lds, const int* off, const int* len, int B, int Tp, int D,
                    float* dst, hipStream_t s);
 int set_layout(wn_model* m, int B, int Tp, const std::vector<int>& off,
-               const std::vector<int>& len, int rows, hipStream_t s);
+               const std::vector<int>& len, int rows, hipStream_t s, int extra_desc_ints = 0);
 int subsample_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
+                      int T, int32_t* enc_lens_host, int pos0, hipStream_t s);
+// Conv2dSubsampling6 (input_layer 2): the same contract, l2 = ((L - 1) / 2 - 2) / 3 frames
+int subsample_conv2d6(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                       int T, int32_t* enc_lens_host, int pos0, hipStream_t s);
 int encode_gate_wait(wn_model* m, hipStream_t s);
 // How subsample_conv2d4 ran (wn_model::front_route, wn_op_conv2d4's route_out).

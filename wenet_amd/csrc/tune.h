@@ -72,6 +72,12 @@ namespace wn {
      (conv2_patch.hip: no conv1 launch, no pixel table, no plane image); 0 = conv1's plane image \
      + gathered conv2 at every size (A/B); 2 = the patch kernel at every size (tests) */         \
   X(x6_conv_patch, 1)                                                                           \
+  /* Conv2dSubsampling6 front end (conv2d6.hip): output frames per tile: 0 = the shipped one,    \
+     5 / 8 / 10 force (A/B, tests) */                                                           \
+  X(conv2d6_ft, 0)                                                                              \
+  /* ... its column split at d_model 512: 0 = the shipped one, 1 = two column halves per tile,  \
+     2 = eight waves side by side (A/B, tests) */                                               \
+  X(conv2d6_wide, 0)                                                                            \
   /* gemm_x6: 4 = clock stamps; 8 = wn_profile_gemm_clocks returns the row-block kernel's      \
      phase stamps (gemm_x6r.hip); WN_ABLATION builds: 1 no MFMAs, 2 no DMA */                  \
   X(x6_probe, 0)                                                                                \

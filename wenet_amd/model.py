@@ -84,6 +84,8 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
             f'encoder {enc_type!r} is outside the accelerated path')
     for k, v in checks.items():
         got = ec.get(k, defaults[k])
+        if k == 'input_layer' and enc_type == 'conformer' and got == 'conv2d6':
+            continue    # Conv2dSubsampling6 (csrc/conv2d6.hip); conv2d8 has no kernel
         if got != v:
             raise NotImplementedError(
                 f'encoder_conf.{k}={got!r} is outside the accelerated path '
@@ -160,7 +162,11 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
     c.max_pos = 5000
     c.norm_eps = ec.get('norm_eps', 1e-5)
     c.encoder_type = 1 if enc_type == 'transformer' else 0
-    c.input_layer = 1 if ec.get('input_layer') == 'conv1d2' else 0
+    c.input_layer = {'conv1d2': 1, 'conv2d6': 2}.get(ec.get('input_layer'), 0)
+    if c.input_layer == 2 and (c.d_model not in (256, 512) or c.feat_dim != 80):
+        raise NotImplementedError(
+            f'encoder_conf.input_layer=\'conv2d6\' with output_size={c.d_model}, '
+            f'input_dim={c.feat_dim} is outside the accelerated path (needs 256 / 512 and 80)')
     c.activation = 1 if ec.get('activation_type', 'swish') == 'gelu' else 0
     c.key_bias = int(bool(ec.get('key_bias', True)))
     cnn_norm = ec.get('cnn_module_norm', 'batch_norm')  # encoder.py default
@@ -406,11 +412,20 @@ class ASRModel:
 
     # ---- exported symbols ------------------------------------------------
     def subsampling_rate(self) -> int:  # asr_model.py:360-365
-        return 2 if self._cfg.input_layer == 1 else 4
+        return {1: 2, 2: 6}.get(self._cfg.input_layer, 4)
 
     def right_context(self) -> int:  # asr_model.py:367-371
-        # Conv1dSubsampling2: 4 (subsampling.py:143); Conv2dSubsampling4: 6
-        return 4 if self._cfg.input_layer == 1 else 6
+        # Conv1dSubsampling2: 4 (subsampling.py:143); Conv2dSubsampling4: 6;
+        # Conv2dSubsampling6: 10 (subsampling.py:258)
+        return {1: 4, 2: 10}.get(self._cfg.input_layer, 6)
+
+    def _sub_frames(self, T: int) -> int:
+        """Output frames the front end makes of T feature frames."""
+        if self._cfg.input_layer == 1:  # Conv1dSubsampling2 (k3, s2, p1)
+            return (T - 1) // 2 + 1
+        if self._cfg.input_layer == 2:  # Conv2dSubsampling6 (k3 s2, k5 s3)
+            return ((T - 1) // 2 - 2) // 3
+        return ((T - 1) // 2 - 1) // 2
 
     def sos_symbol(self) -> int:
         return self.sos
@@ -431,10 +446,7 @@ class ASRModel:
     def _encode(self, speech, lens, chunk, left, want_out: bool):
         B, T, F = speech.shape
         assert F == self._cfg.feat_dim, 'feature dimension mismatch'
-        if self._cfg.input_layer == 1:  # Conv1dSubsampling2 (k3, s2, p1)
-            Tp = (T - 1) // 2 + 1
-        else:
-            Tp = ((T - 1) // 2 - 1) // 2
+        Tp = self._sub_frames(T)
         enc_lens = np.zeros((B, ), dtype=np.int32)
         out = None
         if want_out:
@@ -480,7 +492,7 @@ class ASRModel:
         assert xs.dim() == 3 and xs.size(0) == 1
         xs = xs.detach().to(torch.float32).contiguous()
         time = xs.size(1)
-        chunk = ((time - 1) // 2 - 1) // 2
+        chunk = self._sub_frames(time)
         L, H, d = cfg.n_layers, cfg.n_heads, cfg.d_model
         dk2 = 2 * d // H       # att_cache holds K | V per head (attention.py:226-234)
         lorder = cfg.cnn_kernel - 1 if cfg.causal else 0
@@ -542,7 +554,7 @@ class ASRModel:
         B = xs.size(0)
         xs = xs.detach().to(torch.float32).contiguous()
         time = xs.size(1)
-        chunk = ((time - 1) // 2 - 1) // 2
+        chunk = self._sub_frames(time)
         L, H, d = cfg.n_layers, cfg.n_heads, cfg.d_model
         dk2 = 2 * d // H
         lorder = cfg.cnn_kernel - 1 if cfg.causal else 0

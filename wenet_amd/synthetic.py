@@ -687,6 +687,38 @@ CONFIGS['tiny_dec32'] = {
                        reverse_weight=0.3),
 }
 
+# examples/gigaspeech/s0/conf/train_u2++_conformer.yaml:3-33 (Conv2dSubsampling6, rate 6)
+CONFIGS['gigaspeech_conformer'] = {
+    'input_dim': 80, 'output_dim': 5002,
+    'encoder': 'conformer',
+    'encoder_conf': dict(output_size=512, attention_heads=8, linear_units=2048, num_blocks=12,
+                         dropout_rate=0.1, positional_dropout_rate=0.1,
+                         attention_dropout_rate=0.0, input_layer='conv2d6',
+                         normalize_before=True, cnn_module_kernel=8, use_cnn_module=True,
+                         causal=True, use_dynamic_chunk=True, cnn_module_norm='layer_norm',
+                         activation_type='swish', pos_enc_layer_type='rel_pos',
+                         selfattention_layer_type='rel_selfattn'),
+    'decoder': 'bitransformer',
+    'decoder_conf': dict(attention_heads=8, linear_units=2048, num_blocks=3, r_num_blocks=3,
+                         dropout_rate=0.1, positional_dropout_rate=0.1,
+                         self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0),
+    'model_conf': dict(ctc_weight=0.3, reverse_weight=0.3, lsm_weight=0.1,
+                       length_normalized_loss=False),
+}
+# the same recipe at the narrowest width its front-end kernel has: the test model
+CONFIGS['tiny_conv2d6'] = {
+    'input_dim': 80, 'output_dim': 41,
+    'encoder': 'conformer',
+    'encoder_conf': dict(CONFIGS['gigaspeech_conformer']['encoder_conf'], output_size=256,
+                         attention_heads=4, linear_units=128, num_blocks=2),
+    'decoder': 'bitransformer',
+    'decoder_conf': dict(attention_heads=4, linear_units=96, num_blocks=1, r_num_blocks=1,
+                         dropout_rate=0.1, positional_dropout_rate=0.1,
+                         self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0),
+    'model_conf': dict(ctc_weight=0.3, reverse_weight=0.3, lsm_weight=0.1,
+                       length_normalized_loss=False),
+}
+
 
 def _to_efficonformer(sd, configs, seed):
     """The Conformer-shaped dict of make_state_dict under an EfficientConformerEncoder's shapes
@@ -970,11 +1002,17 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
     b = 1.0 / 3.0
     sd['encoder.embed.conv.0.weight'] = _uniform(seed, 'conv0.w', (d, 1, 3, 3), b)
     sd['encoder.embed.conv.0.bias'] = _uniform(seed, 'conv0.b', (d, ), b)
-    b = 1.0 / math.sqrt(9 * d)
-    sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (d, d, 3, 3), b)
-    sd['encoder.embed.conv.2.bias'] = _uniform(seed, 'conv2.b', (d, ), b)
-    fdim = ((idim - 1) // 2 - 1) // 2
-    lin('encoder.embed.out.0', d, d * fdim)
+    if ec.get('input_layer') == 'conv2d6':   # Conv2dSubsampling6 (subsampling.py:245-253)
+        b = 1.0 / math.sqrt(25 * d)
+        sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (d, d, 5, 5), b)
+        sd['encoder.embed.conv.2.bias'] = _uniform(seed, 'conv2.b', (d, ), b)
+        lin('encoder.embed.linear', d, d * (((idim - 1) // 2 - 2) // 3))
+    else:
+        b = 1.0 / math.sqrt(9 * d)
+        sd['encoder.embed.conv.2.weight'] = _uniform(seed, 'conv2.w', (d, d, 3, 3), b)
+        sd['encoder.embed.conv.2.bias'] = _uniform(seed, 'conv2.b', (d, ), b)
+        fdim = ((idim - 1) // 2 - 1) // 2
+        lin('encoder.embed.out.0', d, d * fdim)
     sd['encoder.embed.pos_enc.pe'] = positional_table(d).numpy()
     norm('encoder.after_norm', d)
     for i in range(ec['num_blocks']):
