@@ -768,6 +768,26 @@ int wn_op_firered_frontend(const float* feats, const float* mean, const float* i
                            float* out, int32_t ldo, int32_t out_rows, const int32_t* lens,
                            const int32_t* out_off, int32_t* out_len, int32_t B, int32_t T,
                            int32_t F, int32_t C, void* stream);
+/* Self attention with Shaw relative-position keys (ShawRelPositionMultiHeadedAttention;
+ * csrc/attention_shaw.hip), fp32, d_k = 64, full context:
+ *   score(i, j) = (q_i . k_j + q_i . E[clamp(j - i, -64, 8) + 64]) * scale,
+ * softmax over the sequence's keys.  Q / K / V / O [rows][ld*]; off / len host [n_seq] (ascending,
+ * disjoint; a length may be 0); E [73][64] contiguous, ONE table for all heads.  mask_mode must be
+ * 0; kbias, p_off, blk_tab and bf16_flags must be NULL / 0: the kernel has none of them and
+ * refuses each by name. */
+int wn_op_attention_shaw(const float* Q, const float* K, const float* V, int32_t ldq, int32_t ldk,
+                         int32_t ldv, int32_t rows, const float* E, float* O, int32_t ldo,
+                         const int32_t* off, const int32_t* len, int32_t n_seq, int32_t n_heads,
+                         float scale, int32_t mask_mode, const float* kbias, const int32_t* p_off,
+                         const int32_t* blk_tab, int32_t bf16_flags, void* stream);
+/* StackNFramesSubsampling (stride 2) up to its projection (csrc/attention_shaw.hip): feats (B, T,
+ * F), F <= 128; GlobalCMVN per frame (mean NULL: none); output row out_off[b] + t, t < out_len[b]
+ * = lens[b] / 2 (host [B], written), = LayerNorm over the 2 F values of frames 2 t | 2 t + 1 (ln_w,
+ * ln_b [2 F], eps 1e-5).  An odd length drops its last frame.  out [out_rows][ldo]. */
+int wn_op_stack_frames_ln(const float* feats, const float* mean, const float* istd,
+                          const float* ln_w, const float* ln_b, float* out, int32_t ldo,
+                          int32_t out_rows, const int32_t* lens, const int32_t* out_off,
+                          int32_t* out_len, int32_t B, int32_t T, int32_t F, void* stream);
 /* The middle of a Branchformer cgMLP (ConvolutionalSpatialGatingUnit, csrc/branchformer.hip),
  * fp32, on packed rows: h [rows][ldh] holds r in columns [0, C) and the gate half in [C, 2 C);
  *   y = (depthwise_conv_K(LayerNorm_C(gate half)) + bias) * r       (gate == 0: without "* r")
@@ -1212,6 +1232,32 @@ typedef struct {
 int wn_model_create_firered(const wn_config* cfg, const wn_firered_config* fcfg,
                             const wn_tensor* weights, int32_t n_weights, int32_t device,
                             wn_model** out);
+
+/* W2v-BERT 2.0 / conformer_shaw encoders (`encoder: conformer` with input_layer stack_n_frames,
+ * pos_enc_layer_type no_pos, selfattention_layer_type shaw_rel_selfattn, conv_bias false; the
+ * recipe of wenet/models/ssl/w2vbert/convert_w2vbert_to_wenet_config_and_ckpt.py) under the
+ * asr_model head: a front end that stacks two frames per row, no positional encoding, and self
+ * attention with Shaw relative-position keys (one 73-row table per layer, shared by its heads).
+ * A struct and an entry point of their own: wn_config and wn_model_create are unchanged. */
+typedef struct {
+  int32_t max_left;           /* ShawRelPositionMultiHeadedAttention.max_left_rel_pos: 64 */
+  int32_t max_right;          /* max_right_rel_pos: 8 */
+  int32_t stack;              /* StackNFramesSubsampling stride: 2 */
+} wn_shaw_config;
+
+/* wn_model_create for such a state dict (encoder.embed.norm / out, per layer
+ * self_attn.rel_k_embed.weight, no linear_pos / pos_bias_u / pos_bias_v, no conv module biases).
+ * cfg: encoder_type 0, input_layer 0, cnn_norm 0 (layer_norm), no chunk sizes, d_model = n_heads
+ * * 64 up to 1024, causal and cnn_kernel as the recipe has them; dec_layers 0 when the decoder's
+ * heads are neither 64 nor 32 wide or the checkpoint has no decoder.  On the handle wn_encode
+ * runs the stacked-frame front end and the layers in fp32, full context only (chunk must be <=
+ * 0): an utterance of L frames gives L / 2 encoder frames, the same alone or batched; the padded
+ * output has T / 2 frames.  The CTC entry points, the alignment and (with a decoder) the
+ * rescoring entry points then work on the encoder output unchanged.  wn_encode_chunk*,
+ * wn_stream_create, wn_op_conv2d4 and a bf16 / fp8 precision are refused on such a handle. */
+int wn_model_create_shaw(const wn_config* cfg, const wn_shaw_config* hcfg,
+                         const wn_tensor* weights, int32_t n_weights, int32_t device,
+                         wn_model** out);
 
 /* Branchformer / E-Branchformer encoders (`encoder: branchformer` / `e_branchformer`,
  * wenet/models/branchformer/, wenet/models/e_branchformer/) under the asr_model head: the

@@ -43,6 +43,11 @@ class WnFireRedConfig(Structure):
         ('attn_norm_eps', c_float)]
 
 
+class WnShawConfig(Structure):
+    """wn_shaw_config: what a W2v-BERT 2.0 / conformer_shaw encoder has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('max_left', 'max_right', 'stack')]
+
+
 class WnBranchformerConfig(Structure):
     """wn_branchformer_config: what a Branchformer / E-Branchformer encoder has on top of
     wn_config."""
@@ -191,6 +196,7 @@ EXPORTS = [
     'wn_op_attention_d32', 'wn_op_attention_d32_relpos', 'wn_attention_d32_relpos_nw4_len',
     'wn_model_encoder_head_cols',
     'wn_model_create_sensevoice', 'wn_sensevoice_set_queries', 'wn_op_sv_front',
+    'wn_model_create_shaw', 'wn_op_attention_shaw', 'wn_op_stack_frames_ln',
 ]
 
 _lib = None
@@ -377,6 +383,12 @@ def lib():
                                            vp, vp, i32, pi32, pi32, i32, i32, f32, vp]
     L.wn_op_firered_frontend.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32,
                                          pi32, i32, i32, i32, i32, vp]
+    L.wn_model_create_shaw.argtypes = [POINTER(WnConfig), POINTER(WnShawConfig),
+                                       POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_attention_shaw.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, pi32, pi32,
+                                       i32, i32, f32, i32, vp, vp, vp, i32, vp]
+    L.wn_op_stack_frames_ln.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32, pi32, i32,
+                                        i32, i32, vp]
     L.wn_model_create_branchformer.argtypes = [POINTER(WnConfig), POINTER(WnBranchformerConfig),
                                                POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_op_csgu_gate.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, pi32,

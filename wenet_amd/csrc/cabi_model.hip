@@ -81,6 +81,7 @@ const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 // wn_model_create_firered (fcfg != nullptr, cabi_firered.hip: the FireRedASR-AED encoder)
 // wn_model_create_branchformer (bcfg != nullptr, cabi_branchformer.hip)
 // wn_model_create_squeezeformer (qcfg != nullptr, cabi_squeezeformer.hip)
+// wn_model_create_shaw (hcfg != nullptr, cabi_shaw.hip)
 }  // extern "C"
 
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -88,7 +89,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                          const wn_firered_config* fcfg, const wn_branchformer_config* bcfg,
                          const wn_squeezeformer_config* qcfg,
                          const wn_efficonformer_config* ecfg, const wn_tensor* weights,
-                         int32_t n_weights, int32_t device, wn_model** out) {
+                         int32_t n_weights, int32_t device, wn_model** out,
+                         const wn_shaw_config* hcfg) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   const bool fr = fcfg != nullptr;
@@ -157,6 +159,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   const bool ef = ecfg != nullptr;
   if (ef) WN_TRY(efficonformer_config_check(c, *ecfg, tcfg || fr || bf || sq));
+  const bool sh = hcfg != nullptr;
+  if (sh) WN_TRY(shaw_config_check(c, *hcfg, tcfg || fr || bf || sq || ef));
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || ef || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 ||
@@ -191,6 +195,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (bf) { m->bf.on = true; m->bf.c = *bcfg; }
   if (sq) { m->sq.on = true; m->sq.c = *qcfg; }
   if (ef) { m->ef.on = true; m->ef.c = *ecfg; }
+  if (sh) { m->sh.on = true; m->sh.c = *hcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -248,6 +253,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     hs.add("fr.conv2.b", b2, C);
     // out Linear(C * F2 -> d): the kernels write the reference's own column order c * F2 + f
     WN_TRY(stage_linear(src, hs, "encoder.embed.out.0", d, C * F2));
+  } else if (sh) {
+    // StackNFramesSubsampling: staged with the layers (shaw_stage, cabi_shaw.hip)
   } else if (ef && ecfg->front_rate == 2) {
     WN_TRY(efficonformer_stage_front2(src, hs, c, m->F1()));   // (cabi_efficonformer.hip)
   } else if (sub6) {
@@ -640,7 +647,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_TRY(stage_linear(src, hs, p + ".conv_module.pointwise_conv2", d, d));
   }
   if (ef) WN_TRY(efficonformer_stage_layers(src, hs, c, *ecfg));   // (cabi_efficonformer.hip)
-  for (int i = 0; !tf && !fr && !bf && !sq && !ef && i < c.n_layers; ++i) {
+  if (sh) WN_TRY(shaw_stage(src, hs, c));                          // (cabi_shaw.hip)
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -809,6 +817,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     W.conv2.w = P("fr.conv2.w"); W.conv2.b = P("fr.conv2.b");
     W.conv2.out = C; W.conv2.in = 9 * C;
     W.sub_out = LIN("encoder.embed.out.0", d, C * F2);
+  } else if (sh) {
+    // (shaw_bind below)
   } else if (ef && ecfg->front_rate == 2) {   // conv2d2: one conv, then the projection
     W.conv1_w = P("conv1.w"); W.conv1_b = P("conv1.b");
     W.sub_out.w = P("sub_out.w"); W.sub_out.b = P("sub_out.b");
@@ -952,11 +962,13 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     }
   } else if (ef) {
     WN_TRY(efficonformer_bind(W, c, *ecfg));   // (cabi_efficonformer.hip)
+  } else if (sh) {
+    WN_TRY(shaw_bind(W, c));                   // (cabi_shaw.hip)
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && !fr && !bf && !sq && !ef && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -1041,7 +1053,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   // (firered, branchformer, squeezeformer: the plain fp32 path, no six-product / row-block images of the
   // encoder's weights; the decoders and the CTC head get theirs as in every other model)
-  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq || ef));
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq || ef || sh));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -1082,6 +1094,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->bf.on = src->bf.on; m->bf.c = src->bf.c;
   m->sq.on = src->sq.on; m->sq.c = src->sq.c;
   m->ef.on = src->ef.on; m->ef.c = src->ef.c;
+  m->sh.on = src->sh.on; m->sh.c = src->sh.c;
   m->pf.on = src->pf.on; m->pf.c = src->pf.c;
   m->sv.on = src->sv.on; m->sv.c = src->sv.c;
   m->device = src->device;
@@ -1110,6 +1123,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
   WN_CHECK(!m->ef.on || precision == PREC_F32,
            "wn_model_set_precision: an Efficient Conformer handle stays fp32 (no bf16 / fp8 "
            "kernels for its encoder)");
+  WN_CHECK(!m->sh.on || precision == PREC_F32,
+           "wn_model_set_precision: a W2v-BERT (shaw) handle stays fp32 (no bf16 / fp8 kernels "
+           "for its encoder)");
   WN_CHECK(!m->pf.on || precision == PREC_F32,
            "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "
            "encoder and decoder)");

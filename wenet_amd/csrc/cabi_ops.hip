@@ -1003,6 +1003,66 @@ int wn_op_firered_frontend(const float* feats, const float* mean, const float* i
   return firered_frontend(a, s);
 }
 
+int wn_op_attention_shaw(const float* Q, const float* K, const float* V, int32_t ldq, int32_t ldk,
+                         int32_t ldv, int32_t rows, const float* E, float* O, int32_t ldo,
+                         const int32_t* off, const int32_t* len, int32_t n_seq, int32_t n_heads,
+                         float scale, int32_t mask_mode, const float* kbias, const int32_t* p_off,
+                         const int32_t* blk_tab, int32_t bf16_flags, void* stream) {
+  WN_CHECK(Q && K && V && E && O && off && len, "attention_shaw: null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 32768 && n_heads > 0 && n_heads < 256,
+           "attention_shaw: n_seq / n_heads");
+  WN_CHECK(rows > 0, "attention_shaw: empty buffers");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           "attention_shaw: rows outside the buffer, unordered or overlapping");
+  int max_len = 0;
+  std::vector<int> h((size_t)2 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  AttnArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = E; a.ldp = 64; a.O = O; a.ldo = ldo;
+  a.q_off = a.kv_off = desc.as<int>(); a.q_len = a.kv_len = a.q_off + n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_q_len = max_len; a.scale = scale;
+  // what the kernel does not have goes through to its own refusals
+  a.mask_mode = mask_mode; a.kbias = kbias; a.p_off = p_off;
+  a.blk_tab = blk_tab; a.n_blk = blk_tab ? 1 : 0;
+  a.o_bf16 = (bf16_flags & 1) != 0; a.qkv_bf16 = (bf16_flags & 2) != 0;
+  return attention_shaw(a, s);
+}
+
+int wn_op_stack_frames_ln(const float* feats, const float* mean, const float* istd,
+                          const float* ln_w, const float* ln_b, float* out, int32_t ldo,
+                          int32_t out_rows, const int32_t* lens, const int32_t* out_off,
+                          int32_t* out_len, int32_t B, int32_t T, int32_t F, void* stream) {
+  WN_CHECK(feats && ln_w && ln_b && out && lens && out_off && out_len,
+           "stack_frames_ln: null argument");
+  WN_CHECK(B > 0 && B < 65536 && T > 0 && F >= 1 && F <= 128 && out_rows > 0,
+           "stack_frames_ln: B / T / F");
+  std::vector<int> h((size_t)2 * B);
+  int max_len = 0;
+  for (int b = 0; b < B; ++b) {
+    WN_CHECK(lens[b] >= 0 && lens[b] <= T, "stack_frames_ln: a length outside [0, T]");
+    out_len[b] = lens[b] / 2;
+    h[b] = out_off[b]; h[B + b] = out_len[b];
+    max_len = std::max(max_len, out_len[b]);
+  }
+  WN_CHECK(packed_ok(out_off, out_len, B, out_rows),
+           "stack_frames_ln: rows outside the buffer, unordered or overlapping");
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  StackFramesArgs a;
+  a.feats = feats; a.mean = mean; a.istd = istd; a.ln_w = ln_w; a.ln_b = ln_b;
+  a.out = out; a.ldo = ldo; a.off = desc.as<int>(); a.len = a.off + B;
+  a.B = B; a.T = T; a.F = F; a.max_len = max_len; a.eps = 1e-5f;
+  return stack_frames_ln(a, s);
+}
+
 // the descriptors both Branchformer hooks share: off | len on the device, the longest length
 static int dwt_hook_layout(const int32_t* off, const int32_t* len, int n_seq, int rows,
                            DevBuf& desc, DwTileArgs* a, hipStream_t s, const char* who) {
@@ -1063,7 +1123,7 @@ int wn_op_conv2d4(wn_model* m, const float* feats_dev, const int32_t* feat_lens_
   struct GateDrop { wn_model* m; ~GateDrop() { m->enc_gate = nullptr; } } gate_drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on &&
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on && !m->sh.on &&
                m->cfg.input_layer == 0,
            "wn_op_conv2d4: needs a Conformer encoder with input_layer 0 (conv2d)");
   WN_CHECK(B > 0, "wn_encode: empty batch");
@@ -1121,7 +1181,7 @@ int wn_op_conv2_patch_into(wn_model* m, const float* feats_dev, const int32_t* f
   struct Drop { wn_model* m; ~Drop() { m->enc_gate = nullptr; m->c2_ext = nullptr; } } drop{m};
   m->pb_valid = false;
   PrecisionScope prec_scope(m);
-  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on &&
+  WN_CHECK(!m->data->layers.empty() && m->cfg.encoder_type == 0 && !m->fr.on && !m->sh.on &&
                m->cfg.input_layer == 0,
            "wn_op_conv2_patch_into: needs a Conformer encoder with input_layer 0 (conv2d)");
   WN_CHECK(B > 0 && B < 65536 && T >= 7, "wn_op_conv2_patch_into: B / T");

@@ -1002,6 +1002,29 @@ int attention_d32(const AttnArgs& a, hipStream_t s);
 constexpr int ATTN_D32_RELPOS_NW4_LEN = 129;
 int attention_d32_relpos(const AttnArgs& a, hipStream_t s);
 
+// ---- W2v-BERT 2.0 / conformer_shaw encoders (attention_shaw.hip), fp32 ----------------------
+// SELF attention for heads of d_k = 64 with Shaw relative-position keys: score (q_i . k_j + q_i .
+// E[clamp(j - i, -SHAW_LEFT, SHAW_RIGHT) + SHAW_LEFT]) * scale; a.P is the table E [SHAW_ROWS][ldp
+// >= 64], ONE table for all heads; bias_u / bias_v stay null.  mask_mode 0 only; kbias, p_off, block
+// lists and the bf16 flags are refused.  Always fp32.
+constexpr int SHAW_LEFT = 64, SHAW_RIGHT = 8, SHAW_ROWS = SHAW_LEFT + SHAW_RIGHT + 1;
+int attention_shaw(const AttnArgs& a, hipStream_t s);
+
+// StackNFramesSubsampling (stride 2) up to its projection: output row off[b] + t of utterance b =
+// LayerNorm_{2F}(CMVN(frame 2 t) | CMVN(frame 2 t + 1)), t < len[b] (= feature length / 2).
+struct StackFramesArgs {
+  const float* feats;     // (B, T, F) padded
+  const float* mean;      // [F] or null (no CMVN)
+  const float* istd;      // [F]
+  const float* ln_w; const float* ln_b;   // [2 F]
+  float* out; int ldo;    // packed rows, 2 F columns
+  const int* off;         // [B] first output row of the utterance
+  const int* len;         // [B] output rows of the utterance
+  int B, T, F, max_len;
+  float eps;
+};
+int stack_frames_ln(const StackFramesArgs& a, hipStream_t s);
+
 // LFR front end (paraformer/layers.py:24-92 on ONE utterance, paraformer.py:329-350): output row
 // t of utterance b stacks the m frames n t - (m - 1) / 2 + f, f < m, each index clamped to
 // [0, len[b] - 1]; then GlobalCMVN over the m F columns, x * xscale + pe[t + 1], and the

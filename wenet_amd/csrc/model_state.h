@@ -182,6 +182,9 @@ struct EncLayer {
   // of a Branchformer's (enc_head_cols() columns per head)
   int ef_rate = 1, ef_kernel = 0;
   bool ef_grouped = false, ef_stride = false;
+  // W2v-BERT 2.0 / conformer_shaw layers (wn_model::sh.on, cabi_shaw.hip): the Conformer's slots
+  // without bias_u / bias_v / pos_w / pos_tab; rel_k_embed.weight [73][64], one table for all heads
+  const float* shaw_tab = nullptr;
 };
 
 struct TfLayer {  // TransformerEncoderLayer (encoder_layer.py:28-127)
@@ -265,6 +268,7 @@ struct ModelData {
   // re-laid-out subsampling weights
   const float* conv1_w = nullptr; const float* conv1_b = nullptr;
   Linear conv2, sub_out;
+  Norm stack_norm;                      // StackNFramesSubsampling's LayerNorm(2 F) (sh.on)
   const float* cmvn_mean = nullptr; const float* cmvn_istd = nullptr;
   const float* pe = nullptr;
   Norm after_norm;
@@ -335,6 +339,12 @@ struct wn_model {
     bool on = false;
     wn_firered_config c = {};
   } fr;
+  // wn_model_create_shaw: a W2v-BERT 2.0 / conformer_shaw encoder (cabi_shaw.hip); data->layers
+  // hold Conformer shapes with a null-bias conv module and shaw_tab = the layer's [73][64] table
+  struct {
+    bool on = false;
+    wn_shaw_config c = {};
+  } sh;
   // wn_model_create_branchformer: a Branchformer (kind 1) / E-Branchformer (kind 2) encoder
   // (cabi_branchformer.hip) behind the Conformer front end
   struct {
@@ -634,9 +644,16 @@ int ffn_x6_pair(wn_model* m, const Linear& w1, const Linear& w2, int act, const 
 int encoder_layers(wn_model* m, int chunk, int left, hipStream_t s);
 int encoder_layers_chunk(wn_model* m, int n_sess, int R, const int* offsets,
                          std::vector<ChunkSess>& sess, float* out, hipStream_t s);
+namespace wn { struct Src; struct HostStage; }
 // (cabi_firered.hip)
 int encode_firered(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
                    float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
+// (cabi_shaw.hip)
+int shaw_config_check(const wn_config& c, const wn_shaw_config& h, bool other_family);
+int shaw_stage(const wn::Src& src, wn::HostStage& hs, const wn_config& c);
+int shaw_bind(ModelData& W, const wn_config& c);
+int encode_shaw(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
+                float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 // (cabi_branchformer.hip)
 int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
@@ -646,7 +663,6 @@ int encode_squeezeformer(wn_model* m, const float* feats_dev, const int32_t* fea
                          int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
                          hipStream_t s);
 // (cabi_efficonformer.hip)
-namespace wn { struct Src; struct HostStage; }
 int efficonformer_config_check(const wn_config& c, const wn_efficonformer_config& e,
                                bool other_family);
 int efficonformer_stage_front2(const wn::Src& src, wn::HostStage& hs, const wn_config& c, int F1);
@@ -674,7 +690,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_stateless_predictor_config* scfg, const wn_firered_config* fcfg,
                       const wn_branchformer_config* bcfg, const wn_squeezeformer_config* qcfg,
                       const wn_efficonformer_config* ecfg, const wn_tensor* weights,
-                      int32_t n_weights, int32_t device, wn_model** out);
+                      int32_t n_weights, int32_t device, wn_model** out,
+                      const wn_shaw_config* hcfg = nullptr);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

@@ -55,6 +55,10 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         # (wenet_amd/efficonformer.py: the encoder's own keys go into a wn_efficonformer_config)
         from wenet_amd.efficonformer import efficonformer_config_from_yaml
         return efficonformer_config_from_yaml(configs)[0]
+    if enc_type == 'conformer' and ec.get('selfattention_layer_type') == 'shaw_rel_selfattn':
+        # (wenet_amd/shaw.py: the W2v-BERT 2.0 recipe, its own keys go into a wn_shaw_config)
+        from wenet_amd.shaw import shaw_config_from_yaml
+        return shaw_config_from_yaml(configs)[0]
     if enc_type == 'conformer':
         checks = dict(input_layer='conv2d', pos_enc_layer_type='rel_pos',
                       selfattention_layer_type='rel_selfattn',
@@ -331,6 +335,12 @@ class ASRModel:
             raise NotImplementedError(
                 "encoder 'efficientConformer' is outside the accelerated path of this class: "
                 'wenet_amd.EfficientConformer (load_model picks it)')
+        if (configs.get('encoder', 'conformer') == 'conformer' and
+                (configs.get('encoder_conf') or {}).get('selfattention_layer_type') ==
+                'shaw_rel_selfattn'):
+            raise NotImplementedError(
+                "selfattention_layer_type 'shaw_rel_selfattn' is outside the accelerated path of "
+                'this class: wenet_amd.ShawConformer (load_model picks it)')
         return config_from_yaml(configs)
 
     def _create(self, L, tensors, n: int, h) -> int:
@@ -1226,6 +1236,12 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
     elif configs.get('encoder') == 'efficientConformer':
         from wenet_amd.efficonformer import EfficientConformer
         model = EfficientConformer(configs, sd, device)
+    elif (configs.get('encoder', 'conformer') == 'conformer' and
+          configs.get('model', 'asr_model') == 'asr_model' and
+          (configs.get('encoder_conf') or {}).get('selfattention_layer_type') ==
+          'shaw_rel_selfattn'):
+        from wenet_amd.shaw import ShawConformer
+        model = ShawConformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

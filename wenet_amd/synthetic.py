@@ -720,6 +720,67 @@ CONFIGS['tiny_conv2d6'] = {
 }
 
 
+# W2v-BERT 2.0 / conformer_shaw (wenet/models/ssl/w2vbert/convert_w2vbert_to_wenet_config_and_ckpt.py:8-62)
+def _shaw(d, heads, ffn, blocks, dec_conf: dict, vocab: int) -> dict:
+    return {
+        'input_dim': 80, 'output_dim': vocab,
+        'encoder': 'conformer',
+        'encoder_conf': dict(causal=True, gradient_checkpointing=True, input_layer='stack_n_frames',
+                             output_size=d, attention_heads=heads, linear_units=ffn,
+                             num_blocks=blocks, dropout_rate=0.1, positional_dropout_rate=0.0,
+                             attention_dropout_rate=0.0, normalize_before=True,
+                             use_dynamic_chunk=False, use_dynamic_left_chunk=False,
+                             pos_enc_layer_type='no_pos', static_chunk_size=-1,
+                             activation_type='swish', conv_bias=False,
+                             selfattention_layer_type='shaw_rel_selfattn', cnn_module_kernel=31,
+                             cnn_module_norm='layer_norm'),
+        'decoder': 'transformer',
+        'decoder_conf': dict(dec_conf, dropout_rate=0.1, positional_dropout_rate=0.1,
+                             self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0),
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False),
+    }
+
+
+# the test model: a decoder of 2 heads of 64, and (make_configs) a global CMVN as a fine-tune has
+CONFIGS['tiny_shaw'] = _shaw(128, 2, 256, 2, dict(attention_heads=2, linear_units=96,
+                                                  num_blocks=2), 41)
+# the 600 M encoder at the converter's widths (no CMVN, its "dummy decoder" of 4 heads of 256)
+CONFIGS['w2vbert_600m'] = dict(_shaw(1024, 16, 4096, 24, dict(attention_head=16,
+                                                              linear_units=4096, num_blocks=6),
+                                     1024), cmvn=None)
+# one block of it under a small vocabulary: the test model at the converter's widths
+CONFIGS['w2vbert_600m_1blk'] = dict(_shaw(1024, 16, 4096, 1, dict(attention_head=16,
+                                                                  linear_units=96, num_blocks=1),
+                                          41), cmvn=None)
+
+
+def _to_shaw(sd, configs, seed):
+    """The Conformer-shaped dict of make_state_dict under the converter's names and shapes:
+    StackNFramesSubsampling (norm over 2 idim, out), no positional table, no linear_pos /
+    pos_bias_u / pos_bias_v, no conv module biases, one rel_k_embed (73, 64) per layer; no
+    decoder when its heads are not 64 or 32 wide (the converter's checkpoint carries none)."""
+    ec, dc = configs['encoder_conf'], configs['decoder_conf']
+    d, idim = ec['output_size'], configs['input_dim']
+    drop = ('encoder.embed.conv.', 'encoder.embed.out.0.', 'encoder.embed.pos_enc.')
+    ends = ('.self_attn.linear_pos.weight', '.self_attn.pos_bias_u', '.self_attn.pos_bias_v',
+            '.conv_module.pointwise_conv1.bias', '.conv_module.depthwise_conv.bias',
+            '.conv_module.pointwise_conv2.bias')
+    no_dec = d // dc.get('attention_heads', 4) not in (64, 32)
+    out = OrderedDict((k, v) for k, v in sd.items()
+                      if not k.startswith(drop) and not (k.startswith('encoder.') and
+                                                         k.endswith(ends))
+                      and not (no_dec and k.startswith('decoder.')))
+    out['encoder.embed.norm.weight'] = _normal(seed, 'embed.norm.w', (2 * idim, ), 0.1, 1.0)
+    out['encoder.embed.norm.bias'] = _normal(seed, 'embed.norm.b', (2 * idim, ), 0.1)
+    b = 1.0 / math.sqrt(2 * idim)
+    out['encoder.embed.out.weight'] = _uniform(seed, 'embed.out.w', (d, 2 * idim), b)
+    out['encoder.embed.out.bias'] = _uniform(seed, 'embed.out.b', (d, ), b)
+    for i in range(ec['num_blocks']):
+        p = f'encoder.encoders.{i}.self_attn.rel_k_embed.weight'
+        out[p] = _normal(seed, p, (73, 64), 1.0)      # torch.nn.Embedding: N(0, 1)
+    return out
+
+
 def _to_efficonformer(sd, configs, seed):
     """The Conformer-shaped dict of make_state_dict under an EfficientConformerEncoder's shapes
     (wenet/models/efficient_conformer/encoder.py:140-215): pos_bias_u / v of a grouped layer are
@@ -1099,6 +1160,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         sd = _to_squeezeformer(sd, configs, seed)
     if configs.get('encoder') == 'efficientConformer':
         sd = _to_efficonformer(sd, configs, seed)
+    if ec.get('selfattention_layer_type') == 'shaw_rel_selfattn':
+        sd = _to_shaw(sd, configs, seed)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
 
