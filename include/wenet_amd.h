@@ -190,6 +190,23 @@ int wn_fbank(wn_model* m, const float* pcm_dev, const int64_t* sample_off_host,
              int32_t B, float* feats_dev, int32_t max_frames,
              int32_t* n_frames_host, void* stream);
 
+/* compute_w2vbert_fbank behind wn_fbank (wenet/dataset/processor.py:259-272; csrc/utt_norm.hip):
+ * per utterance b and mel bin f, over ALL feat_lens_host[b] frames of the utterance,
+ *   std, mean = torch.std_mean(mat, dim=0)  (unbiased, M2 / (n - 1));  out = (mat - mean) / std,
+ * a true division (a constant bin gives the reference's NaN).  feats_dev and out_dev are (B, T, F)
+ * padded, F <= 128, F % 4 == 0, 16-byte aligned; out_dev may be feats_dev.  Frames at or behind
+ * the utterance's end are written as zeros; the one frame of a one-frame utterance is NaN (the
+ * unbiased std of one value).  The statistics are merged in a fixed order that depends on the
+ * utterance's length alone: the same bits alone, batched and at any place of the batch.  Any
+ * handle, a wn_workspace_create one included; its statistics workspace grows on demand. */
+int wn_utt_normalize(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int32_t B,
+                     int32_t T, int32_t F, float* out_dev, void* stream);
+/* on != 0: wn_encode on this W2v-BERT (shaw) handle takes RAW fbank: it computes the statistics
+ * above and divides inside the stacked-frame front end (in front of the handle's GlobalCMVN, if
+ * any), so the normalised tensor never reaches HBM.  Off (the default): wn_encode takes the
+ * features the reference's model takes, as before.  Other handles are refused. */
+int wn_model_set_utt_norm_input(wn_model* m, int32_t on);
+
 /* compute_log_mel_spectrogram (wenet/dataset/processor.py:320-369, the Whisper
  * frontend): hann(400) STFT with hop 160 and reflect padding, power of all
  * frames but the last, slaney mel filters (librosa.filters.mel), log10 with
@@ -788,6 +805,19 @@ int wn_op_stack_frames_ln(const float* feats, const float* mean, const float* is
                           const float* ln_w, const float* ln_b, float* out, int32_t ldo,
                           int32_t out_rows, const int32_t* lens, const int32_t* out_off,
                           int32_t* out_len, int32_t B, int32_t T, int32_t F, void* stream);
+/* The statistics of wn_utt_normalize alone (csrc/utt_norm.hip): feats (B, T, F), F <= 128, lens
+ * host [B] in [0, T]; mean / std [B][F] (device) are written for utterances of 2 or more frames
+ * and left alone for shorter ones. */
+int wn_op_utt_stats(const float* feats, const int32_t* lens, int32_t B, int32_t T, int32_t F,
+                    float* mean, float* std_out, void* stream);
+/* wn_op_stack_frames_ln on RAW features with caller-given utterance statistics umean / ustd
+ * [B][F]: (x - umean[b][f]) / ustd[b][f], then GlobalCMVN (mean NULL: none), then the LayerNorm.
+ * What wn_encode runs under wn_model_set_utt_norm_input. */
+int wn_op_stack_frames_ln_utt(const float* feats, const float* umean, const float* ustd,
+                              const float* mean, const float* istd, const float* ln_w,
+                              const float* ln_b, float* out, int32_t ldo, int32_t out_rows,
+                              const int32_t* lens, const int32_t* out_off, int32_t* out_len,
+                              int32_t B, int32_t T, int32_t F, void* stream);
 /* The middle of a Branchformer cgMLP (ConvolutionalSpatialGatingUnit, csrc/branchformer.hip),
  * fp32, on packed rows: h [rows][ldh] holds r in columns [0, C) and the gate half in [C, 2 C);
  *   y = (depthwise_conv_K(LayerNorm_C(gate half)) + bias) * r       (gate == 0: without "* r")

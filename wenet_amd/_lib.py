@@ -197,6 +197,8 @@ EXPORTS = [
     'wn_model_encoder_head_cols',
     'wn_model_create_sensevoice', 'wn_sensevoice_set_queries', 'wn_op_sv_front',
     'wn_model_create_shaw', 'wn_op_attention_shaw', 'wn_op_stack_frames_ln',
+    'wn_utt_normalize', 'wn_model_set_utt_norm_input', 'wn_op_utt_stats',
+    'wn_op_stack_frames_ln_utt',
 ]
 
 _lib = None
@@ -389,6 +391,12 @@ def lib():
                                        i32, i32, f32, i32, vp, vp, vp, i32, vp]
     L.wn_op_stack_frames_ln.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32, pi32, i32,
                                         i32, i32, vp]
+    L.wn_utt_normalize.argtypes = [vp, vp, pi32, i32, i32, i32, vp, vp]
+    L.wn_model_set_utt_norm_input.argtypes = [vp, i32]
+    L.wn_op_utt_stats.argtypes = [vp, pi32, i32, i32, i32, vp, vp, vp]
+    # feats umean ustd mean istd ln_w ln_b out | ldo out_rows | lens out_off out_len | B T F
+    L.wn_op_stack_frames_ln_utt.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32,
+                                            pi32, i32, i32, i32, vp]
     L.wn_model_create_branchformer.argtypes = [POINTER(WnConfig), POINTER(WnBranchformerConfig),
                                                POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_op_csgu_gate.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, pi32,

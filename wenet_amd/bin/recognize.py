@@ -218,7 +218,8 @@ def padding_order(n_frames: Sequence[int]) -> List[int]:
 
 def check_feature_conf(configs: dict):
     """The feature recipes this path computes on the device: Kaldi fbank (25 ms /
-    10 ms, input_dim bins) and the Whisper log-mel (n_fft 400, hop 160)."""
+    10 ms, input_dim bins), the same under `w2vbert_fbank` (normalised per utterance) and the
+    Whisper log-mel (n_fft 400, hop 160)."""
     dc = configs.get('dataset_conf', {})
     feats_type = dc.get('feats_type', 'fbank')
     if feats_type == 'log_mel_spectrogram':
@@ -227,10 +228,11 @@ def check_feature_conf(configs: dict):
                 or lc.get('num_mel_bins', 80) != configs.get('input_dim', 80)):
             raise NotImplementedError('recognize: log_mel_spectrogram must be n_fft 400 / '
                                       'hop_length 160 with input_dim mel bins')
-    elif feats_type != 'fbank':
+    elif feats_type not in ('fbank', 'w2vbert_fbank'):
         raise NotImplementedError('recognize: fbank or log_mel_spectrogram features only')
     else:
-        fc = dc.get('fbank_conf', {})
+        # (w2vbert_fbank: the same Kaldi fbank, normalised per utterance behind it)
+        fc = dc.get(feats_type + '_conf', {})
         if (fc.get('num_mel_bins', 80) != configs.get('input_dim', 80)
                 or fc.get('frame_length', 25) != 25 or fc.get('frame_shift', 10) != 10):
             raise NotImplementedError('recognize: fbank must be 25 ms / 10 ms frames with '
@@ -251,7 +253,11 @@ def feature_function(model, configs: dict):
         return lambda waves: model.compute_log_mel_spectrogram(waves, **kw), None
     # Kaldi fbank, snip_edges: frames of a waveform are known from its length, so a batch can
     # be put into `padding`'s order BEFORE the features are computed (no device-side reorder)
-    return model.compute_fbank, lambda n: 0 if n < 400 else 1 + (n - 400) // 160
+    def frames_of(n):
+        return 0 if n < 400 else 1 + (n - 400) // 160
+    if dc.get('feats_type', 'fbank') == 'w2vbert_fbank':
+        return model.compute_w2vbert_fbank, frames_of
+    return model.compute_fbank, frames_of
 
 
 def format_line(key: str, text: str) -> str:

@@ -195,7 +195,10 @@ int encode_shaw(wn_model* m, const float* feats_dev, const int32_t* feat_lens_ho
     max_len = std::max(max_len, len[b]);
     if (enc_lens_host) enc_lens_host[b] = len[b];
   }
-  WN_TRY(set_layout(m, B, Tp, off, len, M, s));
+  // raw fbank in (wn_model_set_utt_norm_input): the frame counts travel with the layout
+  const bool utt = m->sh.utt_input;
+  WN_TRY(set_layout(m, B, Tp, off, len, M, s, utt ? B + 16 : 0));
+  if (utt) WN_TRY(m->stage.put(m->utt_len, feat_lens_host, (size_t)B * sizeof(int32_t), s));
   WN_TRY(m->stage.end(s));
   if (M > 0) {
     const int hid = std::max(c.ffn_dim, 2 * d);
@@ -211,7 +214,18 @@ int encode_shaw(wn_model* m, const float* feats_dev, const int32_t* feat_lens_ho
     a.out = m->c2.as<float>(); a.ldo = 2 * F;
     a.off = m->d_off.as<int>(); a.len = m->d_len.as<int>();
     a.B = B; a.T = T; a.F = F; a.max_len = max_len; a.eps = 1e-5f;
-    WN_TRY(stack_frames_ln(a, s));
+    if (utt) {
+      // statistics over every frame of the utterance (the one an odd length drops included), the
+      // division inside the front end: no normalised tensor in HBM
+      int max_frames = 0;
+      for (int b = 0; b < B; ++b) max_frames = std::max(max_frames, (int)feat_lens_host[b]);
+      WN_TRY(utt_stats_handle(m, feats_dev, max_frames, B, T, F, s));
+      StackFramesUttArgs ua;
+      ua.k = a; ua.umean = m->utt_mean.as<float>(); ua.ustd = m->utt_std.as<float>();
+      WN_TRY(stack_frames_ln_utt(ua, s));
+    } else {
+      WN_TRY(stack_frames_ln(a, s));
+    }
     // Linear(2 F -> d); NoPositionalEncoding: no xscale, x unchanged
     WN_TRY(linear(W.sub_out, m->c2.as<float>(), 2 * F, m->x.as<float>(), d, M, s));
     WN_TRY(encoder_layers_shaw(m, s));

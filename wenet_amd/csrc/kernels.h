@@ -1025,6 +1025,39 @@ struct StackFramesArgs {
 };
 int stack_frames_ln(const StackFramesArgs& a, hipStream_t s);
 
+// ---- utterance-normalised fbank (utt_norm.hip), fp32 ----------------------------------------
+// compute_w2vbert_fbank (dataset/processor.py:259-272): per utterance and per mel bin,
+// std, mean = torch.std_mean(mat, dim=0) over the utterance's len[b] frames (unbiased: M2 / (n -
+// 1)), then (mat - mean) / std.  utt_stats: one block per slab of UTT_SLAB frames of one utterance
+// writes three numbers per bin to ws [B][n_slab][3][F] -- the slab's mean, and Welford's (mean, M2)
+// of the values less the utterance's first frame; the count of a slab follows from len[b] and the
+// slab index.  The finish merges an utterance's slabs in index order into mean / std [B][F]; an
+// utterance of fewer than 2 frames writes nothing.
+constexpr int UTT_SLAB = 128;
+struct UttStatsArgs {
+  const float* feats;     // (B, T, F) padded
+  const int* len;         // [B] frames of the utterance (device)
+  float* ws;              // [B][n_slab][3][F]
+  float* mean; float* std;   // [B][F]
+  int B, T, F, n_slab;    // n_slab = cdiv(longest length, UTT_SLAB)
+};
+int utt_stats(const UttStatsArgs& a, hipStream_t s);
+// out[b][t][f] = (feats[b][t][f] - mean[b][f]) / std[b][f] for t < len[b], 0 behind it (a true
+// division: a constant bin gives the reference's 0 / 0).  The one frame of a len[b] == 1
+// utterance is NaN, the reference's value (the unbiased std of one frame), without a read of
+// its statistics row.  out may be feats.  F % 4 == 0, 16-byte aligned pointers.
+int utt_normalize(const float* feats, const int* len, const float* mean, const float* std,
+                  float* out, int B, int T, int F, hipStream_t s);
+// stack_frames_ln on RAW features with the utterance's statistics rows: (x - umean[b][f]) /
+// ustd[b][f], then the optional GlobalCMVN (mean / istd [F]), then the LayerNorm over 2 F values.
+// The statistics cover every frame of the utterance, the one an odd length drops included.
+struct StackFramesUttArgs {
+  StackFramesArgs k;      // as stack_frames_ln
+  const float* umean;     // [B][F]
+  const float* ustd;      // [B][F]
+};
+int stack_frames_ln_utt(const StackFramesUttArgs& a, hipStream_t s);
+
 // LFR front end (paraformer/layers.py:24-92 on ONE utterance, paraformer.py:329-350): output row
 // t of utterance b stacks the m frames n t - (m - 1) / 2 + f, f < m, each index clamped to
 // [0, len[b] - 1]; then GlobalCMVN over the m F columns, x * xscale + pe[t + 1], and the

@@ -344,6 +344,9 @@ struct wn_model {
   struct {
     bool on = false;
     wn_shaw_config c = {};
+    // wn_model_set_utt_norm_input: wn_encode takes RAW fbank, computes the utterance statistics
+    // (utt_norm.hip) and normalises inside the stacked-frame front end
+    bool utt_input = false;
   } sh;
   // wn_model_create_branchformer: a Branchformer (kind 1) / E-Branchformer (kind 2) encoder
   // (cabi_branchformer.hip) behind the Conformer front end
@@ -509,6 +512,8 @@ struct wn_model {
   std::shared_ptr<DevBuf> ctx_buf;
   CtxGraph ctx;
   DevBuf fb_off, fb_nfr;
+  // utterance normalisation (cabi_utt_norm.hip): frame counts, slab partials, mean / std [B][F]
+  DevBuf utt_len, utt_ws, utt_mean, utt_std;
 
   int F1() const { return (cfg.feat_dim - 1) / 2; }
   // conv2's output width: Conv2dSubsampling4 (3 x 3, stride 2) / Conv2dSubsampling6 (5 x 5, stride 3)
@@ -654,6 +659,10 @@ int shaw_stage(const wn::Src& src, wn::HostStage& hs, const wn_config& c);
 int shaw_bind(ModelData& W, const wn_config& c);
 int encode_shaw(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
                 float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
+// (cabi_utt_norm.hip) statistics of the padded batch into m->utt_mean / m->utt_std; m->utt_len
+// already holds the B frame counts (none above T), max_len is the largest of them
+int utt_stats_handle(wn_model* m, const float* feats_dev, int max_len, int B, int T, int F,
+                     hipStream_t s);
 // (cabi_branchformer.hip)
 int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,

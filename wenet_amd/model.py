@@ -983,6 +983,27 @@ class ASRModel:
                              _stream_ptr(self.device)), 'wn_fbank')
         return feats, torch.from_numpy(n_frames.copy())
 
+    def compute_w2vbert_fbank(self, waveforms: List[np.ndarray],
+                              num_mel_bins: Optional[int] = None, dither: float = 0.0
+                              ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """processor.compute_w2vbert_fbank (processor.py:259-272) + padding: compute_fbank, then
+        per utterance and mel bin `std, mean = torch.std_mean(mat, dim=0)` (unbiased) and
+        `(mat - mean) / std`, on the device (wn_utt_normalize), in place -> ((B, Tmax, F)
+        features in HBM, lengths).  Padding frames are zeros."""
+        F = self._cfg.feat_dim
+        if num_mel_bins is not None and num_mel_bins != F:
+            raise NotImplementedError(f'w2vbert_fbank: num_mel_bins must be input_dim ({F})')
+        if dither != 0.0:
+            raise NotImplementedError('w2vbert_fbank: dither 0.0 only (as compute_fbank)')
+        feats, lens = self.compute_fbank(waveforms)
+        B, T, _ = feats.shape
+        _lib.check(
+            self._L.wn_utt_normalize(self._h, feats.data_ptr(),
+                                     _lib.i32p(lens.numpy().astype(np.int32)), B, T, F,
+                                     feats.data_ptr(), _stream_ptr(self.device)),
+            'wn_utt_normalize')
+        return feats, lens
+
     def compute_log_mel_spectrogram(self, waveforms: List[np.ndarray],
                                     num_mel_bins: int = 80, padding: int = 0,
                                     pad_or_trim: bool = False,
@@ -1038,12 +1059,19 @@ class ASRModel:
     def compute_feature(self, wav_file: str) -> torch.Tensor:
         """cli/model.py:47-66 (load_feature): decode_wav -> resample -> the
         feature function `dataset_conf.feats_type` names with its `<type>_conf`
-        -- `fbank` (default) or `log_mel_spectrogram` (the Whisper recipes);
-        `mfcc` is not on this path."""
+        -- `fbank` (default), `w2vbert_fbank` (the W2v-BERT 2.0 family) or
+        `log_mel_spectrogram` (the Whisper recipes); `mfcc` is not on this path."""
         dc = self.configs.get('dataset_conf') or {}
         feats_type = dc.get('feats_type', 'fbank')
         if feats_type == 'fbank':
             feats, lens = self.compute_fbank([self.load_wav(wav_file)])
+        elif feats_type == 'w2vbert_fbank':
+            conf = dc.get('w2vbert_fbank_conf') or {}
+            if conf.get('frame_length', 25) != 25 or conf.get('frame_shift', 10) != 10:
+                raise NotImplementedError('w2vbert_fbank: 25 ms / 10 ms frames only')
+            feats, lens = self.compute_w2vbert_fbank(
+                [self.load_wav(wav_file)], num_mel_bins=conf.get('num_mel_bins', 80),
+                dither=conf.get('dither', 0.0))
         elif feats_type == 'log_mel_spectrogram':
             conf = dc.get('log_mel_spectrogram_conf') or {}
             if conf.get('n_fft', 400) != 400 or conf.get('hop_length', 160) != 160:

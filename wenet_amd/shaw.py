@@ -152,6 +152,17 @@ class ShawConformer(ASRModel):
                 "encoder stays 'fp32'")
         return super().set_compute_dtype(dtype)
 
+    def set_raw_fbank_input(self, on: bool = True) -> 'ShawConformer':
+        """on: every entry that takes features (decode, align, _forward_encoder) takes RAW Kaldi
+        fbank (`compute_fbank`), and the encoder normalises it per utterance as
+        processor.compute_w2vbert_fbank does -- statistics in a pass of their own, the division
+        inside the stacked-frame front end, no normalised tensor in HBM
+        (wn_model_set_utt_norm_input).  Off (the default): features as the reference's model
+        takes them, e.g. from `compute_w2vbert_fbank` / `compute_feature`."""
+        _lib.check(self._L.wn_model_set_utt_norm_input(self._h, int(bool(on))),
+                   'wn_model_set_utt_norm_input')
+        return self
+
     def subsampling_rate(self) -> int:    # StackNFramesSubsampling: stride 2
         return STACK
 

@@ -744,6 +744,11 @@ def _shaw(d, heads, ffn, blocks, dec_conf: dict, vocab: int) -> dict:
 # the test model: a decoder of 2 heads of 64, and (make_configs) a global CMVN as a fine-tune has
 CONFIGS['tiny_shaw'] = _shaw(128, 2, 256, 2, dict(attention_heads=2, linear_units=96,
                                                   num_blocks=2), 41)
+# tiny_shaw fed from audio: the family's feature recipe, compute_w2vbert_fbank (processor.py:259-272)
+CONFIGS['tiny_shaw_w2vbert'] = dict(CONFIGS['tiny_shaw'], dataset_conf={
+    'resample_conf': {'resample_rate': 16000}, 'feats_type': 'w2vbert_fbank',
+    'w2vbert_fbank_conf': {'num_mel_bins': 80, 'frame_shift': 10, 'frame_length': 25,
+                           'dither': 0.0}})
 # the 600 M encoder at the converter's widths (no CMVN, its "dummy decoder" of 4 heads of 256)
 CONFIGS['w2vbert_600m'] = dict(_shaw(1024, 16, 4096, 24, dict(attention_head=16,
                                                               linear_units=4096, num_blocks=6),
