@@ -797,6 +797,24 @@ int wn_op_attention_shaw(const float* Q, const float* K, const float* V, int32_t
                          const int32_t* off, const int32_t* len, int32_t n_seq, int32_t n_heads,
                          float scale, int32_t mask_mode, const float* kbias, const int32_t* p_off,
                          const int32_t* blk_tab, int32_t bf16_flags, void* stream);
+/* Self attention with rotary position embedding and grouped key / value heads
+ * (RopeMultiHeadedAttention with n_kv_head; csrc/attention_rope.hip), fp32, d_k = 64:
+ *   score(i, j) = rot(q_i, i) . rot(k_j, j) * scale,  rot(x, t) = [x1 c_t - x2 s_t | x1 s_t + x2 c_t]
+ * (x1 = x[0:32], x2 = x[32:64]; V is not rotated), i / j the frame index inside the sequence,
+ * softmax over the keys the mask leaves.  Q / O [rows][ld*] with n_heads * 64 columns, K / V with
+ * n_kv_heads * 64; query head h reads K / V head h / (n_heads / n_kv_heads).  tab [max_pos][64]
+ * contiguous, cos[32] | sin[32] per position.  off / len host [n_seq] (ascending, disjoint; a
+ * length may be 0, none may exceed max_pos).  mask_mode 0: keys < len; 2: the chunk window of
+ * wn_op_attention (chunk_size, left_chunks).  mask_mode 1, kbias, p_off, blk_tab and bf16_flags
+ * must be absent / NULL / 0: the kernel has none of them and refuses each by name, as it refuses
+ * n_heads % n_kv_heads != 0, a short or unaligned stride and an unaligned pointer. */
+int wn_op_attention_rope(const float* Q, const float* K, const float* V, int32_t ldq, int32_t ldk,
+                         int32_t ldv, int32_t rows, const float* tab, int32_t max_pos, float* O,
+                         int32_t ldo, const int32_t* off, const int32_t* len, int32_t n_seq,
+                         int32_t n_heads, int32_t n_kv_heads, float scale, int32_t mask_mode,
+                         int32_t chunk_size, int32_t left_chunks, const float* kbias,
+                         const int32_t* p_off, const int32_t* blk_tab, int32_t bf16_flags,
+                         void* stream);
 /* StackNFramesSubsampling (stride 2) up to its projection (csrc/attention_shaw.hip): feats (B, T,
  * F), F <= 128; GlobalCMVN per frame (mean NULL: none); output row out_off[b] + t, t < out_len[b]
  * = lens[b] / 2 (host [B], written), = LayerNorm over the 2 F values of frames 2 t | 2 t + 1 (ln_w,
@@ -1286,6 +1304,30 @@ typedef struct {
  * rescoring entry points then work on the encoder output unchanged.  wn_encode_chunk*,
  * wn_stream_create, wn_op_conv2d4 and a bf16 / fp8 precision are refused on such a handle. */
 int wn_model_create_shaw(const wn_config* cfg, const wn_shaw_config* hcfg,
+                         const wn_tensor* weights, int32_t n_weights, int32_t device,
+                         wn_model** out);
+
+/* Rotary Conformer encoders (`encoder: conformer` with selfattention_layer_type
+ * rope_abs_selfattn, pos_enc_layer_type rope_pos, optionally n_kv_head / head_dim) under the
+ * asr_model head: the conv2d front end, x * sqrt(d) with nothing added, and self attention whose
+ * queries and keys are rotated by their frame index, with n_kv_heads key / value heads shared by
+ * groups of query heads.  A struct and an entry point of their own: wn_config and
+ * wn_model_create are unchanged. */
+typedef struct {
+  int32_t n_kv_heads;         /* n_kv_head, or attention_heads when the recipe has none */
+  int32_t head_dim;           /* 64 */
+  int32_t max_pos;            /* rows of the rotation table: 3000 (RopePositionalEncoding) */
+} wn_rope_config;
+
+/* wn_model_create for such a state dict (no linear_pos / pos_bias_u / pos_bias_v; linear_k /
+ * linear_v of [64 n_kv_heads][d]; the checkpoint's encoder.embed.pos_enc.pe [1][max_pos][32][2],
+ * (cos, sin), passed under the name encoder.embed.pos_enc.rope_pe, from which the table is staged).  cfg: encoder_type 0, input_layer 0, d_model = n_heads * 64,
+ * cnn_norm, causal, use_dynamic_chunk and static_chunk_size as the recipe has them.  On the
+ * handle wn_encode runs the front end and the layers in fp32, chunk / left as on a classic
+ * Conformer handle; an utterance with more than max_pos encoder frames is refused.  The CTC entry
+ * points, the alignment and the rescoring entry points then work on the encoder output
+ * unchanged.  wn_encode_chunk*, wn_stream_create and a bf16 / fp8 precision are refused. */
+int wn_model_create_rope(const wn_config* cfg, const wn_rope_config* rcfg,
                          const wn_tensor* weights, int32_t n_weights, int32_t device,
                          wn_model** out);
 

@@ -7,7 +7,7 @@ The compute path is hand-written HIP for gfx950 in ``libwenet_amd.so`` (C-ABI in
 include/wenet_amd.h); it is loaded lazily and there is NO CPU fallback: using a
 model without the library raises.
 """
-__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "EfficientConformer", "Paraformer", "SenseVoiceSmall", "ShawConformer", "DecodeResult", "StreamingRecognizer",
+__all__ = ["load_model", "ASRModel", "Transducer", "FireRed", "Branchformer", "Squeezeformer", "EfficientConformer", "Paraformer", "SenseVoiceSmall", "ShawConformer", "RopeConformer", "DecodeResult", "StreamingRecognizer",
            "RnntBeamStreamingRecognizer", "CtcEndpointConfig", "CtcEndpointRule", "AlignResult", "force_align",
            "force_align_batch"]
 
@@ -34,6 +34,9 @@ def __getattr__(name):
     if name == "ShawConformer":
         from wenet_amd.shaw import ShawConformer
         return ShawConformer
+    if name == "RopeConformer":
+        from wenet_amd.rope import RopeConformer
+        return RopeConformer
     if name == "Squeezeformer":
         from wenet_amd.squeezeformer import Squeezeformer
         return Squeezeformer

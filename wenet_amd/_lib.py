@@ -48,6 +48,11 @@ class WnShawConfig(Structure):
     _fields_ = [(n, c_int32) for n in ('max_left', 'max_right', 'stack')]
 
 
+class WnRopeConfig(Structure):
+    """wn_rope_config: what a rotary Conformer encoder has on top of wn_config."""
+    _fields_ = [(n, c_int32) for n in ('n_kv_heads', 'head_dim', 'max_pos')]
+
+
 class WnBranchformerConfig(Structure):
     """wn_branchformer_config: what a Branchformer / E-Branchformer encoder has on top of
     wn_config."""
@@ -197,6 +202,7 @@ EXPORTS = [
     'wn_model_encoder_head_cols',
     'wn_model_create_sensevoice', 'wn_sensevoice_set_queries', 'wn_op_sv_front',
     'wn_model_create_shaw', 'wn_op_attention_shaw', 'wn_op_stack_frames_ln',
+    'wn_model_create_rope', 'wn_op_attention_rope',
     'wn_utt_normalize', 'wn_model_set_utt_norm_input', 'wn_op_utt_stats',
     'wn_op_stack_frames_ln_utt',
 ]
@@ -397,6 +403,11 @@ def lib():
     # feats umean ustd mean istd ln_w ln_b out | ldo out_rows | lens out_off out_len | B T F
     L.wn_op_stack_frames_ln_utt.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, pi32, pi32,
                                             pi32, i32, i32, i32, vp]
+    L.wn_model_create_rope.argtypes = [POINTER(WnConfig), POINTER(WnRopeConfig),
+                                       POINTER(WnTensor), i32, i32, POINTER(vp)]
+    L.wn_op_attention_rope.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, pi32,
+                                       pi32, i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, i32,
+                                       vp]
     L.wn_model_create_branchformer.argtypes = [POINTER(WnConfig), POINTER(WnBranchformerConfig),
                                                POINTER(WnTensor), i32, i32, POINTER(vp)]
     L.wn_op_csgu_gate.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, pi32,

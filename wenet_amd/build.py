@@ -29,7 +29,8 @@ SOURCES = ['gemm.hip', 'gemm_bf16.hip', 'gemm_bf16s.hip', 'gemm_bf16p.hip', 'gem
            'efficonformer.hip', 'cabi_efficonformer.hip',
            'attention_d128.hip', 'paraformer.hip', 'cabi_paraformer.hip',
            'attention_d32.hip', 'attention_d32_relpos.hip', 'sensevoice.hip', 'cabi_sensevoice.hip',
-           'attention_shaw.hip', 'cabi_shaw.hip', 'utt_norm.hip', 'cabi_utt_norm.hip']
+           'attention_shaw.hip', 'cabi_shaw.hip', 'utt_norm.hip', 'cabi_utt_norm.hip',
+           'attention_rope.hip', 'cabi_rope.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
          '-fno-gpu-rdc', '-Wno-unused-result']
 # WN_ABLATION=1 python -m wenet_amd.build: a MEASUREMENT build that also compiles the kernel

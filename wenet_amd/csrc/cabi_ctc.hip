@@ -533,6 +533,7 @@ int wn_stream_create(wn_model* m, int32_t n_slots, int32_t beam, int32_t max_fra
   WN_CHECK(m && out, "wn_stream_create: null argument");
   WN_CHECK(!m->fr.on, "wn_stream_create: the FireRed encoder does not stream");
   WN_CHECK(!m->sh.on, "wn_stream_create: a W2v-BERT (shaw) encoder does not stream");
+  WN_CHECK(!m->rp.on, "wn_stream_create: a rotary Conformer encoder does not stream");
   WN_CHECK(!m->bf.on, "wn_stream_create: a Branchformer encoder does not stream");
   WN_CHECK(!m->sq.on, "wn_stream_create: a Squeezeformer encoder does not stream");
   WN_CHECK(!m->ef.on, "wn_stream_create: an Efficient Conformer encoder does not stream");

@@ -113,6 +113,13 @@ int wn_encode(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host
     return encode_shaw(m, feats_dev, feat_lens_host, B, T, enc_out_dev, enc_lens_host,
                        (hipStream_t)stream);
   }
+  if (m->rp.on) {
+    WN_CHECK(m->prec == PREC_F32, "wn_encode: a rotary Conformer handle stays fp32");
+    WN_CHECK(T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
+    WN_HIP(hipSetDevice(m->device));
+    return encode_rope(m, feats_dev, feat_lens_host, B, T, chunk, left, enc_out_dev,
+                       enc_lens_host, (hipStream_t)stream);
+  }
   if (m->bf.on) {
     WN_CHECK(m->prec == PREC_F32, "wn_encode: a Branchformer handle stays fp32");
     WN_CHECK(T >= 7, "wn_encode: at least 7 frames are needed by Conv2dSubsampling4");
@@ -187,6 +194,8 @@ int wn_encode_chunk_batch(wn_model* m, int32_t n_sess, const float* feats_dev, i
   WN_CHECK(!m->fr.on, "wn_encode_chunk: the FireRed encoder does not stream");
   WN_CHECK(!m->sh.on, "wn_encode_chunk: no chunk-by-chunk path for a W2v-BERT (shaw) encoder (the "
                       "Shaw attention's key / value cache)");
+  WN_CHECK(!m->rp.on, "wn_encode_chunk: no chunk-by-chunk path for a rotary Conformer encoder "
+                      "(the table at an offset, the key / value cache)");
   WN_CHECK(!m->bf.on, "wn_encode_chunk: no chunk-by-chunk path for a Branchformer encoder (the "
                       "cgMLP conv cache)");
   WN_CHECK(!m->sq.on, "wn_encode_chunk: no chunk-by-chunk path for a Squeezeformer encoder (the "

@@ -82,6 +82,7 @@ const char* wn_version(void) { return "wenet_amd 0.1 (gfx950, fp32 MFMA)"; }
 // wn_model_create_branchformer (bcfg != nullptr, cabi_branchformer.hip)
 // wn_model_create_squeezeformer (qcfg != nullptr, cabi_squeezeformer.hip)
 // wn_model_create_shaw (hcfg != nullptr, cabi_shaw.hip)
+// wn_model_create_rope (rcfg != nullptr, cabi_rope.hip)
 }  // extern "C"
 
 int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
@@ -90,7 +91,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                          const wn_squeezeformer_config* qcfg,
                          const wn_efficonformer_config* ecfg, const wn_tensor* weights,
                          int32_t n_weights, int32_t device, wn_model** out,
-                         const wn_shaw_config* hcfg) {
+                         const wn_shaw_config* hcfg, const wn_rope_config* rcfg) {
   WN_CHECK(cfg && weights && out, "wn_model_create: null argument");
   const wn_config& c = *cfg;
   const bool fr = fcfg != nullptr;
@@ -161,6 +162,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (ef) WN_TRY(efficonformer_config_check(c, *ecfg, tcfg || fr || bf || sq));
   const bool sh = hcfg != nullptr;
   if (sh) WN_TRY(shaw_config_check(c, *hcfg, tcfg || fr || bf || sq || ef));
+  const bool rp = rcfg != nullptr;
+  if (rp) WN_TRY(rope_config_check(c, *rcfg, tcfg || fr || bf || sq || ef || sh));
   WN_CHECK(c.d_model % 64 == 0 && c.n_heads > 0 && (bf || ef || c.d_model / c.n_heads == 64),
            "d_model / n_heads must be 64 (all reference Conformer configs)");
   WN_CHECK(c.dec_layers == 0 || c.dec_heads == 0 ||
@@ -196,6 +199,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   if (sq) { m->sq.on = true; m->sq.c = *qcfg; }
   if (ef) { m->ef.on = true; m->ef.c = *ecfg; }
   if (sh) { m->sh.on = true; m->sh.c = *hcfg; }
+  if (rp) { m->rp.on = true; m->rp.c = *rcfg; }
   // the block this call fills; the handle (and every clone of it) sees it as const
   const std::shared_ptr<ModelData> data = std::make_shared<ModelData>();
   m->data = data;
@@ -334,7 +338,9 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     float* t = hs.alloc("pe", (size_t)c.max_pos * d);
     WN_CHECK(!tf || src.has("encoder.embed.pos_enc.pe"),
              "transformer encoder: encoder.embed.pos_enc.pe is required");
-    if (src.has("encoder.embed.pos_enc.pe")) {
+    // (rope: that buffer is the rotation table, staged by rope_stage; the sinusoid below serves
+    // the decoders)
+    if (!rp && src.has("encoder.embed.pos_enc.pe")) {
       WN_GET(pe, "encoder.embed.pos_enc.pe", (int64_t)c.max_pos * d);
       memcpy(t, pe, sizeof(float) * c.max_pos * d);
     } else {
@@ -648,7 +654,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   if (ef) WN_TRY(efficonformer_stage_layers(src, hs, c, *ecfg));   // (cabi_efficonformer.hip)
   if (sh) WN_TRY(shaw_stage(src, hs, c));                          // (cabi_shaw.hip)
-  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && i < c.n_layers; ++i) {
+  if (rp) WN_TRY(rope_stage(src, hs, c, *rcfg));                   // (cabi_rope.hip)
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && !rp && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     for (const char* n : {"norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff",
                           "norm_final"})
@@ -964,11 +971,13 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
     WN_TRY(efficonformer_bind(W, c, *ecfg));   // (cabi_efficonformer.hip)
   } else if (sh) {
     WN_TRY(shaw_bind(W, c));                   // (cabi_shaw.hip)
+  } else if (rp) {
+    WN_TRY(rope_bind(W, c, *rcfg));            // (cabi_rope.hip)
   } else {
     W.layers.resize(c.n_layers);
     WN_TRY(W.pos_tabs.ensure((size_t)c.n_layers * c.max_pos * d * sizeof(float)));
   }
-  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && i < c.n_layers; ++i) {
+  for (int i = 0; !tf && !fr && !bf && !sq && !ef && !sh && !rp && i < c.n_layers; ++i) {
     const std::string p = "encoder.encoders." + std::to_string(i);
     EncLayer& L = W.layers[i];
     L.norm_ff_mac = NORM(p + ".norm_ff_macaron");
@@ -1053,7 +1062,7 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
   }
   // (firered, branchformer, squeezeformer: the plain fp32 path, no six-product / row-block images of the
   // encoder's weights; the decoders and the CTC head get theirs as in every other model)
-  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq || ef || sh));
+  WN_TRY(build_x6_images(c, W, /*skip_encoder=*/fr || bf || sq || ef || sh || rp));
   WN_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -1095,6 +1104,7 @@ int wn_model_clone(const wn_model* src, wn_model** out) {
   m->sq.on = src->sq.on; m->sq.c = src->sq.c;
   m->ef.on = src->ef.on; m->ef.c = src->ef.c;
   m->sh.on = src->sh.on; m->sh.c = src->sh.c;
+  m->rp.on = src->rp.on; m->rp.c = src->rp.c;
   m->pf.on = src->pf.on; m->pf.c = src->pf.c;
   m->sv.on = src->sv.on; m->sv.c = src->sv.c;
   m->device = src->device;
@@ -1125,6 +1135,9 @@ int wn_model_set_precision(wn_model* m, int32_t precision) {
            "kernels for its encoder)");
   WN_CHECK(!m->sh.on || precision == PREC_F32,
            "wn_model_set_precision: a W2v-BERT (shaw) handle stays fp32 (no bf16 / fp8 kernels "
+           "for its encoder)");
+  WN_CHECK(!m->rp.on || precision == PREC_F32,
+           "wn_model_set_precision: a rotary Conformer handle stays fp32 (no bf16 / fp8 kernels "
            "for its encoder)");
   WN_CHECK(!m->pf.on || precision == PREC_F32,
            "wn_model_set_precision: a Paraformer handle stays fp32 (no bf16 / fp8 kernels for its "

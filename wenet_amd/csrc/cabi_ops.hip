@@ -1035,6 +1035,43 @@ int wn_op_attention_shaw(const float* Q, const float* K, const float* V, int32_t
   return attention_shaw(a, s);
 }
 
+int wn_op_attention_rope(const float* Q, const float* K, const float* V, int32_t ldq, int32_t ldk,
+                         int32_t ldv, int32_t rows, const float* tab, int32_t max_pos, float* O,
+                         int32_t ldo, const int32_t* off, const int32_t* len, int32_t n_seq,
+                         int32_t n_heads, int32_t n_kv_heads, float scale, int32_t mask_mode,
+                         int32_t chunk_size, int32_t left_chunks, const float* kbias,
+                         const int32_t* p_off, const int32_t* blk_tab, int32_t bf16_flags,
+                         void* stream) {
+  WN_CHECK(Q && K && V && tab && O && off && len, "attention_rope: null argument");
+  WN_CHECK(n_seq > 0 && n_seq < 32768 && n_heads > 0 && n_heads < 256 && n_kv_heads > 0,
+           "attention_rope: n_seq / n_heads / n_kv_heads");
+  WN_CHECK(rows > 0 && max_pos > 0, "attention_rope: empty buffers");
+  WN_CHECK(packed_ok(off, len, n_seq, rows),
+           "attention_rope: rows outside the buffer, unordered or overlapping");
+  int max_len = 0;
+  std::vector<int> h((size_t)2 * n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    h[i] = off[i]; h[n_seq + i] = len[i];
+    max_len = std::max(max_len, len[i]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local DevBuf desc;
+  WN_TRY(upload_ints(desc, h, s));
+  RopeAttnArgs ra;
+  ra.n_kv_heads = n_kv_heads; ra.max_pos = max_pos;
+  AttnArgs& a = ra.a;
+  a.Q = Q; a.K = K; a.V = V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.P = tab; a.ldp = 64; a.O = O; a.ldo = ldo;
+  a.q_off = a.kv_off = desc.as<int>(); a.q_len = a.kv_len = a.q_off + n_seq;
+  a.n_seq = n_seq; a.n_heads = n_heads; a.max_q_len = max_len; a.scale = scale;
+  a.mask_mode = mask_mode; a.chunk_size = chunk_size; a.left_chunks = left_chunks;
+  // what the kernel does not have goes through to its own refusals
+  a.kbias = kbias; a.p_off = p_off;
+  a.blk_tab = blk_tab; a.n_blk = blk_tab ? 1 : 0;
+  a.o_bf16 = (bf16_flags & 1) != 0; a.qkv_bf16 = (bf16_flags & 2) != 0;
+  return attention_rope(ra, s);
+}
+
 int wn_op_stack_frames_ln(const float* feats, const float* mean, const float* istd,
                           const float* ln_w, const float* ln_b, float* out, int32_t ldo,
                           int32_t out_rows, const int32_t* lens, const int32_t* out_off,

@@ -1010,6 +1010,21 @@ int attention_d32_relpos(const AttnArgs& a, hipStream_t s);
 constexpr int SHAW_LEFT = 64, SHAW_RIGHT = 8, SHAW_ROWS = SHAW_LEFT + SHAW_RIGHT + 1;
 int attention_shaw(const AttnArgs& a, hipStream_t s);
 
+// ---- rotary Conformer encoders (attention_rope.hip), fp32 -----------------------------------
+// SELF attention for heads of d_k = 64 with rotary position embedding and grouped K / V heads:
+// score rot(q_i, i) . rot(k_j, j) * scale, rot the reference's google_apply_rotary_emb, i / j the
+// frame index inside the sequence.  a.Q [rows][ldq >= n_heads * 64]; a.K / a.V [rows][ld >=
+// n_kv_heads * 64], query head h reads K / V head h / (n_heads / n_kv_heads); a.P is the table
+// [max_pos][ldp >= 64], cos[32] | sin[32] per position; bias_u / bias_v stay null.  mask_mode 0 or
+// 2; kbias, p_off, block lists and the bf16 flags are refused.  Always fp32.  An args struct of
+// its own: AttnArgs, and with it every other launch, is what it was.
+struct RopeAttnArgs {
+  AttnArgs a;
+  int n_kv_heads = 0;     // 0: = a.n_heads
+  int max_pos = 0;        // rows of the table
+};
+int attention_rope(const RopeAttnArgs& a, hipStream_t s);
+
 // StackNFramesSubsampling (stride 2) up to its projection: output row off[b] + t of utterance b =
 // LayerNorm_{2F}(CMVN(frame 2 t) | CMVN(frame 2 t + 1)), t < len[b] (= feature length / 2).
 struct StackFramesArgs {

@@ -269,6 +269,7 @@ struct ModelData {
   const float* conv1_w = nullptr; const float* conv1_b = nullptr;
   Linear conv2, sub_out;
   Norm stack_norm;                      // StackNFramesSubsampling's LayerNorm(2 F) (sh.on)
+  const float* rope_tab = nullptr;      // [rp.c.max_pos][64] cos[32] | sin[32] (rp.on)
   const float* cmvn_mean = nullptr; const float* cmvn_istd = nullptr;
   const float* pe = nullptr;
   Norm after_norm;
@@ -348,6 +349,13 @@ struct wn_model {
     // (utt_norm.hip) and normalises inside the stacked-frame front end
     bool utt_input = false;
   } sh;
+  // wn_model_create_rope: a rotary Conformer encoder (cabi_rope.hip); data->layers hold Conformer
+  // shapes without bias_u / bias_v / pos_w / pos_tab and a QKV projection (n_heads + 2
+  // n_kv_heads) * 64 wide; data->rope_tab is the rotation table
+  struct {
+    bool on = false;
+    wn_rope_config c = {};
+  } rp;
   // wn_model_create_branchformer: a Branchformer (kind 1) / E-Branchformer (kind 2) encoder
   // (cabi_branchformer.hip) behind the Conformer front end
   struct {
@@ -663,6 +671,12 @@ int encode_shaw(wn_model* m, const float* feats_dev, const int32_t* feat_lens_ho
 // already holds the B frame counts (none above T), max_len is the largest of them
 int utt_stats_handle(wn_model* m, const float* feats_dev, int max_len, int B, int T, int F,
                      hipStream_t s);
+// (cabi_rope.hip)
+int rope_config_check(const wn_config& c, const wn_rope_config& r, bool other_family);
+int rope_stage(const wn::Src& src, wn::HostStage& hs, const wn_config& c, const wn_rope_config& r);
+int rope_bind(ModelData& W, const wn_config& c, const wn_rope_config& r);
+int encode_rope(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B, int T,
+                int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);
 // (cabi_branchformer.hip)
 int encode_branchformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                         int T, int chunk, int left, float* enc_out_dev, int32_t* enc_lens_host,
@@ -700,7 +714,8 @@ int create_model_impl(const wn_config* cfg, const wn_transducer_config* tcfg,
                       const wn_branchformer_config* bcfg, const wn_squeezeformer_config* qcfg,
                       const wn_efficonformer_config* ecfg, const wn_tensor* weights,
                       int32_t n_weights, int32_t device, wn_model** out,
-                      const wn_shaw_config* hcfg = nullptr);
+                      const wn_shaw_config* hcfg = nullptr,
+                      const wn_rope_config* rcfg = nullptr);
 // (model.hip)
 int encode_transformer(wn_model* m, const float* feats_dev, const int32_t* feat_lens_host, int B,
                        int T, float* enc_out_dev, int32_t* enc_lens_host, hipStream_t s);

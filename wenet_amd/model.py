@@ -59,6 +59,10 @@ def config_from_yaml(configs: dict) -> _lib.WnConfig:
         # (wenet_amd/shaw.py: the W2v-BERT 2.0 recipe, its own keys go into a wn_shaw_config)
         from wenet_amd.shaw import shaw_config_from_yaml
         return shaw_config_from_yaml(configs)[0]
+    if enc_type == 'conformer' and ec.get('selfattention_layer_type') == 'rope_abs_selfattn':
+        # (wenet_amd/rope.py: rotary attention, its own keys go into a wn_rope_config)
+        from wenet_amd.rope import rope_config_from_yaml
+        return rope_config_from_yaml(configs)[0]
     if enc_type == 'conformer':
         checks = dict(input_layer='conv2d', pos_enc_layer_type='rel_pos',
                       selfattention_layer_type='rel_selfattn',
@@ -341,6 +345,12 @@ class ASRModel:
             raise NotImplementedError(
                 "selfattention_layer_type 'shaw_rel_selfattn' is outside the accelerated path of "
                 'this class: wenet_amd.ShawConformer (load_model picks it)')
+        if (configs.get('encoder', 'conformer') == 'conformer' and
+                (configs.get('encoder_conf') or {}).get('selfattention_layer_type') ==
+                'rope_abs_selfattn'):
+            raise NotImplementedError(
+                "selfattention_layer_type 'rope_abs_selfattn' is outside the accelerated path of "
+                'this class: wenet_amd.RopeConformer (load_model picks it)')
         return config_from_yaml(configs)
 
     def _create(self, L, tensors, n: int, h) -> int:
@@ -1270,6 +1280,12 @@ def load_model(model_name_or_path: str, device='cuda') -> ASRModel:
           'shaw_rel_selfattn'):
         from wenet_amd.shaw import ShawConformer
         model = ShawConformer(configs, sd, device)
+    elif (configs.get('encoder', 'conformer') == 'conformer' and
+          configs.get('model', 'asr_model') == 'asr_model' and
+          (configs.get('encoder_conf') or {}).get('selfattention_layer_type') ==
+          'rope_abs_selfattn'):
+        from wenet_amd.rope import RopeConformer
+        model = RopeConformer(configs, sd, device)
     elif configs.get('model') == 'firered':   # init_model.py: FireRedModel
         from wenet_amd.firered import FireRed
         model = FireRed(configs, sd, device)

@@ -786,6 +786,65 @@ def _to_shaw(sd, configs, seed):
     return out
 
 
+# rotary Conformer encoders (RopeMultiHeadedAttention, attention.py:599-686; n_kv_head / head_dim,
+# attention.py:47-77)
+def _rope(d, heads, n_kv, ffn, blocks, vocab, causal, norm, dynamic, dec_blocks, r_blocks) -> dict:
+    return {
+        'input_dim': 80, 'output_dim': vocab,
+        'encoder': 'conformer',
+        'encoder_conf': dict(output_size=d, attention_heads=heads, linear_units=ffn,
+                             num_blocks=blocks, dropout_rate=0.1, positional_dropout_rate=0.1,
+                             attention_dropout_rate=0.0, input_layer='conv2d',
+                             normalize_before=True, cnn_module_kernel=15, use_cnn_module=True,
+                             activation_type='swish', pos_enc_layer_type='rope_pos',
+                             selfattention_layer_type='rope_abs_selfattn', n_kv_head=n_kv,
+                             head_dim=64, causal=causal, cnn_module_norm=norm,
+                             use_dynamic_chunk=dynamic, use_dynamic_left_chunk=False),
+        'decoder': 'bitransformer' if r_blocks else 'transformer',
+        'decoder_conf': dict(attention_heads=4, linear_units=96, num_blocks=dec_blocks,
+                             dropout_rate=0.1, positional_dropout_rate=0.1,
+                             self_attention_dropout_rate=0.0, src_attention_dropout_rate=0.0,
+                             **({'r_num_blocks': r_blocks} if r_blocks else {})),
+        'model_conf': dict(ctc_weight=0.3, lsm_weight=0.1, length_normalized_loss=False,
+                           **({'reverse_weight': 0.3} if r_blocks else {})),
+    }
+
+
+# GQA (two query heads per K / V head), causal, dynamic chunk, layer_norm, two decoders
+CONFIGS['tiny_rope'] = _rope(256, 4, 2, 128, 2, 41, True, 'layer_norm', True, 1, 1)
+# MQA (one K / V head), non-causal, batch_norm
+CONFIGS['tiny_rope_mqa'] = _rope(256, 4, 1, 128, 2, 41, False, 'batch_norm', False, 1, 0)
+# the aishell Conformer's widths with the rotary attention, for tools/bench_rope.py
+CONFIGS['aishell_rope'] = _rope(256, 4, 4, 2048, 12, 4233, False, 'batch_norm', False, 6, 0)
+
+
+def rope_table(head_dim: int = 64, max_len: int = 3000, theta: float = 10000.0) -> torch.Tensor:
+    """The `pe` buffer of RopePositionalEncoding (embedding.py:201-214, max_len 1500 * 2;
+    rope_utils.py:5-13): (1, max_len, head_dim / 2, 2), (cos, sin) of position * theta ** (-2 i /
+    head_dim)."""
+    freqs = 1.0 / (theta**(torch.arange(0, head_dim, 2)[:head_dim // 2].float() / head_dim))
+    ang = torch.outer(torch.arange(max_len), freqs).float()
+    return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).unsqueeze(0)
+
+
+def _to_rope(sd, configs, seed):
+    """The Conformer-shaped dict of make_state_dict under a rotary encoder's names and shapes: no
+    linear_pos / pos_bias_u / pos_bias_v, linear_k / linear_v of 64 n_kv_head rows, the rotation
+    table as encoder.embed.pos_enc.pe."""
+    ec = configs['encoder_conf']
+    n_kv = ec.get('n_kv_head') or ec['attention_heads']
+    ends = ('.self_attn.linear_pos.weight', '.self_attn.pos_bias_u', '.self_attn.pos_bias_v')
+    out = OrderedDict((k, v) for k, v in sd.items()
+                      if not (k.startswith('encoder.') and k.endswith(ends)))
+    for i in range(ec['num_blocks']):
+        for n in ('linear_k', 'linear_v'):
+            for e in ('weight', 'bias'):
+                k = f'encoder.encoders.{i}.self_attn.{n}.{e}'
+                out[k] = out[k][:64 * n_kv]
+    out['encoder.embed.pos_enc.pe'] = rope_table().numpy()
+    return out
+
+
 def _to_efficonformer(sd, configs, seed):
     """The Conformer-shaped dict of make_state_dict under an EfficientConformerEncoder's shapes
     (wenet/models/efficient_conformer/encoder.py:140-215): pos_bias_u / v of a grouped layer are
@@ -1167,6 +1226,8 @@ def make_state_dict(configs: dict, seed: int = 0, sharpen_ctc: bool = True,
         sd = _to_efficonformer(sd, configs, seed)
     if ec.get('selfattention_layer_type') == 'shaw_rel_selfattn':
         sd = _to_shaw(sd, configs, seed)
+    if ec.get('selfattention_layer_type') == 'rope_abs_selfattn':
+        sd = _to_rope(sd, configs, seed)
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)))
                        for k, v in sd.items())
 
